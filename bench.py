@@ -23,8 +23,13 @@ Scene, BVH and sampler tables are resident in HBM before the timed region.  With
 (tile t -> rank t % N, the reference's tile enumeration), every rank renders its tiles, the per-tile film buffers are gathered on rank 0 over RCCL
 (the path's one exchange step) and merged there in tile order.
 
-Prints ONE JSON line (rank 0).
-`roofline` describes the dominant kernel (ph::traverse_kernel: BVH traversal + triangle tests; one launch per wavefront round serves that round's
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the line: `value` / `ms_per_step` and the stage times
+of the timed steps, the film hash of the last one.  --full adds what takes work of its own: the roofline's counting pass and PMC record, the
+CPU baseline and, at N > 1 with strong scaling, the weak-scaling leg (each can still be turned off with its --no-* option).
+--dump-outputs DIR writes what the last timed step returned, after the timed region: DIR/film_xyz.npy (h, w, 3) and DIR/film_weight.npy
+(h, w) float32, DIR/ray_counts.npy float64 (camera, regular, shadow rays, paths with zero radiance, paths; rank 0's share at N > 1).  A film
+over 64 MiB is written as a fixed, seeded sample of its pixels, with their row-major indices in DIR/film_pixel_index.npy (float64).
+`roofline` (--full) describes the dominant kernel (ph::traverse_kernel: BVH traversal + triangle tests; one launch per wavefront round serves that round's
 closest-hit and any-hit rays):
   achieved  = ALGORITHMIC bytes / kernel time: 32 B per reference-format node visit + 48 B per triangle test + 64 B ray in / hit out (33 B for any-hit
               rays), SURVEY §8d, counted by an untimed counting build of the same kernel on the same frame; time = HIP events around every traversal
@@ -34,7 +39,7 @@ closest-hit and any-hit rays):
   frac      = traffic / avg launch time / peak: the fraction of the HBM peak the kernel draws at the memory side.  The tree's upper levels are re-read
               by every ray and are served by L2 / Infinity Cache, so the algorithmic rate (`frac_algorithmic` = achieved / peak) is not an HBM
               fraction and can exceed 1; it is reported next to it.  Without a matching PMC run of the workload frac is null.
-`cpu_baseline` times the CPU oracle (oracle/, a port of the reference algorithm — the Rust reference cannot be built here) on a bounded sample of the
+`cpu_baseline` (--full) times the CPU oracle (oracle/, a port of the reference algorithm — the Rust reference cannot be built here) on a bounded sample of the
 same workload (same scene and resolution, the first few Halton samples of every pixel, about 150 M rays) on this box's host cores.
 """
 import argparse
@@ -119,6 +124,25 @@ def find_traffic(key):
     return None, f"no PMC run of workload {key} in {os.path.relpath(TRAFFIC_FILE, ROOT)} (have: {[e.get('workload') for e in tj.get('entries', [])]})"
 
 
+DUMP_CAP_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21   # a film over the cap: this many pixels (48 MiB of xyz + weight + index), drawn with a fixed seed
+
+
+def dump_outputs(out_dir, film, st):
+    """What the last timed step returned -> out_dir/*.npy: the film (xyz, weight; all of it, or a seeded pixel sample above DUMP_CAP_BYTES) and its ray counts."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    xyz, wt = film
+    h, w = wt.shape
+    arrays = {"film_xyz": xyz, "film_weight": wt}
+    if xyz.nbytes + wt.nbytes > DUMP_CAP_BYTES - (1 << 20):
+        idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+        arrays = {"film_xyz": xyz.reshape(h * w, 3)[idx], "film_weight": wt.reshape(h * w)[idx], "film_pixel_index": idx.astype(np.float64)}
+    arrays["ray_counts"] = np.array([st.camera_rays, st.regular_rays, st.shadow_rays, st.paths_zero_radiance, st.paths_total], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a fresh child (this process has not imported torch nor touched HIP), relay
     their output and return code."""
@@ -178,7 +202,12 @@ def main():
     ap.add_argument("--multi-handle", action="store_true",
                     help="N>1 from ONE process: one pbrt_hip_scene_create_multi handle over the N GPUs, the film-tile gather inside the library (RCCL send / recv); "
                          "with --backend gloo the N contexts share GPU 0 (rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the roofline's counting pass, the CPU baseline, the weak-scaling leg at N > 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's film and ray counts to DIR/*.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.multi_handle:
         raise SystemExit(launch_ranks(args.gpus))
@@ -341,11 +370,13 @@ def main():
             elapsed = float(reduce_scalars([elapsed], dist.ReduceOp.MAX, torch.float64)[0])
             rays, reg, shd = (int(v) for v in reduce_scalars([rays, reg, shd], dist.ReduceOp.SUM, torch.int64))
         return scene, tile_buf, dict(elapsed=elapsed, rays=rays, reg=reg, shd=shd, ext_s=ext_s, sh_s=sh_s, shade_s=shade_s, launches=launches, film=film,
-                                     t_setup=t_setup, steps=steps, stage=dict(stage), per_rank=per_rank)
+                                     t_setup=t_setup, steps=steps, stage=dict(stage), per_rank=per_rank, last_st=st)
 
     scaling = args.scaling if n_gpus > 1 else "weak"  # one GPU: the two coincide; the contract's default label
     frame_spp = spp * (n_gpus if (n_gpus > 1 and scaling == "weak") else 1)
     scene, tile_buf, r = run_leg(frame_spp, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["film"], r["last_st"])
 
     out = None
     if rank == 0:
@@ -394,7 +425,7 @@ def main():
                 "bound_note": (f"BVH nodes + leaf records = {resident / 2**20:.0f} MiB " + ("exceed" if resident > INFINITY_CACHE_BYTES else "fit in") + " the 256 MiB Infinity Cache"),
                 "kernel": "ph::traverse_kernel (BVH traversal + triangle tests; one launch per wavefront round serves the round's closest-hit and any-hit rays)",
                 "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None}
-        if not args.no_roofline_count:
+        if args.full and not args.no_roofline_count:
             scene.set_traversal_counting(True)
             # (a multi-device handle's *_tiles_device entry points act on its first device: that device's share of the frame)
             scene.render_path_tiles_device(tile_buf.data_ptr(), max_depth=max_depth, tile_size=tile_size, tile_part=rank, tile_parts=n_gpus)
@@ -489,7 +520,7 @@ def main():
         out["roofline"] = roof
 
     # ---- CPU baseline: the oracle (port of the reference algorithm) on this box's host cores, bounded sample ------------------------
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from oracle_binding import OracleScene
         cores = host_cores()
@@ -508,7 +539,7 @@ def main():
         orc.close()
 
     # ---- N > 1, strong scaling: a short weak-scaling leg alongside (spp x N: every rank traces what one GPU traces at N = 1) ----------------
-    if n_gpus > 1 and scaling == "strong" and not args.no_weak_leg:
+    if n_gpus > 1 and scaling == "strong" and args.full and not args.no_weak_leg:
         scene.close()
         del tile_buf
         torch.cuda.empty_cache()

@@ -28,14 +28,14 @@ if [[ $STAGE != *C* ]]; then exit 0; fi
 bash scripts/kstats.sh r04p_k2 --config 2 --steps 3 --warmup 1 > $O/kstats_config2.txt 2>&1; cp $(ls gpurun_out/r04p_k2_stats/*/*kernel_stats.csv | tail -1) $O/r04_kernel_stats_config2.csv
 bash scripts/kstats.sh r04p_k4 --config 4 --steps 1 --warmup 1 > $O/kstats_config4.txt 2>&1; cp $(ls gpurun_out/r04p_k4_stats/*/*kernel_stats.csv | tail -1) $O/r04_kernel_stats_config4.csv
 echo "kernel traces done"
-python3 bench.py > $O/r04_bench_config2.json 2> $O/bench_config2.err; echo "bench config2 done"
-python3 bench.py --config 4 --steps 3 > $O/r04_bench_config4.json 2> $O/bench_config4.err; echo "bench config4 done"
-python3 bench.py --config 3 > $O/r04_bench_config3_n1.json 2> $O/bench_config3.err
-python3 bench.py --config 1M --steps 10 > $O/r04_bench_1M.json 2> $O/bench_1M.err
-python3 bench.py --config 1 --steps 10 > $O/r04_bench_config1.json 2> $O/bench_config1.err
-python3 bench.py --config 3 --instances 1000 --n-tris 10000 > $O/r04_bench_instanced_1000x10k.json 2> $O/bench_inst.err
-python3 bench.py --gpus 2 --backend gloo --config 3 --steps 2 > $O/r04_bench_config3_2ranks_one_gpu_gloo.json 2> $O/bench_2r.err
-python3 bench.py --gpus 2 --multi-handle --backend gloo --config 3 --steps 2 > $O/r04_bench_config3_multi_handle_2ctx_one_gpu.json 2> $O/bench_mh.err
+python3 bench.py --full > $O/r04_bench_config2.json 2> $O/bench_config2.err; echo "bench config2 done"
+python3 bench.py --full --config 4 --steps 3 > $O/r04_bench_config4.json 2> $O/bench_config4.err; echo "bench config4 done"
+python3 bench.py --full --config 3 > $O/r04_bench_config3_n1.json 2> $O/bench_config3.err
+python3 bench.py --full --config 1M --steps 10 > $O/r04_bench_1M.json 2> $O/bench_1M.err
+python3 bench.py --full --config 1 --steps 10 > $O/r04_bench_config1.json 2> $O/bench_config1.err
+python3 bench.py --full --config 3 --instances 1000 --n-tris 10000 > $O/r04_bench_instanced_1000x10k.json 2> $O/bench_inst.err
+python3 bench.py --full --gpus 2 --backend gloo --config 3 --steps 2 > $O/r04_bench_config3_2ranks_one_gpu_gloo.json 2> $O/bench_2r.err
+python3 bench.py --full --gpus 2 --multi-handle --backend gloo --config 3 --steps 2 > $O/r04_bench_config3_multi_handle_2ctx_one_gpu.json 2> $O/bench_mh.err
 echo "bench lines done"
 for f in $O/r04_bench_*.json; do python3 -c "
 import json,sys

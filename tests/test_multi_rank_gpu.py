@@ -22,7 +22,7 @@ def test_two_ranks_one_gpu_film_identical():
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, capture_output=True, text=True, env=env, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo"] + common, capture_output=True, text=True, env=env, timeout=900)
+                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full"] + common, capture_output=True, text=True, env=env, timeout=900)
     assert two.returncode == 0, two.stderr[-2000:]
     a, b = _last_json(one.stdout), _last_json(two.stdout)
     assert b["n_gpus"] == 2 and a["n_gpus"] == 1

@@ -7,7 +7,6 @@ import ctypes as C
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,12 +15,18 @@ import pbrt_hip
 from oracle_binding import OracleScene, oracle_binding
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
 def kat():
     with open(os.path.join(HERE, "golden", "kat_appendix_c.json")) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def ref_tables():
+    """Data tables of the reference (golden/make_reference_tables.py)."""
+    with open(os.path.join(HERE, "golden", "reference_tables.json")) as f:
         return json.load(f)
 
 
@@ -49,15 +54,11 @@ def test_halton_permutation_known_answers(kat):
         assert sorted(out.tolist()) == list(range(p))
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "core/src/low_discrepency.rs")), reason="reference tree not present")
-def test_prime_tables_match_reference_text():
+def test_prime_tables_match_reference_text(ref_tables):
     """PRIMES / PRIME_SUMS (core/src/low_discrepency.rs:13,102) are data; the oracle regenerates them with a sieve."""
-    src = open(os.path.join(REF, "core/src/low_discrepency.rs")).read()
     lib = oracle_binding().lib
-    for name, fn in (("PRIMES", lib.oracle_prime), ("PRIME_SUMS", lib.oracle_prime_sum)):
-        m = re.search(r"pub const %s: \[usize; PRIME_TABLE_SIZE\] = \[(.*?)\];" % name, src, re.S)
-        assert m, name
-        vals = [int(v) for v in re.findall(r"\d+", m.group(1))]
+    for name, fn in (("primes", lib.oracle_prime), ("prime_sums", lib.oracle_prime_sum)):
+        vals = ref_tables[name]
         assert len(vals) == 1000
         assert vals == [fn(i) for i in range(1000)]
 
@@ -225,16 +226,15 @@ def test_sobol_sampler_properties(host):
     assert st.camera_rays == 100 * 60 * 16 and float(s.film_to_rgb(xyz, wt).mean()) > 0.2
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "core/src/sobol_matrices.rs")), reason="reference tree not present")
-def test_sobol_fixture_matches_reference_tables():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("mk", os.path.join(HERE, "golden", "make_sobol_fixture.py"))
-    mk = importlib.util.module_from_spec(spec); spec.loader.exec_module(mk)
-    src = open(mk.REF).read()
+def test_sobol_fixture_matches_reference_tables(ref_tables):
+    """sobol_subset.npz equals the leading part of the reference's tables: their sha256 was taken from the reference's text
+    (golden/make_reference_tables.py)."""
+    import hashlib
     m32, vdc, vdci = _sobol_tables()
-    assert np.array_equal(m32, np.array(mk.table(src, "SOBOL_MATRICES_32")[: len(m32)], np.uint32))
-    assert np.array_equal(vdc, np.array(mk.table(src, "VD_C_SOBOL_MATRICES")[: len(vdc)], np.uint64))
-    assert np.array_equal(vdci, np.array(mk.table(src, "VD_C_SOBOL_MATRICES_INV")[: len(vdci)], np.uint64))
+    want = ref_tables["sobol_sha256"]
+    assert hashlib.sha256(m32.astype("<u4").tobytes()).hexdigest() == want["m32"]
+    assert hashlib.sha256(vdc.astype("<u8").tobytes()).hexdigest() == want["vdc"]
+    assert hashlib.sha256(vdci.astype("<u8").tobytes()).hexdigest() == want["vdc_inv"]
 
 
 def test_spot_light_closed_form(host):

@@ -254,9 +254,9 @@ def test_procedural_2d_textures_closed_forms():
 
 
 def test_noise_table_and_dots():
-    """The permutation behind DotsTexture must be the reference's (compared with its text when the tree is present); Perlin noise vanishes
+    """The permutation behind DotsTexture must be the reference's (its table stored under golden/); Perlin noise vanishes
     on the integer lattice and is bounded; dots: every value is one of the two operands and both occur."""
-    import os, re
+    import json, os, re
     here = os.path.dirname(os.path.abspath(__file__))
     mine = open(os.path.join(here, "..", "oracle", "oracle_texture.hpp")).read()
     tab = [int(x) for x in re.findall(r"\d+", mine[mine.index("NOISE_PERM[512] = {"):].split("};")[0].split("{", 1)[1])]
@@ -264,11 +264,9 @@ def test_noise_table_and_dots():
     dev = open(os.path.join(here, "..", "pbrt-v3-rs_amd", "csrc", "texture.h")).read()
     dtab = [int(x) for x in re.findall(r"\d+", dev[dev.index("kNoisePerm[512] = {"):].split("};")[0].split("{", 1)[1])]
     assert dtab == tab
-    ref = "/root/reference/core/src/texture/common.rs"
-    if os.path.exists(ref):
-        txt = open(ref).read()
-        rtab = [int(x) for x in re.findall(r"\d+", txt[txt.index("NOISE_PERM: [usize; 2 * NOISE_PERM_SIZE] = ["):].split("];")[0].split("= [", 1)[1])]
-        assert rtab == tab
+    with open(os.path.join(here, "golden", "reference_tables.json")) as f:   # core/src/texture/common.rs's NOISE_PERM (golden/make_reference_tables.py)
+        rtab = json.load(f)["noise_perm"]
+    assert rtab == tab
     s = OracleScene()
     a = s.add_texture_constant((1.0, 1.0, 1.0)); b = s.add_texture_constant((0.0, 0.0, 0.0))
     dots = s.add_texture_dots(a, b, su=10.0, sv=10.0)
