@@ -281,7 +281,9 @@ int pbrt_hip_set_sampler(PbrtHipScene*, int kind, uint32_t samples_per_pixel, co
                          int sample_at_pixel_center);
 
 /* Optional: Sobol generator matrices (core/src/sobol_matrices.rs) as data: 1024*52 u32, then VdC 25x? tables.
- * Required before rendering with kind==1; the library does not embed them. */
+ * Required before rendering with kind==1; the library does not embed them.  Both lengths must be multiples of 52 (INVALID_ARG
+ * otherwise); a render whose path needs more than n32/52 dimensions (5 + 8 (max_depth + 1)) or whose sample bounds' log2
+ * resolution exceeds n_vdc_each/52 is refused with UNSUPPORTED. */
 int pbrt_hip_set_sobol_tables(PbrtHipScene*, const uint32_t* sobol_matrices32, size_t n32,
                               const uint64_t* vdc_matrices, const uint64_t* vdc_matrices_inv, size_t n_vdc_each);
 

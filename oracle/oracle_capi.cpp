@@ -12,7 +12,7 @@ struct OracleScene {
     Renderer r;
     std::string err;
     bool built = false, have_camera = false, have_film = false, have_sampler = false;
-    std::vector<uint32_t> sobol32; std::vector<uint64_t> vdc, vdc_inv;
+    std::vector<uint32_t> sobol32; std::vector<uint64_t> vdc, vdc_inv; std::atomic<bool> sobol_overflow{false};
     RayRecorder rec;
     OracleScene() { r.sc = &sc; }
 };
@@ -788,8 +788,10 @@ int oracle_set_sampler(OracleScene* s, int kind, uint32_t spp, const int sb[4], 
 }
 int oracle_set_sobol_tables(OracleScene* s, const uint32_t* m32, size_t n32, const uint64_t* vdc, const uint64_t* vdc_inv, size_t n_each) {
     if (!s || !m32 || !vdc || !vdc_inv) return -1;
+    if (n32 == 0 || n32 % 52 || n_each % 52) { s->err = "set_sobol_tables: table lengths must be non-zero multiples of 52"; return -1; }
     s->sobol32.assign(m32, m32 + n32); s->vdc.assign(vdc, vdc + n_each); s->vdc_inv.assign(vdc_inv, vdc_inv + n_each);
     s->r.scfg.sobol.m32 = s->sobol32.data(); s->r.scfg.sobol.vdc = s->vdc.data(); s->r.scfg.sobol.vdc_inv = s->vdc_inv.data();
+    s->r.scfg.sobol.n_dims = n32 / 52; s->r.scfg.sobol.overflow = &s->sobol_overflow;
     return 0;
 }
 int oracle_build_accel(OracleScene* s, int split_method, int max_prims) {
@@ -854,6 +856,17 @@ int oracle_occluded_batch(OracleScene* s, const OracleRay* rays, uint8_t* out, u
     return oracle_occluded_batch_stats(s, rays, out, n, nullptr, 0);
 }
 
+// The Sobol tables given must hold every dimension a path of max_depth draws (5 camera dimensions, then at most 8 per vertex) and the VdC
+// matrix for the sample bounds' log2 resolution; max_depth < 0 asks for the camera dimensions only.  The product's check_render_args keeps the
+// same bound, so a render beyond the tables is refused on both sides instead of reading past them.  The oracle-only Whitted integrator draws
+// a data-dependent number of dimensions (2 per light and per specular branch along its recursion tree): it is checked per draw instead
+// (SobolSampler::sobol_sample), and a render that ran out of dimensions returns UNSUPPORTED.
+static bool sobol_tables_cover(const OracleScene* s, int max_depth) {
+    const long long dims = (max_depth < 0 || s->r.integrator == 1) ? 5 : 5 + 8LL * (max_depth + 1);
+    SobolSampler probe(s->r.scfg);
+    return dims <= (long long)(s->sobol32.size() / 52) && probe.log2_res <= (int)(s->vdc.size() / 52);
+}
+
 // n_threads <= 0: all host cores.  record_cap > 0: also capture up to that many regular and shadow rays.
 int oracle_render_path_ex(OracleScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size,
                           int tile_part, int tile_parts, float* out_xyz, float* out_weight, OracleStats* st, int n_threads,
@@ -861,6 +874,7 @@ int oracle_render_path_ex(OracleScene* s, int max_depth, float rr_threshold, int
     if (!s || !pixel_bounds || !out_xyz || !out_weight) return -1;
     if (!s->built || !s->have_camera || !s->have_film || !s->have_sampler) { s->err = "scene incomplete"; return -2; }
     if (s->r.scfg.kind == 1 && !s->r.scfg.sobol.m32) { s->err = "sobol tables not set"; return -2; }
+    if (s->r.scfg.kind == 1 && !sobol_tables_cover(s, max_depth)) { s->err = "render: path depth or sample-bounds resolution exceeds the Sobol tables given"; return -5; }
     Renderer& r = s->r;
     r.max_depth = max_depth; r.rr_threshold = rr_threshold; r.light_strategy = light_strategy;
     for (int i = 0; i < 4; i++) r.pixel_bounds[i] = pixel_bounds[i];
@@ -868,8 +882,10 @@ int oracle_render_path_ex(OracleScene* s, int max_depth, float rr_threshold, int
     r.rec = s->rec.cap ? &s->rec : nullptr;
     if (n_threads <= 0) n_threads = batch_threads();
     auto t0 = std::chrono::steady_clock::now();
+    s->sobol_overflow.store(false);
     r.render(tile_size, tile_part, tile_parts, n_threads, out_xyz, out_weight);
     auto t1 = std::chrono::steady_clock::now();
+    if (s->sobol_overflow.load()) { s->err = "render: the path drew more Sobol dimensions than the tables given"; return -5; }
     if (st) {
         std::memset(st, 0, sizeof(*st));
         st->camera_rays = r.total_stats.camera_rays; st->regular_rays = r.total_stats.regular_rays; st->shadow_rays = r.total_stats.shadow_rays;
@@ -1010,7 +1026,7 @@ int oracle_generate_camera_rays(OracleScene* s, const int pb[4], uint32_t sample
             }
     };
     if (s->r.scfg.kind == 0) { HaltonSampler sp(s->r.scfg); emit(sp); }
-    else { if (!s->r.scfg.sobol.m32) return -2; SobolSampler sp(s->r.scfg); emit(sp); }
+    else { if (!s->r.scfg.sobol.m32) return -2; if (!sobol_tables_cover(s, -1)) return -5; SobolSampler sp(s->r.scfg); emit(sp); }
     return 0;
 }
 

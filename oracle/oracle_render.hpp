@@ -2,6 +2,7 @@
 // Samplers, camera, lights, BSDF, PathIntegrator::li, Film, SamplerIntegrator::render.
 #pragma once
 #include "oracle_scene.hpp"
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -105,7 +106,8 @@ inline uint64_t inverse_radical_inverse(uint64_t base, uint64_t inverse, uint64_
 }
 
 // =============================== Samplers =========================================================================
-struct SobolTables { const uint32_t* m32 = nullptr; const uint64_t* vdc = nullptr; const uint64_t* vdc_inv = nullptr; };
+// n_dims: the dimensions the host gave (52 words each); a draw beyond them sets *overflow and yields 0 instead of reading past the table
+struct SobolTables { const uint32_t* m32 = nullptr; const uint64_t* vdc = nullptr; const uint64_t* vdc_inv = nullptr; size_t n_dims = 0; std::atomic<bool>* overflow = nullptr; };
 
 struct SamplerConfig {
     int kind = 0;  // 0 halton, 1 sobol, 2 random (CPU only)
@@ -217,6 +219,7 @@ struct SobolSampler {
     }
     Float sobol_sample(uint64_t a, uint32_t dim) const {  // sobol_sample_f32, scramble = 0 (:1826-1848)
         uint32_t v = 0;
+        if (dim >= tb.n_dims) { if (tb.overflow) tb.overflow->store(true); return 0.0f; }
         for (size_t i = (size_t)dim * 52; a != 0; a >>= 1, i++) if (a & 1) v ^= tb.m32[i];
         return pmin((Float)v * 0x1.0p-32f, ONE_MINUS_EPSILON);
     }

@@ -1248,6 +1248,8 @@ int pbrt_hip_set_sampler(PbrtHipScene* s, int kind, uint32_t spp, const int sb[4
 int pbrt_hip_set_sobol_tables(PbrtHipScene* s, const uint32_t* m32, size_t n32, const uint64_t* vdc, const uint64_t* vdc_inv, size_t n_each) {
     return ph_guard(s, "pbrt_hip_set_sobol_tables", [&]() -> int {
     if (!s || !m32 || !vdc || !vdc_inv) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_sobol_tables: null argument");
+    // 52 entries per dimension / per VdC matrix: check_render_args bounds every Sobol render by what was given here
+    if (n32 == 0 || n32 % 52 || n_each % 52) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_sobol_tables: table lengths must be non-zero multiples of 52");
     s->sobol32.assign(m32, m32 + n32); s->vdc.assign(vdc, vdc + n_each); s->vdc_inv.assign(vdc_inv, vdc_inv + n_each);
     s->uploaded = false;
     return PBRT_HIP_OK;

@@ -895,6 +895,9 @@ int check_render_args(PbrtHipScene* s, int max_depth, int light_strategy, const 
     if (s->sampler.kind == 1 && s->sobol32.empty()) return set_err(s, PBRT_HIP_ERR_STATE, "render: sobol tables not set (pbrt_hip_set_sobol_tables)");
     // sampler dimension budget: 5 + per bounce (1+2+2) + 2 + 1; HaltonSampler asserts dim <= 1000 (halton.rs:106-110)
     if (5 + 8 * (max_depth + 1) >= (s->sampler.kind == 0 ? 1000 : 1024)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: path would exceed the sampler's dimension table");
+    // ... and the Sobol tables actually given: sobol_sample reads sobol32[dim * 52 + bit], sobol_interval_to_index reads vdc[(log2_resolution - 1) * 52 + c]
+    if (s->sampler.kind == 1 && (5 + 8 * (max_depth + 1) > (int)(s->sobol32.size() / 52) || s->sampler.log2_resolution > (int)(s->vdc.size() / 52)))
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: path depth or sample-bounds resolution exceeds the Sobol tables given (pbrt_hip_set_sobol_tables)");
     return PBRT_HIP_OK;
 }
 
@@ -1384,6 +1387,8 @@ int pbrt_hip_generate_camera_rays(PbrtHipScene* s, const int pb[4], uint32_t sam
     if (!s || !pb || !out_rays) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "generate_camera_rays: null argument");
     if (!s->have_camera || !s->have_sampler) return set_err(s, PBRT_HIP_ERR_STATE, "generate_camera_rays: camera and sampler must be set");
     if (s->sampler.kind == 1 && s->sobol32.empty()) return set_err(s, PBRT_HIP_ERR_STATE, "generate_camera_rays: sobol tables not set");
+    if (s->sampler.kind == 1 && (s->sobol32.size() / 52 < 5 || s->sampler.log2_resolution > (int)(s->vdc.size() / 52)))
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "generate_camera_rays: sample-bounds resolution exceeds the Sobol tables given");
     PH_CHECK(s, hipSetDevice(s->device));
     const int wdt = pb[2] - pb[0], hgt = pb[3] - pb[1];
     if (wdt <= 0 || hgt <= 0) return PBRT_HIP_OK;

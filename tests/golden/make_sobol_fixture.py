@@ -3,7 +3,7 @@
 (core/src/sobol_matrices.rs: SOBOL_MATRICES_32, VD_C_SOBOL_MATRICES, VD_C_SOBOL_MATRICES_INV), read as text.
 
 Only a subset is stored: the first N_DIMS dimensions (52 u32 each) and the first N_M VdC matrices, enough for the parity
-tests (max_depth <= 4 at resolutions <= 256).  The full tables are supplied at run time by the host through
+tests (max_depth <= 4 at resolutions <= 512; check_render_args and the oracle refuse deeper or larger Sobol renders with ERR_UNSUPPORTED).  The full tables are supplied at run time by the host through
 pbrt_hip_set_sobol_tables; the library embeds none.  Run here (the reference tree exists only in the build container):
 
     python tests/golden/make_sobol_fixture.py
