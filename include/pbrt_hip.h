@@ -70,7 +70,7 @@ typedef struct PbrtHipStats {
     double render_seconds;       /* device time of the render phase (HIP events)             */
     double extend_seconds;       /* of which: traversal launches that carry closest-hit rays (from the second wavefront round on they also
                                     carry that round's shadow rays: one launch per round) */
-    double shadow_seconds;       /* of which: any-hit-only traversal launches (0 unless PBRT_HIP_SPLIT_TRAVERSAL is set) */
+    double shadow_seconds;       /* of which: any-hit-only traversal launches (0: the render makes none, shadow rays go with extend) */
     double shade_seconds;        /* of which: raygen + shade + film kernels                  */
     uint64_t extend_launches;    /* number of launches counted in extend_seconds             */
     uint64_t shadow_launches;    /* number of launches counted in shadow_seconds             */

@@ -278,47 +278,14 @@ int upload_light_distribution(PbrtHipScene* s, int light_strategy) {
     return PBRT_HIP_OK;
 }
 
-// The traversal kernel's shape: {LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, waves per SIMD the kernel is compiled for (0 = the compiler's choice)}.  Slot 0 is what ships: 6 waves per
-// SIMD with 12 stack entries in LDS (the kernel needs 59 VGPRs since the round-3 register diet and would fit 8 — but a seventh wave buys nothing and costs the stack an entry: same-box,
-// configs[2] / configs[3] 689.5 / 717.0 ms of traversal per frame at 6 waves x 12 entries against 705.5 / 735.5 at 7 x 11; at 6 waves the depth is worth 12 -> 10 -> 8 -> 6 entries:
-// 687 -> 692 -> 708 -> 759 ms, a 13th nothing), lanes wait for 16 companions at leaves, 6 node steps per pass (27 shapes swept at 7 waves, 6 more at 6; gpurun r03s - r03x, r03aw, r03ax).
-// Round 4: since finished rays are written out at the wave's refill (traverse.h), the refill threshold is worth more — HALF the wave idle before a refill: configs[2] 711.9 / 689.8 /
-// 671.2 / 657.6 / 652.0 / 670.9 / 703.1 / 844.8 ms at 12 / 16 / 20 / 28 / 32 / 36 / 40 / 48 idle lanes (leaf threshold 12 / 16 / 20 and 5 / 6 / 8 node steps per pass within 3 ms of
-// each other at 32; configs[3] 704.2 -> 679.2, configs[1] 29.8 -> 29.4; gpurun r04ac - r04ae).  Slot 1 is the round-3 shape (refill at 20), kept for A/B runs (PBRT_HIP_TRAV_VARIANT=1).
-#define PH_VARIANTS(X) X(0, 16, 32, 12, 6, 6, false) X(1, 16, 20, 12, 6, 6, false)
-#define PH_N_VARIANTS 2
-#define PH_DEFAULT_INST_VARIANT 2   // the 5-wave instancing kernel (launch_traverse_kernel); 1 = the 4-wave form, kept as the A/B slot
-#define PH_DEFAULT_VARIANT 0
-static int trav_variant() {
-    static int v = -1;
-    if (v < 0) { const char* e = std::getenv("PBRT_HIP_TRAV_VARIANT"); v = e ? std::atoi(e) : PH_DEFAULT_VARIANT; if (v < 0 || v >= PH_N_VARIANTS) v = PH_DEFAULT_VARIANT; }
-    return v;
-}
-static int alpha_min() {   // PBRT_HIP_ALPHA_MIN: lanes that wait for an alpha-mask verdict before the wave evaluates the masks together (traverse.h, ALPHA_MIN); A/B aid for the instancing kernel: 0 (inside the leaf step, rounds 2 - 3), 4, 20; default 12
-    static const int v = []() { const char* e = std::getenv("PBRT_HIP_ALPHA_MIN"); const int x = e ? std::atoi(e) : 12; return (x == 0 || x == 4 || x == 20) ? x : 12; }();
-    return v;
-}
-static int variant_lds_depth(int v) {
-    switch (v) {
-#define X(id, lm, rm, ld, ns, wpe, pk) case id: return ld;
-        PH_VARIANTS(X)
-#undef X
-    }
-    return PH_LDS_DEPTH;
-}
-
 int ensure_traversal_workspace(PbrtHipScene* s) {
     if (!s->trav_blocks) {
         hipDeviceProp_t prop;
         PH_CHECK(s, hipGetDeviceProperties(&prop, s->device));
+        // every traversal launch runs as many blocks as the flat scenes' kernel (launch_traverse_kernel) keeps resident: at most its 6 waves per SIMD
         int per_cu = 0;
-        switch (trav_variant()) {
-#define X(id, lm, rm, ld, ns, wpe, pk) case id: PH_CHECK(s, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ph::traverse_kernel<false, false, lm, rm, ld, ns, false, true, 0, wpe>, PH_TRAV_BLOCK, 0)); if (wpe) per_cu = std::min(per_cu, wpe); break;
-            PH_VARIANTS(X)
-#undef X
-        }
-        per_cu = std::min(std::max(per_cu, 1), 8);
-        if (const char* e = std::getenv("PBRT_HIP_TRAV_BLOCKS_PER_CU")) per_cu = std::min(std::max(std::atoi(e), 1), per_cu);  // measurement aid
+        PH_CHECK(s, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ph::traverse_kernel<false, false, 16, 32, 12, 6, false, true, 0, 6>, PH_TRAV_BLOCK, 0));
+        per_cu = std::max(std::min(per_cu, 6), 1);
         s->trav_blocks = (uint32_t)(prop.multiProcessorCount * per_cu);
     }
     const uint32_t total_threads = s->trav_blocks * PH_TRAV_BLOCK;
@@ -327,12 +294,22 @@ int ensure_traversal_workspace(PbrtHipScene* s) {
     if ((rc = ensure_buf(s, s->d_error, 64))) return rc;
     if ((rc = ensure_buf(s, s->d_counts, 64 + 36 * 8))) return rc;
     const int stack_cap = s->inst_recs.empty() ? PH_MAX_STACK : 2 * PH_MAX_STACK;  // with instances the scene-level and object-level entries share one stack
-    const int lds_depth = s->inst_recs.empty() ? variant_lds_depth(trav_variant()) : 11;   // (the shallowest LDS stack any instancing kernel is compiled with)
+    const int lds_depth = s->inst_recs.empty() ? 12 : 11;   // the shallowest LDS stack of the kernels launch_traverse_kernel picks for such a scene: the rest spills here
     if ((rc = ensure_buf(s, s->d_spill, (size_t)(stack_cap - lds_depth) * total_threads * sizeof(uint2)))) return rc;
     return PBRT_HIP_OK;
 }
 
-// p.spill / total_threads / error_flag / counts are filled here.  mode: 0 closest hit, 1 any hit, 2 both queues in one launch (MIXED)
+// One traversal kernel shape (traverse_kernel's template arguments but ANYHIT and MIXED), launched for mode 0 closest hit, 1 any hit or 2 both queues in one launch (MIXED)
+template <bool COUNT, int LEAF_MIN, int REFILL_MIN, int LDS_DEPTH, int NODE_STEPS, bool INST, int ALPHA, int WPE, int ALPHA_MIN>
+static void launch_traverse_shape(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p) {
+    const dim3 g(blocks), b(PH_TRAV_BLOCK);
+    if (mode == 2) hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, true, ALPHA, WPE, ALPHA_MIN>), g, b, 0, s->stream, s->ds, p);
+    else if (mode == 1) hipLaunchKernelGGL((ph::traverse_kernel<true, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN>), g, b, 0, s->stream, s->ds, p);
+    else hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN>), g, b, 0, s->stream, s->ds, p);
+}
+
+// p.spill / total_threads / error_flag / counts are filled here.  mode: as launch_traverse_shape's.  The shape follows the scene: alpha-mask textures (ALPHA 1 = the inlined test for
+// image-map masks, 2 = the general evaluator out of line, traverse.h), object instances (the TransformedPrimitive-aware kernels) and the counting builds.
 void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p_in) {
     ph::TravParams p = p_in;
     p.spill = (uint2*)s->d_spill.p; p.total_threads = s->trav_blocks * PH_TRAV_BLOCK; p.error_flag = (uint32_t*)s->d_error.p;
@@ -340,60 +317,41 @@ void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph
 #if PH_PHASE_CLOCK
     p.phase = (unsigned long long*)s->d_counts.p + 8;   // (the measurement build's phase tallies sit behind the eight counters)
 #endif
-    { static int bt = -1; if (bt < 0) { const char* e = std::getenv("PBRT_HIP_TRAV_BATCH"); bt = e ? std::atoi(e) : PH_BATCH; if (bt != 64 && bt != 128 && bt != 256 && bt != 512 && bt != 1024) bt = 64; } p.batch = (uint32_t)bt; }
-    const dim3 g(blocks), b(PH_TRAV_BLOCK);
-#define PH_LAUNCH3(cnt, lm, rm, ld, ns, inst, wpe, pk)                                                                                                  \
-    do {                                                                                                                                           \
-        if (mode == 2) hipLaunchKernelGGL((ph::traverse_kernel<false, cnt, lm, rm, ld, ns, inst, true, 0, wpe>), g, b, 0, s->stream, s->ds, p);   \
-        else if (mode == 1) hipLaunchKernelGGL((ph::traverse_kernel<true, cnt, lm, rm, ld, ns, inst, false, 0, wpe>), g, b, 0, s->stream, s->ds, p); \
-        else hipLaunchKernelGGL((ph::traverse_kernel<false, cnt, lm, rm, ld, ns, inst, false, 0, wpe>), g, b, 0, s->stream, s->ds, p);             \
-    } while (0)
-#define PH_LAUNCH3AM(cnt, lm, rm, ld, ns, inst, alpha, wpe, amin)                                                                      \
-    do {                                                                                                                              \
-        if (mode == 2) hipLaunchKernelGGL((ph::traverse_kernel<false, cnt, lm, rm, ld, ns, inst, true, alpha, wpe, amin>), g, b, 0, s->stream, s->ds, p);       \
-        else if (mode == 1) hipLaunchKernelGGL((ph::traverse_kernel<true, cnt, lm, rm, ld, ns, inst, false, alpha, wpe, amin>), g, b, 0, s->stream, s->ds, p);  \
-        else hipLaunchKernelGGL((ph::traverse_kernel<false, cnt, lm, rm, ld, ns, inst, false, alpha, wpe, amin>), g, b, 0, s->stream, s->ds, p);                \
-    } while (0)
-#define PH_LAUNCH3A(cnt, lm, rm, ld, ns, inst, alpha, wpe) PH_LAUNCH3AM(cnt, lm, rm, ld, ns, inst, alpha, wpe, 0)
-    if (s->alpha_textures) {  // meshes with alpha-mask textures: the ALPHA variants — 1 = the inlined test for image-map masks, 2 = the general evaluator out of line (traverse.h)
-        const bool inst = !s->inst_recs.empty();
-        if (s->alpha_lean) {
-            if (s->count_traversal) { if (inst) PH_LAUNCH3A(true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 1, 0); else PH_LAUNCH3A(true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 1, 0); }
-            // Round 4: lanes whose candidate hit needs its alpha mask's verdict wait at their record until 12 of the wave's lanes do (traverse.h, ALPHA_MIN): configs[4]'s traversal
-            // 5 301 -> 4 520 ms per frame, same film (thresholds 4 / 8 / 12 / 20: 4 936 / 4 594 / 4 520 / 4 683 ms; same box, gpurun r04n).  PBRT_HIP_ALPHA_MIN=0 is the round-3 form.
-            else if (inst && alpha_min() == 0) PH_LAUNCH3A(false, 24, 12, 11, 5, true, 1, 5);   // (the instancing form, five waves per SIMD: 107 registers where the compiler is free, 20 spilled at 96 — and still faster: configs[4]'s traversal 6.04 -> 5.66 s per frame, gpurun r03aq; before the deferred pops it needed 115 and lost)
-            else if (inst && alpha_min() == 4) PH_LAUNCH3AM(false, 16, 12, 11, 5, true, 1, 5, 4);
-            else if (inst && alpha_min() == 20) PH_LAUNCH3AM(false, 16, 12, 11, 5, true, 1, 5, 20);
-            else if (inst) PH_LAUNCH3AM(false, 16, 12, 11, 5, true, 1, 5, 12);   // (leaf threshold 16: with the mask lanes waiting apart, fewer lanes need to gather at leaves — 4 513 -> 4 466 ms; 32: 4 717; refill at 20: 4 627; 3 / 8 node steps per pass: 4 510 / 4 795, gpurun r04q)
-            else PH_LAUNCH3AM(false, 24, 12, PH_LDS_DEPTH, 5, false, 1, 0, 12);
-        } else {
-            if (s->count_traversal) { if (inst) PH_LAUNCH3A(true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 2, 0); else PH_LAUNCH3A(true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 2, 0); }
-            else if (inst) PH_LAUNCH3AM(false, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 3, true, 2, 0, 12); else PH_LAUNCH3AM(false, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 3, false, 2, 0, 12);
-        }
+    p.batch = PH_BATCH;
+    const bool inst = !s->inst_recs.empty();
+    const int alpha = !s->alpha_textures ? 0 : s->alpha_lean ? 1 : 2;
+    if (s->count_traversal) {   // (pbrt_hip_set_traversal_counting) the default loop shape with one node step per pass
+        if (alpha == 0) { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 0, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 0, 0, 0>(s, mode, blocks, p); }
+        else if (alpha == 1) { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 1, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 1, 0, 0>(s, mode, blocks, p); }
+        else { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 2, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 2, 0, 0>(s, mode, blocks, p); }
         return;
     }
-    if (!s->inst_recs.empty()) {  // scenes with object instances: the TransformedPrimitive-aware kernels
-        if (s->count_traversal) PH_LAUNCH3(true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 0, false);
-        else {
-            static const int iv = []() { const char* e = std::getenv("PBRT_HIP_INST_VARIANT"); const int v = e ? std::atoi(e) : PH_DEFAULT_INST_VARIANT; return (v < 1 || v > 2) ? PH_DEFAULT_INST_VARIANT : v; }();
-            switch (iv) {   // round 3: 96 VGPRs without spills (102 where the compiler is free) and 31 KB of LDS (11 stack entries + 9 parked words per lane): FIVE blocks per CU.  1 000 x 10 k
-                            // instances: 1 181 ms of traversal per frame against 1 293 for the 4-wave form of round 2 (slot 1; 108 VGPRs, 12 + 13 words of LDS), gpurun r03ad; 1 115 with the deferred pops (traverse.h).  Seven more
-                            // loop shapes around 24 / 12 / 5 (16-24 / 12-20 / 4-8) measured 1 308 - 1 387 ms against 1 295 at 4 waves (gpurun r03z), four at 5 waves 1 114 - 1 135 against 1 117 (r03aq).
-                case 1: PH_LAUNCH3(false, 24, 12, PH_LDS_DEPTH, 5, true, 0, false); break;
-                default: PH_LAUNCH3(false, 24, 12, 11, 5, true, 5, false); break;   // (round 4, with finished rays written out at the refill: refill at 20 / 28: 1 044 / 1 101 ms against 1 030; leaf 16: 1 041; gpurun r04af)
-            }
-        }
-        return;
+    // Alpha masks, round 4: lanes whose candidate hit needs its alpha mask's verdict wait at their record until 12 of the wave's lanes do (traverse.h, ALPHA_MIN): configs[4]'s
+    // traversal 5 301 -> 4 520 ms per frame, same film (thresholds 4 / 8 / 12 / 20: 4 936 / 4 594 / 4 520 / 4 683 ms; same box, run r04n).
+    if (alpha == 2) {
+        if (inst) launch_traverse_shape<false, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 3, true, 2, 0, 12>(s, mode, blocks, p);
+        else launch_traverse_shape<false, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 3, false, 2, 0, 12>(s, mode, blocks, p);
+    } else if (alpha == 1) {
+        // (instanced: five waves per SIMD — 107 registers where the compiler is free, 20 spilled at 96, and still faster: configs[4]'s traversal 6.04 -> 5.66 s per frame, run r03aq;
+        // leaf threshold 16: with the mask lanes waiting apart, fewer lanes need to gather at leaves — 4 513 -> 4 466 ms; 32: 4 717; refill at 20: 4 627; 3 / 8 node steps per pass:
+        // 4 510 / 4 795, run r04q)
+        if (inst) launch_traverse_shape<false, 16, 12, 11, 5, true, 1, 5, 12>(s, mode, blocks, p);
+        else launch_traverse_shape<false, 24, 12, PH_LDS_DEPTH, 5, false, 1, 0, 12>(s, mode, blocks, p);
+    } else if (inst) {
+        // Round 3: 96 VGPRs without spills (102 where the compiler is free) and 31 KB of LDS (11 stack entries + 9 parked words per lane): FIVE blocks per CU.  1 000 x 10 k instances:
+        // 1 181 ms of traversal per frame against 1 293 for the 4-wave form of round 2 (108 VGPRs, 12 + 13 words of LDS), run r03ad; 1 115 with the deferred pops (traverse.h).  Seven
+        // more loop shapes around 24 / 12 / 5 (16-24 / 12-20 / 4-8) measured 1 308 - 1 387 ms against 1 295 at 4 waves (r03z), four at 5 waves 1 114 - 1 135 against 1 117 (r03aq).
+        // Round 4, with finished rays written out at the refill: refill at 20 / 28: 1 044 / 1 101 ms against 1 030; leaf 16: 1 041 (r04af).
+        launch_traverse_shape<false, 24, 12, 11, 5, true, 0, 5, 0>(s, mode, blocks, p);
+    } else {
+        // Flat scenes: 6 waves per SIMD with 12 stack entries in LDS (the kernel needs 59 VGPRs since the round-3 register diet and would fit 8 — but a seventh wave buys nothing and
+        // costs the stack an entry: same-box, configs[2] / configs[3] 689.5 / 717.0 ms of traversal per frame at 6 waves x 12 entries against 705.5 / 735.5 at 7 x 11; at 6 waves the
+        // depth is worth 12 -> 10 -> 8 -> 6 entries: 687 -> 692 -> 708 -> 759 ms, a 13th nothing), lanes wait for 16 companions at leaves, 6 node steps per pass (27 shapes swept at
+        // 7 waves, 6 more at 6; runs r03s - r03x, r03aw, r03ax).  Round 4: since finished rays are written out at the wave's refill (traverse.h), the refill threshold is worth more —
+        // HALF the wave idle before a refill: configs[2] 711.9 / 689.8 / 671.2 / 657.6 / 652.0 / 670.9 / 703.1 / 844.8 ms at 12 / 16 / 20 / 28 / 32 / 36 / 40 / 48 idle lanes (leaf
+        // threshold 12 / 16 / 20 and 5 / 6 / 8 node steps per pass within 3 ms of each other at 32; configs[3] 704.2 -> 679.2, configs[1] 29.8 -> 29.4; runs r04ac - r04ae).
+        launch_traverse_shape<false, 16, 32, 12, 6, false, 0, 6, 0>(s, mode, blocks, p);
     }
-    if (s->count_traversal) { PH_LAUNCH3(true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 0, false); return; }
-    switch (trav_variant()) {
-#define X(id, lm, rm, ld, ns, wpe, pk) case id: PH_LAUNCH3(false, lm, rm, ld, ns, false, wpe, pk); break;
-        PH_VARIANTS(X)
-#undef X
-    }
-#undef PH_LAUNCH3
-#undef PH_LAUNCH3A
-#undef PH_LAUNCH3AM
 }
 
 int launch_traverse(PbrtHipScene* s, bool anyhit, const void* d_rays, void* d_out, uint32_t n, float* kernel_ms) {
@@ -1274,8 +1232,7 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
             size_t c = 0;
             while (c < sigs.size() && sigs[c] != sig) c++;
             if (c == sigs.size()) sigs.push_back(sig);
-            static const bool no_sort = std::getenv("PBRT_HIP_NO_MATERIAL_SORT") != nullptr;  // measurement aid: every material in one class
-            m.sort_class = no_sort ? 0u : (uint32_t)std::min<size_t>(c, 6);
+            m.sort_class = (uint32_t)std::min<size_t>(c, 6);
             if (m.none) m.sort_class = 7u;
         }
     }

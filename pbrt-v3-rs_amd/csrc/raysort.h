@@ -4,7 +4,7 @@
 // choice here: every ray's result goes to its own slot and nothing else depends on who traces it when.  After the first diffuse bounce
 // the queues are in path order, i.e. spatially random, and on scenes larger than the caches every node fetch of a ray then misses L2.
 // These kernels produce `order`, a permutation of the round's queue positions grouped by the cell of the ray origin (Morton order
-// of a 16^3 grid over the scene bound, optionally 8^3 cells x direction octant), closest-hit rays first, any-hit rays behind them —
+// of a 16^3 grid over the scene bound), closest-hit rays first, any-hit rays behind them —
 // the traversal kernel walks the queue through it.  Rays are not moved: the kernel that writes a ray (shade) also writes its 4-byte bin key, the two
 // passes here read the keys and write 4 B of `order` per ray.
 //
@@ -29,9 +29,8 @@ struct RaySortParams {
     uint32_t* bin_start;    // [PH_SORT_KEYS] tallies -> exclusive starts (scan kernel)
     uint32_t* bin_cursor;   // [PH_SORT_KEYS] zeroed by the scan kernel
 };
-struct RaySortGrid {        // how a ray is binned
+struct RaySortGrid {        // how a ray is binned: by the cell of its origin in a 16^3 grid over the scene bound
     float lo[3], scale[3];  // cell coordinate = (o - lo) * scale in [0, 1)
-    uint32_t mode;          // 0: off; 1: 16^3 origin cells; 2: 8^3 origin cells x direction octant
 };
 
 PH_DEV uint32_t part1by2(uint32_t v) {  // 4 bits -> every third bit
@@ -41,17 +40,14 @@ PH_DEV uint32_t part1by2(uint32_t v) {  // 4 bits -> every third bit
     return v;
 }
 
-// bin of a ray with origin (ox, oy, oz) and direction (dx, dy, dz); < PH_SORT_BINS
-PH_DEV uint32_t ray_sort_key(const RaySortGrid& g, float ox, float oy, float oz, float dx, float dy, float dz) {
-    const float cells = (g.mode == 2u || g.mode == 3u) ? 8.0f : 16.0f;   // (mode 3: 8^3 cells without the octant — a measurement aid that isolates what the octant is worth)
+// bin of a ray with origin (ox, oy, oz): the Morton index of its cell; < PH_SORT_BINS
+PH_DEV uint32_t ray_sort_key(const RaySortGrid& g, float ox, float oy, float oz) {
     const float fx = (ox - g.lo[0]) * g.scale[0], fy = (oy - g.lo[1]) * g.scale[1], fz = (oz - g.lo[2]) * g.scale[2];
     // NaN / out-of-bound origins land in the border cells: any bin is a correct bin
-    const uint32_t cx = (uint32_t)pmini(pmaxi((int)(fx * cells), 0), (int)cells - 1);
-    const uint32_t cy = (uint32_t)pmini(pmaxi((int)(fy * cells), 0), (int)cells - 1);
-    const uint32_t cz = (uint32_t)pmini(pmaxi((int)(fz * cells), 0), (int)cells - 1);
-    uint32_t key = part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
-    if (g.mode == 2u) key = (key << 3) | (dx < 0.0f ? 1u : 0u) | (dy < 0.0f ? 2u : 0u) | (dz < 0.0f ? 4u : 0u);
-    return key & (PH_SORT_BINS - 1u);
+    const uint32_t cx = (uint32_t)pmini(pmaxi((int)(fx * 16.0f), 0), 15);
+    const uint32_t cy = (uint32_t)pmini(pmaxi((int)(fy * 16.0f), 0), 15);
+    const uint32_t cz = (uint32_t)pmini(pmaxi((int)(fz * 16.0f), 0), 15);
+    return part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
 }
 PH_DEV uint32_t raysort_key_at(const RaySortParams& p, uint32_t i, uint32_t n_cl) {
     return i < n_cl ? p.keys_cl[i] : PH_SORT_BINS + p.keys_sh[i - n_cl];

@@ -248,8 +248,9 @@ PH_DEV f2 map_2d_st(const TexOp& op, const TexCtx& c) {
 
 // The evaluator's value stack lives in LDS as [depth][channel][thread of the block] (conflict-free, no scratch): indexed dynamically by the program, a per-thread array
 // would go to scratch memory — 72 B per thread that the texture pass of configs[4] wrote and re-read 3.2 TB of per frame (round 3).  Kernels that evaluate textures run
-// blocks of at most PH_TEX_LDS_THREADS threads (texture_kernel, the ALPHA = 2 traversal kernel: 256).
+// blocks of at most PH_TEX_LDS_THREADS threads (their launch bounds: texture_kernel, texture_eval_kernel, the ALPHA = 2 traversal kernel's PH_TRAV_BLOCK).
 #define PH_TEX_LDS_THREADS 256
+static_assert(PH_TRAV_BLOCK <= PH_TEX_LDS_THREADS, "the ALPHA = 2 traversal kernel evaluates textures: its blocks must fit the evaluator's LDS stack");
 struct TexStack {
 #if defined(__HIP_DEVICE_COMPILE__)
     float* base;   // &lds[0][0][threadIdx.x]

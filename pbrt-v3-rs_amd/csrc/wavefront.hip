@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void spatial_mark_kernel(DeviceScene sc, WfPar
 // CAMERA: round 0, whose rays are the camera rays — the only ones that carry differentials (path.rs:107, sampler_integrator.rs:358); every later round's vertices are
 //   evaluated without (NODIFF evaluator, texture.h: no EWA / trilinear code, no differentials of the camera ray) — a leaner kernel for five rounds of six.
 template <bool SIMPLE, bool CAMERA, int WAVES = 3>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void texture_kernel(DeviceScene sc, WfParams w, int it) {
+__global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void texture_kernel(DeviceScene sc, WfParams w, int it) {
     const uint32_t n_work = w.m_order ? w.m_bins[sc.ms_tex_keys] : w.ctr[it].n_live;
     const uint32_t* live_in = w.live[it & 1];
     const RayIn* rays_in = w.rays_cl[it & 1];
@@ -606,20 +606,20 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                 float4* d = reinterpret_cast<float4*>(rays_out + ext_slot);
                 const float4 ro = stage[0][0][tid], rdv = stage[0][1][tid];
                 d[0] = ro; d[1] = rdv;
-                if (w.sort_grid.mode) w.keys_cl[ext_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z, rdv.x, rdv.y, rdv.z);
+                w.keys_cl[ext_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
             }
             if (want_mis) {
                 mis_slot = cl_slot + (want_ext ? 1u : 0u);
                 float4* d = reinterpret_cast<float4*>(rays_out + mis_slot);
                 const float4 ro = stage[1][0][tid], rdv = stage[1][1][tid];
                 d[0] = ro; d[1] = rdv;
-                if (w.sort_grid.mode) w.keys_cl[mis_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z, rdv.x, rdv.y, rdv.z);
+                w.keys_cl[mis_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
             }
             if (want_sh) {
                 float4* d = reinterpret_cast<float4*>(w.rays_sh + sh_slot);
                 const float4 ro = stage[2][0][tid], rdv = stage[2][1][tid];
                 d[0] = ro; d[1] = rdv;
-                if (w.sort_grid.mode) w.keys_sh[sh_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z, rdv.x, rdv.y, rdv.z);
+                w.keys_sh[sh_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
             }
             if (still_live) {
                 live_out[lv_slot] = pid;
@@ -995,11 +995,8 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     // run one at a time while paths remain (host reads the live count), up to kMaxNullSkips more.
     const int kMaxNullSkips = 1024;
     const int n_iter_cap = s->has_none_material ? n_iter + kMaxNullSkips : n_iter;
-    static const int sort_mode = []() { const char* e = std::getenv("PBRT_HIP_SORT_RAYS"); int v = e ? std::atoi(e) : 1; return (v < 0 || v > 3) ? 1 : v; }();
-    // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material.
-    // PBRT_HIP_MATERIAL_QUEUES=0 walks the list in queue order as rounds 1 - 3 did (A/B aid; same film)
-    static const bool mq_env = []() { const char* e = std::getenv("PBRT_HIP_MATERIAL_QUEUES"); return !(e && std::atoi(e) == 0); }();
-    const bool mat_queues = mq_env && (s->general_materials || s->textured_materials);
+    // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
+    const bool mat_queues = s->general_materials || s->textured_materials;
     if ((rc = ensure_buf(s, w.d_ctr, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters)))) return rc;
     if ((rc = ensure_buf(s, w.d_stats, 64 + 6 * PHC_N * 8))) return rc;   // DevStats (+ the shade kernel's phase tallies in measurement builds)
     if ((rc = ensure_buf(s, w.d_recL, (size_t)n_px * spp * 16))) return rc;
@@ -1018,11 +1015,9 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         for (DevBuf* b : {&w.d_sL, &w.d_sbeta, &w.d_sA, &w.d_sf2, &w.d_sbold, &w.d_sidx})
             if ((r = ensure_buf(s, *b, 2 * Bc * 16))) return r;   // two buffers each: queue-ordered, read from one and written to the other (WfParams)
         if ((r = ensure_buf(s, w.d_sprev, 2 * Bc * 4))) return r;
-        if (sort_mode) {
-            if ((r = ensure_buf(s, w.d_order, 3 * Bc * 4))) return r;
-            if ((r = ensure_buf(s, w.d_keys_cl, 2 * Bc * 4))) return r;
-            if ((r = ensure_buf(s, w.d_keys_sh, Bc * 4))) return r;
-        }
+        if ((r = ensure_buf(s, w.d_order, 3 * Bc * 4))) return r;
+        if ((r = ensure_buf(s, w.d_keys_cl, 2 * Bc * 4))) return r;
+        if ((r = ensure_buf(s, w.d_keys_sh, Bc * 4))) return r;
         if (s->textured_materials && (r = ensure_buf(s, w.d_tex_out, Bc * sizeof(TexOut)))) return r;
         if (mat_queues) {
             if ((r = ensure_buf(s, w.d_morder, Bc * 4))) return r;
@@ -1048,23 +1043,18 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     const size_t B = (size_t)n_px * chunk_spp;
 
     if ((rc = ensure_traversal_workspace(s))) return rc;
-    // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h)
-    static const int n_heads = []() { const char* e = std::getenv("PBRT_HIP_TRAV_HEADS"); int v = e ? std::atoi(e) : 8; return (v < 1 || v > 8) ? 8 : v; }();
-    static const int sort_blocks = []() { const char* e = std::getenv("PBRT_HIP_SORT_BLOCKS"); int v = e ? std::atoi(e) : 1024; return (v < 64 || v > 8192) ? 1024 : v; }();
-    static const int head_chunk = []() { const char* e = std::getenv("PBRT_HIP_HEAD_CHUNK"); int v = e ? std::atoi(e) : 49152; return (v < 1024 || v > (1 << 24) || (v & 1023)) ? 49152 : v; }();  // a multiple of every batch size
+    // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h): 8 heads, served in chunks of 49 152 rays (a multiple of every batch size); 1 024 blocks per sort pass
+    const uint32_t n_heads = 8, head_chunk = 49152, sort_blocks = 1024;
     ph::RaySortParams sortp{};
     ph::RaySortGrid sort_grid{};
-    if (sort_mode) {
-        if ((rc = ensure_buf(s, w.d_sort_bins, 2 * PH_SORT_KEYS * 4))) return rc;
-        sortp.order = (uint32_t*)w.d_order.p; sortp.bin_start = (uint32_t*)w.d_sort_bins.p; sortp.bin_cursor = sortp.bin_start + PH_SORT_KEYS;
-        sortp.keys_cl = (const uint32_t*)w.d_keys_cl.p; sortp.keys_sh = (const uint32_t*)w.d_keys_sh.p;
-        sort_grid.mode = (uint32_t)sort_mode;
-        for (int k = 0; k < 3; k++) {
-            const float ext = s->bvh.root_hi[k] - s->bvh.root_lo[k];
-            sort_grid.lo[k] = s->bvh.root_lo[k]; sort_grid.scale[k] = ext > 0.0f ? 1.0f / ext : 0.0f;
-        }
+    if ((rc = ensure_buf(s, w.d_sort_bins, 2 * PH_SORT_KEYS * 4))) return rc;
+    sortp.order = (uint32_t*)w.d_order.p; sortp.bin_start = (uint32_t*)w.d_sort_bins.p; sortp.bin_cursor = sortp.bin_start + PH_SORT_KEYS;
+    sortp.keys_cl = (const uint32_t*)w.d_keys_cl.p; sortp.keys_sh = (const uint32_t*)w.d_keys_sh.p;
+    for (int k = 0; k < 3; k++) {
+        const float ext = s->bvh.root_hi[k] - s->bvh.root_lo[k];
+        sort_grid.lo[k] = s->bvh.root_lo[k]; sort_grid.scale[k] = ext > 0.0f ? 1.0f / ext : 0.0f;
     }
-    if (n_heads > 1 && (rc = ensure_buf(s, w.d_heads, (size_t)(n_iter_cap + 2) * 8 * 64))) return rc;
+    if ((rc = ensure_buf(s, w.d_heads, (size_t)(n_iter_cap + 2) * n_heads * 64))) return rc;
     ph::MatSortParams msp{};
     if (mat_queues) {
         if ((rc = ensure_buf(s, w.d_mbins, (size_t)(2 * PH_MS_BINS + 1) * 4))) return rc;
@@ -1122,7 +1112,6 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         return PBRT_HIP_OK;
     };
     PH_CHECK(s, hipEventRecord(e_begin, s->stream));
-    static const bool split_traversal = std::getenv("PBRT_HIP_SPLIT_TRAVERSAL") != nullptr;  // measurement aid: one launch per ray kind
     uint64_t regular = 0, shadow = 0;
     std::vector<ph::IterCounters> hctr((size_t)n_iter_cap + 2);
     const uint32_t shade_blocks = (uint32_t)std::min<size_t>((B + 255) / 256, 256 * 16);
@@ -1133,7 +1122,7 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         const uint32_t cs = std::min(chunk_spp, spp - s0);
         wp.chunk_spp = cs; wp.s0 = s0; wp.B = n_px * cs; wp.identity_slots = identity ? 1u : 0u;
         PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters), s->stream));
-        if (n_heads > 1) PH_CHECK(s, hipMemsetAsync(w.d_heads.p, 0, (size_t)(n_iter_cap + 2) * 8 * 64, s->stream));
+        PH_CHECK(s, hipMemsetAsync(w.d_heads.p, 0, (size_t)(n_iter_cap + 2) * n_heads * 64, s->stream));
         if (identity) hipLaunchKernelGGL(ph::preset_counters_kernel, dim3(1), dim3(1), 0, s->stream, wp.ctr, wp.stats, wp.B);
         if ((rc = timed(2, [&]() { hipLaunchKernelGGL(ph::raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp); }))) return rc;
         int iters_run = 0;
@@ -1149,28 +1138,20 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
             iters_run = it + 1;
             ph::TravParams tp{};
             tp.rays = wp.rays_cl[it & 1]; tp.out = wp.hits_cl; tp.n = 0; tp.n_ptr = &c->n_cl; tp.counter = &c->head_cl;
-            if (n_heads > 1) { tp.heads = (uint32_t*)w.d_heads.p + (size_t)it * 8 * 16; tp.n_heads = (uint32_t)n_heads; tp.head_chunk = (uint32_t)head_chunk; }
-            if (it > 0 && !split_traversal) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
+            tp.heads = (uint32_t*)w.d_heads.p + (size_t)it * n_heads * 16; tp.n_heads = n_heads; tp.head_chunk = head_chunk;
+            if (it > 0) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
                 tp.rays2 = wp.rays_sh; tp.out2 = wp.occ; tp.n2_ptr = &c->n_sh;
-                if (sort_mode) {  // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
-                    sortp.n_cl = &c->n_cl; sortp.n_sh = &c->n_sh;
-                    if ((rc = timed(3, [&]() {
-                            (void)hipMemsetAsync(sortp.bin_start, 0, PH_SORT_KEYS * 4, s->stream);
-                            hipLaunchKernelGGL(ph::raysort_hist_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
-                            hipLaunchKernelGGL(ph::raysort_scan_kernel, dim3(1), dim3(1024), 0, s->stream, sortp);
-                            hipLaunchKernelGGL(ph::raysort_scatter_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
-                        }))) return rc;
-                    tp.order = sortp.order;
-                }
+                // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
+                sortp.n_cl = &c->n_cl; sortp.n_sh = &c->n_sh;
+                if ((rc = timed(3, [&]() {
+                        (void)hipMemsetAsync(sortp.bin_start, 0, PH_SORT_KEYS * 4, s->stream);
+                        hipLaunchKernelGGL(ph::raysort_hist_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
+                        hipLaunchKernelGGL(ph::raysort_scan_kernel, dim3(1), dim3(1024), 0, s->stream, sortp);
+                        hipLaunchKernelGGL(ph::raysort_scatter_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
+                    }))) return rc;
+                tp.order = sortp.order;
                 if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 2, s->trav_blocks, tp); }))) return rc;
-            } else {
-                if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 0, s->trav_blocks, tp); }))) return rc;
-                if (it > 0) {
-                    tp.rays = wp.rays_sh; tp.out = wp.occ; tp.n_ptr = &c->n_sh; tp.counter = &c->head_sh;
-                    tp.heads = nullptr; tp.n_heads = 0;   // the round's queue heads were drained by the closest-hit launch: this one pulls from its own single head
-                    if ((rc = timed(1, [&]() { launch_traverse_kernel(s, 1, s->trav_blocks, tp); }))) return rc;
-                }
-            }
+            } else if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 0, s->trav_blocks, tp); }))) return rc;
             // the shade side's work queues: this round's list regrouped by what has to be done for each path (matsort.h)
             if (mat_queues) {
                 msp.s_idx = wp.s_idx[it & 1]; msp.n_live = &c->n_live;
@@ -1185,17 +1166,12 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
             // light-distribution pass must skip as the reference's `continue` does (path.rs:142-157)
             if (s->textured_materials) {
                 if ((rc = timed(2, [&]() {
-                        // waves per SIMD the variants are compiled for (PBRT_HIP_TEX_WAVES = "<camera round><later rounds>", e.g. 23; A/B aid)
-                        static const int tw = []() { const char* e = std::getenv("PBRT_HIP_TEX_WAVES"); const int v = e ? std::atoi(e) : 0; return (v / 10 >= 2 && v / 10 <= 3 && v % 10 >= 2 && v % 10 <= 4) ? v : 0; }();
-                        const dim3 g(shade_blocks), b(256);
+                        const dim3 g(shade_blocks), b(PH_TEX_LDS_THREADS);
                         if (it == 0) {   // camera rays: differentials, filtered look-ups
                             if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
-                            else if (tw / 10 == 3) hipLaunchKernelGGL((ph::texture_kernel<false, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
                             else hipLaunchKernelGGL((ph::texture_kernel<false, true, 2>), g, b, 0, s->stream, s->ds, wp, it);
                         } else {
-                            if (s->simple_textures) { if (tw % 10 == 3) hipLaunchKernelGGL((ph::texture_kernel<true, false, 3>), g, b, 0, s->stream, s->ds, wp, it); else hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it); }
-                            else if (tw % 10 == 2) hipLaunchKernelGGL((ph::texture_kernel<false, false, 2>), g, b, 0, s->stream, s->ds, wp, it);
-                            else if (tw % 10 == 4) hipLaunchKernelGGL((ph::texture_kernel<false, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
+                            if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
                             else hipLaunchKernelGGL((ph::texture_kernel<false, false, 3>), g, b, 0, s->stream, s->ds, wp, it);
                         }
                     }))) return rc;
@@ -1409,3 +1385,9 @@ int pbrt_hip_generate_camera_rays(PbrtHipScene* s, const int pb[4], uint32_t sam
 }
 
 }  // extern "C"
+
+// Compiled, never launched: they fix the register budget of the out-of-line evaluator the launched forms call (TexEval::run, texture.h).  The backend compiles
+// a device function for the largest waves per SIMD among its callers, so these two keep it at 4 waves without differentials and 3 with them — the budget the
+// texture pass was tuned with.  Without them the later-round general pass spills 356 VGPRs instead of 48 and configs[4] loses 1.2 % (texture pass + 3.4 %).
+template __global__ void ph::texture_kernel<false, false, 4>(DeviceScene, ph::WfParams, int);
+template __global__ void ph::texture_kernel<false, true, 3>(DeviceScene, ph::WfParams, int);

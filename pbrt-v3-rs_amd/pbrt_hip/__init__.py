@@ -627,22 +627,17 @@ class Scene:
         """Material::bump with the float texture `texture` as displacement map."""
         self._chk(self.b.fn("set_material_bump")(self.h, material, texture))
 
-    def texture_eval(self, texture, uv, derivs=None, p=None, dpdx=None, dpdy=None):
+    def texture_eval(self, texture, uv, derivs=None, p=None, dpdx=None, dpdy=None, nodiff=False):
         """Evaluates `texture` at uv (n,2) with (du/dx, dv/dx, du/dy, dv/dy) (n,4) and, for the 3D textures, the hit point p (n,3) with dp/dx, dp/dy;
-        returns (n,3).  A probe for the parity tests."""
+        returns (n,3).  A probe for the parity tests.  nodiff=True: the product's evaluator for contexts without differentials
+        (pbrt_hip_texture_eval_batch_nodiff), which ignores the derivatives."""
         uv = np.asarray(uv, np.float32).reshape(-1, 2)
         z3 = np.zeros((len(uv), 3), np.float32)
         d = np.zeros((len(uv), 4), np.float32) if derivs is None else np.asarray(derivs, np.float32).reshape(-1, 4)
         cols = [uv, d] + [z3 if a is None else np.asarray(a, np.float32).reshape(-1, 3) for a in (p, dpdx, dpdy)]
         inp = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype=np.float32)
         out = np.zeros((len(uv), 3), np.float32)
-        self._chk(self.b.fn("texture_eval_batch")(self.h, texture, len(uv), _ptr(inp, C.c_float), _ptr(out, C.c_float)))
-        if self.b.has("texture_eval_batch_nodiff") and not inp[:, 2:6].any() and not inp[:, 9:15].any():   # (the product only: the oracle has one evaluator)
-            # contexts without differentials: the renderer evaluates them with the NODIFF form of the evaluator (every ray but a camera ray) — the two must agree bit for bit
-            out2 = np.zeros_like(out)
-            self._chk(self.b.fn("texture_eval_batch_nodiff")(self.h, texture, len(uv), _ptr(inp, C.c_float), _ptr(out2, C.c_float)))
-            if not np.array_equal(out.view(np.uint32), out2.view(np.uint32)):
-                raise AssertionError("texture_eval: the no-differentials evaluator differs from the general one on zero differentials")
+        self._chk(self.b.fn("texture_eval_batch_nodiff" if nodiff else "texture_eval_batch")(self.h, texture, len(uv), _ptr(inp, C.c_float), _ptr(out, C.c_float)))
         return out
 
     def mipmap_pyramid(self, mipmap):

@@ -15,6 +15,16 @@ def _bits_equal(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
+def _texture_eval(sc, texture, uv, derivs=None, p=None, dpdx=None, dpdy=None):
+    """sc.texture_eval.  On the product, when no context carries differentials (uv and p), the NODIFF evaluator the renderer uses for every ray
+    but a camera ray must give the same bits as the general one."""
+    out = sc.texture_eval(texture, uv, derivs, p, dpdx, dpdy)
+    if not isinstance(sc, OracleScene) and not any(a is not None and np.asarray(a, np.float32).any() for a in (derivs, dpdx, dpdy)):
+        assert _bits_equal(out, sc.texture_eval(texture, uv, derivs, p, dpdx, dpdy, nodiff=True)), \
+            "the no-differentials evaluator differs from the general one on zero differentials"
+    return out
+
+
 @pytest.mark.parametrize("w,h", [(16, 8), (5, 3), (33, 20), (1, 7)])
 @pytest.mark.parametrize("wrap", ["repeat", "clamp", "black"])
 def test_pyramid_equals_the_oracles(w, h, wrap):
@@ -42,7 +52,7 @@ def test_lookups_bit_exact(trilinear, wrap, as_float):
         tex = sc.add_texture_mix(sc.add_texture_scale(t, k), t, amt)
         if sc is orc: set_libm_mode(1)
         try:
-            outs.append((sc.texture_eval(t, uv, d), sc.texture_eval(tex, uv, d)))
+            outs.append((_texture_eval(sc, t, uv, d), _texture_eval(sc, tex, uv, d)))
         finally:
             set_libm_mode(0)
     assert _bits_equal(outs[0][0], outs[1][0])
@@ -311,7 +321,7 @@ def test_procedural_2d_lookups_bit_exact():
         texs.append(sc.add_texture_mix(texs[0], texs[4], sc.add_texture_bilerp(0.0, 1.0, 0.25, 0.75)))
         if sc is orc: set_libm_mode(1)
         try:
-            outs.append([sc.texture_eval(t, uv, d) for t in texs])
+            outs.append([_texture_eval(sc, t, uv, d) for t in texs])
         finally:
             set_libm_mode(0)
     for a, b in zip(*outs):
@@ -350,7 +360,7 @@ def test_procedural_3d_lookups_and_scene_bit_exact():
         texs.append(sc.add_texture_mix(texs[3], texs[4], texs[1]))
         if sc is orc: set_libm_mode(1)
         try:
-            outs.append([sc.texture_eval(t, uv, p=pts, dpdx=dx, dpdy=dy) for t in texs])
+            outs.append([_texture_eval(sc, t, uv, p=pts, dpdx=dx, dpdy=dy) for t in texs])
         finally:
             set_libm_mode(0)
     for a, b in zip(*outs):
@@ -394,7 +404,7 @@ def test_2d_mappings_lookups_and_scene_bit_exact():
         texs = textures(sc)
         if sc is orc: set_libm_mode(1)
         try:
-            outs.append([sc.texture_eval(t, np.zeros((n, 2), np.float32), p=pts, dpdx=dx, dpdy=dy) for t in texs])
+            outs.append([_texture_eval(sc, t, np.zeros((n, 2), np.float32), p=pts, dpdx=dx, dpdy=dy) for t in texs])
         finally:
             set_libm_mode(0)
     for a, b in zip(*outs):
