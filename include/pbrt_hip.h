@@ -51,6 +51,8 @@ typedef struct PbrtHipRay {
  * For a hit inside an object instance prim is the triangle's number in add_mesh order (object meshes included) and pad[1] =
  * instance number + 1 (add_instance call order); t, b0..b2 are those of the instance-space ray, as TransformedPrimitive::intersect
  * leaves them in `r.t_max` (transformed_primitive.rs:56).  pad[1] = 0 otherwise.
+ * A quadric shape (pbrt_hip_add_sphere / _add_quadric / _add_hyperboloid) takes ONE slot of that primitive list, in call order with the meshes' triangles: a hit on it
+ * reports t and prim, b0 = b1 = b2 = 0 and pad[1] = 0.
  * pad[0] carries the library's leaf-order index of the hit triangle and pad[2] its material class | material id << 3 (internal shortcuts for the shade stage and its work queues); ignore them. */
 typedef struct PbrtHipHit {
     float t;
@@ -155,6 +157,25 @@ int pbrt_hip_add_mesh(PbrtHipScene*, const float* P, uint32_t n_verts, const uin
 int pbrt_hip_object_begin(PbrtHipScene*, uint32_t* out_object_id);
 int pbrt_hip_object_end(PbrtHipScene*);
 int pbrt_hip_add_instance(PbrtHipScene*, uint32_t object_id, const float instance_to_world[16], const float world_to_instance[16]);
+
+/* The reference's six quadric shapes.  object_to_world is handed over as the reference's Transform holds it — the matrix AND the inverse the CTM accumulated (row-major;
+ * transform.rs:644-656 multiplies the inverses, nothing is inverted here).  Parameters are clamped and derived as the constructors do; phi_max in degrees; flags bit 0 =
+ * reverse orientation (swaps_handedness is taken from the matrix).  Each shape takes one slot of the primitive list (see PbrtHipHit) and its Shape::world_bound
+ * (object_to_world(object_bound)) enters the BVH.
+ *   pbrt_hip_add_sphere       Sphere::new (shapes/src/sphere.rs:21-44): radius, zmin, zmax, phimax
+ *   pbrt_hip_add_hyperboloid  Hyperboloid::new (hyperboloid.rs:37-110): p1, p2, phimax
+ *   pbrt_hip_add_quadric      kind 0 Cylinder::new (cylinder.rs:21-42; a, b = zmin, zmax), 1 Cone::new (cone.rs:21-40; a = height), 2 Paraboloid::new (paraboloid.rs:21-42;
+ *                             a, b = zmin, zmax), 3 Disk::new (disk.rs:21-40; a = height, b = innerradius)
+ * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: a quadric between object_begin and object_end; a quadric right after pbrt_hip_add_light_diffuse_area lights that no mesh
+ * has claimed (it would be the area light's shape: Shape::sample of the quadrics is not provided); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a
+ * quadric.  pbrt_hip_build_accel refuses a scene that holds quadrics together with object instances or alpha-mask textures; pbrt_hip_build_accel_device refuses any scene
+ * with a quadric (the host builders make its tree). */
+int pbrt_hip_add_sphere(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
+                        uint32_t material_id, uint32_t flags);
+int pbrt_hip_add_hyperboloid(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], const float p1[3], const float p2[3], float phi_max_deg,
+                             uint32_t material_id, uint32_t flags);
+int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const float o2w_minv[16], float radius, float a, float b, float phi_max_deg,
+                         uint32_t material_id, uint32_t flags);
 
 /* Alpha masks: the float textures behind a mesh's `alpha` / `shadowalpha` parameters (TriangleMesh::alpha_mask, shadow_alpha_mask: shapes/src/triangle.rs:291-312),
  * for the mesh added last; 0xFFFFFFFF keeps the constant given to add_mesh.  A candidate hit is rejected where the texture evaluates to exactly 0 at the hit's

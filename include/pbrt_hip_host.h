@@ -71,6 +71,13 @@ void pbrt_hip_host_gen_random_tris(uint64_t n_tris, uint64_t seed, float* out_P,
 int pbrt_hip_host_build_bvh(const float* P, const uint32_t* idx, uint64_t n_tris, int split_method, int max_prims_in_node,
                             int n_threads, uint32_t* out_ordered_prims, uint32_t* out_leaf_last, void* out_nodes,
                             uint64_t* out_info, float* out_root_bounds);
+/* TEST / INSPECTION HOOK, not an interface to build on (the packed shape layout below may change): the same over triangles AND quadric shapes: prim_shape[t] = 0 for a triangle (idx[3t..3t+2]), or 1 + k for shape k of `shapes`, which takes that slot of the primitive list.
+ * A shape is 40 floats: kind (0 cylinder, 1 cone, 2 paraboloid, 3 disk, 4 sphere, 5 hyperboloid), object_to_world[16], its inverse[16], and 7 parameters —
+ * sphere {radius, zmin, zmax, phimax}, kinds 0..3 {radius, a, b, phimax} as pbrt_hip_add_quadric takes them, hyperboloid {p1[3], p2[3], phimax}.  The shapes go through the
+ * constructors and the Shape::world_bound of the capture calls. */
+int pbrt_hip_host_build_bvh_shapes(const float* P, const uint32_t* idx, uint64_t n_prims, const uint32_t* prim_shape, const float* shapes, uint64_t n_shapes,
+                                   int split_method, int max_prims_in_node, int n_threads, uint32_t* out_ordered_prims, uint32_t* out_leaf_last, void* out_nodes,
+                                   uint64_t* out_info, float* out_root_bounds);
 /* The same outputs from the device builders (csrc/bvh_sah_device.hip: split_method 0, csrc/bvh_device.hip: split_method 1) on GPU `device`.  out_seconds: wall time of the build incl. transfers. */
 int pbrt_hip_device_build_bvh(int device, const float* P, const uint32_t* idx, uint64_t n_tris, int split_method, int max_prims_in_node, uint32_t* out_ordered_prims,
                               uint32_t* out_leaf_last, void* out_nodes, uint64_t* out_info, float* out_root_bounds, double* out_seconds);

@@ -195,6 +195,7 @@ int upload_scene(PbrtHipScene* s) {
     if ((rc = upload_vec(s, s->infinite_lights, &d.infinite_lights))) return rc;
     d.n_infinite = (uint32_t)s->infinite_lights.size();
     if ((rc = upload_vec(s, s->inst_recs, &d.instances))) return rc;
+    if ((rc = upload_vec(s, s->quadrics, &d.quadrics))) return rc;
     d.n_instances = (uint32_t)s->inst_recs.size();
     // a forest whose trees are all single leaves has no interior node at all (d.nodes == nullptr): the records still need their bounds / root / transform
     if (!s->inst_recs.empty() && !s->top_items.empty() && d.tris) {   // instance leaf records + hints (patch_inst_records_kernel)
@@ -300,12 +301,12 @@ int ensure_traversal_workspace(PbrtHipScene* s) {
 }
 
 // One traversal kernel shape (traverse_kernel's template arguments but ANYHIT and MIXED), launched for mode 0 closest hit, 1 any hit or 2 both queues in one launch (MIXED)
-template <bool COUNT, int LEAF_MIN, int REFILL_MIN, int LDS_DEPTH, int NODE_STEPS, bool INST, int ALPHA, int WPE, int ALPHA_MIN>
+template <bool COUNT, int LEAF_MIN, int REFILL_MIN, int LDS_DEPTH, int NODE_STEPS, bool INST, int ALPHA, int WPE, int ALPHA_MIN, bool QUADRIC = false>
 static void launch_traverse_shape(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p) {
     const dim3 g(blocks), b(PH_TRAV_BLOCK);
-    if (mode == 2) hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, true, ALPHA, WPE, ALPHA_MIN>), g, b, 0, s->stream, s->ds, p);
-    else if (mode == 1) hipLaunchKernelGGL((ph::traverse_kernel<true, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN>), g, b, 0, s->stream, s->ds, p);
-    else hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN>), g, b, 0, s->stream, s->ds, p);
+    if (mode == 2) hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, true, ALPHA, WPE, ALPHA_MIN, QUADRIC>), g, b, 0, s->stream, s->ds, p);
+    else if (mode == 1) hipLaunchKernelGGL((ph::traverse_kernel<true, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN, QUADRIC>), g, b, 0, s->stream, s->ds, p);
+    else hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN, QUADRIC>), g, b, 0, s->stream, s->ds, p);
 }
 
 // p.spill / total_threads / error_flag / counts are filled here.  mode: as launch_traverse_shape's.  The shape follows the scene: alpha-mask textures (ALPHA 1 = the inlined test for
@@ -320,6 +321,13 @@ void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph
     p.batch = PH_BATCH;
     const bool inst = !s->inst_recs.empty();
     const int alpha = !s->alpha_textures ? 0 : s->alpha_lean ? 1 : 2;
+    if (!s->quadrics.empty()) {
+        // Scenes with quadric shapes (traverse.h, QUADRIC; build_accel refuses them together with instances or alpha-mask textures): the flat kernel's loop shape with the analytic test
+        // out of line.  A kernel is allocated its callees' registers (quadric_test: 136, interval arithmetic + f64 atan2), so the compiler chooses the occupancy (WPE 0: 3 waves) — DESIGN §4.4 has the numbers.
+        if (s->count_traversal) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 0, 0, 0, true>(s, mode, blocks, p);
+        else launch_traverse_shape<false, 16, 32, 12, 6, false, 0, 0, 0, true>(s, mode, blocks, p);
+        return;
+    }
     if (s->count_traversal) {   // (pbrt_hip_set_traversal_counting) the default loop shape with one node step per pass
         if (alpha == 0) { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 0, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 0, 0, 0>(s, mode, blocks, p); }
         else if (alpha == 1) { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 1, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 1, 0, 0>(s, mode, blocks, p); }
@@ -956,6 +964,152 @@ int pbrt_hip_add_mesh(PbrtHipScene* s, const float* P, uint32_t n_verts, const u
     });
 }
 
+}  // extern "C"
+
+// ---- quadric shapes ------------------------------------------------------------------------------------------------------------------------------------------------
+// What the three capture calls share: the refusals, the shape's MeshRec and primitive slot, Shape::world_bound (core/src/geometry/shape.rs: object_to_world(object_bound))
+static void quadric_world_bound(const float o2w_m[16], const float obj_lo[3], const float obj_hi[3], float wb[6]) {
+    float lo[3], hi[3];   // Bounds3::new of the two corners, then Transform::transform_bounds
+    for (int k = 0; k < 3; k++) { lo[k] = obj_lo[k] < obj_hi[k] ? obj_lo[k] : obj_hi[k]; hi[k] = obj_lo[k] > obj_hi[k] ? obj_lo[k] : obj_hi[k]; }
+    phost::transform_bounds(o2w_m, lo, hi, wb);
+}
+static int add_quadric_common(PbrtHipScene* s, const char* what, QuadricRec& q, const float o2w_m[16], const float o2w_minv[16], const float obj_lo[3], const float obj_hi[3],
+                              uint32_t material_id, uint32_t flags) {
+    if (material_id >= s->materials.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": unknown material id");
+    if (s->open_object >= 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, std::string(what) + ": quadric shapes inside an object definition are not supported");
+    if (!s->lights.empty() && s->lights.back().type == PH_L_AREA && s->lights.back().prim == 0xFFFFFFFFu)
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, std::string(what) + ": a quadric cannot be the shape of a diffuse area light (the unclaimed area lights created last would be its); attach them to a mesh");
+    std::memcpy(q.o2w, o2w_m, 64); std::memcpy(q.w2o, o2w_minv, 64);
+    const float* m = o2w_m;   // Transform::swaps_handedness (transform.rs:593-599)
+    const float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
+    const bool swaps = det < 0.0f, rev = (flags & 1u) != 0u;
+    q.flip = (rev != swaps) ? 1u : 0u;
+    float wb[6];
+    quadric_world_bound(o2w_m, obj_lo, obj_hi, wb);
+    const uint32_t prim = (uint32_t)(s->idx.size() / 3);
+    MeshRec mr{};
+    mr.vert_base = (uint32_t)s->quadrics.size(); mr.tri_base = prim; mr.n_tris = 1;
+    mr.flags = PH_MESH_QUADRIC | (rev ? PH_MESH_REV : 0u) | (swaps ? PH_MESH_SWAP : 0u);
+    mr.material = material_id; mr.first_light = -1;
+    s->prim_quadric.resize(prim, 0u);
+    s->prim_quadric.push_back((uint32_t)s->quadrics.size() + 1u);
+    s->quadrics.push_back(q);
+    s->quadric_bounds.insert(s->quadric_bounds.end(), wb, wb + 6);
+    for (int k = 0; k < 3; k++) s->idx.push_back(0u);   // the slot's index triple; never read
+    s->tri_mesh.push_back((uint32_t)s->meshes.size());
+    s->tri_flags.push_back(0u);
+    s->meshes.push_back(mr);
+    s->top_items.push_back(prim);
+    // the quadric code lives in the general-BSDF / texture-pass instantiations of the shade kernels (wavefront.hip), like the radiance maps'
+    s->general_materials = true; s->textured_materials = true;
+    s->built = false; s->uploaded = false;
+    return PBRT_HIP_OK;
+}
+static float to_phi_max(float phi_max_deg) { return hm::clampf(phi_max_deg, 0.0f, 360.0f) * (hm::kPi / 180.0f); }   // f32::to_radians
+static float acos_f64(float x) { return (float)std::acos((double)x); }   // transcendentals: f64, rounded once
+
+// The constructors proper: parameters clamped and derived as the reference does, and the corners of object_bound()
+static void sphere_rec(float radius, float z_min, float z_max, float phi_max_deg, QuadricRec& q, float lo[3], float hi[3]) {   // Sphere::new (shapes/src/sphere.rs:21-44), object_bound (:53-58)
+    q.kind = PH_Q_SPHERE; q.radius = radius;
+    const float zlo = z_min < z_max ? z_min : z_max, zhi = z_min > z_max ? z_min : z_max;
+    q.z_min = hm::clampf(zlo, -radius, radius); q.z_max = hm::clampf(zhi, -radius, radius);
+    q.theta_min = acos_f64(hm::clampf(zlo / radius, -1.0f, 1.0f)); q.theta_max = acos_f64(hm::clampf(zhi / radius, -1.0f, 1.0f));
+    q.phi_max = to_phi_max(phi_max_deg);
+    lo[0] = lo[1] = -radius; lo[2] = q.z_min; hi[0] = hi[1] = radius; hi[2] = q.z_max;
+}
+static void hyperboloid_rec(const float p1_in[3], const float p2_in[3], float phi_max_deg, QuadricRec& q, float lo[3], float hi[3]) {   // Hyperboloid::new (hyperboloid.rs:37-110), object_bound (:112-122)
+    q.kind = PH_Q_HYPERBOLOID;
+    hm::V3 p1 = hm::ld(p1_in), p2 = hm::ld(p2_in);
+    const float radius1 = std::sqrt(p1.x * p1.x + p1.y * p1.y), radius2 = std::sqrt(p2.x * p2.x + p2.y * p2.y);
+    const float r_max = radius1 > radius2 ? radius1 : radius2;
+    q.z_min = p1.z < p2.z ? p1.z : p2.z; q.z_max = p1.z > p2.z ? p1.z : p2.z;
+    if (p2.z == 0.0f) { const hm::V3 t = p1; p1 = p2; p2 = t; }
+    hm::V3 pp = p1;
+    float ah = 0.0f, ch = 0.0f;
+    for (int count = 0;; count++) {   // the search for finite implicit coefficients (:70-88)
+        pp = hm::add(pp, hm::mulf(hm::sub(p2, p1), 2.0f));
+        const float xy1 = pp.x * pp.x + pp.y * pp.y, xy2 = p2.x * p2.x + p2.y * p2.y;
+        ah = (1.0f / xy1 - (pp.z * pp.z) / (xy1 * p2.z * p2.z)) / (1.0f - (xy2 * pp.z * pp.z) / (xy1 * p2.z * p2.z));
+        ch = (ah * xy2 - 1.0f) / (p2.z * p2.z);
+        if (std::isfinite(ah) || count > 100000) break;
+    }
+    q.ah = ah; q.ch = ch; q.radius = r_max;
+    q.p1[0] = p1.x; q.p1[1] = p1.y; q.p1[2] = p1.z; q.p2[0] = p2.x; q.p2[1] = p2.y; q.p2[2] = p2.z;
+    q.phi_max = to_phi_max(phi_max_deg);
+    lo[0] = lo[1] = -r_max; lo[2] = q.z_min; hi[0] = hi[1] = r_max; hi[2] = q.z_max;
+}
+// Cylinder::new (cylinder.rs:21-42), Cone::new (cone.rs:21-40), Paraboloid::new (paraboloid.rs:21-42), Disk::new (disk.rs:21-40) and their object_bound
+static void quadric_rec(int kind, float radius, float a, float b, float phi_max_deg, QuadricRec& q, float lo[3], float hi[3]) {
+    q.kind = (uint32_t)kind; q.radius = radius; q.z_min = 0.0f; q.z_max = 1.0f; q.height = 1.0f;
+    lo[0] = lo[1] = -radius; hi[0] = hi[1] = radius; lo[2] = hi[2] = 0.0f;
+    if (kind == PH_Q_CYLINDER || kind == PH_Q_PARABOLOID) { q.z_min = a < b ? a : b; q.z_max = a > b ? a : b; lo[2] = q.z_min; hi[2] = q.z_max; }
+    else if (kind == PH_Q_CONE) { q.height = a; lo[2] = 0.0f; hi[2] = a; }
+    else { q.height = a; q.inner_radius = b; lo[2] = a; hi[2] = a; }
+    q.phi_max = to_phi_max(phi_max_deg);
+}
+
+extern "C" {
+
+int pbrt_hip_add_sphere(PbrtHipScene* s, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg, uint32_t material_id, uint32_t flags) {
+    return ph_guard(s, "pbrt_hip_add_sphere", [&]() -> int {
+    if (!s || !o2w_m || !o2w_minv) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_sphere: null argument");
+    QuadricRec q{}; float lo[3], hi[3];
+    sphere_rec(radius, z_min, z_max, phi_max_deg, q, lo, hi);
+    return add_quadric_common(s, "add_sphere", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
+    });
+}
+int pbrt_hip_add_hyperboloid(PbrtHipScene* s, const float o2w_m[16], const float o2w_minv[16], const float p1[3], const float p2[3], float phi_max_deg, uint32_t material_id, uint32_t flags) {
+    return ph_guard(s, "pbrt_hip_add_hyperboloid", [&]() -> int {
+    if (!s || !o2w_m || !o2w_minv || !p1 || !p2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_hyperboloid: null argument");
+    QuadricRec q{}; float lo[3], hi[3];
+    hyperboloid_rec(p1, p2, phi_max_deg, q, lo, hi);
+    return add_quadric_common(s, "add_hyperboloid", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
+    });
+}
+int pbrt_hip_add_quadric(PbrtHipScene* s, int kind, const float o2w_m[16], const float o2w_minv[16], float radius, float a, float b, float phi_max_deg, uint32_t material_id, uint32_t flags) {
+    return ph_guard(s, "pbrt_hip_add_quadric", [&]() -> int {
+    if (!s || !o2w_m || !o2w_minv) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_quadric: null argument");
+    if (kind < 0 || kind > 3) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_quadric: kind must be 0 cylinder, 1 cone, 2 paraboloid or 3 disk");
+    QuadricRec q{}; float lo[3], hi[3];
+    quadric_rec(kind, radius, a, b, phi_max_deg, q, lo, hi);
+    return add_quadric_common(s, "add_quadric", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
+    });
+}
+
+// Host-only run of the BVH builder over triangles AND quadric shapes (include/pbrt_hip_host.h), for inspection and tests; needs no GPU.  The shapes go through the same constructors
+// and the same world_bound as the capture calls above.
+int pbrt_hip_host_build_bvh_shapes(const float* P, const uint32_t* idx, uint64_t n_prims, const uint32_t* prim_shape, const float* shapes, uint64_t n_shapes, int split_method,
+                                   int max_prims_in_node, int n_threads, uint32_t* out_ordered_prims, uint32_t* out_leaf_last, void* out_nodes, uint64_t* out_info, float* out_root_bounds) {
+    return ph_guard(nullptr, "pbrt_hip_host_build_bvh_shapes", [&]() -> int {
+    if (!idx || !prim_shape || (n_shapes && !shapes)) return PBRT_HIP_ERR_INVALID_ARG;
+    std::vector<float> bounds(6 * (size_t)n_shapes);
+    for (uint64_t k = 0; k < n_shapes; k++) {
+        const float* sp = shapes + 40 * k; const float* par = sp + 33;
+        const int kind = (int)sp[0];
+        QuadricRec q{}; float lo[3], hi[3];
+        if (kind == PH_Q_SPHERE) sphere_rec(par[0], par[1], par[2], par[3], q, lo, hi);
+        else if (kind == PH_Q_HYPERBOLOID) hyperboloid_rec(par, par + 3, par[6], q, lo, hi);
+        else if (kind >= 0 && kind <= 3) quadric_rec(kind, par[0], par[1], par[2], par[3], q, lo, hi);
+        else return PBRT_HIP_ERR_INVALID_ARG;
+        quadric_world_bound(sp + 1, lo, hi, &bounds[6 * k]);
+    }
+    for (uint64_t t = 0; t < n_prims; t++) if (prim_shape[t] > n_shapes) return PBRT_HIP_ERR_INVALID_ARG;
+    phost::BuildInput in{P, idx, (size_t)n_prims, nullptr, nullptr};
+    in.prim_quadric = prim_shape; in.quad_bounds = bounds.data();
+    phost::BuildOutput out;
+    const int rc = phost::build_bvh(in, split_method, max_prims_in_node, n_threads, out);
+    if (rc) return rc;
+    for (size_t i = 0; i < out.tris.size(); i++) {
+        if (out_ordered_prims) out_ordered_prims[i] = out.tris[i].prim;
+        if (out_leaf_last) out_leaf_last[i] = (out.tris[i].flags & PH_TRI_LAST) ? 1u : 0u;
+    }
+    if (out_nodes && !out.nodes.empty()) std::memcpy(out_nodes, out.nodes.data(), out.nodes.size() * sizeof(Node64));
+    if (out_info) { out_info[0] = out.interior_nodes; out_info[1] = out.leaf_nodes; out_info[2] = out.max_leaf_prims; out_info[3] = (uint64_t)out.max_depth; out_info[4] = out.root_ref; }
+    if (out_root_bounds) { for (int k = 0; k < 3; k++) { out_root_bounds[k] = out.root_lo[k]; out_root_bounds[3 + k] = out.root_hi[k]; } }
+    return 0;
+    });
+}
+
 // ObjectBegin / ObjectEnd / ObjectInstance (api/src/lib.rs:911-1000)
 int pbrt_hip_object_begin(PbrtHipScene* s, uint32_t* out_object_id) {
     return ph_guard(s, "pbrt_hip_object_begin", [&]() -> int {
@@ -1218,6 +1372,12 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
     return ph_guard(s, "pbrt_hip_build_accel", [&]() -> int {
     if (!s) return PBRT_HIP_ERR_INVALID_ARG;
     if (split_method == 2) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: splitmethod 'middle' panics in the reference (quirk B6, sah.rs:67-76)");
+    if (!s->quadrics.empty()) {   // before any work
+        if (s->build_on_device) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel_device: a scene with quadric shapes is built on the host (pbrt_hip_build_accel)");
+        if (!s->objects.empty() || !s->instances.empty()) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: quadric shapes together with object definitions or instances are not supported");
+        if (s->alpha_textures) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: quadric shapes together with alpha-mask textures are not supported");
+        s->prim_quadric.resize(s->idx.size() / 3, 0u);
+    }
     // every DiffuseAreaLight belongs to a shape (api/src/lib.rs:783-812 creates them per triangle): one that no add_mesh claimed would be sampled
     // through a primitive that does not exist
     for (size_t i = 0; i < s->lights.size(); i++)
@@ -1244,6 +1404,7 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
     }
     phost::BuildInput in;
     in.P = s->P.data(); in.idx = s->idx.data(); in.n_tris = s->idx.size() / 3; in.tri_flags = build_flags.data(); in.tri_mesh = s->tri_mesh.data();
+    if (!s->quadrics.empty()) { in.prim_quadric = s->prim_quadric.data(); in.quad_bounds = s->quadric_bounds.data(); }
     auto fail = [&](int brc) {
         if (brc == -2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "build_accel: the reference's HLBVH build asserts on this input (hlbvh.rs:338/356/418)");
         return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "build_accel: bad arguments");

@@ -418,6 +418,9 @@ int build_bvh(const BuildInput& in, int split_method, int max_prims_in_node, int
         if (p.id & PH_ITEM_INST) {  // TransformedPrimitive::world_bound, computed by the caller
             const float* bb = in.inst_bounds + 6 * (size_t)(p.id & ~PH_ITEM_INST);
             for (int k = 0; k < 3; k++) { p.b.lo[k] = bb[k]; p.b.hi[k] = bb[3 + k]; }
+        } else if (in.prim_quadric && in.prim_quadric[p.id]) {  // Shape::world_bound of a quadric, computed by the caller
+            const float* bb = in.quad_bounds + 6 * (size_t)(in.prim_quadric[p.id] - 1u);
+            for (int k = 0; k < 3; k++) { p.b.lo[k] = bb[k]; p.b.hi[k] = bb[3 + k]; }
         } else {
             const size_t t = p.id;
             const float* a = in.P + 3 * (size_t)in.idx[3 * t];
@@ -443,6 +446,12 @@ int build_bvh(const BuildInput& in, int split_method, int max_prims_in_node, int
         const uint32_t id = B.prims[i].id;
         TriRec& t = out.tris[i];
         if (id & PH_ITEM_INST) { std::memset(&t, 0, sizeof t); t.prim = id & ~PH_ITEM_INST; t.flags = PH_TRI_INSTANCE; continue; }
+        if (in.prim_quadric && in.prim_quadric[id]) {
+            std::memset(&t, 0, sizeof t);
+            const uint32_t q = in.prim_quadric[id] - 1u; std::memcpy(&t.p0[0], &q, 4);
+            t.prim = id; t.flags = (in.tri_flags ? (in.tri_flags[id] & ~PH_TRI_LAST) : 0u) | PH_TRI_QUADRIC; t.mesh = in.tri_mesh ? in.tri_mesh[id] : 0u;
+            continue;
+        }
         const float* p0 = in.P + 3 * (size_t)in.idx[3 * (size_t)id];
         const float* p1 = in.P + 3 * (size_t)in.idx[3 * (size_t)id + 1];
         const float* p2 = in.P + 3 * (size_t)in.idx[3 * (size_t)id + 2];

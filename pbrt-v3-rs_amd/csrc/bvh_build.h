@@ -25,6 +25,10 @@ struct BuildInput {
     const uint32_t* items = nullptr;
     size_t n_items = 0;
     const float* inst_bounds = nullptr;
+    // Optional quadric shapes: prim_quadric[t] = 0, or 1 + q for a primitive slot that holds a quadric (Sphere, Cylinder, ...) instead of a triangle; its bound is
+    // quad_bounds[6q..6q+5] = Shape::world_bound = object_to_world(object_bound) (core/src/geometry/shape.rs), computed by the caller.  Its TriRec carries PH_TRI_QUADRIC and q.
+    const uint32_t* prim_quadric = nullptr;
+    const float* quad_bounds = nullptr;
 };
 #define PH_ITEM_INST 0x80000000u
 

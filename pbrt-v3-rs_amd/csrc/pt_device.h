@@ -474,6 +474,27 @@ PH_DEV SurfHit make_surface_hit_any(const DeviceScene& sc, f3 rd_world, float ti
     si.dpdu_s = xf_vec(I.i2w, si.dpdu_s);
     return si;
 }
+// The same for a scene that may hold quadric shapes (QUADRIC instantiations of the shade / texture kernels only): a hit whose leaf record is a quadric repeats the shape's test on the
+// same ray out of line and takes the world-space SurfaceInteraction from it (quadric.h: quadric_surface); shading frame = geometric frame.  `qs` keeps what the texture pass needs beyond SurfHit.
+template <bool QUADRIC> PH_DEV SurfHit make_surface_hit_q(const DeviceScene& sc, f3 ro, f3 rd_world, float time, uint32_t tri_index, uint32_t inst, float b0, float b1, float b2, MeshRec& m_out, QSurf* qs) {
+    if (QUADRIC) {
+        const float4* tp = reinterpret_cast<const float4*>(sc.tris + tri_index);
+        const float4 a = tp[0];
+        const uint32_t rflags = __float_as_uint(tp[1].w);
+        if (rflags & PH_TRI_QUADRIC) {
+            m_out = sc.meshes[__float_as_uint(tp[2].w)];
+            float rod[6] = {ro.x, ro.y, ro.z, rd_world.x, rd_world.y, rd_world.z};
+            quadric_surface(sc.self, __float_as_uint(a.x), rod, qs);
+            SurfHit si;
+            si.p = qs->p; si.p_error = qs->p_error; si.wo = qs->wo; si.n = qs->n;
+            si.ns = qs->n; si.dpdu_s = qs->dpdu;   // shading frame = geometric frame (SurfaceInteraction::new); transform_surface_interaction's face_forward(ns, n) of two equal normals changes nothing
+            si.time = time; si.prim = __float_as_uint(a.w);
+            return si;
+        }
+        qs->hit = 0u;
+    }
+    return make_surface_hit_any(sc, rd_world, time, tri_index, inst, b0, b1, b2, m_out);
+}
 PH_DEV spec area_L(const LightRec& l, f3 n, f3 w) {  // DiffuseAreaLight::l (lights/src/diffuse.rs:220-226)
     return (l.two_sided || dot(n, w) > 0.0f) ? mks(l.L[0], l.L[1], l.L[2]) : mks1(0.0f);
 }

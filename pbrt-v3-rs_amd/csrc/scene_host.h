@@ -22,6 +22,11 @@ struct SceneHostState {
     bool any_n = false, any_s = false, any_uv = false;
     std::vector<uint32_t> idx, tri_mesh, tri_flags;
     std::vector<MeshRec> meshes;
+    // quadric shapes (add_sphere / add_quadric / add_hyperboloid): each owns one MeshRec and ONE slot of the primitive list (idx holds three zeros for it, tri_flags 0: the builder sets PH_TRI_QUADRIC in the leaf record from prim_quadric);
+    // quadric_bounds = its Shape::world_bound {lo xyz, hi xyz}; prim_quadric[prim] = 0, or 1 + the quadric in that slot (sized with the primitive list once a quadric exists)
+    std::vector<QuadricRec> quadrics;
+    std::vector<float> quadric_bounds;
+    std::vector<uint32_t> prim_quadric;
     std::vector<MaterialRec> materials;
     std::vector<LobeRec> lobes;
     // textures: every texture id owns a flattened postfix program (its children's programs followed by its own op)

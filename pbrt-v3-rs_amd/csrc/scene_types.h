@@ -36,6 +36,8 @@ struct alignas(64) Node64 {
 #define PH_TRI_ALPHATEX 32u  // the mesh's alpha or shadowalpha is a texture: the traversal kernel (ALPHA variants) evaluates it at the candidate hit
 #define PH_TRI_NEXT_INST 64u  // the next record of this leaf is an instance (see PH_LEAF_INST_HINT)
 #define PH_TRI_INSTANCE 16u  // not a triangle: a TransformedPrimitive (object instance); `prim` = index into DeviceScene::instances
+#define PH_TRI_QUADRIC 128u  // not a triangle: a quadric shape (sphere, cylinder, disk, cone, paraboloid, hyperboloid); p0[0] = the bit pattern of its index into DeviceScene::quadrics,
+                             // prim / mesh / class and material bits as for a triangle.  Only the QUADRIC instantiations of the traversal kernel know the bit (traverse.h)
 struct alignas(16) TriRec {
     float p0[3]; uint32_t prim;   // prim = index in add_mesh order
     float p1[3]; uint32_t flags;
@@ -55,6 +57,20 @@ struct InstRec {
     uint32_t root_ref, flags;
 };
 
+// One quadric of the reference's shapes crate (shapes/src/{sphere,cylinder,disk,cone,paraboloid,hyperboloid}.rs), as its constructor leaves it: parameters clamped and derived on the
+// host (api.hip: add_quadric_common).  It takes ONE slot of the primitive list and owns one MeshRec (PH_MESH_QUADRIC; vert_base = its index here).
+enum { PH_Q_CYLINDER = 0, PH_Q_CONE = 1, PH_Q_PARABOLOID = 2, PH_Q_DISK = 3, PH_Q_SPHERE = 4, PH_Q_HYPERBOLOID = 5 };
+struct alignas(16) QuadricRec {
+    float w2o[16], o2w[16];   // row-major 4x4: the Transform's inverse and matrix as the caller handed them over (never inverted here)
+    uint32_t kind, flip;      // flip = reverse_orientation ^ transform_swaps_handedness
+    float radius, z_min, z_max, phi_max;
+    float theta_min, theta_max;     // sphere
+    float height, inner_radius;     // cone, disk
+    float ah, ch;                   // hyperboloid (hyperboloid.rs:70-88)
+    float p1[3], p2[3];             // hyperboloid, after the constructor's swap
+    uint32_t pad_[2];
+};
+
 // ---- shading-side geometry (indexed by prim, add_mesh order) ---------------------------------------------------------
 struct MeshRec {
     uint32_t vert_base, tri_base, n_tris;
@@ -68,6 +84,7 @@ struct MeshRec {
 #define PH_MESH_UV 4u
 #define PH_MESH_REV 8u
 #define PH_MESH_SWAP 16u
+#define PH_MESH_QUADRIC 32u   // the record stands for one quadric: n_tris = 1, vert_base = its index into DeviceScene::quadrics, no vertices
 
 // One BxDF of a material's BSDF (core/src/reflection/*.rs).  Constant textures make the list a property of the material, so the
 // host builds it (api.hip) and the device walks it (bsdf_general.h).
@@ -257,4 +274,5 @@ struct DeviceScene {
     const uint32_t* sobol32;
     const uint64_t* vdc;
     const uint64_t* vdc_inv;
+    const QuadricRec* quadrics;   // null unless the scene holds a quadric shape
 };

@@ -510,6 +510,19 @@ static __device__ __noinline__ float envmap_pdf(const DeviceScene* dsc, uint32_t
 // The texture-evaluation context of a hit, out of line.  Everything texture evaluation needs beyond what the integrator carries is rebuilt
 // here from the TriRec the traversal reported: uv (triangle.rs:584), the geometric dp/du, dp/dv (:548-574, carried to world space for an
 // instance: transform.rs:566-590) and — for camera rays only — du/dv d x/y.
+// the context itself, from the hit's uv and world-space dp/du, dp/dv: shared by triangles (hit_tex_ctx) and quadric shapes (texture_kernel's QUADRIC instantiations)
+PH_DEV TexCtx tex_ctx_from(const CameraRec* cam, uint32_t spp, f2 uv, f3 dpdu, f3 dpdv, f3 p, f3 n, f3 ro, f3 rd, f2 p_film, f2 lens, uint32_t camera_ray) {
+    TexCtx ctx;
+    ctx.uv = uv;
+    ctx.dudx = ctx.dvdx = ctx.dudy = ctx.dvdy = 0.0f;
+    ctx.p = p; ctx.dpdx = mk3(0.0f, 0.0f, 0.0f); ctx.dpdy = ctx.dpdx;
+    if (camera_ray) {
+        const CameraRec cm = *cam;
+        const RayDiff rdf = camera_ray_differentials(cm, p_film, lens, ro, rd, spp);
+        compute_differentials(p, n, dpdu, dpdv, rdf, ctx);
+    }
+    return ctx;
+}
 PH_DEV TexCtx hit_tex_ctx(const DeviceScene* dsc, const CameraRec* cam, uint32_t spp, uint32_t tri_index, uint32_t inst,
                                                   f3 bary, f3 p, f3 n, f3 ro, f3 rd, f2 p_film, f2 lens, uint32_t camera_ray) {
     const DeviceScene& sc = *dsc;
@@ -533,16 +546,7 @@ PH_DEV TexCtx hit_tex_ctx(const DeviceScene* dsc, const CameraRec* cam, uint32_t
         const InstRec& I = sc.instances[inst - 1u];
         if (!(I.flags & PH_INST_IDENTITY)) { dpdu = xf_vec(I.i2w, dpdu); dpdv = xf_vec(I.i2w, dpdv); }
     }
-    TexCtx ctx;
-    ctx.uv = mk2((bary.x * uv0.x + bary.y * uv1.x) + bary.z * uv2.x, (bary.x * uv0.y + bary.y * uv1.y) + bary.z * uv2.y);
-    ctx.dudx = ctx.dvdx = ctx.dudy = ctx.dvdy = 0.0f;
-    ctx.p = p; ctx.dpdx = mk3(0.0f, 0.0f, 0.0f); ctx.dpdy = ctx.dpdx;
-    if (camera_ray) {
-        const CameraRec cm = *cam;
-        const RayDiff rdf = camera_ray_differentials(cm, p_film, lens, ro, rd, spp);
-        compute_differentials(p, n, dpdu, dpdv, rdf, ctx);
-    }
-    return ctx;
+    return tex_ctx_from(cam, spp, mk2((bary.x * uv0.x + bary.y * uv1.x) + bary.z * uv2.x, (bary.x * uv0.y + bary.y * uv1.y) + bary.z * uv2.y), dpdu, dpdv, p, n, ro, rd, p_film, lens, camera_ray);
 }
 // `tex.evaluate(..).clamp_default()` (matte.rs:63, plastic.rs:62-70, mirror.rs:53, substrate.rs:60-61)
 template <bool SIMPLE = false, bool NODIFF = false>
@@ -628,6 +632,8 @@ struct BumpOut { f3 ns, dpdu_s; };
 struct BumpIn { uint32_t tex, tri_index, inst; f3 bary, p, n, ns, dpdu_s; TexCtx c; };
 // arguments travel through one private struct: with ~40 scalar arguments (most of them on the stack) this function, out of line, corrupted values of OTHER
 // lanes of the wave in the one-lobe kernel on gfx950
+template <bool SIMPLE, bool NODIFF>
+PH_DEV void bump_shading(const DeviceScene* dsc, uint32_t tex, const TexCtx& c, f3 p, f3 n, f3 ns, f3 dpdu_s, f3 dpdv_s, f3 dndu, f3 dndv, BumpOut* out);
 template <bool SIMPLE = false, bool NODIFF = false>
 PH_DEV void hit_bump(const DeviceScene* dsc, const BumpIn* in, BumpOut* out) {
     const DeviceScene& sc = *dsc;
@@ -688,6 +694,11 @@ PH_DEV void hit_bump(const DeviceScene* dsc, const BumpIn* in, BumpOut* out) {
         const InstRec& I = sc.instances[inst - 1u];
         if (!(I.flags & PH_INST_IDENTITY)) { dpdv_s = xf_vec(I.i2w, dpdv_s); dndu = xf_normal(I.w2i, dndu); dndv = xf_normal(I.w2i, dndv); }
     }
+    bump_shading<SIMPLE, NODIFF>(dsc, tex, c, p, n, ns, dpdu_s, dpdv_s, dndu, dndv, out);
+}
+// Material::bump proper (material.rs:62-101), from the shading frame's dp/du, dp/dv, dn/du, dn/dv however the shape supplied them (triangles: hit_bump; quadric shapes: texture_kernel)
+template <bool SIMPLE, bool NODIFF>
+PH_DEV void bump_shading(const DeviceScene* dsc, uint32_t tex, const TexCtx& c, f3 p, f3 n, f3 ns, f3 dpdu_s, f3 dpdv_s, f3 dndu, f3 dndv, BumpOut* out) {
     float du = 0.5f * (pabs(c.dudx) + pabs(c.dudy));
     if (du == 0.0f) du = 0.0005f;
     TexCtx cu = c; cu.p = p + du * dpdu_s; cu.uv = mk2(c.uv.x + du, c.uv.y + 0.0f);

@@ -504,6 +504,7 @@ int pbrt_hip_set_last_mesh_alpha_textures(PbrtHipScene* s, uint32_t alpha_tex, u
     if (!s || s->meshes.empty()) return set_err(s, PBRT_HIP_ERR_STATE, "set_last_mesh_alpha_textures: no mesh has been added");
     if ((alpha_tex != 0xFFFFFFFFu && alpha_tex >= s->textures.size()) || (shadow_alpha_tex != 0xFFFFFFFFu && shadow_alpha_tex >= s->textures.size()))
         return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_last_mesh_alpha_textures: unknown texture");
+    if (s->meshes.back().flags & PH_MESH_QUADRIC) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_last_mesh_alpha_textures: the shape added last is a quadric; alpha masks on quadric shapes are not supported");
     MeshRec& m = s->meshes.back();
     if (alpha_tex != 0xFFFFFFFFu) m.alpha_tex1 = alpha_tex + 1u;
     if (shadow_alpha_tex != 0xFFFFFFFFu) m.shadow_alpha_tex1 = shadow_alpha_tex + 1u;

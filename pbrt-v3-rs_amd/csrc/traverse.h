@@ -22,6 +22,7 @@
 #pragma once
 #include "dmath.h"
 #include "scene_types.h"
+#include "quadric.h"
 
 namespace ph {
 
@@ -355,10 +356,15 @@ static __device__ __forceinline__ bool alpha_accept_lean(const DeviceScene& sc, 
 //   profiles/r04_phase_clock_config4_*).  A lane whose candidate hit needs the mask's verdict now stays at its record with `alpha_wait` set; once ALPHA_MIN lanes of the wave wait (or
 //   the wave has no interior-node work left) they fetch their records again, repeat the triangle test — same ray, same t_max, same numbers; cheaper than carrying t and the
 //   barycentrics in registers this kernel does not have — and evaluate their masks together.  The order of tests along a ray is unchanged, so the result is.
+// QUADRIC = true adds the reference's six quadric shapes (quadric.h): a leaf record with PH_TRI_QUADRIC names a QuadricRec, and the lane runs the analytic test out of line instead of the
+//   triangle test — one "primitive test" of the reference either way, same place in the leaf's order, same `r.t_max = t`.  RayState keeps no direction, so the lane reads its ray's
+//   from the queue again (the instancing kernel's lesson — that line has left the caches by then — is accepted here: no speed target for quadric scenes yet).  An accepted
+//   quadric is remembered like a triangle, by its record; the ray retires with zero barycentrics.  Instantiated only for scenes that hold a quadric (launch_traverse_kernel): with
+//   QUADRIC = false every line below compiles to what it was.
 // WPE > 0 compiles the kernel for exactly that many waves per SIMD (= resident 256-thread blocks per CU): the register allocator then fits the budget
 // (7: 72 VGPRs, 8: 64) instead of taking what it likes; 0 leaves the choice to the compiler (same code as before).
 template <bool ANYHIT, bool COUNT = false, int LEAF_MIN = PH_LEAF_MIN, int REFILL_MIN = PH_REFILL_MIN, int LDS_DEPTH = PH_LDS_DEPTH, int NODE_STEPS = 1, bool INST = false, bool MIXED = false,
-          int ALPHA = 0, int WPE = 0, int ALPHA_MIN = 0>
+          int ALPHA = 0, int WPE = 0, int ALPHA_MIN = 0, bool QUADRIC = false>
 __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : 1, WPE ? WPE : 8))) void traverse_kernel(DeviceScene sc, TravParams p) {
     __shared__ uint2 lds_stack[LDS_DEPTH][PH_TRAV_BLOCK];
     // INST: the scene-level ray's origin and what ray_setup derived from it (six IEEE divides), parked while the lane walks an instance: leaving an instance is then nine LDS reads instead of
@@ -450,6 +456,8 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
                     if (hit_tri != 0xFFFFFFFFu) {
                         const float4* tp = reinterpret_cast<const float4*>(sc.tris + hit_tri);
                         const float4 a = tp[0], b = tp[1], c = tp[2];
+                        if (QUADRIC && (__float_as_uint(b.w) & PH_TRI_QUADRIC)) hb0 = hb1 = hb2 = 0.0f;
+                        else
                         tri_bary(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), hb0, hb1, hb2);
                         hit_prim = __float_as_uint(a.w); hit_cls = (__float_as_uint(b.w) >> PH_TRI_CLASS_SHIFT) & PH_TRI_KEY_MASK;
                     } else { hit_prim = 0xFFFFFFFFu; hit_tri = 0u; hit_cls = 0u; hb0 = hb1 = hb2 = 0.0f; }
@@ -636,7 +644,14 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
                         if (COUNT) c_tris[(MIXED && ah) ? 1 : 0]++;
                         const bool second_meeting = ALPHA && ALPHA_MIN > 0 && alpha_wait;   // the lane waited at this record for its alpha mask's verdict: the test below is the one it already passed
                         alpha_wait = false;
-                        if (tri_test(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), t, b0, b1, b2)) {
+                        // Shape::intersect / intersect_p of a quadric (quadric.h): the ray's direction comes from the queue again.  (With QUADRIC = false the condition below IS the triangle test.)
+                        auto quadric_leaf = [&]() -> bool {
+                            const float4 rdq = reinterpret_cast<const float4*>((MIXED && ah) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index)[1];
+                            t = quadric_test(sc.self, __float_as_uint(a.x), r.ox, r.oy, r.oz, r.t_max, rdq.x, rdq.y, rdq.z);
+                            b0 = b1 = b2 = 0.0f;
+                            return t > 0.0f;
+                        };
+                        if ((QUADRIC && (flags & PH_TRI_QUADRIC)) ? quadric_leaf() : tri_test(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), t, b0, b1, b2)) {
                             // post-t rejections: degenerate triangle (triangle.rs:567-570 / 862-866), alpha == 0 (:603 / :886-893)
                             const uint32_t reject = ah ? (PH_TRI_BOGUS | PH_TRI_ALPHA0 | PH_TRI_SALPHA0) : (PH_TRI_BOGUS | PH_TRI_ALPHA0);
                             bool accept = !(flags & reject);

@@ -154,6 +154,8 @@ __global__ __launch_bounds__(256) void raygen_kernel(DeviceScene sc, WfParams w)
 // ---------------------------------------------------------------------------------------------------------------------------
 // SpatialLightDistribution::lookup, first half (spatial.rs:166-236): every path that is about to sample a light at a new
 // vertex names its voxel; the first path to touch a voxel claims a pool slot for it (spatial_compute_kernel fills it).
+// QUADRIC: the scene may hold quadric shapes, whose hit point comes from the shape's own test (pt_device.h: make_surface_hit_q)
+template <bool QUADRIC = false>
 __global__ __launch_bounds__(256) void spatial_mark_kernel(DeviceScene sc, WfParams w, int it) {
     const uint32_t n_live = w.ctr[it].n_live;
     const SpatialRec& sr = w.spatial;
@@ -174,6 +176,12 @@ __global__ __launch_bounds__(256) void spatial_mark_kernel(DeviceScene sc, WfPar
         // ... and so is a hit for which this round's texture pass found no BSDF (a TranslucentMaterial whose reflect and transmit are black there)
         if (w.any_rt && sc.materials[sc.meshes[__float_as_uint(c.w)].material].rt_mode && (w.tex_out[j].bumped & PH_TEXOUT_NULL_BSDF)) continue;
         f3 p = h0.z * mk3(a.x, a.y, a.z) + h0.w * mk3(b.x, b.y, b.z) + h1.x * mk3(c.x, c.y, c.z);  // = SurfHit::p (make_surface_hit_tv)
+        if (QUADRIC && (__float_as_uint(b.w) & PH_TRI_QUADRIC)) {
+            const RayIn ray = load_ray(w.rays_cl[it & 1] + idx4.x);
+            float rod[6] = {ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz};
+            QSurf qs; quadric_surface(sc.self, __float_as_uint(a.x), rod, &qs);
+            p = qs.p;
+        }
         const uint32_t inst = __float_as_uint(h1.z);
         if (inst != 0u && !(sc.instances[inst - 1u].flags & PH_INST_IDENTITY)) {  // world-space p of an instanced hit (make_surface_hit_any)
             f3 pe; p = xf_point_abs_err(sc.instances[inst - 1u].i2w, p, mk3(0.0f, 0.0f, 0.0f), pe);
@@ -196,7 +204,8 @@ __global__ __launch_bounds__(256) void spatial_mark_kernel(DeviceScene sc, WfPar
 // SIMPLE: the scene's textures are constants, image maps, scale and mix only: the evaluator is compiled without the procedural classes and fits more waves.
 // CAMERA: round 0, whose rays are the camera rays — the only ones that carry differentials (path.rs:107, sampler_integrator.rs:358); every later round's vertices are
 //   evaluated without (NODIFF evaluator, texture.h: no EWA / trilinear code, no differentials of the camera ray) — a leaner kernel for five rounds of six.
-template <bool SIMPLE, bool CAMERA, int WAVES = 3>
+// QUADRIC: the scene may hold quadric shapes: their uv, dp/du, dp/dv, dn/du, dn/dv come from the shape's parametric form (quadric.h) instead of from the TriRec.
+template <bool SIMPLE, bool CAMERA, int WAVES = 3, bool QUADRIC = false>
 __global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void texture_kernel(DeviceScene sc, WfParams w, int it) {
     const uint32_t n_work = w.m_order ? w.m_bins[sc.ms_tex_keys] : w.ctr[it].n_live;
     const uint32_t* live_in = w.live[it & 1];
@@ -221,7 +230,10 @@ __global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per
         const RayIn ray = load_ray(rays_in + idx4.x);
         const f3 rd = mk3(ray.dx, ray.dy, ray.dz);
         MeshRec m;
-        const SurfHit si = make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
+        QSurf qs; qs.hit = 0u;
+        const SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs)
+                                   : make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
+        const bool on_quadric = QUADRIC && (m.flags & PH_MESH_QUADRIC) != 0u;
         const MaterialRec& mr = sc.materials[m.material];
         if (mr.none || !(mr.textured || mr.bump_tex1)) continue;
         const uint32_t camera_ray = (CAMERA && bounces == 0u && !(flags & F_NODIFF)) ? 1u : 0u;  // only camera rays carry differentials
@@ -233,7 +245,8 @@ __global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per
             p_film = mk2(w.rec_L[gsi].w, w.rec_py[gsi]);
             if (w.cam.lens_radius > 0.0f) { const float4 la = w.s_A[it & 1][w.s_prev[it & 1][i]]; lens = mk2(la.x, la.y); }
         }
-        const TexCtx ctx = hit_tex_ctx(sc.self, w.cam_dev, w.sp.spp, __float_as_uint(h1.y), __float_as_uint(h1.z), mk3(h0.z, h0.w, h1.x), si.p, si.n,
+        const TexCtx ctx = on_quadric ? tex_ctx_from(w.cam_dev, w.sp.spp, mk2(qs.u, qs.v), qs.dpdu, qs.dpdv, si.p, si.n, mk3(ray.ox, ray.oy, ray.oz), rd, p_film, lens, camera_ray)
+                                      : hit_tex_ctx(sc.self, w.cam_dev, w.sp.spp, __float_as_uint(h1.y), __float_as_uint(h1.z), mk3(h0.z, h0.w, h1.x), si.p, si.n,
                                        mk3(ray.ox, ray.oy, ray.oz), rd, p_film, lens, camera_ray);
         PHC_END(0);
         TexOut out;
@@ -244,6 +257,8 @@ __global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per
             BumpIn bi; bi.tex = mr.bump_tex1 - 1u; bi.tri_index = __float_as_uint(h1.y); bi.inst = __float_as_uint(h1.z); bi.bary = mk3(h0.z, h0.w, h1.x);
             bi.p = si.p; bi.n = si.n; bi.ns = si.ns; bi.dpdu_s = si.dpdu_s; bi.c = ctx;
             BumpOut bo;
+            if (on_quadric) bump_shading<SIMPLE, !CAMERA>(sc.self, bi.tex, ctx, si.p, si.n, si.ns, si.dpdu_s, qs.dpdv, qs.dndu, qs.dndv, &bo);
+            else
             hit_bump<SIMPLE, !CAMERA>(sc.self, &bi, &bo);
             out.ns[0] = bo.ns.x; out.ns[1] = bo.ns.y; out.ns[2] = bo.ns.z; out.dpdu_s[0] = bo.dpdu_s.x; out.dpdu_s[1] = bo.dpdu_s.y; out.dpdu_s[2] = bo.dpdu_s.z;
             out.bumped = 1u;
@@ -314,7 +329,8 @@ template <> struct BsdfOps<true> {
 #endif
 #define PH_SHADE_WAVES(GEN, TEX) ((GEN) && (TEX) ? PH_SHADE_GEN_TEX_WAVES : (((GEN) || (TEX)) ? 3 : 4))
 #define PH_SHADE_ATTR __attribute__((amdgpu_waves_per_eu(PH_SHADE_WAVES(GEN, TEX), PH_SHADE_WAVES(GEN, TEX))))
-template <bool GEN, bool TEX = false>
+// QUADRIC: the scene may hold quadric shapes (instantiated with GEN and TEX only: api.hip, add_quadric_common): a new vertex on one takes its interaction from the shape's own test
+template <bool GEN, bool TEX = false, bool QUADRIC = false>
 __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(DeviceScene sc, WfParams w, int it) {
     using BO = BsdfOps<GEN>;
     __shared__ float4 stage[3][2][PH_SHADE_BLOCK];           // [ext, mis, shadow][ray halves][thread]
@@ -418,7 +434,9 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                     const float4 h1 = hp[1];
                     MeshRec m;
                     PHC_BEGIN(1);
-                    SurfHit si = make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
+                    QSurf qs;
+                    SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs)
+                                         : make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
                     if (emit) {
                         if (m.first_light >= 0) L = L + beta * area_L(sc.lights[(uint32_t)m.first_light + (hprim - m.tri_base)], si.n, -rd);
                         else L = L + beta * mks1(0.0f);
@@ -997,6 +1015,7 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     const int n_iter_cap = s->has_none_material ? n_iter + kMaxNullSkips : n_iter;
     // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
     const bool mat_queues = s->general_materials || s->textured_materials;
+    const bool has_quadrics = !s->quadrics.empty();   // the QUADRIC instantiations of the texture, light-distribution and shade passes
     if ((rc = ensure_buf(s, w.d_ctr, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters)))) return rc;
     if ((rc = ensure_buf(s, w.d_stats, 64 + 6 * PHC_N * 8))) return rc;   // DevStats (+ the shade kernel's phase tallies in measurement builds)
     if ((rc = ensure_buf(s, w.d_recL, (size_t)n_px * spp * 16))) return rc;
@@ -1168,22 +1187,26 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
                 if ((rc = timed(2, [&]() {
                         const dim3 g(shade_blocks), b(PH_TEX_LDS_THREADS);
                         if (it == 0) {   // camera rays: differentials, filtered look-ups
-                            if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
+                            if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, true, 2, true>), g, b, 0, s->stream, s->ds, wp, it);
+                            else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
                             else hipLaunchKernelGGL((ph::texture_kernel<false, true, 2>), g, b, 0, s->stream, s->ds, wp, it);
                         } else {
-                            if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
+                            if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, false, 3, true>), g, b, 0, s->stream, s->ds, wp, it);
+                            else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
                             else hipLaunchKernelGGL((ph::texture_kernel<false, false, 3>), g, b, 0, s->stream, s->ds, wp, it);
                         }
                     }))) return rc;
             }
             if (spatial && (it < max_depth || s->has_none_material)) {  // vertices reached at bounce == max_depth sample no light (path.rs:136-139)
                 if ((rc = timed(2, [&]() {
-                        hipLaunchKernelGGL(ph::spatial_mark_kernel, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                        if (has_quadrics) hipLaunchKernelGGL(ph::spatial_mark_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                        else hipLaunchKernelGGL(ph::spatial_mark_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
                         hipLaunchKernelGGL(ph::spatial_compute_kernel, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, wp.spatial);
                     }))) return rc;
             }
             if ((rc = timed(2, [&]() {
-                    if (s->textured_materials) {
+                    if (has_quadrics) hipLaunchKernelGGL((ph::shade_kernel<true, true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);   // (quadrics set both flags)
+                    else if (s->textured_materials) {
                         if (s->general_materials) hipLaunchKernelGGL((ph::shade_kernel<true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
                         else hipLaunchKernelGGL((ph::shade_kernel<false, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
                     } else if (s->general_materials) hipLaunchKernelGGL(ph::shade_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);

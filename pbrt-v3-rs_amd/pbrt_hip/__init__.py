@@ -117,6 +117,9 @@ class Binding:
             "object_begin": (C.c_int, [vp, u32p]),
             "object_end": (C.c_int, [vp]),
             "add_instance": (C.c_int, [vp, C.c_uint32, fp, fp]),
+            "add_sphere": (C.c_int, [vp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
+            "add_hyperboloid": (C.c_int, [vp, fp, fp, fp, fp, C.c_float, C.c_uint32, C.c_uint32]),
+            "add_quadric": (C.c_int, [vp, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
             "add_mipmap": (C.c_int, [vp, C.c_int, C.c_int, fp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, u32p]),
             "add_texture_constant": (C.c_int, [vp, fp, u32p]),
             "add_texture_scale": (C.c_int, [vp, C.c_uint32, C.c_uint32, u32p]),
@@ -410,6 +413,26 @@ class Scene:
         flags = (1 if reverse_orientation else 0) | (2 if swaps_handedness else 0)
         self._chk(self.b.fn("add_mesh")(self.h, _ptr(P, C.c_float), len(P), _ptr(idx, C.c_uint32), len(idx) // 3, _ptr(N, C.c_float),
                                         _ptr(S, C.c_float), _ptr(UV, C.c_float), material, first_area_light, flags, C.c_float(alpha), C.c_float(shadow_alpha)))
+
+    # Quadric shapes (shapes/src/{sphere,hyperboloid,cylinder,cone,paraboloid,disk}.rs).  object_to_world is handed over as the reference's Transform holds it: the matrix
+    # AND its inverse.  Each takes one slot of the primitive list, in call order with the meshes' triangles.
+    def add_sphere(self, object_to_world, world_to_object, radius=1.0, z_min=None, z_max=None, phi_max=360.0, material=0, reverse_orientation=False):
+        z_min = -radius if z_min is None else z_min
+        z_max = radius if z_max is None else z_max
+        self._chk(self.b.fn("add_sphere")(self.h, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(z_min),
+                                          C.c_float(z_max), C.c_float(phi_max), material, 1 if reverse_orientation else 0))
+
+    def add_hyperboloid(self, object_to_world, world_to_object, p1, p2, phi_max=360.0, material=0, reverse_orientation=False):
+        self._chk(self.b.fn("add_hyperboloid")(self.h, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), _ptr(_f32(p1), C.c_float),
+                                               _ptr(_f32(p2), C.c_float), C.c_float(phi_max), material, 1 if reverse_orientation else 0))
+
+    QUADRIC_KINDS = {"cylinder": 0, "cone": 1, "paraboloid": 2, "disk": 3}
+
+    def add_quadric(self, kind, object_to_world, world_to_object, radius, a, b, phi_max=360.0, material=0, reverse_orientation=False):
+        """kind: "cylinder" (a, b = zmin, zmax) | "cone" (a = height) | "paraboloid" (a, b = zmin, zmax) | "disk" (a = height, b = innerradius), or its number"""
+        k = self.QUADRIC_KINDS[kind] if isinstance(kind, str) else int(kind)
+        self._chk(self.b.fn("add_quadric")(self.h, k, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(a),
+                                           C.c_float(b), C.c_float(phi_max), material, 1 if reverse_orientation else 0))
 
     def object_begin(self) -> int:
         """ObjectBegin (api/src/lib.rs:911-925): meshes added until object_end() belong to the returned object."""
