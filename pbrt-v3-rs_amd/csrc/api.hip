@@ -283,10 +283,10 @@ int ensure_traversal_workspace(PbrtHipScene* s) {
     if (!s->trav_blocks) {
         hipDeviceProp_t prop;
         PH_CHECK(s, hipGetDeviceProperties(&prop, s->device));
-        // every traversal launch runs as many blocks as the flat scenes' kernel (launch_traverse_kernel) keeps resident: at most its 6 waves per SIMD
+        // EVERY shape launches the grid the flat scenes' mixed kernel keeps resident, at most its 6 waves per SIMD — also the shapes that fit fewer blocks per CU
         int per_cu = 0;
-        PH_CHECK(s, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ph::traverse_kernel<false, false, 16, 32, 12, 6, false, true, 0, 6>, PH_TRAV_BLOCK, 0));
-        per_cu = std::max(std::min(per_cu, 6), 1);
+        PH_CHECK(s, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ph::traverse_kernel<ph::ShapeFlat, ph::TRAV_MIXED>, PH_TRAV_BLOCK, 0));
+        per_cu = std::max(std::min(per_cu, ph::ShapeFlat::wpe), 1);
         s->trav_blocks = (uint32_t)(prop.multiProcessorCount * per_cu);
     }
     const uint32_t total_threads = s->trav_blocks * PH_TRAV_BLOCK;
@@ -294,23 +294,27 @@ int ensure_traversal_workspace(PbrtHipScene* s) {
     if ((rc = ensure_buf(s, s->d_counter, 64))) return rc;
     if ((rc = ensure_buf(s, s->d_error, 64))) return rc;
     if ((rc = ensure_buf(s, s->d_counts, 64 + 36 * 8))) return rc;
-    const int stack_cap = s->inst_recs.empty() ? PH_MAX_STACK : 2 * PH_MAX_STACK;  // with instances the scene-level and object-level entries share one stack
-    const int lds_depth = s->inst_recs.empty() ? 12 : 11;   // the shallowest LDS stack of the kernels launch_traverse_kernel picks for such a scene: the rest spills here
-    if ((rc = ensure_buf(s, s->d_spill, (size_t)(stack_cap - lds_depth) * total_threads * sizeof(uint2)))) return rc;
+    const bool inst = !s->inst_recs.empty();
+    if ((rc = ensure_buf(s, s->d_spill, (size_t)(ph::trav_stack_cap(inst) - ph::TravShapes::spill_lds_depth(inst)) * total_threads * sizeof(uint2)))) return rc;
     return PBRT_HIP_OK;
 }
 
-// One traversal kernel shape (traverse_kernel's template arguments but ANYHIT and MIXED), launched for mode 0 closest hit, 1 any hit or 2 both queues in one launch (MIXED)
-template <bool COUNT, int LEAF_MIN, int REFILL_MIN, int LDS_DEPTH, int NODE_STEPS, bool INST, int ALPHA, int WPE, int ALPHA_MIN, bool QUADRIC = false>
+// One traversal kernel shape, launched for mode 0 closest hit, 1 any hit or 2 both queues in one launch (ph::TravMode)
+template <class Shape>
 static void launch_traverse_shape(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p) {
     const dim3 g(blocks), b(PH_TRAV_BLOCK);
-    if (mode == 2) hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, true, ALPHA, WPE, ALPHA_MIN, QUADRIC>), g, b, 0, s->stream, s->ds, p);
-    else if (mode == 1) hipLaunchKernelGGL((ph::traverse_kernel<true, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN, QUADRIC>), g, b, 0, s->stream, s->ds, p);
-    else hipLaunchKernelGGL((ph::traverse_kernel<false, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, false, ALPHA, WPE, ALPHA_MIN, QUADRIC>), g, b, 0, s->stream, s->ds, p);
+    if (mode == ph::TRAV_MIXED) hipLaunchKernelGGL((ph::traverse_kernel<Shape, ph::TRAV_MIXED>), g, b, 0, s->stream, s->ds, p);
+    else if (mode == ph::TRAV_ANY) hipLaunchKernelGGL((ph::traverse_kernel<Shape, ph::TRAV_ANY>), g, b, 0, s->stream, s->ds, p);
+    else hipLaunchKernelGGL((ph::traverse_kernel<Shape, ph::TRAV_CLOSEST>), g, b, 0, s->stream, s->ds, p);
+}
+// Row `shape` of the table (ph::pick_shape)
+template <class... S>
+static void dispatch_traverse_shape(ph::ShapeTable<S...>, int shape, PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p) {
+    static constexpr void (*launchers[])(PbrtHipScene*, int, uint32_t, const ph::TravParams&) = {&launch_traverse_shape<S>...};
+    launchers[shape](s, mode, blocks, p);
 }
 
-// p.spill / total_threads / error_flag / counts are filled here.  mode: as launch_traverse_shape's.  The shape follows the scene: alpha-mask textures (ALPHA 1 = the inlined test for
-// image-map masks, 2 = the general evaluator out of line, traverse.h), object instances (the TransformedPrimitive-aware kernels) and the counting builds.
+// p.spill / total_threads / error_flag / counts are filled here.  mode: as launch_traverse_shape's.  The shape follows the scene (traverse.h, pick_shape).
 void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p_in) {
     ph::TravParams p = p_in;
     p.spill = (uint2*)s->d_spill.p; p.total_threads = s->trav_blocks * PH_TRAV_BLOCK; p.error_flag = (uint32_t*)s->d_error.p;
@@ -319,47 +323,8 @@ void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph
     p.phase = (unsigned long long*)s->d_counts.p + 8;   // (the measurement build's phase tallies sit behind the eight counters)
 #endif
     p.batch = PH_BATCH;
-    const bool inst = !s->inst_recs.empty();
     const int alpha = !s->alpha_textures ? 0 : s->alpha_lean ? 1 : 2;
-    if (!s->quadrics.empty()) {
-        // Scenes with quadric shapes (traverse.h, QUADRIC; build_accel refuses them together with instances or alpha-mask textures): the flat kernel's loop shape with the analytic test
-        // out of line.  A kernel is allocated its callees' registers (quadric_test: 136, interval arithmetic + f64 atan2), so the compiler chooses the occupancy (WPE 0: 3 waves) — DESIGN §4.4 has the numbers.
-        if (s->count_traversal) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 0, 0, 0, true>(s, mode, blocks, p);
-        else launch_traverse_shape<false, 16, 32, 12, 6, false, 0, 0, 0, true>(s, mode, blocks, p);
-        return;
-    }
-    if (s->count_traversal) {   // (pbrt_hip_set_traversal_counting) the default loop shape with one node step per pass
-        if (alpha == 0) { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 0, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 0, 0, 0>(s, mode, blocks, p); }
-        else if (alpha == 1) { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 1, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 1, 0, 0>(s, mode, blocks, p); }
-        else { if (inst) launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, true, 2, 0, 0>(s, mode, blocks, p); else launch_traverse_shape<true, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 1, false, 2, 0, 0>(s, mode, blocks, p); }
-        return;
-    }
-    // Alpha masks, round 4: lanes whose candidate hit needs its alpha mask's verdict wait at their record until 12 of the wave's lanes do (traverse.h, ALPHA_MIN): configs[4]'s
-    // traversal 5 301 -> 4 520 ms per frame, same film (thresholds 4 / 8 / 12 / 20: 4 936 / 4 594 / 4 520 / 4 683 ms; same box, run r04n).
-    if (alpha == 2) {
-        if (inst) launch_traverse_shape<false, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 3, true, 2, 0, 12>(s, mode, blocks, p);
-        else launch_traverse_shape<false, PH_LEAF_MIN, PH_REFILL_MIN, PH_LDS_DEPTH, 3, false, 2, 0, 12>(s, mode, blocks, p);
-    } else if (alpha == 1) {
-        // (instanced: five waves per SIMD — 107 registers where the compiler is free, 20 spilled at 96, and still faster: configs[4]'s traversal 6.04 -> 5.66 s per frame, run r03aq;
-        // leaf threshold 16: with the mask lanes waiting apart, fewer lanes need to gather at leaves — 4 513 -> 4 466 ms; 32: 4 717; refill at 20: 4 627; 3 / 8 node steps per pass:
-        // 4 510 / 4 795, run r04q)
-        if (inst) launch_traverse_shape<false, 16, 12, 11, 5, true, 1, 5, 12>(s, mode, blocks, p);
-        else launch_traverse_shape<false, 24, 12, PH_LDS_DEPTH, 5, false, 1, 0, 12>(s, mode, blocks, p);
-    } else if (inst) {
-        // Round 3: 96 VGPRs without spills (102 where the compiler is free) and 31 KB of LDS (11 stack entries + 9 parked words per lane): FIVE blocks per CU.  1 000 x 10 k instances:
-        // 1 181 ms of traversal per frame against 1 293 for the 4-wave form of round 2 (108 VGPRs, 12 + 13 words of LDS), run r03ad; 1 115 with the deferred pops (traverse.h).  Seven
-        // more loop shapes around 24 / 12 / 5 (16-24 / 12-20 / 4-8) measured 1 308 - 1 387 ms against 1 295 at 4 waves (r03z), four at 5 waves 1 114 - 1 135 against 1 117 (r03aq).
-        // Round 4, with finished rays written out at the refill: refill at 20 / 28: 1 044 / 1 101 ms against 1 030; leaf 16: 1 041 (r04af).
-        launch_traverse_shape<false, 24, 12, 11, 5, true, 0, 5, 0>(s, mode, blocks, p);
-    } else {
-        // Flat scenes: 6 waves per SIMD with 12 stack entries in LDS (the kernel needs 59 VGPRs since the round-3 register diet and would fit 8 — but a seventh wave buys nothing and
-        // costs the stack an entry: same-box, configs[2] / configs[3] 689.5 / 717.0 ms of traversal per frame at 6 waves x 12 entries against 705.5 / 735.5 at 7 x 11; at 6 waves the
-        // depth is worth 12 -> 10 -> 8 -> 6 entries: 687 -> 692 -> 708 -> 759 ms, a 13th nothing), lanes wait for 16 companions at leaves, 6 node steps per pass (27 shapes swept at
-        // 7 waves, 6 more at 6; runs r03s - r03x, r03aw, r03ax).  Round 4: since finished rays are written out at the wave's refill (traverse.h), the refill threshold is worth more —
-        // HALF the wave idle before a refill: configs[2] 711.9 / 689.8 / 671.2 / 657.6 / 652.0 / 670.9 / 703.1 / 844.8 ms at 12 / 16 / 20 / 28 / 32 / 36 / 40 / 48 idle lanes (leaf
-        // threshold 12 / 16 / 20 and 5 / 6 / 8 node steps per pass within 3 ms of each other at 32; configs[3] 704.2 -> 679.2, configs[1] 29.8 -> 29.4; runs r04ac - r04ae).
-        launch_traverse_shape<false, 16, 32, 12, 6, false, 0, 6, 0>(s, mode, blocks, p);
-    }
+    dispatch_traverse_shape(ph::TravShapes{}, ph::pick_shape(!s->inst_recs.empty(), alpha, !s->quadrics.empty(), s->count_traversal), s, mode, blocks, p);
 }
 
 int launch_traverse(PbrtHipScene* s, bool anyhit, const void* d_rays, void* d_out, uint32_t n, float* kernel_ms) {

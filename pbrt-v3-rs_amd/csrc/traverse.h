@@ -18,48 +18,34 @@
 //
 // Execution shape: persistent waves pull rays from a global counter (one atomic per refill, wave-aggregated with
 // ballot/popcount), per-lane replacement of finished rays, while-while traversal, traversal stack in LDS
-// ([depth][lane] so every push/pop is conflict-free) spilling to a per-lane global region beyond PH_LDS_DEPTH.
+// ([depth][lane] so every push/pop is conflict-free) spilling to a per-lane global region beyond the shape's lds_depth.
 #pragma once
 #include "dmath.h"
 #include "scene_types.h"
 #include "quadric.h"
+
+constexpr int PH_TRAV_BLOCK = 256;  // threads per traversal block (texture.h checks it against the texture evaluator's LDS stack)
+constexpr int PH_MAX_STACK = 64;    // the reference's nodes_to_visit[64] (bvh/mod.rs:185)
+constexpr int PH_BATCH = 64;        // rays a wave claims per global atomic (TravParams::batch)
 
 namespace ph {
 
 struct alignas(16) RayIn { float ox, oy, oz, t_max, dx, dy, dz, time; };           // = PbrtHipRay
 struct alignas(16) HitOut { float t; uint32_t prim; float b0, b1, b2; uint32_t pad[3]; };  // = PbrtHipHit
 
-#ifndef PH_TRAV_BLOCK
-#define PH_TRAV_BLOCK 256
-#endif
-#ifndef PH_LDS_DEPTH
-#define PH_LDS_DEPTH 12
-#endif
-#define PH_MAX_STACK 64  // the reference's nodes_to_visit[64] (bvh/mod.rs:185)
-
 // Rays, queue order and results are touched once per launch: they are read / written with the non-temporal hint so that they do not displace tree nodes from the caches
-// (configs[2] / configs[3] traversal 705.4 -> 701.9 / 735.8 -> 732.4 ms per frame, same-box A/B gpurun r03al; -DPH_STREAM_NT=0 is the plain form).
-#ifndef PH_STREAM_NT
-#define PH_STREAM_NT 1
-#endif
-#if PH_STREAM_NT && defined(__HIP_DEVICE_COMPILE__)
+// (configs[2] / configs[3] traversal 705.4 -> 701.9 / 735.8 -> 732.4 ms per frame against plain loads and stores, same-box A/B, run r03al).
 typedef float ph_v4f __attribute__((ext_vector_type(4)));
 static __device__ __forceinline__ float4 ph_stream_load(const float4* p) { const ph_v4f v = __builtin_nontemporal_load(reinterpret_cast<const ph_v4f*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
 static __device__ __forceinline__ uint32_t ph_stream_load(const uint32_t* p) { return __builtin_nontemporal_load(p); }
 static __device__ __forceinline__ void ph_stream_store(float4 v, float4* p) { const ph_v4f w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<ph_v4f*>(p)); }
-#define PH_STREAM_LOAD(p) ph_stream_load(p)
-#define PH_STREAM_STORE(v, p) ph_stream_store(v, p)
-#else
-#define PH_STREAM_LOAD(p) (*(p))
-#define PH_STREAM_STORE(v, p) (*(p) = (v))
-#endif
 struct TravParams {
     const RayIn* rays;
     void* out;              // HitOut* (closest) or uint8_t* (any-hit)
     uint32_t n;             // ray count, or (n_ptr != nullptr) read from device memory: no host sync between wavefront stages
     const uint32_t* n_ptr;
     uint32_t* counter;      // work-queue head, zeroed before launch
-    uint2* spill;           // [PH_MAX_STACK - PH_LDS_DEPTH][total_threads]
+    uint2* spill;           // [trav_stack_cap(inst) - TravShapes::spill_lds_depth(inst)][total_threads]
     uint32_t total_threads;
     uint32_t* error_flag;   // set to 1 on stack overflow (the reference would panic on index 64)
     uint32_t batch;         // rays a wave claims per global atomic
@@ -141,7 +127,8 @@ PH_DEV float vmin3(float a, float b, float c) {
 #endif
 }
 
-// Bounds3::intersect_p_inv without its final `t_min < ray.t_max` clause; returns t_min via reference.
+// Bounds3::intersect_p_inv without its final `t_min < ray.t_max` clause; returns t_min via reference.  One box at a time: the scene's root and an instance's root bounds
+// (a node step tests its two boxes with node_boxes below).
 // Quirk B1 (z far plane not widened) is reproduced.  The reference interleaves four "miss" comparisons with four conditional updates of t_min / t_max
 // (bounds3.rs:299-323); here the three entry distances go through one v_max3_f32, the three exit distances through one v_min3_f32 and the verdict is
 // `t_min <= t_max`.  Same answer in every case:
@@ -173,9 +160,6 @@ PH_DEV bool box_test(const RayState& r, float xn, float xf, float yn, float yf, 
 // the registers the load filled; the near / far choice (dir_is_neg, bounds3.rs:296-298 indexes the bounds with it) is made on the two products afterwards — the same
 // operands meet in the same operations, so every product has the bits box_test's have —, the widening factor goes onto (far x, far y) as one more packed multiply.
 // 15 VALU instructions per box instead of 22.  The NaN test of the x slab is symmetric in (near, far) and widening keeps a NaN a NaN and a number a number, so it reads the raw pair.
-#ifndef PH_NODE_PK
-#define PH_NODE_PK 1
-#endif
 typedef float ph_v2f __attribute__((ext_vector_type(2)));
 // A per-lane condition as the wave's lane mask (the active lanes' bits) and back: conditions combined as masks cost scalar instructions, not vector ones.
 typedef unsigned long long ph_mask;
@@ -317,23 +301,12 @@ PH_DEV void tri_bary(const RayState& r, f3 p0, f3 p1, f3 p2, float& b0_out, floa
 // of every such node (the far one when it is popped), and nothing else.
 //
 // Loop shape (wave64): ONE loop, every lane advances its own ray by at most one interior-node step per iteration; lanes that
-// have reached a leaf wait until at least PH_LEAF_MIN lanes are at leaves (or no lane has node work left), then all of them
+// have reached a leaf wait until at least leaf_min lanes are at leaves (or no lane has node work left), then all of them
 // test ONE triangle each.  A nested "all lanes walk until everybody is at a leaf" (while-while) loop measured 15 % VALU lane
 // utilisation on incoherent rays at wave64 (profiles/r01_v1_*); this shape keeps the node code at >80 % and only runs the leaf
 // code when a quarter of the wave needs it.  Finished lanes are refilled from a wave-local batch of PH_BATCH consecutive rays
 // (one global atomic per batch, not per refill).
-#ifndef PH_LEAF_MIN
-#define PH_LEAF_MIN 20
-#endif
-#ifndef PH_REFILL_MIN
-#define PH_REFILL_MIN 12
-#endif
-#ifndef PH_BATCH
-#define PH_BATCH 64
-#endif
-#ifndef PH_LEAF_STEPS
-#define PH_LEAF_STEPS 1   // triangles a lane may test per leaf step (a leaf holds up to max_prims_in_node of them)
-#endif
+// (A lane tests one triangle per leaf step although a leaf holds up to max_prims_in_node of them: two per step measured slower three times, DESIGN §4.3 and HISTORY.)
 // INST = true adds object instancing (TransformedPrimitive): a leaf record may name an instance; the lane then carries its ray
 // into instance space, walks the object's aggregate above its current stack height and returns to the scene-level leaf where it
 // left it (same order of primitive tests as the reference's recursion).  Compiled separately so scenes without instances keep
@@ -359,13 +332,75 @@ static __device__ __forceinline__ bool alpha_accept_lean(const DeviceScene& sc, 
 // QUADRIC = true adds the reference's six quadric shapes (quadric.h): a leaf record with PH_TRI_QUADRIC names a QuadricRec, and the lane runs the analytic test out of line instead of the
 //   triangle test — one "primitive test" of the reference either way, same place in the leaf's order, same `r.t_max = t`.  RayState keeps no direction, so the lane reads its ray's
 //   from the queue again (the instancing kernel's lesson — that line has left the caches by then — is accepted here: no speed target for quadric scenes yet).  An accepted
-//   quadric is remembered like a triangle, by its record; the ray retires with zero barycentrics.  Instantiated only for scenes that hold a quadric (launch_traverse_kernel): with
+//   quadric is remembered like a triangle, by its record; the ray retires with zero barycentrics.  Instantiated only for scenes that hold a quadric (pick_shape): with
 //   QUADRIC = false every line below compiles to what it was.
 // WPE > 0 compiles the kernel for exactly that many waves per SIMD (= resident 256-thread blocks per CU): the register allocator then fits the budget
 // (7: 72 VGPRs, 8: 64) instead of taking what it likes; 0 leaves the choice to the compiler (same code as before).
-template <bool ANYHIT, bool COUNT = false, int LEAF_MIN = PH_LEAF_MIN, int REFILL_MIN = PH_REFILL_MIN, int LDS_DEPTH = PH_LDS_DEPTH, int NODE_STEPS = 1, bool INST = false, bool MIXED = false,
-          int ALPHA = 0, int WPE = 0, int ALPHA_MIN = 0, bool QUADRIC = false>
-__global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : 1, WPE ? WPE : 8))) void traverse_kernel(DeviceScene sc, TravParams p) {
+//
+// A kernel is traverse_kernel of (Shape, MODE): MODE is the ray kind(s) a launch serves, Shape one of the structs below (the upper-case names above are its members).
+enum TravMode : int { TRAV_CLOSEST = 0, TRAV_ANY = 1, TRAV_MIXED = 2 };   // (MIXED above = TRAV_MIXED, ANYHIT = TRAV_ANY)
+
+// What a shape does not state: the loop of the counting builds (one node step per pass, the compiler's choice of occupancy), which no timed run uses.
+struct ShapeDefaults {
+    static constexpr bool count = false, inst = false, quadric = false;
+    static constexpr int leaf_min = 20, refill_min = 12;   // lanes that must stand at leaves before a leaf step fires / idle before the wave refills
+    static constexpr int lds_depth = 12;                   // stack entries kept in LDS, the rest spills (ensure_traversal_workspace)
+    static constexpr int node_steps = 1;                   // interior-node steps per pass of the loop
+    static constexpr int alpha = 0, alpha_min = 0, wpe = 0;
+};
+// Flat scenes: 6 waves per SIMD with 12 stack entries in LDS (the kernel needs 59 VGPRs since the round-3 register diet and would fit 8 — but a seventh wave buys nothing and
+// costs the stack an entry: same-box, configs[2] / configs[3] 689.5 / 717.0 ms of traversal per frame at 6 waves x 12 entries against 705.5 / 735.5 at 7 x 11; at 6 waves the
+// depth is worth 12 -> 10 -> 8 -> 6 entries: 687 -> 692 -> 708 -> 759 ms, a 13th nothing), lanes wait for 16 companions at leaves, 6 node steps per pass (27 shapes swept at
+// 7 waves, 6 more at 6; runs r03s - r03x, r03aw, r03ax).  Round 4: since finished rays are written out at the wave's refill, the refill threshold is worth more —
+// HALF the wave idle before a refill: configs[2] 711.9 / 689.8 / 671.2 / 657.6 / 652.0 / 670.9 / 703.1 / 844.8 ms at 12 / 16 / 20 / 28 / 32 / 36 / 40 / 48 idle lanes (leaf
+// threshold 12 / 16 / 20 and 5 / 6 / 8 node steps per pass within 3 ms of each other at 32; configs[3] 704.2 -> 679.2, configs[1] 29.8 -> 29.4; runs r04ac - r04ae).
+struct ShapeFlat : ShapeDefaults { static constexpr int leaf_min = 16, refill_min = 32, node_steps = 6, wpe = 6; };
+// Instances, round 3: 96 VGPRs without spills (102 where the compiler is free) and 31 KB of LDS (11 stack entries + 9 parked words per lane): FIVE blocks per CU.  1 000 x 10 k instances:
+// 1 181 ms of traversal per frame against 1 293 for the 4-wave form of round 2 (108 VGPRs, 12 + 13 words of LDS), run r03ad; 1 115 with the deferred pops.  Seven
+// more loop shapes around 24 / 12 / 5 (16-24 / 12-20 / 4-8) measured 1 308 - 1 387 ms against 1 295 at 4 waves (r03z), four at 5 waves 1 114 - 1 135 against 1 117 (r03aq).
+// Round 4, with finished rays written out at the refill: refill at 20 / 28: 1 044 / 1 101 ms against 1 030; leaf 16: 1 041 (r04af).
+struct ShapeInst : ShapeDefaults { static constexpr bool inst = true; static constexpr int leaf_min = 24, lds_depth = 11, node_steps = 5, wpe = 5; };
+// Alpha masks, round 4: lanes whose candidate hit needs its alpha mask's verdict wait at their record until alpha_min = 12 of the wave's lanes do: configs[4]'s
+// traversal 5 301 -> 4 520 ms per frame, same film (thresholds 4 / 8 / 12 / 20: 4 936 / 4 594 / 4 520 / 4 683 ms; same box, run r04n).
+struct ShapeFlatAlphaLean : ShapeDefaults { static constexpr int leaf_min = 24, node_steps = 5, alpha = 1, alpha_min = 12; };
+// (instanced: five waves per SIMD — 107 registers where the compiler is free, 20 spilled at 96, and still faster: configs[4]'s traversal 6.04 -> 5.66 s per frame, run r03aq;
+// leaf threshold 16: with the mask lanes waiting apart, fewer lanes need to gather at leaves — 4 513 -> 4 466 ms; 32: 4 717; refill at 20: 4 627; 3 / 8 node steps per pass:
+// 4 510 / 4 795, run r04q)
+struct ShapeInstAlphaLean : ShapeDefaults { static constexpr bool inst = true; static constexpr int leaf_min = 16, lds_depth = 11, node_steps = 5, alpha = 1, alpha_min = 12, wpe = 5; };
+template <bool INST> struct ShapeAlphaGeneral : ShapeDefaults { static constexpr bool inst = INST; static constexpr int node_steps = 3, alpha = 2, alpha_min = 12; };
+// Quadric scenes: the flat kernel's loop shape with the analytic test out of line.  A kernel is allocated its callees' registers (quadric_test: 136, interval arithmetic + f64 atan2),
+// so the compiler chooses the occupancy (wpe 0: 3 waves) — DESIGN §4.4 has the numbers.
+struct ShapeQuadric : ShapeFlat { static constexpr bool quadric = true; static constexpr int wpe = 0; };
+// The counting builds (pbrt_hip_set_traversal_counting): the default loop with the scene's features.
+template <bool INST, int ALPHA, bool QUADRIC = false> struct ShapeCount : ShapeDefaults { static constexpr bool count = true, inst = INST, quadric = QUADRIC; static constexpr int alpha = ALPHA; };
+
+// Every shape that is compiled.  The host takes from here the kernel it launches AND the spill region it allocates for it.
+template <class... S> struct ShapeTable {
+    // the row with these features, -1 if there is none
+    static constexpr int find(bool inst, int alpha, bool quadric, bool count) { int i = 0, at = -1; ((at = (S::inst == inst && S::alpha == alpha && S::quadric == quadric && S::count == count) ? i : at, i++), ...); return at; }
+    // the shallowest LDS stack among the shapes a scene with / without instances can run, timed or counting: the spill region is sized for it
+    static constexpr int spill_lds_depth(bool inst) { int d = PH_MAX_STACK; ((d = (S::inst == inst && S::lds_depth < d) ? S::lds_depth : d), ...); return d; }
+};
+using TravShapes = ShapeTable<ShapeFlat, ShapeInst, ShapeFlatAlphaLean, ShapeInstAlphaLean, ShapeAlphaGeneral<false>, ShapeAlphaGeneral<true>, ShapeQuadric,
+                              ShapeCount<false, 0>, ShapeCount<true, 0>, ShapeCount<false, 1>, ShapeCount<true, 1>, ShapeCount<false, 2>, ShapeCount<true, 2>, ShapeCount<false, 0, true>>;
+// The scene's row of TravShapes.  alpha: 0 no alpha-mask textures, 1 image-map masks only (the inlined test), 2 any texture class (the general evaluator out of line).
+// A scene with quadrics has neither instances nor alpha-mask textures (build_accel refuses it otherwise).
+constexpr int pick_shape(bool inst, int alpha, bool quadric, bool count) { return quadric ? TravShapes::find(false, 0, true, count) : TravShapes::find(inst, alpha, false, count); }
+constexpr bool every_scene_has_a_shape() {
+    for (int k = 0; k < 24; k++) if (pick_shape(k & 1, (k >> 1) % 3, k >= 12, k % 12 >= 6) < 0) return false;
+    return true;
+}
+static_assert(every_scene_has_a_shape(), "a combination of scene features has no row in TravShapes");
+constexpr int trav_stack_cap(bool inst) { return inst ? 2 * PH_MAX_STACK : PH_MAX_STACK; }   // with instances the scene-level and object-level entries share one stack
+
+template <class Shape, int MODE>
+__global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(Shape::wpe ? Shape::wpe : 1, Shape::wpe ? Shape::wpe : 8))) void traverse_kernel(DeviceScene sc, TravParams p) {
+    constexpr bool ANYHIT = MODE == TRAV_ANY, MIXED = MODE == TRAV_MIXED, COUNT = Shape::count, INST = Shape::inst, QUADRIC = Shape::quadric;
+    constexpr int LEAF_MIN = Shape::leaf_min, REFILL_MIN = Shape::refill_min, LDS_DEPTH = Shape::lds_depth, NODE_STEPS = Shape::node_steps, ALPHA = Shape::alpha, ALPHA_MIN = Shape::alpha_min;
+    static_assert(MODE == TRAV_CLOSEST || MODE == TRAV_ANY || MODE == TRAV_MIXED, "no such mode");
+    static_assert(LDS_DEPTH >= TravShapes::spill_lds_depth(INST), "the spill region starts at the shallowest LDS stack of the table's rows: a shape outside the table would write past it");
+    static_assert(ALPHA_MIN == 0 || ALPHA != 0, "the alpha phase needs an alpha test");
+    static_assert(!QUADRIC || (!INST && ALPHA == 0), "build_accel refuses quadrics together with instances or alpha-mask textures: no such kernel");
     __shared__ uint2 lds_stack[LDS_DEPTH][PH_TRAV_BLOCK];
     // INST: the scene-level ray's origin and what ray_setup derived from it (six IEEE divides), parked while the lane walks an instance: leaving an instance is then nine LDS reads instead of
     // a reload of the ray and a second ray_setup.  The direction is not parked — the scene-level one stays in three registers of its own (re-reading it from the ray queue at every instance cost 4 %:
@@ -415,7 +450,7 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
     auto push = [&](uint32_t ref, float tmin) {
         uint2 e = make_uint2(ref, __float_as_uint(tmin));
         if (sp < LDS_DEPTH) lds_stack[sp][tid] = e;
-        else if (sp < (INST ? 2 * PH_MAX_STACK : PH_MAX_STACK)) p.spill[(size_t)(sp - LDS_DEPTH) * p.total_threads + gtid] = e;  // INST: scene + object entries share the stack
+        else if (sp < trav_stack_cap(INST)) p.spill[(size_t)(sp - LDS_DEPTH) * p.total_threads + gtid] = e;  // INST: scene + object entries share the stack
         else { *p.error_flag = 1u; return; }
         sp++;
     };
@@ -462,8 +497,8 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
                         hit_prim = __float_as_uint(a.w); hit_cls = (__float_as_uint(b.w) >> PH_TRI_CLASS_SHIFT) & PH_TRI_KEY_MASK;
                     } else { hit_prim = 0xFFFFFFFFu; hit_tri = 0u; hit_cls = 0u; hb0 = hb1 = hb2 = 0.0f; }
                 }
-                PH_STREAM_STORE(make_float4(r.t_max, __uint_as_float(hit_prim), hb0, hb1), hp);
-                PH_STREAM_STORE(make_float4(hb2, __uint_as_float(hit_tri), __uint_as_float(INST ? hit_inst : 0u), __uint_as_float(hit_cls)), hp + 1);  // pad[0] = the hit's TriRec, pad[1] = instance + 1, pad[2] = material class | material id << 3
+                ph_stream_store(make_float4(r.t_max, __uint_as_float(hit_prim), hb0, hb1), hp);
+                ph_stream_store(make_float4(hb2, __uint_as_float(hit_tri), __uint_as_float(INST ? hit_inst : 0u), __uint_as_float(hit_cls)), hp + 1);  // pad[0] = the hit's TriRec, pad[1] = instance + 1, pad[2] = material class | material id << 3
             }
             has_ray = false;
             if (COUNT) c_rays[(MIXED && ah) ? 1 : 0]++;
@@ -504,10 +539,10 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
                 if (avail) {
                     const uint32_t rank = (uint32_t)__popcll(idle & lane_lt);
                     if (!has_ray && rank < avail) {
-                        ray_index = p.order ? PH_STREAM_LOAD(p.order + batch_next + rank) : batch_next + rank;
+                        ray_index = p.order ? ph_stream_load(p.order + batch_next + rank) : batch_next + rank;
                         if (MIXED) ah = ray_index >= n_first;
                         const float4* rp = reinterpret_cast<const float4*>((MIXED && ah) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index);
-                        const float4 a = PH_STREAM_LOAD(rp), b = PH_STREAM_LOAD(rp + 1);
+                        const float4 a = ph_stream_load(rp), b = ph_stream_load(rp + 1);
                         RayIn in; in.ox = a.x; in.oy = a.y; in.oz = a.z; in.t_max = a.w; in.dx = b.x; in.dy = b.y; in.dz = b.z; in.time = b.w;
                         ray_setup(r, in);
                         has_ray = true; sp = 0; occluded = false; alpha_wait = false;
@@ -546,7 +581,6 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
             if (COUNT) c_nodes[(MIXED && ah) ? 1 : 0]++;
             // q0 = x0[0],x0[1],y0[0],y0[1]; q1 = z0[0],z0[1],x1[0],x1[1]; q2 = y1[0],y1[1],z1[0],z1[1]
             float t0, t1;
-#if PH_NODE_PK
             ph_mask m0, m1;
             node_boxes(r, q0, q1, q2, m0, t0, m1, t1);
             // bvh/mod.rs:206-214: dir_is_neg[axis] -> second child first
@@ -559,20 +593,6 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
             const uint32_t near_ref = neg_axis ? q3.y : q3.x, far_ref = neg_axis ? q3.x : q3.y;
             const bool near_hit = lane_of((m_neg & m1) | (~m_neg & m0)), far_hit = lane_of((m_neg & m0) | (~m_neg & m1));
             const float far_t = neg_axis ? t0 : t1;
-#else
-            bool h0, h1;
-            h0 = box_test(r, r.nx() ? q0.y : q0.x, r.nx() ? q0.x : q0.y, r.ny() ? q0.w : q0.z, r.ny() ? q0.z : q0.w,
-                               r.nz() ? q1.y : q1.x, r.nz() ? q1.x : q1.y, t0);
-            h1 = box_test(r, r.nx() ? q1.w : q1.z, r.nx() ? q1.z : q1.w, r.ny() ? q2.y : q2.x, r.ny() ? q2.x : q2.y,
-                               r.nz() ? q2.w : q2.z, r.nz() ? q2.z : q2.w, t1);
-            h0 = h0 & (t0 < r.t_max);
-            h1 = h1 & (t1 < r.t_max);
-            const int neg_axis = (int)((r.sgn >> q3.z) & 1u);
-            // bvh/mod.rs:206-214: dir_is_neg[axis] -> second child first
-            const uint32_t near_ref = neg_axis ? q3.y : q3.x, far_ref = neg_axis ? q3.x : q3.y;
-            const bool near_hit = neg_axis ? h1 : h0, far_hit = neg_axis ? h0 : h1;
-            const float far_t = neg_axis ? t0 : t1;
-#endif
             if (COUNT && ah) {
                 // any-hit rays stop early, so "nodes the reference visits" is counted as it goes: the near child always, the far child when
                 // it is popped — also when its box test fails, hence the NaN-keyed entry (pop() counts it and skips it)
@@ -597,10 +617,7 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(W
                 const bool fire_leaf = lm != 0ull && ((uint32_t)__popcll(lm) >= (uint32_t)LEAF_MIN || nm == 0ull || exhausted);  // queue drained: no throughput left to protect, only the tail's latency
                 const bool fire_alpha = am != 0ull && ((uint32_t)__popcll(am) >= (uint32_t)(ALPHA_MIN > 0 ? ALPHA_MIN : 1) || nm == 0ull || exhausted);
                 if (fire_leaf || fire_alpha) {
-#pragma unroll
-                    for (int ls = 0; ls < PH_LEAF_STEPS; ls++)
-                    // (the lane's state as it is NOW: with more than one triangle per step a lane may have left its leaf, or begun to wait, in the step before; the waiting lanes join the first only)
-                    if ((has_ray && cur < PH_NEED_POP && (cur & PH_LEAF_BIT) && !(ALPHA && ALPHA_MIN > 0 && alpha_wait) && (ls == 0 ? at_leaf : true) && fire_leaf) || (ls == 0 && waiting && fire_alpha)) {
+                    if ((at_leaf && fire_leaf) || (waiting && fire_alpha)) {
                         PHC_BEGIN(9);
                         const uint32_t ti = INST ? (cur & ~(PH_LEAF_BIT | PH_LEAF_INST_HINT)) : (cur & ~PH_LEAF_BIT);
                         const float4* tp = reinterpret_cast<const float4*>(sc.tris + ti);
