@@ -361,6 +361,23 @@ int pbrt_hip_render_path(PbrtHipScene*, int max_depth, float rr_threshold, int l
                          const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                          float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
 
+/* Integrator::render for WhittedIntegrator (core/src/integrator/sampler_integrator.rs:243-415 + integrators/src/whitted.rs:51-118, with
+ * SamplerIntegrator::specular_reflect / specular_transmit, sampler_integrator.rs:79-238).  Film, sampler, camera, tile enumeration, pixel_bounds and the
+ * output convention are pbrt_hip_render_path's.  li per camera ray: a miss adds every light's le (whitted.rs:57-61); a Material "none" surface is passed at the
+ * same depth (:63-66); a hit gets its differentials, bump map and BSDF with allow_multiple_lobes = false — smooth glass is SpecularReflection(Kr, dielectric)
+ * followed by SpecularTransmission(Kt), each where its colour is not black, instead of FresnelSpecular (glass.rs:112-129) —, adds its emission (:84) and, for
+ * every light in order, one sample `f * Li * |wi.ns| / pdf` behind one occlusion ray, sent only where the sample is valid, f is not black and the pdf is not
+ * zero (:88-104): no MIS, no light distribution, no Russian roulette.  If depth + 1 < max_depth the reflected and then the refracted ray are followed (:108-113),
+ * each with the ray differentials of sampler_integrator.rs:96-119 / :171-230 when its parent carries some, and `L += reflected + refracted`.
+ * Evaluated as the recursion it is: every level keeps its partial L and the factors its child's value is multiplied by.
+ * max_depth in [0, 16], INVALID_ARG beyond.  UNSUPPORTED, before any work: a render whose recursion COULD draw more sampler dimensions than the tables hold —
+ * 5 + V * 2 * n_lights + I * 4 must stay below 1000 (Halton, halton.rs:106-110) / 1024 (Sobol) and within the n32 / 52 dimensions given to pbrt_hip_set_sobol_tables,
+ * where, with d = max(max_depth, 1), the recursion tree has V = 2^d - 1 vertices of which I = 2^(d-1) - 1 lie above the last level if the scene's materials hold specular
+ * reflection AND specular transmission lobes, V = d and I = d - 1 with one of the two kinds, V = 1 and I = min(d - 1, 1) with neither; and a handle made by pbrt_hip_scene_create_multi (several devices render with pbrt_hip_render_path only).
+ * out_stats: camera_rays, regular_rays, shadow_rays and render_seconds are filled, the rest is zero. */
+int pbrt_hip_render_whitted(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                            float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
+
 /* Multi-GPU form: writes this rank's FilmTiles (contrib rgb + weight, 4 floats per tile pixel, tiles in
  * increasing index order, each tile's pixel bounds as Film::get_film_tile computes them) into a DEVICE buffer
  * the caller owns (e.g. a torch tensor) so the host can gather them with RCCL; then any rank calls

@@ -420,6 +420,7 @@ void pbrt_hip_scene_destroy(PbrtHipScene* s) {
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
     free_wavefront(s);
+    free_whitted(s);
     free_owned(s);
     free_tree_dev(s);
     for (DevBuf* b : {&s->d_ld_func, &s->d_ld_cdf, &s->d_counter, &s->d_spill, &s->d_error, &s->d_counts, &s->d_rays_tmp, &s->d_out_tmp})

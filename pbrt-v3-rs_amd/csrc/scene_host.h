@@ -101,6 +101,7 @@ struct PbrtHipScene : SceneHostState {
 
     // wavefront workspace (allocated lazily by the renderer, see wavefront.hip)
     struct Wavefront* wf = nullptr;
+    struct WhittedWorkspace* wh = nullptr;   // the Whitted driver's (whitted.hip)
 };
 
 namespace phost {
@@ -133,6 +134,14 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
                  PbrtHipStats* out_stats);
 int merge_tiles(PbrtHipScene* s, int tile_size, int parts, const void* const* d_bufs, float* out_xyz, float* out_weight);
 DevBuf& tile_buffer_of(PbrtHipScene* s);  // the handle's own tile buffer (wavefront workspace)
+int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight);   // the handle's tile buffer -> film, the other parts taken as empty
+// The sample side of a frame for a second integrator (whitted.hip): the rank's pixel list (tile by tile, row-major) and the records [sample][pixel] it fills —
+// rec_L = {L.rgb, p_film.x} (NaN p_film.x: no sample taken), rec_py = p_film.y, px_rounded[pixel] = 1 where a film position rounded up onto the next pixel's coordinate
+struct SampleRecords { uint32_t n_px; const int2* px_xy; float4* rec_L; float* rec_py; uint8_t* px_rounded; };
+int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out);
+int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer);
+// whitted.hip
+void free_whitted(PbrtHipScene* s);
 // ORs the voxels whose light distribution the context's last spatial render filled into `touched` (one byte per voxel, sized on first use); *count = voxels set so far
 int spatial_voxels_touched(PbrtHipScene* s, std::vector<uint8_t>& touched, uint64_t* count);
 // multi.hip

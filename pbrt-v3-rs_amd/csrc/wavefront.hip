@@ -24,6 +24,7 @@
 #include "raysort.h"
 #include "phase_clock.h"
 #include "matsort.h"
+#include "wf_device.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -78,34 +79,6 @@ struct WfParams {
     const uint32_t* m_order; const uint32_t* m_bins;
     unsigned long long* phase;   // PH_PHASE_CLOCK builds: the shade kernel's phase tallies (phase_clock.h)
 };
-
-PH_DEV uint32_t wave_alloc(uint32_t* ctr, bool want) {
-    const uint64_t m = __ballot(want);
-    if (m == 0ull) return 0u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const int leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(ctr, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    return base + (uint32_t)__popcll(m & lt);
-}
-
-PH_DEV SamplerCursor cursor_for(const DeviceScene& sc, const SamplerRec& sp, int px, int py, uint32_t s, uint32_t dim, const HaltonLds* lds = nullptr) {
-    SamplerCursor c; c.px = px; c.py = py; c.dim = dim; c.lds = lds;
-    if (sp.kind == 0) c.index = (uint64_t)halton_pixel_offset(sp, px, py) + (uint64_t)s * sp.sample_stride;  // halton.rs:143
-    else c.index = sobol_interval_to_index(sc, (uint32_t)sp.log2_resolution, s, px - sp.bounds[0], py - sp.bounds[1]);
-    return c;
-}
-PH_DEV void store_ray(RayIn* dst, const RayIn& r) {
-    float4* p = reinterpret_cast<float4*>(dst);
-    p[0] = make_float4(r.ox, r.oy, r.oz, r.t_max); p[1] = make_float4(r.dx, r.dy, r.dz, r.time);
-}
-PH_DEV RayIn load_ray(const RayIn* src) {
-    const float4* p = reinterpret_cast<const float4*>(src);
-    float4 a = p[0], b = p[1];
-    RayIn r; r.ox = a.x; r.oy = a.y; r.oz = a.z; r.t_max = a.w; r.dx = b.x; r.dy = b.y; r.dz = b.z; r.time = b.w; return r;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // K1: one thread per (pixel, sample) of the chunk
@@ -1311,6 +1284,61 @@ DevBuf& tile_buffer_of(PbrtHipScene* s) {
     return s->wf->d_tilebuf;
 }
 
+
+// Film::merge_film_tile for a handle that rendered one part of the tiles into its own tile buffer
+int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight) {
+    int rc;
+    // a single rank holds only its own tiles: the other parts contribute nothing (zero buffers are not needed: merge
+    // addresses only tiles t with t % parts == part when every other part's pointer aliases an all-zero slot)
+    if (tile_parts == 1) {
+        const void* bufs[1] = {s->wf->d_tilebuf.p};
+        return merge_tiles(s, tile_size, 1, bufs, out_xyz, out_weight);
+    }
+    // partial frame: merge this part against zeroed stand-ins for the missing ones
+    std::vector<DevBuf> zeros((size_t)tile_parts);
+    std::vector<const void*> bufs((size_t)tile_parts);
+    for (int i = 0; i < tile_parts; i++) {
+        if (i == tile_part) { bufs[i] = s->wf->d_tilebuf.p; continue; }
+        const size_t fl = tile_buffer_floats_for(s, tile_size, i, tile_parts);
+        if (hipMalloc(&zeros[i].p, fl * 4) != hipSuccess) { for (auto& z : zeros) if (z.p) (void)hipFree(z.p); return set_err(s, PBRT_HIP_ERR_OOM, "render: out of device memory"); }
+        (void)hipMemset(zeros[i].p, 0, fl * 4);
+        bufs[i] = zeros[i].p;
+    }
+    // setup_tiles(part) was used for rendering; merge needs the frame-wide tile grid only (sb/ntx/nty/slots are part-independent)
+    rc = merge_tiles(s, tile_size, tile_parts, bufs.data(), out_xyz, out_weight);
+    for (auto& z : zeros) if (z.p) (void)hipFree(z.p);
+    return rc;
+}
+
+// The sample side of a frame for an integrator that brings its own rounds (whitted.hip): the rank's tile and pixel lists and the per-sample records
+// {L.rgb, p_film.x} {p_film.y} the film pass reads ...
+int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out) {
+    int rc;
+    if ((rc = setup_tiles(s, tile_size, part, parts))) return rc;
+    Wavefront& w = *s->wf;
+    const size_t n_px = w.px_xy.size(), spp = s->sampler.spp;
+    out->n_px = (uint32_t)n_px; out->px_xy = (const int2*)w.d_px.p;
+    if (n_px == 0) return PBRT_HIP_OK;
+    if ((uint64_t)n_px * spp >= (1ull << 40)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: too many samples");
+    if ((rc = ensure_buf(s, w.d_recL, n_px * spp * 16))) return rc;
+    if ((rc = ensure_buf(s, w.d_recpy, n_px * spp * 4))) return rc;
+    if ((rc = ensure_buf(s, w.d_rounded, n_px))) return rc;
+    PH_CHECK(s, hipMemsetAsync(w.d_rounded.p, 0, n_px, s->stream));
+    out->rec_L = (float4*)w.d_recL.p; out->rec_py = (float*)w.d_recpy.p; out->px_rounded = (uint8_t*)w.d_rounded.p;
+    return PBRT_HIP_OK;
+}
+// ... and that pass: FilmTile::add_sample over the records, into d_tile_buffer
+int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer) {
+    Wavefront& w = *s->wf;
+    ph::FilmParams fp{};
+    fp.film = s->film; fp.tiles = (const ph::TileInfo*)w.d_tiles.p; fp.n_tiles = (uint32_t)w.tiles.size();
+    fp.slot_w = w.slot_w; fp.slot_h = w.slot_h; fp.spp = s->sampler.spp; fp.n_px = r.n_px; fp.rec_L = r.rec_L; fp.rec_py = r.rec_py; fp.px_rounded = r.px_rounded; fp.tile_buf = (float4*)d_tile_buffer;
+    const uint64_t film_threads = (uint64_t)fp.n_tiles * w.slot_w * w.slot_h;
+    hipLaunchKernelGGL(ph::film_tiles_kernel, dim3((uint32_t)((film_threads + 255) / 256)), dim3(256), 0, s->stream, fp);
+    PH_CHECK(s, hipGetLastError());
+    return PBRT_HIP_OK;
+}
+
 }  // namespace phost
 
 using namespace phost;
@@ -1358,26 +1386,7 @@ int pbrt_hip_render_path(PbrtHipScene* s, int max_depth, float rr_threshold, int
     const size_t floats = tile_buffer_floats_for(s, tile_size, tile_part, tile_parts);
     if ((rc = ensure_buf(s, s->wf->d_tilebuf, floats * 4))) return rc;
     if ((rc = render_tiles(s, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts, s->wf->d_tilebuf.p, out_stats))) return rc;
-    // a single rank holds only its own tiles: the other parts contribute nothing (zero buffers are not needed: merge
-    // addresses only tiles t with t % parts == part when every other part's pointer aliases an all-zero slot)
-    if (tile_parts == 1) {
-        const void* bufs[1] = {s->wf->d_tilebuf.p};
-        return merge_tiles(s, tile_size, 1, bufs, out_xyz, out_weight);
-    }
-    // partial frame: merge this part against zeroed stand-ins for the missing ones
-    std::vector<DevBuf> zeros((size_t)tile_parts);
-    std::vector<const void*> bufs((size_t)tile_parts);
-    for (int i = 0; i < tile_parts; i++) {
-        if (i == tile_part) { bufs[i] = s->wf->d_tilebuf.p; continue; }
-        const size_t fl = tile_buffer_floats_for(s, tile_size, i, tile_parts);
-        if (hipMalloc(&zeros[i].p, fl * 4) != hipSuccess) { for (auto& z : zeros) if (z.p) (void)hipFree(z.p); return set_err(s, PBRT_HIP_ERR_OOM, "render: out of device memory"); }
-        (void)hipMemset(zeros[i].p, 0, fl * 4);
-        bufs[i] = zeros[i].p;
-    }
-    // setup_tiles(part) was used for rendering; merge needs the frame-wide tile grid only (sb/ntx/nty/slots are part-independent)
-    rc = merge_tiles(s, tile_size, tile_parts, bufs.data(), out_xyz, out_weight);
-    for (auto& z : zeros) if (z.p) (void)hipFree(z.p);
-    return rc;
+    return merge_own_tiles(s, tile_size, tile_part, tile_parts, out_xyz, out_weight);
     });
 }
 

@@ -65,6 +65,7 @@ Api::Api(int device) : check_only_(device < 0), ctm_(identity_xform()), camera_t
 }
 Api::Api(const std::vector<int>& devices) : check_only_(false), ctm_(identity_xform()), camera_to_world_(identity_xform()) {
     scene_ = pbrt_hip_scene_create_multi(devices.empty() ? nullptr : devices.data(), (int)devices.size());
+    if (scene_) n_devices_ = pbrt_hip_scene_devices(scene_, nullptr, 0);
     if (!scene_) {
         const char* e = pbrt_hip_last_error(nullptr);
         error = std::string("no usable gfx950 device: ") + (e ? e : "");
@@ -874,8 +875,10 @@ int Api::pbrt_world_end(RenderReport& rep) {
     if (!check(brc, "build_accel")) return PBRT_HIP_ERR_DEVICE;
     rep.build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 
-    // ---- integrator (path.rs:287-327)
-    if (integrator_name_ != "path") { error = "Integrator \"" + integrator_name_ + "\" is outside the hot-path scope (supported: path)"; return PBRT_HIP_ERR_UNSUPPORTED; }
+    // ---- integrator (path.rs:287-327, whitted.rs:121-150: "maxdepth" 5 and "pixelbounds", read the same way)
+    const bool whitted = integrator_name_ == "whitted";
+    if (integrator_name_ != "path" && !whitted) { error = "Integrator \"" + integrator_name_ + "\" is outside the hot-path scope (supported: path, whitted)"; return PBRT_HIP_ERR_UNSUPPORTED; }
+    if (whitted && n_devices_ > 1) { error = "Integrator \"whitted\" renders on one device (--devices with more than one GPU: path only)"; return PBRT_HIP_ERR_UNSUPPORTED; }
     const int max_depth = integrator_p_.find_one_int("maxdepth", 5);
     int pb[4] = {sb[0], sb[1], sb[2], sb[3]};
     if (const std::vector<int>* v = integrator_p_.find_ints("pixelbounds")) {
@@ -894,12 +897,14 @@ int Api::pbrt_world_end(RenderReport& rep) {
 
     rep.xres = xres; rep.yres = yres; std::memcpy(rep.crop, cb, sizeof cb);
     rep.n_triangles = n_tris_; rep.n_lights = n_lights_; rep.n_instances = n_instances_; rep.warnings = warnings;
+    rep.integrator = integrator_name_;
     rep.spp = spp; rep.max_depth = max_depth; rep.light_strategy = strategy; std::memcpy(rep.pixel_bounds, pb, sizeof pb);
     if (check_only_) { rep.out_file = filename; return PBRT_HIP_OK; }
     const size_t npix = (size_t)std::max(0, cb[2] - cb[0]) * (size_t)std::max(0, cb[3] - cb[1]);
     std::vector<float> xyz(npix * 3), wt(npix), rgb(npix * 3);
-    int rc = pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
-    if (!check(rc, "render_path")) return rc;
+    int rc = whitted ? pbrt_hip_render_whitted(scene_, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
+                     : pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
+    if (!check(rc, whitted ? "render_whitted" : "render_path")) return rc;
     if (!check(pbrt_hip_film_to_rgb(scene_, xyz.data(), wt.data(), rgb.data()), "film_to_rgb")) return PBRT_HIP_ERR_DEVICE;
     std::string err;
     if (!write_image(filename, rgb.data(), cb[2] - cb[0], cb[3] - cb[1], err)) { error = err; return PBRT_HIP_ERR_INVALID_ARG; }

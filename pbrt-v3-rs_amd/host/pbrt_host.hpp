@@ -53,6 +53,7 @@ struct RenderReport {
     std::string out_file;
     double build_seconds = 0, load_seconds = 0;
     uint64_t n_triangles = 0, n_lights = 0, n_instances = 0;  // n_triangles counts instanced triangles once per instance
+    std::string integrator;  // "path" or "whitted"
     int spp = 0, max_depth = 0, light_strategy = 0, pixel_bounds[4] = {0, 0, 0, 0};
     std::vector<std::string> warnings;
 };
@@ -132,6 +133,7 @@ class Api {
     std::map<std::string, uint64_t> object_tris_;
     std::string current_object_;                // "" outside ObjectBegin/ObjectEnd
     uint64_t n_instances_ = 0;
+    int n_devices_ = 1;   // GPUs behind scene_ (--devices)
     bool verify_options(const char* func);
     bool verify_world(const char* func);
     void concat(const Xform& t);

@@ -103,6 +103,7 @@ class Binding:
             "intersect_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, fp]),
             "occluded_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, fp]),
             "tile_buffer_floats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+            "render_whitted": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
             "render_path_tiles_device": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Stats)]),
             "merge_tiles_device": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), fp, fp]),
             "add_material_none": (C.c_int, [vp, u32p]),
@@ -727,6 +728,15 @@ class Scene:
         st = Stats()
         self._chk(self.b.fn("render_path")(self.h, max_depth, C.c_float(rr_threshold), light_strategy, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts,
                                            _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
+        return xyz, wt, st
+
+    def render_whitted(self, max_depth=5, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1):
+        """WhittedIntegrator (pbrt_hip_render_whitted): the same film, tiles and return value as render_path."""
+        h, w = self._film_hw()
+        xyz = np.zeros((h, w, 3), np.float32); wt = np.zeros((h, w), np.float32)
+        pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
+        st = Stats()
+        self._chk(self.b.fn("render_whitted")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
         return xyz, wt, st
 
     def film_to_rgb(self, xyz, weight):
