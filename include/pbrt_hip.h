@@ -167,7 +167,7 @@ int pbrt_hip_add_instance(PbrtHipScene*, uint32_t object_id, const float instanc
  *   pbrt_hip_add_quadric      kind 0 Cylinder::new (cylinder.rs:21-42; a, b = zmin, zmax), 1 Cone::new (cone.rs:21-40; a = height), 2 Paraboloid::new (paraboloid.rs:21-42;
  *                             a, b = zmin, zmax), 3 Disk::new (disk.rs:21-40; a = height, b = innerradius)
  * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: a quadric between object_begin and object_end; a quadric right after pbrt_hip_add_light_diffuse_area lights that no mesh
- * has claimed (it would be the area light's shape: Shape::sample of the quadrics is not provided); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a
+ * has claimed (it would be the area light's shape; a sphere light is made by pbrt_hip_add_sphere_light, the other quadrics' Shape::sample is not provided); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a
  * quadric.  pbrt_hip_build_accel refuses a scene that holds quadrics together with object instances or alpha-mask textures; pbrt_hip_build_accel_device refuses any scene
  * with a quadric (the host builders make its tree). */
 int pbrt_hip_add_sphere(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
@@ -176,6 +176,18 @@ int pbrt_hip_add_hyperboloid(PbrtHipScene*, const float o2w_m[16], const float o
                              uint32_t material_id, uint32_t flags);
 int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const float o2w_minv[16], float radius, float a, float b, float phi_max_deg,
                          uint32_t material_id, uint32_t flags);
+
+/* A sphere that is the shape of a DiffuseAreaLight (Shape "sphere" under AreaLightSource "diffuse": api/src/lib.rs:783-812 makes the shape, then the light of lights/src/diffuse.rs:46-82
+ * around it): pbrt_hip_add_sphere with the same arguments, plus one light that joins the scene's lights in call order.  The light's area is Sphere::area — phi_max * radius *
+ * (z_max - z_min) of the constructor's clamped values — so a partial sphere emits and is sampled as the reference does it: Sphere::sample_solid_angle (shapes/src/sphere.rs:344-410)
+ * draws from the cone the FULL sphere subtends, or from the full sphere's area where the reference point lies inside it, and DiffuseAreaLight::sample_li (diffuse.rs:114-129) takes the point
+ * as it comes.  A ray that meets the sphere sees L on the side its normal faces (reverse orientation and the transform's handedness included), on both sides if two_sided (diffuse.rs:220-226).
+ * pbrt_hip_render_whitted renders such a scene; pbrt_hip_render_path and pbrt_hip_render_path_tiles_device return PBRT_HIP_ERR_UNSUPPORTED before any work (message: "sphere light"), because
+ * PathIntegrator::li also needs Sphere::pdf_solid_angle for its MIS weight; the handle stays usable.  The batch intersection entry points treat the sphere as ordinary geometry.
+ * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: between object_begin and object_end, as for any quadric; while pbrt_hip_add_light_diffuse_area lights that no mesh has claimed are pending.
+ * The other five quadrics cannot be lights, and the pbrt_hip_render front end does not read Shape "sphere". */
+int pbrt_hip_add_sphere_light(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
+                              uint32_t material_id, uint32_t flags, const float L_rgb[3], int two_sided);
 
 /* Alpha masks: the float textures behind a mesh's `alpha` / `shadowalpha` parameters (TriangleMesh::alpha_mask, shadow_alpha_mask: shapes/src/triangle.rs:291-312),
  * for the mesh added last; 0xFFFFFFFF keeps the constant given to add_mesh.  A candidate hit is rejected where the texture evaluates to exactly 0 at the hit's
@@ -367,7 +379,8 @@ int pbrt_hip_render_path(PbrtHipScene*, int max_depth, float rr_threshold, int l
  * same depth (:63-66); a hit gets its differentials, bump map and BSDF with allow_multiple_lobes = false — smooth glass is SpecularReflection(Kr, dielectric)
  * followed by SpecularTransmission(Kt), each where its colour is not black, instead of FresnelSpecular (glass.rs:112-129) —, adds its emission (:84) and, for
  * every light in order, one sample `f * Li * |wi.ns| / pdf` behind one occlusion ray, sent only where the sample is valid, f is not black and the pdf is not
- * zero (:88-104): no MIS, no light distribution, no Russian roulette.  If depth + 1 < max_depth the reflected and then the refracted ray are followed (:108-113),
+ * zero (:88-104): no MIS, no light distribution, no Russian roulette.  A light made by pbrt_hip_add_sphere_light is sampled by Sphere::sample_solid_angle (shapes/src/sphere.rs:344-410)
+ * and seen by the rays that meet its sphere; this is the only integrator that renders such a scene.  If depth + 1 < max_depth the reflected and then the refracted ray are followed (:108-113),
  * each with the ray differentials of sampler_integrator.rs:96-119 / :171-230 when its parent carries some, and `L += reflected + refracted`.
  * Evaluated as the recursion it is: every level keeps its partial L and the factors its child's value is multiplied by.
  * max_depth in [0, 16], INVALID_ARG beyond.  UNSUPPORTED, before any work: a render whose recursion COULD draw more sampler dimensions than the tables hold —

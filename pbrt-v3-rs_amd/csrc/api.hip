@@ -1024,6 +1024,26 @@ int pbrt_hip_add_sphere(PbrtHipScene* s, const float o2w_m[16], const float o2w_
     return add_quadric_common(s, "add_sphere", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
     });
 }
+// pbrt_hip_add_sphere plus the DiffuseAreaLight whose shape is that sphere (lights/src/diffuse.rs:46-82): one LightRec in call order, bound to the sphere's primitive slot
+int pbrt_hip_add_sphere_light(PbrtHipScene* s, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg, uint32_t material_id, uint32_t flags,
+                              const float L_rgb[3], int two_sided) {
+    return ph_guard(s, "pbrt_hip_add_sphere_light", [&]() -> int {
+    if (!s || !o2w_m || !o2w_minv || !L_rgb) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_sphere_light: null argument");
+    if (!s->lights.empty() && s->lights.back().type == PH_L_AREA && s->lights.back().prim == 0xFFFFFFFFu)
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_sphere_light: the diffuse area lights created last have no mesh yet; attach them first (the sphere brings its own light)");
+    QuadricRec q{}; float lo[3], hi[3];
+    sphere_rec(radius, z_min, z_max, phi_max_deg, q, lo, hi);
+    const int rc = add_quadric_common(s, "add_sphere_light", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
+    if (rc) return rc;
+    LightRec l{}; l.type = PH_L_AREA; l.two_sided = two_sided ? 1 : 0; l.prim = s->meshes.back().tri_base;
+    l.area = q.phi_max * q.radius * (q.z_max - q.z_min);   // Sphere::area (sphere.rs), of the constructor's clamped values
+    for (int c = 0; c < 3; c++) l.L[c] = L_rgb[c];
+    s->meshes.back().first_light = (int32_t)s->lights.size();
+    s->lights.push_back(l);
+    s->sphere_lights++;
+    return PBRT_HIP_OK;
+    });
+}
 int pbrt_hip_add_hyperboloid(PbrtHipScene* s, const float o2w_m[16], const float o2w_minv[16], const float p1[3], const float p2[3], float phi_max_deg, uint32_t material_id, uint32_t flags) {
     return ph_guard(s, "pbrt_hip_add_hyperboloid", [&]() -> int {
     if (!s || !o2w_m || !o2w_minv || !p1 || !p2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_hyperboloid: null argument");

@@ -48,6 +48,7 @@ struct SceneHostState {
     bool general_materials = false;  // some material is not matte: the renderer uses the general BSDF kernel
     bool simple_textures = false;    // every texture program is made of constants, image maps (uv mapping), scale and mix: the texture pass runs its lean instantiation (set at upload)
     std::vector<LightRec> lights;
+    uint32_t sphere_lights = 0;      // lights whose shape is a sphere (add_sphere_light): the Whitted driver samples them, the path integrator refuses the scene
     // DiffuseAreaLights of shapes inside an object definition ("Area lights not supported with object instancing", api/src/lib.rs:877-881): the primitives keep their emission,
     // Scene::lights never sees them.  MeshRec::first_light = -2 - index on the host; uploaded behind the scene's lights (DeviceScene::n_lights does not count them).
     std::vector<LightRec> emission_only;

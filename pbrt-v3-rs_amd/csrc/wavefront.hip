@@ -892,6 +892,13 @@ int check_render_args(PbrtHipScene* s, int max_depth, int light_strategy, const 
     return PBRT_HIP_OK;
 }
 
+// PathIntegrator::li weights a light sample against Light::pdf_li, i.e. Shape::pdf_solid_angle of the light's shape (shape.rs:86-107).  For a sphere that is Sphere::pdf_solid_angle,
+// which nothing here can be checked against bit for bit, so a scene with a sphere light renders under the Whitted integrator only.  Before any work.
+static int refuse_sphere_lights(PbrtHipScene* s) {
+    if (s->sphere_lights == 0) return PBRT_HIP_OK;
+    return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: the scene holds a sphere light (pbrt_hip_add_sphere_light), which the path integrator does not sample; render it with pbrt_hip_render_whitted");
+}
+
 // SpatialLightDistribution::new (spatial.rs:57-88): voxel resolution from the scene bounds, tables reset for this render
 // (the reference builds the distribution in Integrator::preprocess and fills it lazily while rendering, so the cost of the
 // voxel distributions is inside the timed render here too).
@@ -1360,6 +1367,7 @@ int pbrt_hip_render_path_tiles_device(PbrtHipScene* s, int max_depth, float rr_t
     return ph_guard(s, "pbrt_hip_render_path_tiles_device", [&]() -> int {
     int rc = check_render_args(s, max_depth, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts);
     if (rc) return rc;
+    if ((rc = refuse_sphere_lights(s))) return rc;
     if (!d_tile_buffer) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render: null tile buffer");
     return render_tiles(s, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts, d_tile_buffer, out_stats);
     });
@@ -1380,6 +1388,7 @@ int pbrt_hip_render_path(PbrtHipScene* s, int max_depth, float rr_threshold, int
     return ph_guard(s, "pbrt_hip_render_path", [&]() -> int {
     int rc = check_render_args(s, max_depth, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts);
     if (rc) return rc;
+    if ((rc = refuse_sphere_lights(s))) return rc;
     if (!out_xyz || !out_weight) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render: null output");
     if (s->multi) return render_path_multi(s, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
     if (!s->wf) s->wf = new Wavefront();

@@ -119,6 +119,7 @@ class Binding:
             "object_end": (C.c_int, [vp]),
             "add_instance": (C.c_int, [vp, C.c_uint32, fp, fp]),
             "add_sphere": (C.c_int, [vp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
+            "add_sphere_light": (C.c_int, [vp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, fp, C.c_int]),
             "add_hyperboloid": (C.c_int, [vp, fp, fp, fp, fp, C.c_float, C.c_uint32, C.c_uint32]),
             "add_quadric": (C.c_int, [vp, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
             "add_mipmap": (C.c_int, [vp, C.c_int, C.c_int, fp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, u32p]),
@@ -422,6 +423,14 @@ class Scene:
         z_max = radius if z_max is None else z_max
         self._chk(self.b.fn("add_sphere")(self.h, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(z_min),
                                           C.c_float(z_max), C.c_float(phi_max), material, 1 if reverse_orientation else 0))
+
+    def add_sphere_light(self, object_to_world, world_to_object, radius=1.0, z_min=None, z_max=None, phi_max=360.0, material=0, reverse_orientation=False, L=(1, 1, 1),
+                         two_sided=False):
+        """add_sphere plus the DiffuseAreaLight whose shape is that sphere (radiance L): the light joins the scene's lights in call order.  Rendered by render_whitted only."""
+        z_min = -radius if z_min is None else z_min
+        z_max = radius if z_max is None else z_max
+        self._chk(self.b.fn("add_sphere_light")(self.h, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(z_min),
+                                                C.c_float(z_max), C.c_float(phi_max), material, 1 if reverse_orientation else 0, _ptr(_f32(L), C.c_float), 1 if two_sided else 0))
 
     def add_hyperboloid(self, object_to_world, world_to_object, p1, p2, phi_max=360.0, material=0, reverse_orientation=False):
         self._chk(self.b.fn("add_hyperboloid")(self.h, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), _ptr(_f32(p1), C.c_float),
