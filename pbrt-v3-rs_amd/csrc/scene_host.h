@@ -136,13 +136,16 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
 int merge_tiles(PbrtHipScene* s, int tile_size, int parts, const void* const* d_bufs, float* out_xyz, float* out_weight);
 DevBuf& tile_buffer_of(PbrtHipScene* s);  // the handle's own tile buffer (wavefront workspace)
 int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight);   // the handle's tile buffer -> film, the other parts taken as empty
-// The sample side of a frame for a second integrator (whitted.hip): the rank's pixel list (tile by tile, row-major) and the records [sample][pixel] it fills —
+// The sample side of a frame, shared by the integrators: the rank's pixel list (tile by tile, row-major) and the records [sample][pixel] an integrator fills —
 // rec_L = {L.rgb, p_film.x} (NaN p_film.x: no sample taken), rec_py = p_film.y, px_rounded[pixel] = 1 where a film position rounded up onto the next pixel's coordinate
 struct SampleRecords { uint32_t n_px; const int2* px_xy; float4* rec_L; float* rec_py; uint8_t* px_rounded; };
-int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out);
-int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer);
+int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out);   // tile and pixel lists; n_px == 0: nothing to render
+int samples_alloc(PbrtHipScene* s, SampleRecords* out);                                        // the records, px_rounded cleared
+int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer);            // the film pass over them
+size_t path_chunk_bytes_per_path(bool general_materials, bool textured_materials);   // what the path driver's chunk table (chunk_plan.h) sums to, for scripts/chunk_plan_check.cpp
 // whitted.hip
 void free_whitted(PbrtHipScene* s);
+size_t whitted_chunk_bytes_per_sample(uint32_t n_frames);   // ... and the Whitted driver's
 // ORs the voxels whose light distribution the context's last spatial render filled into `touched` (one byte per voxel, sized on first use); *count = voxels set so far
 int spatial_voxels_touched(PbrtHipScene* s, std::vector<uint8_t>& touched, uint64_t* count);
 // multi.hip

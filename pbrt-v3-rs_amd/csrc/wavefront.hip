@@ -25,6 +25,7 @@
 #include "phase_clock.h"
 #include "matsort.h"
 #include "wf_device.h"
+#include "chunk_plan.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -793,6 +794,21 @@ struct Wavefront {
     DevBuf d_morder, d_mkeys, d_mbins;  // shade-side work queues (matsort.h)
     size_t n_vox = 0;   // voxels of the last spatial render's table (d_vox_slot)
     std::vector<hipEvent_t> events;
+    // The buffers that grow with the chunk, with their bytes per path (chunk_plan.h): 463 B, 591 B with a texture pass.  Two closest-hit ray queues of 2B rays, one hit queue of 2B,
+    // the path state read from one half and written to the other (WfParams).  The shade-side queues count in the estimate of every scene, as they always have, though a scene of
+    // constant matte never allocates them: 6 B in 463 do not move the chunk size of such a scene off the one it was measured with.
+    phost::ChunkTable chunk_table(bool textured, bool mat_queues) {
+        const size_t ray = sizeof(ph::RayIn), hit = sizeof(ph::HitOut);
+        return {{&d_rays_cl[0], 2 * ray}, {&d_rays_cl[1], 2 * ray}, {&d_hits, 2 * hit}, {&d_rays_sh, ray}, {&d_occ, 1}, {&d_live[0], 4}, {&d_live[1], 4},
+                {&d_sL, 2 * 16}, {&d_sbeta, 2 * 16}, {&d_sA, 2 * 16}, {&d_sf2, 2 * 16}, {&d_sbold, 2 * 16}, {&d_sidx, 2 * 16}, {&d_sprev, 2 * 4},
+                {&d_order, 3 * 4}, {&d_keys_cl, 2 * 4}, {&d_keys_sh, 4}, {&d_tex_out, textured ? sizeof(TexOut) : 0, textured}, {&d_morder, 4, mat_queues}, {&d_mkeys, 2, mat_queues}};
+    }
+    std::vector<DevBuf*> all_bufs() {   // every device buffer of the workspace: the table above and the ones whose size does not follow the chunk
+        std::vector<DevBuf*> v{&d_tiles, &d_px, &d_ctr, &d_stats, &d_cam, &d_recL, &d_recpy, &d_rounded, &d_tilebuf, &d_xyz, &d_w,
+                               &d_vox_slot, &d_sp_pool, &d_sp_list, &d_sp_ctr, &d_sp_halton, &d_sort_bins, &d_heads, &d_mbins};
+        for (const phost::ChunkBuf& c : chunk_table(false, false)) v.push_back(c.buf);
+        return v;
+    }
 };
 
 namespace phost {
@@ -800,15 +816,13 @@ namespace phost {
 void free_wavefront(PbrtHipScene* s) {
     Wavefront* w = s->wf;
     if (!w) return;
-    for (DevBuf* b : {&w->d_tiles, &w->d_px, &w->d_rays_cl[0], &w->d_rays_cl[1], &w->d_hits, &w->d_rays_sh, &w->d_occ, &w->d_live[0], &w->d_live[1], &w->d_ctr,
-                      &w->d_stats, &w->d_cam, &w->d_tex_out, &w->d_sL, &w->d_sbeta, &w->d_sA, &w->d_sf2, &w->d_sbold, &w->d_sidx, &w->d_sprev, &w->d_rounded, &w->d_recL, &w->d_recpy, &w->d_tilebuf, &w->d_xyz, &w->d_w,
-                      &w->d_vox_slot, &w->d_sp_pool, &w->d_sp_list, &w->d_sp_ctr, &w->d_sp_halton, &w->d_order, &w->d_sort_bins, &w->d_heads, &w->d_keys_cl, &w->d_keys_sh, &w->d_morder, &w->d_mkeys, &w->d_mbins})
-        if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : w->all_bufs()) release_buf(*b);
     for (hipEvent_t e : w->events) (void)hipEventDestroy(e);
     delete w;
     s->wf = nullptr;
 }
 
+size_t path_chunk_bytes_per_path(bool general, bool textured) { Wavefront w; return chunk_bytes_per_path(w.chunk_table(textured, general || textured)); }
 static int sat_i(float v) { if (v != v) return 0; if (v >= 2147483648.0f) return 2147483647; if (v <= -2147483648.0f) return (int)0x80000000; return (int)v; }
 
 // Frame-wide tile grid: Film::get_sample_bounds (film/mod.rs:150-159), the tile counts of SamplerIntegrator::render (sampler_integrator.rs:252-259)
@@ -955,90 +969,32 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     if ((rc = upload_scene(s))) return rc;
     const bool spatial = light_strategy == 2 && s->lights.size() > 1;  // one light -> uniform (light_distrib/mod.rs:59-64)
     if ((rc = upload_light_distribution(s, light_strategy == 2 ? 0 : light_strategy))) return rc;
-    if ((rc = setup_tiles(s, tile_size, part, parts))) return rc;
-    Wavefront& w = *s->wf;
-    const uint32_t n_px = (uint32_t)w.px_xy.size();
-    const uint32_t spp = s->sampler.spp;
     if (out_stats) std::memset(out_stats, 0, sizeof(*out_stats));
-    const size_t tile_floats = tile_buffer_floats_for(s, tile_size, part, parts);
-    if (n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_floats * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
-    if ((uint64_t)n_px * spp >= (1ull << 40)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: too many samples");
+    SampleRecords rec{};
+    if ((rc = samples_begin(s, tile_size, part, parts, &rec))) return rc;
+    Wavefront& w = *s->wf;
+    const uint32_t n_px = rec.n_px, spp = s->sampler.spp;
+    if (n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
 
     // ---- chunking: B = n_px * chunk_spp paths in flight ----------------------------------------------------------------------
-    // 128 Mi paths per chunk where the card has room for them (353 B of queues and path state per path, 481 B with a texture pass: 47 – 65 GB of the MI355X's 288 GB):
-    // large chunks bin better (more rays per origin cell and round) and pay fewer launch tails — configs[2] 913 -> 878 ms per frame, configs[3] 934 -> 898 ms against the
-    // 32 Mi of round 1 (gpurun r02aa; 256 Mi, the whole frame at once, adds nothing: 875 / 899 ms).  At most 30 % of the device's memory goes to one chunk.
-    const size_t per_path = 2 * 2 * sizeof(ph::RayIn) + 2 * sizeof(ph::HitOut) + sizeof(ph::RayIn) + 1 + 2 * 4 + 6 * 2 * 16 + 2 * 4   // ray / hit queues, live lists, path state (two buffers)
-                            + 3 * 4 + 3 * 4 + (s->textured_materials ? sizeof(TexOut) : 0)                                                // + bin keys and order + the texture pass's records
-                            + 4 + 2;                                                                                                       // + the shade-side work queues' order and keys
-    // everything in this context that grows with the chunk, as allocated now: a chunk may reuse it
-    auto chunk_bufs = [&]() { return std::vector<DevBuf*>{&w.d_rays_cl[0], &w.d_rays_cl[1], &w.d_hits, &w.d_rays_sh, &w.d_occ, &w.d_live[0], &w.d_live[1], &w.d_sL, &w.d_sbeta, &w.d_sA, &w.d_sf2,
-                                                         &w.d_sbold, &w.d_sidx, &w.d_sprev, &w.d_order, &w.d_keys_cl, &w.d_keys_sh, &w.d_tex_out, &w.d_morder, &w.d_mkeys}; };
-    size_t max_paths = 128u << 20;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) {
-            size_t held = 0;
-            for (DevBuf* b : chunk_bufs()) held += b->bytes;
-            const size_t rec_need = (size_t)n_px * spp * 20, rec_have = w.d_recL.bytes + w.d_recpy.bytes;
-            size_t avail = free_b / 10 * 8 + held;   // what this context holds already counts as available to it; other contexts on the card (repeated-ordinal handles, other ranks) keep theirs
-            avail = avail > (rec_need > rec_have ? rec_need - rec_have : 0) ? avail - (rec_need > rec_have ? rec_need - rec_have : 0) : 0;
-            max_paths = std::max<size_t>(1u << 20, std::min<size_t>(max_paths, std::min(total_b / 10 * 3, avail) / per_path));
-        }
-    }
-    if (const char* e = std::getenv("PBRT_HIP_MAX_PATHS")) { long long v = std::atoll(e); if (v > 0) max_paths = (size_t)v; }
-    uint32_t chunk_spp = (uint32_t)std::max<size_t>(1, std::min<size_t>(spp, max_paths / std::max<uint32_t>(n_px, 1)));
+    // 128 Mi paths per chunk where the card has room for them (463 B of queues and path state per path, 591 B with a texture pass: 62 – 79 GB of the MI355X's 288 GB):
+    // large chunks bin better (more rays per origin cell and round) and pay fewer launch tails — configs[2] 913 -> 878 ms per frame, configs[3] 934 -> 898 ms against the 32 Mi of round 1 (256 Mi, the whole frame at once, adds nothing: 875 / 899 ms).
+    static const ChunkPolicy kChunks{128u << 20, 1u << 20, 0x7FFF0000ull, "render"};
+    // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
+    const bool mat_queues = s->general_materials || s->textured_materials;
+    const ChunkTable chunk = w.chunk_table(s->textured_materials, mat_queues);
+    const size_t rec_need = (size_t)n_px * spp * 20, rec_have = w.d_recL.bytes + w.d_recpy.bytes;   // planned before the sample records are allocated: what they still need is set aside
+    uint32_t chunk_spp = plan_chunk_spp_now(kChunks, chunk, rec_need > rec_have ? rec_need - rec_have : 0, n_px, spp);
     const int n_iter = max_depth + 1;
     // Material "none" surfaces are passed through without counting a bounce, so a path may need more rounds than max_depth + 1: those are
     // run one at a time while paths remain (host reads the live count), up to kMaxNullSkips more.
     const int kMaxNullSkips = 1024;
     const int n_iter_cap = s->has_none_material ? n_iter + kMaxNullSkips : n_iter;
-    // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
-    const bool mat_queues = s->general_materials || s->textured_materials;
     const bool has_quadrics = !s->quadrics.empty();   // the QUADRIC instantiations of the texture, light-distribution and shade passes
     if ((rc = ensure_buf(s, w.d_ctr, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters)))) return rc;
     if ((rc = ensure_buf(s, w.d_stats, 64 + 6 * PHC_N * 8))) return rc;   // DevStats (+ the shade kernel's phase tallies in measurement builds)
-    if ((rc = ensure_buf(s, w.d_recL, (size_t)n_px * spp * 16))) return rc;
-    if ((rc = ensure_buf(s, w.d_recpy, (size_t)n_px * spp * 4))) return rc;
-    if ((rc = ensure_buf(s, w.d_rounded, (size_t)n_px))) return rc;
-    PH_CHECK(s, hipMemsetAsync(w.d_rounded.p, 0, (size_t)n_px, s->stream));
-    auto alloc_chunk = [&](size_t Bc) -> int {
-        int r;
-        if ((r = ensure_buf(s, w.d_rays_cl[0], 2 * Bc * sizeof(ph::RayIn)))) return r;
-        if ((r = ensure_buf(s, w.d_rays_cl[1], 2 * Bc * sizeof(ph::RayIn)))) return r;
-        if ((r = ensure_buf(s, w.d_hits, 2 * Bc * sizeof(ph::HitOut)))) return r;
-        if ((r = ensure_buf(s, w.d_rays_sh, Bc * sizeof(ph::RayIn)))) return r;
-        if ((r = ensure_buf(s, w.d_occ, Bc))) return r;
-        if ((r = ensure_buf(s, w.d_live[0], Bc * 4))) return r;
-        if ((r = ensure_buf(s, w.d_live[1], Bc * 4))) return r;
-        for (DevBuf* b : {&w.d_sL, &w.d_sbeta, &w.d_sA, &w.d_sf2, &w.d_sbold, &w.d_sidx})
-            if ((r = ensure_buf(s, *b, 2 * Bc * 16))) return r;   // two buffers each: queue-ordered, read from one and written to the other (WfParams)
-        if ((r = ensure_buf(s, w.d_sprev, 2 * Bc * 4))) return r;
-        if ((r = ensure_buf(s, w.d_order, 3 * Bc * 4))) return r;
-        if ((r = ensure_buf(s, w.d_keys_cl, 2 * Bc * 4))) return r;
-        if ((r = ensure_buf(s, w.d_keys_sh, Bc * 4))) return r;
-        if (s->textured_materials && (r = ensure_buf(s, w.d_tex_out, Bc * sizeof(TexOut)))) return r;
-        if (mat_queues) {
-            if ((r = ensure_buf(s, w.d_morder, Bc * 4))) return r;
-            if ((r = ensure_buf(s, w.d_mkeys, Bc * 2))) return r;
-        }
-        return PBRT_HIP_OK;
-    };
-    // the estimate above can be wrong (fragmentation, another context allocating meanwhile): on hipErrorOutOfMemory the chunk is halved and tried again before the call gives up
-    // (test hook: PBRT_HIP_TEST_CHUNK_OOM=k makes the first k attempts of every render call fail as an out-of-memory allocation would)
-    int forced_oom = 0;
-    if (const char* e = std::getenv("PBRT_HIP_TEST_CHUNK_OOM")) forced_oom = std::max(0, std::atoi(e));
-    bool retried = false;
-    for (;;) {
-        if ((size_t)n_px * chunk_spp >= 0x7FFF0000ull) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: tile range too large for one rank; use more tile_parts");
-        if (forced_oom > 0) { forced_oom--; rc = set_err(s, PBRT_HIP_ERR_OOM, "render: out of device memory (forced by PBRT_HIP_TEST_CHUNK_OOM)"); }
-        else rc = alloc_chunk((size_t)n_px * chunk_spp);
-        if (rc == PBRT_HIP_OK) { if (retried) s->err.clear(); break; }   // a retry that succeeded leaves no error text behind
-        retried = true;
-        if (rc != PBRT_HIP_ERR_OOM || chunk_spp == 1) return rc;
-        for (DevBuf* b : chunk_bufs()) if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
-        chunk_spp = (chunk_spp + 1) / 2;
-    }
+    if ((rc = samples_alloc(s, &rec))) return rc;
+    if ((rc = chunk_alloc_or_halve(s, kChunks, chunk, n_px, chunk_spp))) return rc;
     const size_t B = (size_t)n_px * chunk_spp;
 
     if ((rc = ensure_traversal_workspace(s))) return rc;
@@ -1075,7 +1031,7 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     }
     for (int i = 0; i < 4; i++) wp.pixel_bounds[i] = pixel_bounds[i];
     wp.max_depth = max_depth; wp.rr_threshold = rr_threshold;
-    wp.n_px = n_px; wp.px_xy = (const int2*)w.d_px.p;
+    wp.n_px = n_px; wp.px_xy = rec.px_xy;
     wp.rays_cl[0] = (ph::RayIn*)w.d_rays_cl[0].p; wp.rays_cl[1] = (ph::RayIn*)w.d_rays_cl[1].p;
     wp.hits_cl = (ph::HitOut*)w.d_hits.p; wp.rays_sh = (ph::RayIn*)w.d_rays_sh.p; wp.occ = (uint8_t*)w.d_occ.p;
     wp.live[0] = (uint32_t*)w.d_live[0].p; wp.live[1] = (uint32_t*)w.d_live[1].p;
@@ -1085,7 +1041,7 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         wp.s_f2[k] = (float4*)w.d_sf2.p + (size_t)k * B; wp.s_bold[k] = (float4*)w.d_sbold.p + (size_t)k * B; wp.s_idx[k] = (uint4*)w.d_sidx.p + (size_t)k * B;
         wp.s_prev[k] = (uint32_t*)w.d_sprev.p + (size_t)k * B;
     }
-    wp.rec_L = (float4*)w.d_recL.p; wp.rec_py = (float*)w.d_recpy.p; wp.px_rounded = (uint8_t*)w.d_rounded.p;
+    wp.rec_L = rec.rec_L; wp.rec_py = rec.rec_py; wp.px_rounded = rec.px_rounded;
     wp.sort_grid = sort_grid; wp.keys_cl = (uint32_t*)w.d_keys_cl.p; wp.keys_sh = (uint32_t*)w.d_keys_sh.p;
     wp.m_order = mat_queues ? (const uint32_t*)w.d_morder.p : nullptr; wp.m_bins = mat_queues ? (const uint32_t*)w.d_mbins.p : nullptr;
 
@@ -1199,11 +1155,8 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     }
 
     // ---- film: per-tile accumulation in reference order ---------------------------------------------------------------------------
-    ph::FilmParams fp{};
-    fp.film = s->film; fp.tiles = (const ph::TileInfo*)w.d_tiles.p; fp.n_tiles = (uint32_t)w.tiles.size();
-    fp.slot_w = w.slot_w; fp.slot_h = w.slot_h; fp.spp = spp; fp.n_px = n_px; fp.rec_L = wp.rec_L; fp.rec_py = wp.rec_py; fp.px_rounded = wp.px_rounded; fp.tile_buf = (float4*)d_tile_buffer;
-    const uint64_t film_threads = (uint64_t)fp.n_tiles * w.slot_w * w.slot_h;
-    if ((rc = timed(2, [&]() { hipLaunchKernelGGL(ph::film_tiles_kernel, dim3((uint32_t)((film_threads + 255) / 256)), dim3(256), 0, s->stream, fp); }))) return rc;
+    int film_rc = PBRT_HIP_OK;
+    if ((rc = timed(2, [&]() { film_rc = samples_to_tiles(s, rec, d_tile_buffer); })) || (rc = film_rc)) return rc;
     PH_CHECK(s, hipEventRecord(e_end, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
 
@@ -1298,14 +1251,14 @@ int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_part
     // a single rank holds only its own tiles: the other parts contribute nothing (zero buffers are not needed: merge
     // addresses only tiles t with t % parts == part when every other part's pointer aliases an all-zero slot)
     if (tile_parts == 1) {
-        const void* bufs[1] = {s->wf->d_tilebuf.p};
+        const void* bufs[1] = {tile_buffer_of(s).p};
         return merge_tiles(s, tile_size, 1, bufs, out_xyz, out_weight);
     }
     // partial frame: merge this part against zeroed stand-ins for the missing ones
     std::vector<DevBuf> zeros((size_t)tile_parts);
     std::vector<const void*> bufs((size_t)tile_parts);
     for (int i = 0; i < tile_parts; i++) {
-        if (i == tile_part) { bufs[i] = s->wf->d_tilebuf.p; continue; }
+        if (i == tile_part) { bufs[i] = tile_buffer_of(s).p; continue; }
         const size_t fl = tile_buffer_floats_for(s, tile_size, i, tile_parts);
         if (hipMalloc(&zeros[i].p, fl * 4) != hipSuccess) { for (auto& z : zeros) if (z.p) (void)hipFree(z.p); return set_err(s, PBRT_HIP_ERR_OOM, "render: out of device memory"); }
         (void)hipMemset(zeros[i].p, 0, fl * 4);
@@ -1317,16 +1270,21 @@ int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_part
     return rc;
 }
 
-// The sample side of a frame for an integrator that brings its own rounds (whitted.hip): the rank's tile and pixel lists and the per-sample records
-// {L.rgb, p_film.x} {p_film.y} the film pass reads ...
+// The sample side of a frame, the same for every integrator: the rank's tile and pixel lists ...
 int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out) {
     int rc;
     if ((rc = setup_tiles(s, tile_size, part, parts))) return rc;
     Wavefront& w = *s->wf;
     const size_t n_px = w.px_xy.size(), spp = s->sampler.spp;
     out->n_px = (uint32_t)n_px; out->px_xy = (const int2*)w.d_px.p;
-    if (n_px == 0) return PBRT_HIP_OK;
     if ((uint64_t)n_px * spp >= (1ull << 40)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: too many samples");
+    return PBRT_HIP_OK;
+}
+// ... the per-sample records {L.rgb, p_film.x} {p_film.y} the film pass reads (a step of its own: the path driver sizes its chunk first) ...
+int samples_alloc(PbrtHipScene* s, SampleRecords* out) {
+    int rc;
+    Wavefront& w = *s->wf;
+    const size_t n_px = out->n_px, spp = s->sampler.spp;
     if ((rc = ensure_buf(s, w.d_recL, n_px * spp * 16))) return rc;
     if ((rc = ensure_buf(s, w.d_recpy, n_px * spp * 4))) return rc;
     if ((rc = ensure_buf(s, w.d_rounded, n_px))) return rc;
@@ -1391,10 +1349,9 @@ int pbrt_hip_render_path(PbrtHipScene* s, int max_depth, float rr_threshold, int
     if ((rc = refuse_sphere_lights(s))) return rc;
     if (!out_xyz || !out_weight) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render: null output");
     if (s->multi) return render_path_multi(s, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
-    if (!s->wf) s->wf = new Wavefront();
-    const size_t floats = tile_buffer_floats_for(s, tile_size, tile_part, tile_parts);
-    if ((rc = ensure_buf(s, s->wf->d_tilebuf, floats * 4))) return rc;
-    if ((rc = render_tiles(s, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts, s->wf->d_tilebuf.p, out_stats))) return rc;
+    DevBuf& tiles = tile_buffer_of(s);
+    if ((rc = ensure_buf(s, tiles, tile_buffer_floats_for(s, tile_size, tile_part, tile_parts) * 4))) return rc;
+    if ((rc = render_tiles(s, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part, tile_parts, tiles.p, out_stats))) return rc;
     return merge_own_tiles(s, tile_size, tile_part, tile_parts, out_xyz, out_weight);
     });
 }

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Show that two source trees compile to the same device code: kernel by kernel, the compiler's resource report and the instruction stream.
 
-    python scripts/traverse_shapes_isa_identity.py PARENT_TREE THIS_TREE > report.md
+    python scripts/traverse_shapes_isa_identity.py PARENT_TREE THIS_TREE [SOURCE ...] > report.md
 
-Both trees' api.hip and wavefront.hip are compiled device-side only with the Makefile's flags plus -Rpass-analysis=kernel-resource-usage (no GPU needed), the gfx950 code
+Both trees' sources (api.hip and wavefront.hip unless others are named) are compiled device-side only with the Makefile's flags plus -Rpass-analysis=kernel-resource-usage (no GPU needed), the gfx950 code
 objects are disassembled, and every function is paired by its demangled name.  A traverse_kernel spelled with the positional template arguments of before the shape table
 (<ANYHIT, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, MIXED, ALPHA, WPE, ALPHA_MIN, QUADRIC>) is paired with the <Shape, MODE> that has the same values.
 Instructions are compared as text without addresses and encodings; the literal of the s_add_u32 behind an s_getpc_b64 (the distance to a callee, a matter of lay-out) is masked
@@ -101,7 +101,9 @@ def n_differing(a, b):
 
 
 def main():
+    global SOURCES
     parent_tree, this_tree = sys.argv[1], sys.argv[2]
+    SOURCES = tuple(sys.argv[3:]) or SOURCES
     with tempfile.TemporaryDirectory() as tmp:
         parent, this = build(parent_tree, tmp, "parent"), build(this_tree, tmp, "this")
     bad = 0

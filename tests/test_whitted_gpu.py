@@ -197,6 +197,22 @@ def test_recursion_scene_in_chunks_and_tile_parts(recursion_pair, monkeypatch):
     assert rays == [want[2].camera_rays, want[2].regular_rays, want[2].shadow_rays]
 
 
+def test_chunk_oom_retry_halves_the_chunk_and_leaves_the_workspace_usable(recursion_pair, monkeypatch):
+    """The Whitted driver's side of tests/test_render_gpu.py's retry test (the loop is shared, chunk_plan.h): two forced out-of-memory attempts take the 4 spp to chunks of 1,
+    the film does not change and no error text survives; a third exhausts the halving and the call fails; the buffers released on the way are allocated again by the next call."""
+    prod = recursion_pair[("halton", False)][0]
+    want = prod.render_whitted(max_depth=5)
+    monkeypatch.setenv("PBRT_HIP_TEST_CHUNK_OOM", "2")
+    assert_same_film(prod.render_whitted(max_depth=5), want, "4 -> 2 -> 1 spp")
+    assert prod.last_error() == ""
+    monkeypatch.setenv("PBRT_HIP_TEST_CHUNK_OOM", "3")   # 4 -> 2 -> 1 spp and still failing: the call gives up with ERR_OOM
+    with pytest.raises(pbrt_hip.PbrtHipError) as e:
+        prod.render_whitted(max_depth=5)
+    assert e.value.code == pbrt_hip.ERR_OOM
+    monkeypatch.delenv("PBRT_HIP_TEST_CHUNK_OOM")
+    assert_same_film(prod.render_whitted(max_depth=5), want, "after the call that gave up")
+
+
 # ---- 3. the reference's own pixels --------------------------------------------------------------------------------------------------------------------------------
 PIXELS = [(n, s) for n, s in WHITTED if n not in ("samplers_random", "lights_diffuse")] + [("dof", 128), ("six:fbm", 128), ("six:2d-checkerboard", 128), ("mappings", 128)]
 
