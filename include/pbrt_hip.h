@@ -391,6 +391,22 @@ int pbrt_hip_render_path(PbrtHipScene*, int max_depth, float rr_threshold, int l
 int pbrt_hip_render_whitted(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                             float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
 
+/* Memory for the sample records.  A render keeps one 20-byte record {L.rgb, p_film} per camera sample until the film pass has replayed FilmTile::add_sample over it
+ * (core/src/film/film_tile.rs:62-108).  The reference holds O(pixels): every worker thread adds its samples to its FilmTile as they are made and Film::merge_film_tile
+ * (core/src/film/mod.rs:220-279) folds the tile into the film.  Here the records of a frame are resident in BANDS: consecutive runs of this rank's 16x16 (tile_size) tiles,
+ * in increasing tile index, each band with all of its samples.  A FilmTile takes samples of its own tile only (film_tile.rs:62-108; Film::get_film_tile, film/mod.rs:182-198),
+ * so a band is rendered and passed to the film on its own and the film, the weights and every counter equal the one-band render bit for bit, for every filter.
+ * `bytes` bounds pixels * spp * 20 B of one band; a band is never less than one tile, so a budget below one tile's records renders one tile per band and
+ * pbrt_hip_get_render_footprint reports the overshoot (not an error).  0 = automatic: one band whenever all records fit beside the smallest chunk of paths in the
+ * memory that is free or already held by the handle, else half of the memory the chunk planner counts as available.  The setting holds until it is changed and
+ * applies to every render entry point and to every device of a handle made by pbrt_hip_scene_create_multi. */
+int pbrt_hip_set_sample_record_budget(PbrtHipScene*, uint64_t bytes);
+/* What the last render of the handle came to (film/mod.rs and film_tile.rs keep no such tally; a measurement aid): out[0] bands, out[1] tiles in the largest band,
+ * out[2] peak sample-record bytes (the largest band's pixels * spp * 20), out[3] the budget that applied (the automatic one where none was set), out[4] paths per
+ * chunk, out[5] bytes of the chunk-scaled buffers for them, out[6] = out[7] = 0.  All zero before the first render; out[0] = 0 after a render without pixels.
+ * A multi-device handle reports, entry by entry, the largest value any of its devices came to. */
+int pbrt_hip_get_render_footprint(PbrtHipScene*, uint64_t out[8]);
+
 /* Multi-GPU form: writes this rank's FilmTiles (contrib rgb + weight, 4 floats per tile pixel, tiles in
  * increasing index order, each tile's pixel bounds as Film::get_film_tile computes them) into a DEVICE buffer
  * the caller owns (e.g. a torch tensor) so the host can gather them with RCCL; then any rank calls

@@ -61,4 +61,10 @@ inline int chunk_alloc_or_halve(PbrtHipScene* s, const ChunkPolicy& pol, const C
         chunk_spp = (chunk_spp + 1) / 2;
     }
 }
+// What the render's chunk came to, for pbrt_hip_get_render_footprint: paths per chunk and the bytes of the table's buffers for them
+inline void chunk_note_footprint(PbrtHipScene* s, size_t paths, const ChunkTable& t) {
+    size_t per_path = 0;
+    for (const ChunkBuf& c : t) if (c.allocated) per_path += c.per_path;
+    s->footprint[4] = paths; s->footprint[5] = paths * per_path;
+}
 }  // namespace phost

@@ -172,6 +172,7 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
     std::vector<size_t> floats((size_t)n);
     for (int k = 0; k < n; k++) {
         floats[k] = tile_buffer_floats_for(s, tile_size, tile_part + tile_parts * k, parts);
+        devs[k]->record_budget = s->record_budget;   // the sample-record budget (pbrt_hip_set_sample_record_budget) applies to every device
         PH_CHECK(s, hipSetDevice(devs[k]->device));
         if ((rc = ensure_buf(devs[k], tile_buffer_of(devs[k]), floats[k] * 4))) { s->err = devs[k]->err; return rc; }
     }
@@ -198,6 +199,10 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
     }
     for (int k = 0; k < n; k++)
         if (rcs[k] != PBRT_HIP_OK) { if (k) s->err = "device " + std::to_string(devs[k]->device) + ": " + devs[k]->err; m.replicas_current = false; return rcs[k]; }
+
+    // the footprint of the render (pbrt_hip_get_render_footprint): per entry the largest any device came to
+    for (int k = 1; k < n; k++)
+        for (int i = 0; i < 8; i++) s->footprint[i] = std::max(s->footprint[i], devs[k]->footprint[i]);
 
     // ---- the exchange step, then Film::merge_film_tile on the first device ------------------------------------------------------------------
     if ((rc = exchange(s, devs, floats))) return rc;

@@ -1,6 +1,7 @@
 // Host-side scene object behind the opaque PbrtHipScene handle (include/pbrt_hip.h).
 #pragma once
 #include "../../include/pbrt_hip.h"
+#include "band_plan.h"
 #include "bvh_build.h"
 #include "guard.h"
 #include "scene_types.h"
@@ -103,6 +104,11 @@ struct PbrtHipScene : SceneHostState {
     // wavefront workspace (allocated lazily by the renderer, see wavefront.hip)
     struct Wavefront* wf = nullptr;
     struct WhittedWorkspace* wh = nullptr;   // the Whitted driver's (whitted.hip)
+
+    // sample records (band_plan.h): the caller's byte budget for them, 0 = automatic (pbrt_hip_set_sample_record_budget), and what the last render came to
+    // (pbrt_hip_get_render_footprint: bands, tiles in the largest band, peak record bytes, the budget that applied, paths per chunk, chunk-scaled bytes, 0, 0)
+    uint64_t record_budget = 0;
+    uint64_t footprint[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace phost {
@@ -137,11 +143,15 @@ int merge_tiles(PbrtHipScene* s, int tile_size, int parts, const void* const* d_
 DevBuf& tile_buffer_of(PbrtHipScene* s);  // the handle's own tile buffer (wavefront workspace)
 int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight);   // the handle's tile buffer -> film, the other parts taken as empty
 // The sample side of a frame, shared by the integrators: the rank's pixel list (tile by tile, row-major) and the records [sample][pixel] an integrator fills —
-// rec_L = {L.rgb, p_film.x} (NaN p_film.x: no sample taken), rec_py = p_film.y, px_rounded[pixel] = 1 where a film position rounded up onto the next pixel's coordinate
-struct SampleRecords { uint32_t n_px; const int2* px_xy; float4* rec_L; float* rec_py; uint8_t* px_rounded; };
+// rec_L = {L.rgb, p_film.x} (NaN p_film.x: no sample taken), rec_py = p_film.y, px_rounded[pixel] = 1 where a film position rounded up onto the next pixel's coordinate.
+// The records of a frame are resident band by band (band_plan.h): `bands` are the rank's, band_px the pixels of the largest, which the buffers are sized for.  A driver takes
+// one band at a time (samples_band): n_px, px_xy and `band` are then that band's, and a record's pixel index counts from the band's first pixel.
+struct SampleRecords { uint32_t n_px; const int2* px_xy; float4* rec_L; float* rec_py; uint8_t* px_rounded; SampleBand band; uint32_t band_px; std::vector<SampleBand> bands; };
 int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out);   // tile and pixel lists; n_px == 0: nothing to render
-int samples_alloc(PbrtHipScene* s, SampleRecords* out);                                        // the records, px_rounded cleared
-int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer);            // the film pass over them
+int samples_plan_bands(PbrtHipScene* s, SampleRecords* out, size_t chunk_held, size_t chunk_per_path);   // the bands, under the handle's budget or the automatic one
+int samples_alloc(PbrtHipScene* s, SampleRecords* out);                                        // the records of the largest band
+int samples_band(PbrtHipScene* s, const SampleRecords& r, size_t band, SampleRecords* out);   // one band of them, px_rounded cleared
+int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer);            // the film pass over a band, into its tiles' slots
 size_t path_chunk_bytes_per_path(bool general_materials, bool textured_materials);   // what the path driver's chunk table (chunk_plan.h) sums to, for scripts/chunk_plan_check.cpp
 // whitted.hip
 void free_whitted(PbrtHipScene* s);

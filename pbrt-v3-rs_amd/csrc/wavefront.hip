@@ -50,11 +50,11 @@ struct WfParams {
     CameraRec cam; SamplerRec sp;
     int32_t pixel_bounds[4];
     int32_t max_depth; float rr_threshold;
-    uint32_t n_px;          // pixels in this rank's tiles
+    uint32_t n_px;          // pixels of the band being rendered (band_plan.h): a run of this rank's tiles, all of them where the records fit
     uint32_t chunk_spp, s0; // samples [s0, s0+chunk_spp) of every pixel in this chunk
     uint32_t B;             // n_px * chunk_spp
     uint32_t identity_slots; // every pixel of the rank's tiles lies inside pixel_bounds
-    // pixel list
+    // pixel list, from the band's first pixel on
     const int2* px_xy;
     // queues
     RayIn* rays_cl[2]; HitOut* hits_cl; RayIn* rays_sh; uint8_t* occ; uint32_t* live[2];
@@ -65,9 +65,9 @@ struct WfParams {
     // pending light sample (s_A, s_f2, s_bold — known in the middle of the vertex code, before the survivor's slot is) is written at the WRITING thread's own position
     // and found again through s_prev.  (Rounds 1-2 addressed all of this by path id: scattered 16-byte records from six 2 GB arrays.)
     float4* s_L[2]; float4* s_beta[2]; float4* s_A[2]; float4* s_f2[2]; float4* s_bold[2]; uint4* s_idx[2]; uint32_t* s_prev[2];
-    // per-sample records of the whole render: {L.rgb, p_film.x} {p_film.y}
+    // per-sample records of the band, [sample][pixel of the band]: {L.rgb, p_film.x} {p_film.y}
     float4* rec_L; float* rec_py;
-    uint8_t* px_rounded;    // per pixel of the rank's list: some sample's f32 film position rounded UP onto the next pixel's coordinate (film_tiles_kernel looks at those pixels' samples from the neighbour's side too)
+    uint8_t* px_rounded;    // per pixel of the band: some sample's f32 film position rounded UP onto the next pixel's coordinate (film_tiles_kernel looks at those pixels' samples from the neighbour's side too)
     // light sampling: SpatialLightDistribution tables when enabled, else the scene-wide Distribution1D of DeviceScene
     SpatialRec spatial;
     // materials that evaluate a texture per hit (texture.h): device copy of `cam` for the out-of-line evaluation
@@ -652,12 +652,13 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
 // exactly the terms the reference adds, in the same order.
 struct FilmParams {
     FilmRec film;
-    const TileInfo* tiles; uint32_t n_tiles;
+    const TileInfo* tiles; uint32_t n_tiles;    // the band's tiles (band_plan.h): a run of the rank's tile list
     uint32_t slot_w, slot_h;      // per-tile slot in the tile buffer: slot_w*slot_h float4 {contrib rgb, weight sum}
-    uint32_t spp, n_px;
-    const float4* rec_L; const float* rec_py;   // [sample][pixel of the rank's pixel list]
-    const uint8_t* px_rounded;                  // pixels with a sample that rounded up onto the next pixel's coordinate (raygen_kernel)
-    float4* tile_buf;
+    uint32_t spp, n_px;           // n_px: pixels of the band
+    uint32_t px_base;             // the band's first pixel in the rank's pixel list (TileInfo::px_off counts from the rank's first)
+    const float4* rec_L; const float* rec_py;   // [sample][pixel of the band]
+    const uint8_t* px_rounded;                  // pixels of the band with a sample that rounded up onto the next pixel's coordinate (raygen_kernel)
+    float4* tile_buf;             // the slot of the band's first tile
 };
 __global__ __launch_bounds__(256) void film_tiles_kernel(FilmParams p) {
     const uint32_t slot_px = p.slot_w * p.slot_h;
@@ -683,7 +684,7 @@ __global__ __launch_bounds__(256) void film_tiles_kernel(FilmParams p) {
         const int tw = t.tb[2] - t.tb[0];
         for (int sy = sy0; sy <= sy1; sy++)
             for (int sx = sx0; sx <= sx1; sx++) {
-                const size_t pix = (size_t)t.px_off + (size_t)(sy - t.tb[1]) * tw + (size_t)(sx - t.tb[0]);
+                const size_t pix = (size_t)(t.px_off - p.px_base) + (size_t)(sy - t.tb[1]) * tw + (size_t)(sx - t.tb[0]);
                 const bool up_x = sx < sx0n, up_y = sy < sy0n;   // only samples rounded up onto the next column / row matter from here ...
                 if ((up_x || up_y) && !p.px_rounded[pix]) continue;   // ... and raygen noted which pixels have any (a few per cent of them at 512 spp)
                 for (uint32_t s = 0; s < p.spp; s++) {
@@ -973,8 +974,8 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     SampleRecords rec{};
     if ((rc = samples_begin(s, tile_size, part, parts, &rec))) return rc;
     Wavefront& w = *s->wf;
-    const uint32_t n_px = rec.n_px, spp = s->sampler.spp;
-    if (n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
+    const uint32_t spp = s->sampler.spp;
+    if (rec.n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
 
     // ---- chunking: B = n_px * chunk_spp paths in flight ----------------------------------------------------------------------
     // 128 Mi paths per chunk where the card has room for them (463 B of queues and path state per path, 591 B with a texture pass: 62 – 79 GB of the MI355X's 288 GB):
@@ -983,6 +984,9 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
     const bool mat_queues = s->general_materials || s->textured_materials;
     const ChunkTable chunk = w.chunk_table(s->textured_materials, mat_queues);
+    // the bands of tiles whose sample records are resident together (band_plan.h); every size below is the largest band's, and the buffers serve all bands
+    if ((rc = samples_plan_bands(s, &rec, chunk_bytes_held(chunk), chunk_bytes_per_path(chunk)))) return rc;
+    const uint32_t n_px = rec.band_px;
     const size_t rec_need = (size_t)n_px * spp * 20, rec_have = w.d_recL.bytes + w.d_recpy.bytes;   // planned before the sample records are allocated: what they still need is set aside
     uint32_t chunk_spp = plan_chunk_spp_now(kChunks, chunk, rec_need > rec_have ? rec_need - rec_have : 0, n_px, spp);
     const int n_iter = max_depth + 1;
@@ -996,6 +1000,7 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     if ((rc = samples_alloc(s, &rec))) return rc;
     if ((rc = chunk_alloc_or_halve(s, kChunks, chunk, n_px, chunk_spp))) return rc;
     const size_t B = (size_t)n_px * chunk_spp;
+    chunk_note_footprint(s, B, chunk);
 
     if ((rc = ensure_traversal_workspace(s))) return rc;
     // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h): 8 heads, served in chunks of 49 152 rays (a multiple of every batch size); 1 024 blocks per sort pass
@@ -1031,7 +1036,6 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     }
     for (int i = 0; i < 4; i++) wp.pixel_bounds[i] = pixel_bounds[i];
     wp.max_depth = max_depth; wp.rr_threshold = rr_threshold;
-    wp.n_px = n_px; wp.px_xy = rec.px_xy;
     wp.rays_cl[0] = (ph::RayIn*)w.d_rays_cl[0].p; wp.rays_cl[1] = (ph::RayIn*)w.d_rays_cl[1].p;
     wp.hits_cl = (ph::HitOut*)w.d_hits.p; wp.rays_sh = (ph::RayIn*)w.d_rays_sh.p; wp.occ = (uint8_t*)w.d_occ.p;
     wp.live[0] = (uint32_t*)w.d_live[0].p; wp.live[1] = (uint32_t*)w.d_live[1].p;
@@ -1041,7 +1045,6 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         wp.s_f2[k] = (float4*)w.d_sf2.p + (size_t)k * B; wp.s_bold[k] = (float4*)w.d_sbold.p + (size_t)k * B; wp.s_idx[k] = (uint4*)w.d_sidx.p + (size_t)k * B;
         wp.s_prev[k] = (uint32_t*)w.d_sprev.p + (size_t)k * B;
     }
-    wp.rec_L = rec.rec_L; wp.rec_py = rec.rec_py; wp.px_rounded = rec.px_rounded;
     wp.sort_grid = sort_grid; wp.keys_cl = (uint32_t*)w.d_keys_cl.p; wp.keys_sh = (uint32_t*)w.d_keys_sh.p;
     wp.m_order = mat_queues ? (const uint32_t*)w.d_morder.p : nullptr; wp.m_bins = mat_queues ? (const uint32_t*)w.d_mbins.p : nullptr;
 
@@ -1073,90 +1076,97 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     wp.tex_out = nullptr;
     if (s->textured_materials) wp.tex_out = (TexOut*)w.d_tex_out.p;
 
-    for (uint32_t s0 = 0; s0 < spp; s0 += chunk_spp) {
-        const uint32_t cs = std::min(chunk_spp, spp - s0);
-        wp.chunk_spp = cs; wp.s0 = s0; wp.B = n_px * cs; wp.identity_slots = identity ? 1u : 0u;
-        PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters), s->stream));
-        PH_CHECK(s, hipMemsetAsync(w.d_heads.p, 0, (size_t)(n_iter_cap + 2) * n_heads * 64, s->stream));
-        if (identity) hipLaunchKernelGGL(ph::preset_counters_kernel, dim3(1), dim3(1), 0, s->stream, wp.ctr, wp.stats, wp.B);
-        if ((rc = timed(2, [&]() { hipLaunchKernelGGL(ph::raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp); }))) return rc;
-        int iters_run = 0;
-        for (int it = 0; it < n_iter_cap; it++) {
-            ph::IterCounters* c = (ph::IterCounters*)w.d_ctr.p + it;
-            if (it >= n_iter) {  // only with "none" materials: go on while some path is still alive
-                uint32_t live = 0;
-                PH_CHECK(s, hipMemcpyAsync(&live, &c->n_live, 4, hipMemcpyDeviceToHost, s->stream));
-                PH_CHECK(s, hipStreamSynchronize(s->stream));
-                if (live == 0) break;
-                if (it == n_iter_cap - 1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: a path crossed more than 1024 'none' surfaces");
-            }
-            iters_run = it + 1;
-            ph::TravParams tp{};
-            tp.rays = wp.rays_cl[it & 1]; tp.out = wp.hits_cl; tp.n = 0; tp.n_ptr = &c->n_cl; tp.counter = &c->head_cl;
-            tp.heads = (uint32_t*)w.d_heads.p + (size_t)it * n_heads * 16; tp.n_heads = n_heads; tp.head_chunk = head_chunk;
-            if (it > 0) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
-                tp.rays2 = wp.rays_sh; tp.out2 = wp.occ; tp.n2_ptr = &c->n_sh;
-                // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
-                sortp.n_cl = &c->n_cl; sortp.n_sh = &c->n_sh;
-                if ((rc = timed(3, [&]() {
-                        (void)hipMemsetAsync(sortp.bin_start, 0, PH_SORT_KEYS * 4, s->stream);
-                        hipLaunchKernelGGL(ph::raysort_hist_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
-                        hipLaunchKernelGGL(ph::raysort_scan_kernel, dim3(1), dim3(1024), 0, s->stream, sortp);
-                        hipLaunchKernelGGL(ph::raysort_scatter_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
-                    }))) return rc;
-                tp.order = sortp.order;
-                if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 2, s->trav_blocks, tp); }))) return rc;
-            } else if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 0, s->trav_blocks, tp); }))) return rc;
-            // the shade side's work queues: this round's list regrouped by what has to be done for each path (matsort.h)
-            if (mat_queues) {
-                msp.s_idx = wp.s_idx[it & 1]; msp.n_live = &c->n_live;
+    // band by band: the per-spp chunk loop over the band's pixels, then the film pass over its tiles.  Counters, statistics, time spans and the spatial light distribution's
+    // voxel tables run on through the bands.
+    for (size_t band = 0; band < rec.bands.size(); band++) {
+        SampleRecords br{};
+        if ((rc = samples_band(s, rec, band, &br))) return rc;
+        wp.n_px = br.n_px; wp.px_xy = br.px_xy; wp.rec_L = br.rec_L; wp.rec_py = br.rec_py; wp.px_rounded = br.px_rounded;
+        for (uint32_t s0 = 0; s0 < spp; s0 += chunk_spp) {
+            const uint32_t cs = std::min(chunk_spp, spp - s0);
+            wp.chunk_spp = cs; wp.s0 = s0; wp.B = br.n_px * cs; wp.identity_slots = identity ? 1u : 0u;
+            PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters), s->stream));
+            PH_CHECK(s, hipMemsetAsync(w.d_heads.p, 0, (size_t)(n_iter_cap + 2) * n_heads * 64, s->stream));
+            if (identity) hipLaunchKernelGGL(ph::preset_counters_kernel, dim3(1), dim3(1), 0, s->stream, wp.ctr, wp.stats, wp.B);
+            if ((rc = timed(2, [&]() { hipLaunchKernelGGL(ph::raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp); }))) return rc;
+            int iters_run = 0;
+            for (int it = 0; it < n_iter_cap; it++) {
+                ph::IterCounters* c = (ph::IterCounters*)w.d_ctr.p + it;
+                if (it >= n_iter) {  // only with "none" materials: go on while some path is still alive
+                    uint32_t live = 0;
+                    PH_CHECK(s, hipMemcpyAsync(&live, &c->n_live, 4, hipMemcpyDeviceToHost, s->stream));
+                    PH_CHECK(s, hipStreamSynchronize(s->stream));
+                    if (live == 0) break;
+                    if (it == n_iter_cap - 1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: a path crossed more than 1024 'none' surfaces");
+                }
+                iters_run = it + 1;
+                ph::TravParams tp{};
+                tp.rays = wp.rays_cl[it & 1]; tp.out = wp.hits_cl; tp.n = 0; tp.n_ptr = &c->n_cl; tp.counter = &c->head_cl;
+                tp.heads = (uint32_t*)w.d_heads.p + (size_t)it * n_heads * 16; tp.n_heads = n_heads; tp.head_chunk = head_chunk;
+                if (it > 0) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
+                    tp.rays2 = wp.rays_sh; tp.out2 = wp.occ; tp.n2_ptr = &c->n_sh;
+                    // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
+                    sortp.n_cl = &c->n_cl; sortp.n_sh = &c->n_sh;
+                    if ((rc = timed(3, [&]() {
+                            (void)hipMemsetAsync(sortp.bin_start, 0, PH_SORT_KEYS * 4, s->stream);
+                            hipLaunchKernelGGL(ph::raysort_hist_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
+                            hipLaunchKernelGGL(ph::raysort_scan_kernel, dim3(1), dim3(1024), 0, s->stream, sortp);
+                            hipLaunchKernelGGL(ph::raysort_scatter_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
+                        }))) return rc;
+                    tp.order = sortp.order;
+                    if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 2, s->trav_blocks, tp); }))) return rc;
+                } else if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 0, s->trav_blocks, tp); }))) return rc;
+                // the shade side's work queues: this round's list regrouped by what has to be done for each path (matsort.h)
+                if (mat_queues) {
+                    msp.s_idx = wp.s_idx[it & 1]; msp.n_live = &c->n_live;
+                    if ((rc = timed(2, [&]() {
+                            (void)hipMemsetAsync(msp.bin_start, 0, (PH_MS_BINS + 1) * 4, s->stream);
+                            hipLaunchKernelGGL(ph::matsort_hist_kernel, dim3(sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
+                            hipLaunchKernelGGL(ph::matsort_scan_kernel, dim3(1), dim3(PH_MS_BINS), 0, s->stream, msp);
+                            hipLaunchKernelGGL(ph::matsort_scatter_kernel, dim3(sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
+                        }))) return rc;
+                }
+                // the texture pass first: besides colours and bumped frames it finds the hits that have no BSDF at all (TexOut::bumped, PH_TEXOUT_NULL_BSDF), which the
+                // light-distribution pass must skip as the reference's `continue` does (path.rs:142-157)
+                if (s->textured_materials) {
+                    if ((rc = timed(2, [&]() {
+                            const dim3 g(shade_blocks), b(PH_TEX_LDS_THREADS);
+                            if (it == 0) {   // camera rays: differentials, filtered look-ups
+                                if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, true, 2, true>), g, b, 0, s->stream, s->ds, wp, it);
+                                else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
+                                else hipLaunchKernelGGL((ph::texture_kernel<false, true, 2>), g, b, 0, s->stream, s->ds, wp, it);
+                            } else {
+                                if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, false, 3, true>), g, b, 0, s->stream, s->ds, wp, it);
+                                else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
+                                else hipLaunchKernelGGL((ph::texture_kernel<false, false, 3>), g, b, 0, s->stream, s->ds, wp, it);
+                            }
+                        }))) return rc;
+                }
+                if (spatial && (it < max_depth || s->has_none_material)) {  // vertices reached at bounce == max_depth sample no light (path.rs:136-139)
+                    if ((rc = timed(2, [&]() {
+                            if (has_quadrics) hipLaunchKernelGGL(ph::spatial_mark_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                            else hipLaunchKernelGGL(ph::spatial_mark_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                            hipLaunchKernelGGL(ph::spatial_compute_kernel, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, wp.spatial);
+                        }))) return rc;
+                }
                 if ((rc = timed(2, [&]() {
-                        (void)hipMemsetAsync(msp.bin_start, 0, (PH_MS_BINS + 1) * 4, s->stream);
-                        hipLaunchKernelGGL(ph::matsort_hist_kernel, dim3(sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
-                        hipLaunchKernelGGL(ph::matsort_scan_kernel, dim3(1), dim3(PH_MS_BINS), 0, s->stream, msp);
-                        hipLaunchKernelGGL(ph::matsort_scatter_kernel, dim3(sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
+                        if (has_quadrics) hipLaunchKernelGGL((ph::shade_kernel<true, true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);   // (quadrics set both flags)
+                        else if (s->textured_materials) {
+                            if (s->general_materials) hipLaunchKernelGGL((ph::shade_kernel<true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                            else hipLaunchKernelGGL((ph::shade_kernel<false, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                        } else if (s->general_materials) hipLaunchKernelGGL(ph::shade_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                        else hipLaunchKernelGGL(ph::shade_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
                     }))) return rc;
             }
-            // the texture pass first: besides colours and bumped frames it finds the hits that have no BSDF at all (TexOut::bumped, PH_TEXOUT_NULL_BSDF), which the
-            // light-distribution pass must skip as the reference's `continue` does (path.rs:142-157)
-            if (s->textured_materials) {
-                if ((rc = timed(2, [&]() {
-                        const dim3 g(shade_blocks), b(PH_TEX_LDS_THREADS);
-                        if (it == 0) {   // camera rays: differentials, filtered look-ups
-                            if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, true, 2, true>), g, b, 0, s->stream, s->ds, wp, it);
-                            else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
-                            else hipLaunchKernelGGL((ph::texture_kernel<false, true, 2>), g, b, 0, s->stream, s->ds, wp, it);
-                        } else {
-                            if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, false, 3, true>), g, b, 0, s->stream, s->ds, wp, it);
-                            else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
-                            else hipLaunchKernelGGL((ph::texture_kernel<false, false, 3>), g, b, 0, s->stream, s->ds, wp, it);
-                        }
-                    }))) return rc;
-            }
-            if (spatial && (it < max_depth || s->has_none_material)) {  // vertices reached at bounce == max_depth sample no light (path.rs:136-139)
-                if ((rc = timed(2, [&]() {
-                        if (has_quadrics) hipLaunchKernelGGL(ph::spatial_mark_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                        else hipLaunchKernelGGL(ph::spatial_mark_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                        hipLaunchKernelGGL(ph::spatial_compute_kernel, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, wp.spatial);
-                    }))) return rc;
-            }
-            if ((rc = timed(2, [&]() {
-                    if (has_quadrics) hipLaunchKernelGGL((ph::shade_kernel<true, true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);   // (quadrics set both flags)
-                    else if (s->textured_materials) {
-                        if (s->general_materials) hipLaunchKernelGGL((ph::shade_kernel<true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                        else hipLaunchKernelGGL((ph::shade_kernel<false, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                    } else if (s->general_materials) hipLaunchKernelGGL(ph::shade_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                    else hipLaunchKernelGGL(ph::shade_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                }))) return rc;
+            PH_CHECK(s, hipMemcpyAsync(hctr.data(), w.d_ctr.p, (size_t)(iters_run + 1) * sizeof(ph::IterCounters), hipMemcpyDeviceToHost, s->stream));
+            PH_CHECK(s, hipStreamSynchronize(s->stream));
+            for (int it = 0; it < iters_run; it++) { regular += hctr[it].n_cl; shadow += hctr[it].n_sh; }
         }
-        PH_CHECK(s, hipMemcpyAsync(hctr.data(), w.d_ctr.p, (size_t)(iters_run + 1) * sizeof(ph::IterCounters), hipMemcpyDeviceToHost, s->stream));
-        PH_CHECK(s, hipStreamSynchronize(s->stream));
-        for (int it = 0; it < iters_run; it++) { regular += hctr[it].n_cl; shadow += hctr[it].n_sh; }
-    }
 
-    // ---- film: per-tile accumulation in reference order ---------------------------------------------------------------------------
-    int film_rc = PBRT_HIP_OK;
-    if ((rc = timed(2, [&]() { film_rc = samples_to_tiles(s, rec, d_tile_buffer); })) || (rc = film_rc)) return rc;
+        // ---- film: per-tile accumulation in reference order ---------------------------------------------------------------------------
+        int film_rc = PBRT_HIP_OK;
+        if ((rc = timed(2, [&]() { film_rc = samples_to_tiles(s, br, d_tile_buffer); })) || (rc = film_rc)) return rc;
+    }
     PH_CHECK(s, hipEventRecord(e_end, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
 
@@ -1273,31 +1283,62 @@ int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_part
 // The sample side of a frame, the same for every integrator: the rank's tile and pixel lists ...
 int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out) {
     int rc;
+    std::memset(s->footprint, 0, sizeof s->footprint);
+    s->footprint[3] = s->record_budget;
     if ((rc = setup_tiles(s, tile_size, part, parts))) return rc;
     Wavefront& w = *s->wf;
     const size_t n_px = w.px_xy.size(), spp = s->sampler.spp;
     out->n_px = (uint32_t)n_px; out->px_xy = (const int2*)w.d_px.p;
+    out->band = {0u, (uint32_t)w.tiles.size(), 0u, (uint32_t)n_px}; out->band_px = (uint32_t)n_px; out->bands.clear();
     if ((uint64_t)n_px * spp >= (1ull << 40)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: too many samples");
     return PBRT_HIP_OK;
 }
-// ... the per-sample records {L.rgb, p_film.x} {p_film.y} the film pass reads (a step of its own: the path driver sizes its chunk first) ...
+// ... the bands of tiles whose records are resident together (band_plan.h), under the handle's budget (pbrt_hip_set_sample_record_budget) or, where none is set, the automatic
+// one.  chunk_held / chunk_per_path: what the driver's chunk table holds from an earlier render and its bytes per path (chunk_plan.h) ...
+int samples_plan_bands(PbrtHipScene* s, SampleRecords* out, size_t chunk_held, size_t chunk_per_path) {
+    Wavefront& w = *s->wf;
+    const uint32_t spp = s->sampler.spp;
+    uint64_t budget = s->record_budget;
+    if (budget == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = 0;
+        budget = auto_record_budget(band_record_bytes(out->n_px, spp), free_b, total_b, w.d_recL.bytes + w.d_recpy.bytes + chunk_held, (uint64_t)out->n_px * chunk_per_path);
+    }
+    std::vector<uint32_t> tile_px(w.tiles.size());
+    for (size_t t = 0; t < w.tiles.size(); t++) tile_px[t] = (uint32_t)((w.tiles[t].tb[2] - w.tiles[t].tb[0]) * (w.tiles[t].tb[3] - w.tiles[t].tb[1]));
+    out->bands = plan_bands(tile_px.data(), tile_px.size(), spp, budget);
+    uint32_t band_px = 0, band_tiles = 0;
+    for (const SampleBand& b : out->bands) { band_px = std::max(band_px, b.n_px); band_tiles = std::max(band_tiles, b.n_tiles); }
+    out->band_px = band_px;
+    s->footprint[0] = out->bands.size(); s->footprint[1] = band_tiles; s->footprint[2] = band_record_bytes(band_px, spp); s->footprint[3] = budget;
+    return PBRT_HIP_OK;
+}
+// ... the per-sample records {L.rgb, p_film.x} {p_film.y} the film pass reads, for the largest band (a step of its own: the path driver sizes its chunk first) ...
 int samples_alloc(PbrtHipScene* s, SampleRecords* out) {
     int rc;
     Wavefront& w = *s->wf;
-    const size_t n_px = out->n_px, spp = s->sampler.spp;
+    const size_t n_px = out->band_px, spp = s->sampler.spp;
     if ((rc = ensure_buf(s, w.d_recL, n_px * spp * 16))) return rc;
     if ((rc = ensure_buf(s, w.d_recpy, n_px * spp * 4))) return rc;
     if ((rc = ensure_buf(s, w.d_rounded, n_px))) return rc;
-    PH_CHECK(s, hipMemsetAsync(w.d_rounded.p, 0, n_px, s->stream));
     out->rec_L = (float4*)w.d_recL.p; out->rec_py = (float*)w.d_recpy.p; out->px_rounded = (uint8_t*)w.d_rounded.p;
     return PBRT_HIP_OK;
 }
-// ... and that pass: FilmTile::add_sample over the records, into d_tile_buffer
+// ... one band of them: its pixels of the rank's list and the same record buffers, px_rounded cleared ...
+int samples_band(PbrtHipScene* s, const SampleRecords& r, size_t band, SampleRecords* out) {
+    const SampleBand& b = r.bands[band];
+    out->n_px = b.n_px; out->px_xy = r.px_xy + b.px0; out->rec_L = r.rec_L; out->rec_py = r.rec_py; out->px_rounded = r.px_rounded;
+    out->band = b; out->band_px = b.n_px;
+    PH_CHECK(s, hipMemsetAsync(r.px_rounded, 0, b.n_px, s->stream));
+    return PBRT_HIP_OK;
+}
+// ... and that pass: FilmTile::add_sample over the band's records, into its tiles' slots of d_tile_buffer
 int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer) {
     Wavefront& w = *s->wf;
     ph::FilmParams fp{};
-    fp.film = s->film; fp.tiles = (const ph::TileInfo*)w.d_tiles.p; fp.n_tiles = (uint32_t)w.tiles.size();
-    fp.slot_w = w.slot_w; fp.slot_h = w.slot_h; fp.spp = s->sampler.spp; fp.n_px = r.n_px; fp.rec_L = r.rec_L; fp.rec_py = r.rec_py; fp.px_rounded = r.px_rounded; fp.tile_buf = (float4*)d_tile_buffer;
+    fp.film = s->film; fp.tiles = (const ph::TileInfo*)w.d_tiles.p + r.band.tile0; fp.n_tiles = r.band.n_tiles;
+    fp.slot_w = w.slot_w; fp.slot_h = w.slot_h; fp.spp = s->sampler.spp; fp.n_px = r.n_px; fp.px_base = r.band.px0; fp.rec_L = r.rec_L; fp.rec_py = r.rec_py; fp.px_rounded = r.px_rounded;
+    fp.tile_buf = (float4*)d_tile_buffer + (size_t)r.band.tile0 * w.slot_w * w.slot_h;
     const uint64_t film_threads = (uint64_t)fp.n_tiles * w.slot_w * w.slot_h;
     hipLaunchKernelGGL(ph::film_tiles_kernel, dim3((uint32_t)((film_threads + 255) / 256)), dim3(256), 0, s->stream, fp);
     PH_CHECK(s, hipGetLastError());
@@ -1316,6 +1357,22 @@ int pbrt_hip_tile_buffer_floats(PbrtHipScene* s, int tile_size, int tile_part, i
     if (!s->have_film) return set_err(s, PBRT_HIP_ERR_STATE, "tile_buffer_floats: set_film first");
     if (tile_size <= 0 || tile_parts <= 0 || tile_part < 0 || tile_part >= tile_parts) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "tile_buffer_floats: bad partition");
     *out_floats = tile_buffer_floats_for(s, tile_size, tile_part, tile_parts);
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_set_sample_record_budget(PbrtHipScene* s, uint64_t bytes) {
+    return ph_guard(s, "pbrt_hip_set_sample_record_budget", [&]() -> int {
+    if (!s) return PBRT_HIP_ERR_INVALID_ARG;
+    s->record_budget = bytes;   // (a multi-device handle hands it to every device's context when it renders, multi.hip)
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_get_render_footprint(PbrtHipScene* s, uint64_t out[8]) {
+    return ph_guard(s, "pbrt_hip_get_render_footprint", [&]() -> int {
+    if (!s || !out) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "get_render_footprint: null argument");
+    std::memcpy(out, s->footprint, sizeof s->footprint);
     return PBRT_HIP_OK;
     });
 }

@@ -49,7 +49,7 @@ struct WhParams {
     int32_t pixel_bounds[4];
     int32_t max_depth;
     uint32_t n_frames;           // frames per sample: max(max_depth, 1)
-    uint32_t n_px, chunk_spp, s0, B;
+    uint32_t n_px, chunk_spp, s0, B;   // n_px: pixels of the band being rendered (band_plan.h); px_xy starts at the band's first pixel, the records are [sample][pixel of the band]
     uint32_t diffs;              // the scene has textures or bump maps: rays carry differentials (nothing else reads them)
     const int2* px_xy;
     float4* rec_L; float* rec_py; uint8_t* px_rounded;

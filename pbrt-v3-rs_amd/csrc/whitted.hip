@@ -78,16 +78,20 @@ static int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_
     if ((rc = samples_begin(s, tile_size, part, parts, &rec))) return rc;
     if (out_stats) std::memset(out_stats, 0, sizeof(*out_stats));
     if (rec.n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
-    if ((rc = samples_alloc(s, &rec))) return rc;
     if (!s->wh) s->wh = new WhittedWorkspace();
     WhittedWorkspace& w = *s->wh;
-    const uint32_t n_px = rec.n_px, spp = s->sampler.spp, n_frames = (uint32_t)std::max(max_depth, 1);
+    const uint32_t spp = s->sampler.spp, n_frames = (uint32_t)std::max(max_depth, 1);
+    const ChunkTable chunk = w.chunk_table(n_frames);
+    // the bands of tiles whose sample records are resident together (band_plan.h); every size below is the largest band's, and the buffers serve all bands
+    if ((rc = samples_plan_bands(s, &rec, chunk_bytes_held(chunk), chunk_bytes_per_path(chunk)))) return rc;
+    if ((rc = samples_alloc(s, &rec))) return rc;
+    const uint32_t n_px = rec.band_px;
 
     // ---- chunking: n_px * chunk_spp samples in flight; an occlusion-ray position (PH_WH_SLICE per sample) has to fit 32 bits
     static const ChunkPolicy kChunks{32u << 20, 1u << 16, 0x7FFF0000ull / PH_WH_SLICE, "render_whitted"};
-    const ChunkTable chunk = w.chunk_table(n_frames);
     uint32_t chunk_spp = plan_chunk_spp_now(kChunks, chunk, 0, n_px, spp);
     if ((rc = chunk_alloc_or_halve(s, kChunks, chunk, n_px, chunk_spp))) return rc;
+    chunk_note_footprint(s, (size_t)n_px * chunk_spp, chunk);
     if ((rc = ensure_buf(s, w.d_ctr, 2 * sizeof(ph::WhCounters)))) return rc;
     if ((rc = ensure_buf(s, w.d_stats, 64))) return rc;
     if ((rc = ensure_traversal_workspace(s))) return rc;
@@ -95,9 +99,8 @@ static int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_
     ph::WhParams wp{};
     wp.cam = s->cam; wp.sp = s->sampler;
     for (int i = 0; i < 4; i++) wp.pixel_bounds[i] = pixel_bounds[i];
-    wp.max_depth = max_depth; wp.n_frames = n_frames; wp.n_px = n_px;
+    wp.max_depth = max_depth; wp.n_frames = n_frames;
     wp.diffs = (s->textured_materials || s->bump_materials) ? 1u : 0u;
-    wp.px_xy = rec.px_xy; wp.rec_L = rec.rec_L; wp.rec_py = rec.rec_py; wp.px_rounded = rec.px_rounded;
     for (int k = 0; k < 2; k++) { wp.rays_cl[k] = (ph::RayIn*)w.d_rays_cl[k].p; wp.rays_sh[k] = (ph::RayIn*)w.d_rays_sh[k].p; wp.live[k] = (uint32_t*)w.d_live[k].p; }
     wp.hits_cl = (ph::HitOut*)w.d_hits.p; wp.occ = (uint8_t*)w.d_occ.p;
     wp.ctr = (ph::WhCounters*)w.d_ctr.p; wp.stats = (ph::WhDevStats*)w.d_stats.p;
@@ -109,40 +112,46 @@ static int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_
     uint64_t regular = 0, shadow = 0;
     // every round finishes a sample, a light slice or one level of some sample's recursion, so the rounds of a chunk are bounded by the tree a sample can have
     const unsigned long long max_rounds = 1024ull + 1024ull * ((1ull << n_frames) * (2ull + s->lights.size() / PH_WH_SLICE));
-    for (uint32_t s0 = 0; s0 < spp; s0 += chunk_spp) {
-        const uint32_t cs = std::min(chunk_spp, spp - s0);
-        wp.chunk_spp = cs; wp.s0 = s0; wp.B = n_px * cs;
-        const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)wp.B + 255) / 256, 256 * 16);
-        PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, 2 * sizeof(ph::WhCounters), s->stream));
-        hipLaunchKernelGGL(ph::whitted_raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp);
-        PH_CHECK(s, hipGetLastError());
-        for (unsigned long long round = 0;; round++) {
-            const int par = (int)(round & 1);
-            ph::WhCounters c{};
-            PH_CHECK(s, hipMemcpyAsync(&c, wp.ctr + par, sizeof c, hipMemcpyDeviceToHost, s->stream));
-            PH_CHECK(s, hipStreamSynchronize(s->stream));
-            if (c.n_live == 0) break;
-            if (round >= max_rounds) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render_whitted: a sample crossed too many 'none' surfaces");
-            regular += c.n_cl; shadow += c.n_sh;
-            PH_CHECK(s, hipMemsetAsync(wp.ctr + (par ^ 1), 0, sizeof(ph::WhCounters), s->stream));
-            if (c.n_cl || c.n_sh) {
-                ph::TravParams tp{};
-                tp.rays = wp.rays_cl[par]; tp.out = wp.hits_cl; tp.n_ptr = &wp.ctr[par].n_cl; tp.counter = &wp.ctr[par].head;
-                tp.rays2 = wp.rays_sh[par]; tp.out2 = wp.occ; tp.n2_ptr = &wp.ctr[par].n_sh;
-                launch_traverse_kernel(s, 2, std::min<uint32_t>(s->trav_blocks, (c.n_cl + c.n_sh + PH_TRAV_BLOCK - 1) / PH_TRAV_BLOCK), tp);
-                PH_CHECK(s, hipGetLastError());
-            }
-            if (wp.diffs && c.n_cl) {
-                if (has_quadrics) hipLaunchKernelGGL(ph::whitted_vertex_kernel<true>, dim3(blocks), dim3(PH_TEX_LDS_THREADS), 0, s->stream, s->ds, wp, par);
-                else hipLaunchKernelGGL(ph::whitted_vertex_kernel<false>, dim3(blocks), dim3(PH_TEX_LDS_THREADS), 0, s->stream, s->ds, wp, par);
-                PH_CHECK(s, hipGetLastError());
-            }
-            if (has_quadrics) hipLaunchKernelGGL(ph::whitted_state_kernel<true>, dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, par);
-            else hipLaunchKernelGGL(ph::whitted_state_kernel<false>, dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, par);
+    // band by band: the per-spp chunk loop over the band's pixels, then the film pass over its tiles; the counters run on through the bands
+    for (size_t band = 0; band < rec.bands.size(); band++) {
+        SampleRecords br{};
+        if ((rc = samples_band(s, rec, band, &br))) return rc;
+        wp.n_px = br.n_px; wp.px_xy = br.px_xy; wp.rec_L = br.rec_L; wp.rec_py = br.rec_py; wp.px_rounded = br.px_rounded;
+        for (uint32_t s0 = 0; s0 < spp; s0 += chunk_spp) {
+            const uint32_t cs = std::min(chunk_spp, spp - s0);
+            wp.chunk_spp = cs; wp.s0 = s0; wp.B = br.n_px * cs;
+            const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)wp.B + 255) / 256, 256 * 16);
+            PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, 2 * sizeof(ph::WhCounters), s->stream));
+            hipLaunchKernelGGL(ph::whitted_raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp);
             PH_CHECK(s, hipGetLastError());
+            for (unsigned long long round = 0;; round++) {
+                const int par = (int)(round & 1);
+                ph::WhCounters c{};
+                PH_CHECK(s, hipMemcpyAsync(&c, wp.ctr + par, sizeof c, hipMemcpyDeviceToHost, s->stream));
+                PH_CHECK(s, hipStreamSynchronize(s->stream));
+                if (c.n_live == 0) break;
+                if (round >= max_rounds) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render_whitted: a sample crossed too many 'none' surfaces");
+                regular += c.n_cl; shadow += c.n_sh;
+                PH_CHECK(s, hipMemsetAsync(wp.ctr + (par ^ 1), 0, sizeof(ph::WhCounters), s->stream));
+                if (c.n_cl || c.n_sh) {
+                    ph::TravParams tp{};
+                    tp.rays = wp.rays_cl[par]; tp.out = wp.hits_cl; tp.n_ptr = &wp.ctr[par].n_cl; tp.counter = &wp.ctr[par].head;
+                    tp.rays2 = wp.rays_sh[par]; tp.out2 = wp.occ; tp.n2_ptr = &wp.ctr[par].n_sh;
+                    launch_traverse_kernel(s, 2, std::min<uint32_t>(s->trav_blocks, (c.n_cl + c.n_sh + PH_TRAV_BLOCK - 1) / PH_TRAV_BLOCK), tp);
+                    PH_CHECK(s, hipGetLastError());
+                }
+                if (wp.diffs && c.n_cl) {
+                    if (has_quadrics) hipLaunchKernelGGL(ph::whitted_vertex_kernel<true>, dim3(blocks), dim3(PH_TEX_LDS_THREADS), 0, s->stream, s->ds, wp, par);
+                    else hipLaunchKernelGGL(ph::whitted_vertex_kernel<false>, dim3(blocks), dim3(PH_TEX_LDS_THREADS), 0, s->stream, s->ds, wp, par);
+                    PH_CHECK(s, hipGetLastError());
+                }
+                if (has_quadrics) hipLaunchKernelGGL(ph::whitted_state_kernel<true>, dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, par);
+                else hipLaunchKernelGGL(ph::whitted_state_kernel<false>, dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, par);
+                PH_CHECK(s, hipGetLastError());
+            }
         }
+        if ((rc = samples_to_tiles(s, br, d_tile_buffer))) return rc;
     }
-    if ((rc = samples_to_tiles(s, rec, d_tile_buffer))) return rc;
     PH_CHECK(s, hipEventRecord(s->ev1, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
 

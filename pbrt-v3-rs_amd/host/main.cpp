@@ -14,6 +14,7 @@ static void usage() {
                  "  --device N             GPU ordinal (default 0)\n"
                  "  --devices A,B,...      render every frame on several GPUs of this node (tiles dealt round-robin, film tiles gathered over RCCL); 'all' = every visible GPU\n"
                  "  --tile-size N          sample tile edge (default 16, as the reference)\n"
+                 "  --sample-record-budget BYTES   device memory for the per-sample records: the frame renders in bands of whole tiles, the image is the same (default 0: automatic)\n"
                  "  --sobol-tables FILE    raw Sobol generator matrices (needed for Sampler \"sobol\")\n"
                  "  --check                parse and validate only: no GPU is touched and nothing is rendered\n"
                  "  --convert-image IN OUT       decode an image file (PFM, TGA, PNG, EXR) the way ImageTexture would see it and write it as .pfm / .exr / .png / .tga\n"
@@ -21,7 +22,7 @@ static void usage() {
 }
 
 int main(int argc, char** argv) {
-    std::string outfile, sobol; int device = 0, tile = 16; bool quiet = false, has_crop = false, check = false; float crop[4] = {0, 1, 0, 1};
+    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false; float crop[4] = {0, 1, 0, 1};
     std::vector<std::string> files;
     std::vector<int> devices; bool multi = false;
     for (int i = 1; i < argc; i++) {
@@ -37,6 +38,7 @@ int main(int argc, char** argv) {
                 for (size_t p = 0; p < v.size();) { size_t q = v.find(',', p); if (q == std::string::npos) q = v.size(); devices.push_back(std::atoi(v.substr(p, q - p).c_str())); p = q + 1; }
         }
         else if (a == "--tile-size") { need(1); tile = std::atoi(argv[++i]); }
+        else if (a == "--sample-record-budget") { need(1); record_budget = std::strtoull(argv[++i], nullptr, 10); }
         else if (a == "--sobol-tables") { need(1); sobol = argv[++i]; }
         else if (a == "--quiet") quiet = true;
         else if (a == "--check") check = true;
@@ -56,7 +58,7 @@ int main(int argc, char** argv) {
         std::unique_ptr<pbrt_host::Api> api_owner((multi && !check) ? new pbrt_host::Api(devices) : new pbrt_host::Api(check ? -1 : device));
         pbrt_host::Api& api = *api_owner;
         if (!api.error.empty()) { std::fprintf(stderr, "Error: %s\n", api.error.c_str()); return 3; }
-        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.quiet = quiet;
+        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet;
         api.has_crop_override = has_crop; std::memcpy(api.crop_override, crop, sizeof crop);
         pbrt_host::RenderReport rep;
         if (!pbrt_host::parse_file(fn, api, &rep)) { std::fprintf(stderr, "Error: %s: %s\n", fn.c_str(), api.error.c_str()); return 1; }

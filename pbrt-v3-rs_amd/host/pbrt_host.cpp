@@ -902,6 +902,7 @@ int Api::pbrt_world_end(RenderReport& rep) {
     if (check_only_) { rep.out_file = filename; return PBRT_HIP_OK; }
     const size_t npix = (size_t)std::max(0, cb[2] - cb[0]) * (size_t)std::max(0, cb[3] - cb[1]);
     std::vector<float> xyz(npix * 3), wt(npix), rgb(npix * 3);
+    if (!check(pbrt_hip_set_sample_record_budget(scene_, sample_record_budget), "set_sample_record_budget")) return PBRT_HIP_ERR_INVALID_ARG;
     int rc = whitted ? pbrt_hip_render_whitted(scene_, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
                      : pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
     if (!check(rc, whitted ? "render_whitted" : "render_path")) return rc;

@@ -108,6 +108,7 @@ class Api {
     float crop_override[4] = {0, 1, 0, 1};  // --cropwindow x0 x1 y0 y1
     std::string sobol_tables_file;  // raw little-endian: u32[1024*52], u64[25*52], u64[26*52]
     int tile_size = 16;
+    unsigned long long sample_record_budget = 0;   // --sample-record-budget BYTES (pbrt_hip_set_sample_record_budget); 0 = automatic
     bool quiet = false;
     std::vector<std::string> warnings;
     std::string error;

@@ -155,6 +155,8 @@ class Binding:
             "scene_create_multi": (vp, [ip, C.c_int]),
             "scene_devices": (C.c_int, [vp, ip, C.c_int]),
             "selftest_rccl_gather": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint64)]),
+            "set_sample_record_budget": (C.c_int, [vp, C.c_uint64]),
+            "get_render_footprint": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -747,6 +749,17 @@ class Scene:
         st = Stats()
         self._chk(self.b.fn("render_whitted")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
         return xyz, wt, st
+
+    def set_sample_record_budget(self, nbytes=0):
+        """Bound on the bytes of sample records resident at once (pbrt_hip_set_sample_record_budget): the frame renders in bands of whole tiles, bit for bit the
+        one-band film.  0 = automatic.  Holds until changed."""
+        self._chk(self.b.fn("set_sample_record_budget")(self.h, int(nbytes)))
+
+    def render_footprint(self):
+        """What the last render came to (pbrt_hip_get_render_footprint)."""
+        c = (C.c_uint64 * 8)()
+        self._chk(self.b.fn("get_render_footprint")(self.h, c))
+        return {"bands": int(c[0]), "band_tiles": int(c[1]), "record_bytes": int(c[2]), "record_budget": int(c[3]), "chunk_paths": int(c[4]), "chunk_bytes": int(c[5])}
 
     def film_to_rgb(self, xyz, weight):
         rgb = np.zeros_like(xyz)
