@@ -1361,7 +1361,7 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
     if (!s->quadrics.empty()) {   // before any work
         if (s->build_on_device) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel_device: a scene with quadric shapes is built on the host (pbrt_hip_build_accel)");
         if (!s->objects.empty() || !s->instances.empty()) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: quadric shapes together with object definitions or instances are not supported");
-        if (s->alpha_textures) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: quadric shapes together with alpha-mask textures are not supported");
+        // (alpha-mask textures on the scene's triangle meshes are traversal's business: the QUADRIC rows with alpha of TravShapes)
         s->prim_quadric.resize(s->idx.size() / 3, 0u);
     }
     // every DiffuseAreaLight belongs to a shape (api/src/lib.rs:783-812 creates them per triangle): one that no add_mesh claimed would be sampled

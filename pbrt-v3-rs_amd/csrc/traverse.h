@@ -334,6 +334,9 @@ static __device__ __forceinline__ bool alpha_accept_lean(const DeviceScene& sc, 
 //   from the queue again (the instancing kernel's lesson — that line has left the caches by then — is accepted here: no speed target for quadric scenes yet).  An accepted
 //   quadric is remembered like a triangle, by its record; the ray retires with zero barycentrics.  Instantiated only for scenes that hold a quadric (pick_shape): with
 //   QUADRIC = false every line below compiles to what it was.
+//   QUADRIC with ALPHA != 0 (quadrics beside alpha-masked meshes): a quadric record carries no PH_TRI_ALPHATEX (set_last_mesh_alpha_textures refuses a quadric), so a lane at one never sets
+//   alpha_wait and a waiting lane always stands at a triangle.  The leaf step has ONE test site for both (a second copy of the test gave wrong hits on this toolchain); a lane
+//   tests its leaf's records one at a time in the leaf's order, so a quadric accepted ahead of a masked triangle has shortened t_max before that triangle is tested (and re-tested).
 // WPE > 0 compiles the kernel for exactly that many waves per SIMD (= resident 256-thread blocks per CU): the register allocator then fits the budget
 // (7: 72 VGPRs, 8: 64) instead of taking what it likes; 0 leaves the choice to the compiler (same code as before).
 //
@@ -371,6 +374,12 @@ template <bool INST> struct ShapeAlphaGeneral : ShapeDefaults { static constexpr
 // Quadric scenes: the flat kernel's loop shape with the analytic test out of line.  A kernel is allocated its callees' registers (quadric_test: 136, interval arithmetic + f64 atan2),
 // so the compiler chooses the occupancy (wpe 0: 3 waves) — DESIGN §4.4 has the numbers.
 struct ShapeQuadric : ShapeFlat { static constexpr bool quadric = true; static constexpr int wpe = 0; };
+// Quadrics next to alpha-masked triangle meshes: ShapeQuadric's loop with the alpha phase of the flat alpha kernels (alpha_min = 12).  A lane at a quadric record never waits — a quadric
+// has no mask —, a lane at a masked triangle waits at its record as in ShapeFlatAlphaLean; both kinds of record go through the ONE test site of the leaf step.  Lean: quadric_test's
+// registers stay the kernel's (the inlined mask test needs fewer).  General: the kernel is allocated the larger of its two callees, alpha_accept's evaluator, and carries that one's
+// LDS value stack and noise table beside the traversal stack (24 576 + 18 432 + 512 B = 43 520 B per block, as ShapeAlphaGeneral<false>) — DESIGN §4.4 has the numbers.
+struct ShapeQuadricAlphaLean : ShapeQuadric { static constexpr int alpha = 1, alpha_min = 12; };
+struct ShapeQuadricAlphaGeneral : ShapeQuadric { static constexpr int alpha = 2, alpha_min = 12; };
 // The counting builds (pbrt_hip_set_traversal_counting): the default loop with the scene's features.
 template <bool INST, int ALPHA, bool QUADRIC = false> struct ShapeCount : ShapeDefaults { static constexpr bool count = true, inst = INST, quadric = QUADRIC; static constexpr int alpha = ALPHA; };
 
@@ -382,10 +391,11 @@ template <class... S> struct ShapeTable {
     static constexpr int spill_lds_depth(bool inst) { int d = PH_MAX_STACK; ((d = (S::inst == inst && S::lds_depth < d) ? S::lds_depth : d), ...); return d; }
 };
 using TravShapes = ShapeTable<ShapeFlat, ShapeInst, ShapeFlatAlphaLean, ShapeInstAlphaLean, ShapeAlphaGeneral<false>, ShapeAlphaGeneral<true>, ShapeQuadric,
-                              ShapeCount<false, 0>, ShapeCount<true, 0>, ShapeCount<false, 1>, ShapeCount<true, 1>, ShapeCount<false, 2>, ShapeCount<true, 2>, ShapeCount<false, 0, true>>;
+                              ShapeCount<false, 0>, ShapeCount<true, 0>, ShapeCount<false, 1>, ShapeCount<true, 1>, ShapeCount<false, 2>, ShapeCount<true, 2>, ShapeCount<false, 0, true>,
+                              ShapeQuadricAlphaLean, ShapeQuadricAlphaGeneral, ShapeCount<false, 1, true>, ShapeCount<false, 2, true>>;
 // The scene's row of TravShapes.  alpha: 0 no alpha-mask textures, 1 image-map masks only (the inlined test), 2 any texture class (the general evaluator out of line).
-// A scene with quadrics has neither instances nor alpha-mask textures (build_accel refuses it otherwise).
-constexpr int pick_shape(bool inst, int alpha, bool quadric, bool count) { return quadric ? TravShapes::find(false, 0, true, count) : TravShapes::find(inst, alpha, false, count); }
+// A scene with quadrics has no instances (build_accel refuses it otherwise); it may have alpha-mask textures on its triangle meshes, and its row follows their class.
+constexpr int pick_shape(bool inst, int alpha, bool quadric, bool count) { return quadric ? TravShapes::find(false, alpha, true, count) : TravShapes::find(inst, alpha, false, count); }
 constexpr bool every_scene_has_a_shape() {
     for (int k = 0; k < 24; k++) if (pick_shape(k & 1, (k >> 1) % 3, k >= 12, k % 12 >= 6) < 0) return false;
     return true;
@@ -400,7 +410,7 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
     static_assert(MODE == TRAV_CLOSEST || MODE == TRAV_ANY || MODE == TRAV_MIXED, "no such mode");
     static_assert(LDS_DEPTH >= TravShapes::spill_lds_depth(INST), "the spill region starts at the shallowest LDS stack of the table's rows: a shape outside the table would write past it");
     static_assert(ALPHA_MIN == 0 || ALPHA != 0, "the alpha phase needs an alpha test");
-    static_assert(!QUADRIC || (!INST && ALPHA == 0), "build_accel refuses quadrics together with instances or alpha-mask textures: no such kernel");
+    static_assert(!QUADRIC || !INST, "build_accel refuses quadrics together with instances: no such kernel");
     __shared__ uint2 lds_stack[LDS_DEPTH][PH_TRAV_BLOCK];
     // INST: the scene-level ray's origin and what ray_setup derived from it (six IEEE divides), parked while the lane walks an instance: leaving an instance is then nine LDS reads instead of
     // a reload of the ray and a second ray_setup.  The direction is not parked — the scene-level one stays in three registers of its own (re-reading it from the ray queue at every instance cost 4 %:

@@ -8,7 +8,8 @@ objects are disassembled, and every function is paired by its demangled name.  A
 (<ANYHIT, COUNT, LEAF_MIN, REFILL_MIN, LDS_DEPTH, NODE_STEPS, INST, MIXED, ALPHA, WPE, ALPHA_MIN, QUADRIC>) is paired with the <Shape, MODE> that has the same values.
 Instructions are compared as text without addresses and encodings; the literal of the s_add_u32 behind an s_getpc_b64 (the distance to a callee, a matter of lay-out) is masked
 and the s_nop padding behind a function's last instruction is dropped (the order of the functions in the code object may differ).
-Exit status 1 if a function is missing on either side or differs in resources or instructions."""
+A function that one tree alone has (a new or a dropped instantiation) is listed with its resources in a table of its own.
+Exit status 1 if a function of the parent is missing here or a pair differs in resources or instructions."""
 import difflib
 import os
 import re
@@ -115,7 +116,8 @@ def main():
           "  \"differing\" counts instructions that are not common to both streams (addresses and encodings dropped, the pc-relative literal of a call masked, padding between functions dropped).\n" % " and ".join("`%s`" % s for s in SOURCES))
     print("Functions: %d in the parent, %d here; `traverse_kernel` instantiations: %d in the parent, %d here; in one tree only: %s.\n"
           % (len(parent), len(this), len(trav), sum("traverse_kernel" in k for k in this), ", ".join("`%s`" % k for k in only) or "none"))
-    bad += len(only)
+    gone = [k for k in only if k in parent]   # a function this tree alone has is an addition, listed below with its resources; one the parent alone has is a difference
+    bad += len(gone)
     print("| function (this tree's spelling) | parent's spelling | " + " | ".join(f.split(" [")[0] for f in FIELDS) + " | instructions | differing |")
     print("|---|---|" + "---|" * (len(FIELDS) + 2))
     for k in sorted(set(parent) & set(this), key=lambda k: ("traverse_kernel" not in k, k)):
@@ -128,7 +130,16 @@ def main():
         d = 0 if p["isa"] == t["isa"] else n_differing(p["isa"], t["isa"])
         bad += d != 0
         print("| `%s` | %s | %s | %d | %s |" % (k, "`%s`" % p["spelled"] if p["spelled"] != k.split(": ", 1)[1] else "same", " | ".join(cells), len(t["isa"]), d if d == 0 else "**%d**" % d))
-    print("\n%s" % ("Every pair has the same resources and the same instructions." if not bad else "%d differences (bold above)." % bad))
+    if only:   # a function one tree alone has: its resources, so that a new instantiation is listed with what it costs
+        print("\nIn one tree only:\n")
+        print("| function | tree | " + " | ".join(f.split(" [")[0] for f in FIELDS) + " | instructions |")
+        print("|---|---|" + "---|" * (len(FIELDS) + 1))
+        for k in only:
+            f1 = parent.get(k) or this[k]
+            print("| `%s` | %s | %s | %d |" % (k, "parent" if k in parent else "this", " | ".join((f1["res"] or {}).get(f, "-") for f in FIELDS), len(f1["isa"])))
+    added = len(only) - len(gone)
+    print("\n%s%s" % ("Every pair has the same resources and the same instructions." if not bad else "%d differences (bold above; functions the parent alone has count)." % bad,
+                      "  %d functions are new in this tree." % added if added else ""))
     return 1 if bad else 0
 
 
