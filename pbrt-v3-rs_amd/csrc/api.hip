@@ -1411,7 +1411,6 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
         if (brc != 0) return fail(brc);
     } else {
         if (s->open_object >= 0) return set_err(s, PBRT_HIP_ERR_STATE, "build_accel: an object definition is still open (missing ObjectEnd)");
-        if (s->build_on_device && split_method != 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel_device: scenes with object instances are built on the device with the SAH method only");
         // One aggregate per instanced object (make_accelerator at ObjectInstance time, lib.rs:953-971) and the scene's own over its triangles and TransformedPrimitives,
         // in one node array and one TriRec array: [scene | objects] (bvh_build.h)
         std::vector<uint32_t> tri0(s->objects.size()), tri1(s->objects.size()), inst_object(s->instances.size());
@@ -1428,7 +1427,9 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
             PH_CHECK(s, hipSetDevice(s->device));
             std::string e;
             const phost::ForestSpec spec = layout.spec(isc);
-            const int brc = phost::build_sah_device(in, max_prims_in_node, s->stream, s->bvh, e, &s->tree_dev_nodes, &s->tree_dev_tris, &spec, &trees);
+            // SAH leaves the forest where it was built (tree_dev_*); HLBVH hands it back in s->bvh, as it does without instances (the SAH over the treelet roots is the host's)
+            const int brc = split_method == 1 ? phost::build_hlbvh_device(in, max_prims_in_node, s->stream, s->bvh, e, &spec, &trees)
+                                              : phost::build_sah_device(in, max_prims_in_node, s->stream, s->bvh, e, &s->tree_dev_nodes, &s->tree_dev_tris, &spec, &trees);
             if (brc == -1) return set_err(s, PBRT_HIP_ERR_DEVICE, "build_accel_device: " + e);
             if (brc != 0) return fail(brc);
             if (s->tree_dev_tris) s->tree_dev_n_tris = layout.items.size();

@@ -432,8 +432,10 @@ int build_bvh(const BuildInput& in, int split_method, int max_prims_in_node, int
     }
     const bool prof = std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr;
     auto t_prims = std::chrono::steady_clock::now();
-    B.pool.resize(2 * n + 4096 * Builder::kArenaChunk);  // room for the partly used chunks of every thread the build may start
     if (n_threads <= 0) n_threads = (int)std::thread::hardware_concurrency();
+    // room for the partly used chunks of every thread the build may start.  Up to 32768 primitives the SAH recursion never forks and HLBVH starts at most one thread per treelet and
+    // per n_threads, so a small tree (a forest has hundreds of them) does not pay for 4096 chunks
+    B.pool.resize(2 * n + (n <= 32768 ? std::min<size_t>((size_t)std::max(n_threads, 1), n) + 2 : 4096) * Builder::kArenaChunk);
     B.spare_threads = n_threads > 1 ? n_threads - 1 : 0;
     BNode* root = split_method == 1 ? B.build_hlbvh(std::max(n_threads, 1)) : B.build(0, n);
     if (B.panic) return -2;  // one of the reference's assertions fired (hlbvh.rs:338/356/418)

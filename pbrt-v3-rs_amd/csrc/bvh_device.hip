@@ -12,11 +12,18 @@
 //
 // Inside a treelet emit_lbvh always splits a sorted range into a lower and an upper part, so the depth-first leaf order of a treelet IS the sorted
 // order; the scene's leaf order is the treelets' ranges concatenated in the depth-first order of the upper SAH tree.
+//
+// Scenes with object instances: the forest form (f_* kernels below, build_hlbvh_forest_device) makes the scene's aggregate and every instanced object's in the same launches —
+// bounds, codes and treelets per tree, a stable sort by (tree, code), the level kernels over the treelets of all trees; per tree on the host what the flat build does on the
+// host, in hlbvh_forest_stitch.h.  The flat build keeps its own kernels.
 #include "scene_host.h"
 #include "host_math.h"
+#include "hlbvh_forest_stitch.h"
 #include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
+#include <thread>
 
 namespace phd {
 
@@ -279,6 +286,174 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint32_t* ids, const 
     tris[q] = r;
 }
 
+// What must stay in step with the flat kernels above: f_morton_kernel = morton_kernel (the code of a centroid), f_emit_roots_kernel = emit_roots_kernel (EmitItem / TreeletInfo
+// layout), f_convert_kernel = convert_kernel and f_gather_kernel = gather_kernel (Node64 / TriRec fields) — and the pool-slot rule of emit_level_kernel that f_convert_kernel and
+// f_roots_kernel rely on: a treelet's root lives in slot 2 x its first position, a leaf in 2 x its first position + 1, any other interior node in 2 x its split position, so a
+// slot j belongs to the treelet of position j / 2.
+// ---- the forest form (scenes with object instances): all trees of [scene | object | object ..] side by side ----------------------------------------------------------------
+// A POSITION of the item list belongs to the same tree before and after the sort (the sort is by (tree, code) and the items start grouped by tree), so one table says which.
+__global__ __launch_bounds__(256) void f_tree_of_kernel(const uint32_t* tree_start, uint32_t n_trees, uint32_t n, uint32_t* tree_of) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t lo = 0, hi = n_trees;   // the last tree whose start is <= i
+    while (lo + 1 < hi) { const uint32_t mid = (lo + hi) >> 1; if (tree_start[mid] <= i) lo = mid; else hi = mid; }
+    tree_of[i] = lo;
+}
+// K1, forest: bounds of the items at positions [i0, i1) (a triangle, or PH_ITEM_INST | k with the bound inst_bounds[6k ..]) and, per tree, the union of them
+__global__ __launch_bounds__(256) void f_bounds_kernel(const float* P, const uint32_t* idx, const uint32_t* items, const float* inst_bounds, const uint32_t* tree_of, uint32_t i0, uint32_t i1,
+                                                       float* blo, float* bhi, uint32_t* tb /*[n_trees][6]: ord(min xyz), ord(max xyz)*/) {
+    const uint32_t first = i0 + blockIdx.x * blockDim.x, i = first + threadIdx.x;
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    const bool ok = i < i1;
+    if (ok) {
+        const uint32_t item = items[i];
+        if (item & PH_ITEM_INST) {
+            const float* bb = inst_bounds + 6 * (size_t)(item & ~PH_ITEM_INST);
+            for (int k = 0; k < 3; k++) { lo[k] = bb[k]; hi[k] = bb[3 + k]; }
+        } else {
+            const float* a = P + 3 * (size_t)idx[3 * (size_t)item];
+            const float* b = P + 3 * (size_t)idx[3 * (size_t)item + 1];
+            const float* c = P + 3 * (size_t)idx[3 * (size_t)item + 2];
+            for (int k = 0; k < 3; k++) { lo[k] = fmn(fmn(a[k], b[k]), c[k]); hi[k] = fmx(fmx(a[k], b[k]), c[k]); }
+        }
+        for (int k = 0; k < 3; k++) { blo[3 * (size_t)i + k] = lo[k]; bhi[3 * (size_t)i + k] = hi[k]; }
+    }
+    const uint32_t last = first + blockDim.x - 1u < i1 ? first + blockDim.x - 1u : i1 - 1u;
+    const uint32_t t_first = tree_of[first], t_last = tree_of[last];   // (first < i1 for every block of the grid)
+    if (t_first == t_last) {   // the whole block in one tree: reduce in LDS first (the same for every thread of the block)
+        __shared__ uint32_t sm[6];
+        if (threadIdx.x < 3) { sm[threadIdx.x] = 0xFFFFFFFFu; sm[3 + threadIdx.x] = 0u; }
+        __syncthreads();
+        if (ok) for (int k = 0; k < 3; k++) { atomicMin(&sm[k], f2ord(lo[k])); atomicMax(&sm[3 + k], f2ord(hi[k])); }
+        __syncthreads();
+        if (threadIdx.x < 3) { atomicMin(&tb[6 * (size_t)t_first + threadIdx.x], sm[threadIdx.x]); atomicMax(&tb[6 * (size_t)t_first + 3 + threadIdx.x], sm[3 + threadIdx.x]); }
+    } else if (ok) {
+        uint32_t* g = tb + 6 * (size_t)tree_of[i];
+        for (int k = 0; k < 3; k++) { atomicMin(&g[k], f2ord(lo[k])); atomicMax(&g[3 + k], f2ord(hi[k])); }
+    }
+}
+// TransformedPrimitive::world_bound of every instance: Transform::transform_bounds (transform.rs:552-561) of its object's tree bounds — phost::transform_bounds, expression by expression
+__global__ __launch_bounds__(256) void f_inst_bounds_kernel(const uint32_t* tb, const uint32_t* inst_tree, const float* i2w, uint32_t n_inst, float* inst_bounds) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_inst) return;
+    const float* m = i2w + 16 * (size_t)k;
+    const uint32_t* g = tb + 6 * (size_t)inst_tree[k];
+    float lo[3], hi[3], ob[6];
+    for (int a = 0; a < 3; a++) { lo[a] = ord2f(g[a]); hi[a] = ord2f(g[3 + a]); ob[a] = ob[3 + a] = 0.0f; }
+    for (int c = 0; c < 8; c++) {   // corners in the reference's order: lll hll lhl llh lhh hhl hlh hhh
+        const bool hx = c == 1 || c == 5 || c == 6 || c == 7, hy = c == 2 || c == 4 || c == 5 || c == 7, hz = c == 3 || c == 4 || c == 6 || c == 7;
+        const float x = hx ? hi[0] : lo[0], y = hy ? hi[1] : lo[1], z = hz ? hi[2] : lo[2];
+        const float xp = m[0] * x + m[1] * y + m[2] * z + m[3], yp = m[4] * x + m[5] * y + m[6] * z + m[7];
+        const float zp = m[8] * x + m[9] * y + m[10] * z + m[11], wp = m[12] * x + m[13] * y + m[14] * z + m[15];
+        float q[3];
+        if (wp == 1.0f) { q[0] = xp; q[1] = yp; q[2] = zp; } else { const float inv = 1.0f / wp; q[0] = inv * xp; q[1] = inv * yp; q[2] = inv * zp; }
+        for (int a = 0; a < 3; a++) {
+            if (c == 0) { ob[a] = ob[3 + a] = q[a]; }
+            else { ob[a] = ob[a] < q[a] ? ob[a] : q[a]; ob[3 + a] = ob[3 + a] > q[a] ? ob[3 + a] : q[a]; }
+        }
+    }
+    for (int a = 0; a < 6; a++) inst_bounds[6 * (size_t)k + a] = ob[a];
+}
+// K2, forest: a code is relative to the bounds of its own tree.  vals = the item's position before the sort.
+__global__ __launch_bounds__(256) void f_morton_kernel(const float* blo, const float* bhi, uint32_t n, const uint32_t* tb, const uint32_t* tree_of, uint32_t* codes, uint32_t* codes_keep, uint32_t* ids) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* g = tb + 6 * (size_t)tree_of[i];
+    uint32_t c[3];
+    for (int k = 0; k < 3; k++) {
+        const float glo = ord2f(g[k]), ghi = ord2f(g[3 + k]);
+        const float ctr = 0.5f * (blo[3 * (size_t)i + k] + bhi[3 * (size_t)i + k]);
+        float o = ctr - glo;
+        if (ghi > glo) o = o / (ghi - glo);
+        c[k] = left_shift_3(__float_as_uint(o * 1024.0f));
+    }
+    const uint32_t code = (c[2] << 2) | (c[1] << 1) | c[0];
+    codes[i] = code; codes_keep[i] = code; ids[i] = i;
+}
+// K3, forest: after the passes over the code, passes over the tree of every item (keys = that tree) bring each tree's items back to its own range, in code order
+__global__ __launch_bounds__(256) void f_lookup_kernel(const uint32_t* ids, const uint32_t* table, uint32_t n, uint32_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = table[ids[i]];
+}
+// K4, forest: a treelet is a maximal run of equal (tree, top 12 code bits).  Count the run heads per block, scan, write them out in order.
+__device__ __forceinline__ bool f_is_head(const uint32_t* codes, const uint32_t* tree_of, uint32_t i) { return i == 0u || tree_of[i] != tree_of[i - 1u] || (codes[i] >> 18) != (codes[i - 1u] >> 18); }
+__global__ __launch_bounds__(256) void f_heads_count_kernel(const uint32_t* codes, const uint32_t* tree_of, uint32_t n, uint32_t* block_counts) {
+    __shared__ uint32_t wave_n[4];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool head = i < n && f_is_head(codes, tree_of, i);
+    const uint64_t m = __ballot(head);
+    if ((threadIdx.x & 63u) == 0u) wave_n[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0u) block_counts[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+}
+__global__ __launch_bounds__(256) void f_heads_write_kernel(const uint32_t* codes, const uint32_t* tree_of, uint32_t n, const uint32_t* block_base /*scanned*/, uint32_t n_treelets, uint32_t* tl_first /*n_treelets + 1*/,
+                                                            uint32_t* tl_of_pos) {
+    __shared__ uint32_t wave_n[4];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool head = i < n && f_is_head(codes, tree_of, i);
+    const uint64_t m = __ballot(head);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (i >= n) return;
+    uint32_t at = block_base[blockIdx.x] + (uint32_t)__popcll(m & (lane == 0u ? 0ull : (~0ull >> (64u - lane))));   // heads before this position
+    for (uint32_t w = 0; w < wave; w++) at += wave_n[w];
+    if (head) { if (at < n_treelets) tl_first[at] = i; tl_of_pos[i] = at; } else tl_of_pos[i] = at - 1u;   // (position 0 is a head: at >= 1 here)
+    if (i == 0u) tl_first[n_treelets] = n;
+}
+__global__ __launch_bounds__(256) void f_emit_roots_kernel(const uint32_t* tl_first, uint32_t n_treelets, EmitItem* items, uint32_t* lvl, uint32_t* n_items, TreeletInfo* info) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0) { lvl[0] = 0u; lvl[1] = n_treelets; *n_items = n_treelets; }
+    if (t >= n_treelets) return;
+    const uint32_t first = tl_first[t], cnt = tl_first[t + 1u] - first;
+    items[t] = EmitItem{first, cnt, PHD_NONE, t, 29 - 12, 2u, 0u, 0u};
+    info[t] = TreeletInfo{first, cnt, 0u, 0u, 0u, 0u, {0u, 0u}};
+}
+// the treelet roots' boxes, side by side for one read-back
+__global__ __launch_bounds__(256) void f_roots_kernel(const DNode* pool, const uint32_t* tl_first, uint32_t n_treelets, float* rb /*6 per treelet*/) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_treelets) return;
+    const DNode& r = pool[2 * (size_t)tl_first[t]];
+    for (int k = 0; k < 3; k++) { rb[6 * (size_t)t + k] = r.lo[k]; rb[6 * (size_t)t + 3 + k] = r.hi[k]; }
+}
+// K6a, forest: one thread per pool slot (a slot belongs to the treelet of position slot / 2)
+__global__ __launch_bounds__(256) void f_convert_kernel(const DNode* pool, uint32_t n, const uint32_t* tl_of_pos, const uint32_t* tl_first, const uint32_t* tl_dense_base, const uint32_t* tl_out_base, Node64* nodes) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 2u * n) return;
+    const DNode nd = pool[j];
+    if (nd.kid0 == PHD_NONE) return;   // a leaf, or a slot no treelet used (the pool is cleared to 0xFF first)
+    const uint32_t t = tl_of_pos[j >> 1], T0 = tl_first[t];
+    const DNode a = pool[nd.kid0], b = pool[nd.kid1];
+    auto ref = [&](const DNode& c) { return c.kid0 == PHD_NONE ? (PH_LEAF_BIT | (tl_out_base[t] + (c.first - T0))) : tl_dense_base[t] + c.dense; };
+    Node64 o;
+    o.x0[0] = a.lo[0]; o.x0[1] = a.hi[0]; o.y0[0] = a.lo[1]; o.y0[1] = a.hi[1]; o.z0[0] = a.lo[2]; o.z0[1] = a.hi[2];
+    o.x1[0] = b.lo[0]; o.x1[1] = b.hi[0]; o.y1[0] = b.lo[1]; o.y1[1] = b.hi[1]; o.z1[0] = b.lo[2]; o.z1[1] = b.hi[2];
+    o.c0 = ref(a); o.c1 = ref(b); o.axis = nd.axis; o.pad = 0;
+    nodes[tl_dense_base[t] + nd.dense] = o;
+}
+// K6b, forest: leaf records in the final order; an instance's record is what build_bvh writes (prim, PH_TRI_INSTANCE, the rest zero until the scene is uploaded)
+__global__ __launch_bounds__(256) void f_gather_kernel(const uint32_t* ids, const uint32_t* leaf_last, const uint32_t* tl_of_pos, const uint32_t* tl_first, const uint32_t* tl_out_base, uint32_t n, const uint32_t* items,
+                                                       const float* P, const uint32_t* idx, const uint32_t* tri_flags, const uint32_t* tri_mesh, TriRec* tris) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = tl_of_pos[i];
+    const uint32_t q = tl_out_base[t] + (i - tl_first[t]);
+    const uint32_t id = items[ids[i]];
+    const uint32_t last = leaf_last[i] ? PH_TRI_LAST : 0u;
+    TriRec r;
+    if (id & PH_ITEM_INST) {
+        r.p0[0] = r.p0[1] = r.p0[2] = 0.0f; r.prim = id & ~PH_ITEM_INST;
+        r.p1[0] = r.p1[1] = r.p1[2] = 0.0f; r.flags = PH_TRI_INSTANCE | last;
+        r.p2[0] = r.p2[1] = r.p2[2] = 0.0f; r.mesh = 0u;
+    } else {
+        const float* p0 = P + 3 * (size_t)idx[3 * (size_t)id]; const float* p1 = P + 3 * (size_t)idx[3 * (size_t)id + 1]; const float* p2 = P + 3 * (size_t)idx[3 * (size_t)id + 2];
+        r.p0[0] = p0[0]; r.p0[1] = p0[1]; r.p0[2] = p0[2]; r.prim = id;
+        r.p1[0] = p1[0]; r.p1[1] = p1[1]; r.p1[2] = p1[2]; r.flags = ((tri_flags ? tri_flags[id] : 0u) & ~PH_TRI_LAST) | last;
+        r.p2[0] = p2[0]; r.p2[1] = p2[1]; r.p2[2] = p2[2]; r.mesh = tri_mesh ? tri_mesh[id] : 0u;
+    }
+    tris[q] = r;
+}
+
 }  // namespace phd
 
 namespace phost {
@@ -286,9 +461,184 @@ namespace phost {
 #define PHD_CHECK(call)                                                                 \
     do { hipError_t e__ = (call); if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); (void)hipGetLastError(); goto fail; } } while (0)
 
-// Builds the HLBVH of `in` on the current device.  Returns 0, -1 (bad arguments / device failure, `err` says which), -2 (one of the reference's HLBVH assertions fires on this input).
-int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err) {
+// The forest form: the scene's aggregate and the aggregates of its instanced objects, laid out [scene | object | object ..] as build_forest_host lays them out, every kernel over all
+// trees at once.  The host waits for the device where the flat build does — for the number of treelets, for the treelet roots (the SAH over them, per tree, is the host's:
+// hlbvh_forest_stitch.h) and for the result.
+static int build_hlbvh_forest_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, const ForestSpec& F, std::vector<ForestTreeOut>* trees_out) {
+    if (in.n_tris >= 0x3FFFFFFFu || F.n_items >= 0x3FFFFFFFu || F.n_trees == 0 || !F.tree_start || !F.items) { err = "device build: bad arguments (a forest needs its items and tree ranges; at most 2^30 primitives)"; return -1; }
+    const uint32_t n = (uint32_t)F.n_items;
+    if (n == 0) return 0;
+    const uint32_t n_trees = F.n_trees;
+    const uint32_t* tree_start = F.tree_start;
+    for (uint32_t t = 0; t < n_trees; t++) if (tree_start[t] >= tree_start[t + 1] || tree_start[t + 1] > n) { err = "device build: empty or unordered tree range"; return -1; }
+    if (tree_start[0] != 0 || tree_start[n_trees] != n) { err = "device build: tree ranges do not cover the items"; return -1; }
+    const size_t n_inst = F.n_inst;
+    const uint32_t top_end = tree_start[1];
+    if (n_inst && (n_trees < 2 || !F.inst_tree || !F.inst_i2w)) { err = "device build: instances without object trees"; return -1; }
+    for (size_t k = 0; k < n_inst; k++) if (F.inst_tree[k] == 0 || F.inst_tree[k] >= n_trees) { err = "device build: an instance names no object tree"; return -1; }
+    for (uint32_t i = 0; i < n; i++) {   // every index a kernel follows
+        const uint32_t it = F.items[i];
+        if ((it & PH_ITEM_INST) ? (i >= top_end || (size_t)(it & ~PH_ITEM_INST) >= n_inst) : (size_t)it >= in.n_tris) { err = "device build: an item names no triangle or instance"; return -1; }
+    }
+    const uint32_t max_prims = (uint32_t)(max_prims_in_node & 0xff);   // bvh/mod.rs:357 `as u8`
+    auto t0 = std::chrono::steady_clock::now();
+    const bool prof = std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr;
+    auto lap = [&](const char* what) { if (prof) { (void)hipStreamSynchronize(stream); std::fprintf(stderr, "build_hlbvh_forest_device n=%u trees=%u: %-28s at %.3f s\n", n, n_trees, what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } };
+    std::vector<void*> allocs;
+    auto dalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; } allocs.push_back(p); return p; };
+    size_t n_verts = 0;
+    for (size_t i = 0; i < 3 * in.n_tris; i++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[i] + 1);
+    float* dP = (float*)dalloc(n_verts * 12); uint32_t* dIdx = (uint32_t*)dalloc(in.n_tris * 12);
+    uint32_t* d_items = (uint32_t*)dalloc((size_t)n * 4); uint32_t* d_tree_start = (uint32_t*)dalloc(((size_t)n_trees + 1) * 4); uint32_t* tree_of = (uint32_t*)dalloc((size_t)n * 4);
+    uint32_t* d_inst_tree = (uint32_t*)dalloc(n_inst * 4); float* d_i2w = (float*)dalloc(n_inst * 64); float* d_inst_bounds = (float*)dalloc(n_inst * 24);
+    float* blo = (float*)dalloc((size_t)n * 12); float* bhi = (float*)dalloc((size_t)n * 12);
+    uint32_t* tb = (uint32_t*)dalloc((size_t)n_trees * 24);
+    uint32_t* keys[2] = {(uint32_t*)dalloc((size_t)n * 4), (uint32_t*)dalloc((size_t)n * 4)};
+    uint32_t* vals[2] = {(uint32_t*)dalloc((size_t)n * 4), (uint32_t*)dalloc((size_t)n * 4)};
+    uint32_t* codes_keep = (uint32_t*)dalloc((size_t)n * 4);
+    const uint32_t nb = std::min<uint32_t>(1024u, (n + 2047u) / 2048u), per = (((n + nb - 1u) / nb) + 255u) & ~255u;
+    uint32_t* bh = (uint32_t*)dalloc((size_t)256 * nb * 4);
+    const uint32_t n_blocks = (n + 255u) / 256u;
+    uint32_t* head_counts = (uint32_t*)dalloc(((size_t)n_blocks + 1) * 4);
+    uint32_t* tl_of_pos = (uint32_t*)dalloc((size_t)n * 4);
+    uint32_t* leaf_last = (uint32_t*)dalloc((size_t)n * 4);
+    phd::DNode* pool = (phd::DNode*)dalloc((size_t)2 * n * sizeof(phd::DNode));
+    phd::EmitItem* items = (phd::EmitItem*)dalloc((size_t)2 * n * sizeof(phd::EmitItem));
+    uint32_t* lvl = (uint32_t*)dalloc((PHD_MAX_LEVELS + 2) * 4); uint32_t* n_items = (uint32_t*)dalloc(16);
+    uint32_t* d_flags = in.tri_flags ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr; uint32_t* d_mesh = in.tri_mesh ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr;
+    TriRec* d_tris = (TriRec*)dalloc((size_t)n * sizeof(TriRec));
+    std::vector<uint32_t> tb_init((size_t)n_trees * 6);
+    std::vector<phd::TreeletInfo> info;
+    std::vector<float> rb;
+    std::vector<StitchTreelet> tl;
+    StitchPlan plan;
+    uint32_t nt = 0;
+    int rc = -1;
+    for (void* p : allocs) if (!p) { err = "device build: out of device memory"; goto fail; }
+    {
+        for (uint32_t t = 0; t < n_trees; t++) for (int k = 0; k < 3; k++) { tb_init[6 * (size_t)t + k] = 0xFFFFFFFFu; tb_init[6 * (size_t)t + 3 + k] = 0u; }
+        PHD_CHECK(hipMemcpyAsync(dP, in.P, n_verts * 12, hipMemcpyHostToDevice, stream));
+        PHD_CHECK(hipMemcpyAsync(dIdx, in.idx, in.n_tris * 12, hipMemcpyHostToDevice, stream));
+        PHD_CHECK(hipMemcpyAsync(d_items, F.items, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        PHD_CHECK(hipMemcpyAsync(d_tree_start, tree_start, ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, stream));
+        PHD_CHECK(hipMemcpyAsync(tb, tb_init.data(), (size_t)n_trees * 24, hipMemcpyHostToDevice, stream));
+        if (n_inst) {
+            PHD_CHECK(hipMemcpyAsync(d_inst_tree, F.inst_tree, n_inst * 4, hipMemcpyHostToDevice, stream));
+            PHD_CHECK(hipMemcpyAsync(d_i2w, F.inst_i2w, n_inst * 64, hipMemcpyHostToDevice, stream));
+        }
+        if (d_flags) PHD_CHECK(hipMemcpyAsync(d_flags, in.tri_flags, in.n_tris * 4, hipMemcpyHostToDevice, stream));
+        if (d_mesh) PHD_CHECK(hipMemcpyAsync(d_mesh, in.tri_mesh, in.n_tris * 4, hipMemcpyHostToDevice, stream));
+        PHD_CHECK(hipMemsetAsync(head_counts, 0, ((size_t)n_blocks + 1) * 4, stream));
+        PHD_CHECK(hipMemsetAsync(pool, 0xFF, (size_t)2 * n * sizeof(phd::DNode), stream));
+        PHD_CHECK(hipMemsetAsync(leaf_last, 0, (size_t)n * 4, stream));
+        PHD_CHECK(hipMemsetAsync(lvl, 0, (PHD_MAX_LEVELS + 2) * 4, stream));
+        const dim3 g(n_blocks), b(256);
+        lap("allocations and uploads");
+        hipLaunchKernelGGL(phd::f_tree_of_kernel, g, b, 0, stream, d_tree_start, n_trees, n, tree_of);
+        // K1: the objects' trees first — the scene's tree holds TransformedPrimitives, whose bounds are the objects' tree bounds carried to world space
+        if (n > top_end) hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((n - top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, tree_of, top_end, n, blo, bhi, tb);
+        if (n_inst) hipLaunchKernelGGL(phd::f_inst_bounds_kernel, dim3((uint32_t)((n_inst + 255u) / 256u)), b, 0, stream, tb, d_inst_tree, d_i2w, (uint32_t)n_inst, d_inst_bounds);
+        hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, tree_of, 0u, top_end, blo, bhi, tb);
+        hipLaunchKernelGGL(phd::f_morton_kernel, g, b, 0, stream, blo, bhi, n, tb, tree_of, keys[0], codes_keep, vals[0]);
+        int cur = 0;
+        auto sort_pass = [&](int shift) {
+            hipLaunchKernelGGL(phd::rs_hist_kernel, dim3(nb), dim3(PHD_RS_BLOCK), 0, stream, keys[cur], n, per, shift, bh);
+            hipLaunchKernelGGL(phd::scan_kernel, dim3(1), dim3(1024), 0, stream, bh, 256u * nb);
+            hipLaunchKernelGGL(phd::rs_scatter_kernel, dim3(nb), dim3(PHD_RS_BLOCK), 0, stream, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, per, shift, bh);
+            cur ^= 1;
+        };
+        for (int pass = 0; pass < 4; pass++) sort_pass(pass * 8);   // K3: by the 30-bit code ..
+        if (n_trees > 1) {                                          // .. then by the tree, as many digits as n_trees - 1 has
+            hipLaunchKernelGGL(phd::f_lookup_kernel, g, b, 0, stream, vals[cur], tree_of, n, keys[cur]);
+            for (int shift = 0; shift < 32 && ((n_trees - 1u) >> shift) != 0u; shift += 8) sort_pass(shift);
+        }
+        uint32_t* ids = vals[cur]; uint32_t* codes = keys[cur];
+        hipLaunchKernelGGL(phd::f_lookup_kernel, g, b, 0, stream, ids, codes_keep, n, codes);
+        // K4: run heads, counted and compacted
+        hipLaunchKernelGGL(phd::f_heads_count_kernel, g, b, 0, stream, codes, tree_of, n, head_counts);
+        hipLaunchKernelGGL(phd::scan_kernel, dim3(1), dim3(1024), 0, stream, head_counts, n_blocks + 1u);
+        PHD_CHECK(hipGetLastError());
+        PHD_CHECK(hipMemcpyAsync(&nt, head_counts + n_blocks, 4, hipMemcpyDeviceToHost, stream));
+        PHD_CHECK(hipStreamSynchronize(stream));
+        lap("bounds, codes, sort, heads");
+        if (nt == 0 || nt > n) { err = "device build: treelet count out of range"; goto fail; }
+        uint32_t* d_tl_first = (uint32_t*)dalloc(((size_t)nt + 1) * 4); uint32_t* d_tl_dense = (uint32_t*)dalloc((size_t)nt * 4); uint32_t* d_tl_out = (uint32_t*)dalloc((size_t)nt * 4);
+        phd::TreeletInfo* d_info = (phd::TreeletInfo*)dalloc((size_t)nt * sizeof(phd::TreeletInfo)); float* d_rb = (float*)dalloc((size_t)nt * 24);
+        if (!d_tl_first || !d_tl_dense || !d_tl_out || !d_info || !d_rb) { err = "device build: out of device memory"; goto fail; }
+        const dim3 gt((nt + 255u) / 256u);
+        hipLaunchKernelGGL(phd::f_heads_write_kernel, g, b, 0, stream, codes, tree_of, n, head_counts, nt, d_tl_first, tl_of_pos);
+        hipLaunchKernelGGL(phd::f_emit_roots_kernel, gt, b, 0, stream, d_tl_first, nt, items, lvl, n_items, d_info);
+        {   // K5: emit_lbvh, level by level, over the treelets of all trees
+            auto grid_of = [&](int L) { const uint64_t most = std::min<uint64_t>((uint64_t)n, (uint64_t)nt << std::min(L, 24)); return dim3((uint32_t)((most + 255u) / 256u)); };
+            for (int L = 0; L < PHD_MAX_LEVELS; L++) {
+                hipLaunchKernelGGL(phd::emit_level_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, n_items, codes, max_prims, pool, leaf_last, d_info);
+                hipLaunchKernelGGL(phd::emit_close_level_kernel, dim3(1), dim3(64), 0, stream, lvl, L, n_items);
+            }
+            for (int L = PHD_MAX_LEVELS - 1; L >= 0; L--) hipLaunchKernelGGL(phd::emit_up_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, ids, blo, bhi, pool);
+            for (int L = 0; L < PHD_MAX_LEVELS; L++) hipLaunchKernelGGL(phd::emit_down_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, pool, d_info);
+        }
+        hipLaunchKernelGGL(phd::f_roots_kernel, gt, b, 0, stream, pool, d_tl_first, nt, d_rb);
+        PHD_CHECK(hipGetLastError());
+        info.resize(nt); rb.resize(6 * (size_t)nt);
+        PHD_CHECK(hipMemcpyAsync(info.data(), d_info, (size_t)nt * sizeof(phd::TreeletInfo), hipMemcpyDeviceToHost, stream));
+        PHD_CHECK(hipMemcpyAsync(rb.data(), d_rb, (size_t)nt * 24, hipMemcpyDeviceToHost, stream));
+        PHD_CHECK(hipStreamSynchronize(stream));
+        lap("treelets");
+        tl.resize(nt);
+        for (uint32_t t = 0; t < nt; t++) {
+            StitchTreelet& q = tl[t];
+            q.first = info[t].first; q.n = info[t].n; q.interior = info[t].interior; q.leaves = info[t].leaves; q.max_leaf = info[t].max_leaf; q.depth = info[t].depth;
+            for (int k = 0; k < 3; k++) { q.lo[k] = rb[6 * (size_t)t + k]; q.hi[k] = rb[6 * (size_t)t + 3 + k]; }
+        }
+        const int prc = plan_hlbvh_forest(tl.data(), nt, tree_start, n_trees, plan);
+        if (prc == -2) { rc = -2; err = "the reference's HLBVH build asserts on this input (hlbvh.rs:338/356/418)"; goto fail; }
+        if (prc != 0) { err = "device build: the treelets do not tile the trees"; goto fail; }
+        lap("SAH over the treelet roots");
+        out.interior_nodes = plan.interior_nodes;
+        Node64* d_nodes = (Node64*)dalloc(std::max<size_t>(out.interior_nodes, 1) * sizeof(Node64));
+        if (!d_nodes) { err = "device build: out of device memory"; goto fail; }
+        PHD_CHECK(hipMemcpyAsync(d_tl_dense, plan.dense_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
+        PHD_CHECK(hipMemcpyAsync(d_tl_out, plan.out_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(phd::f_convert_kernel, dim3((uint32_t)(((uint64_t)2 * n + 255u) / 256u)), b, 0, stream, pool, n, tl_of_pos, d_tl_first, d_tl_dense, d_tl_out, d_nodes);
+        hipLaunchKernelGGL(phd::f_gather_kernel, g, b, 0, stream, ids, leaf_last, tl_of_pos, d_tl_first, d_tl_out, n, d_items, dP, dIdx, d_flags, d_mesh, d_tris);
+        PHD_CHECK(hipGetLastError());
+        out.nodes.resize(out.interior_nodes);
+        out.tris.resize(n);
+        if (out.interior_nodes) PHD_CHECK(hipMemcpyAsync(out.nodes.data(), d_nodes, out.interior_nodes * sizeof(Node64), hipMemcpyDeviceToHost, stream));
+        PHD_CHECK(hipMemcpyAsync(out.tris.data(), d_tris, (size_t)n * sizeof(TriRec), hipMemcpyDeviceToHost, stream));
+        PHD_CHECK(hipStreamSynchronize(stream));
+        lap("nodes, records, downloads");
+        place_upper_nodes(plan, out.nodes.data());
+        {   // the host builder's node numbering, tree by tree (trees are independent: spread them over a few threads where there is much to do)
+            const uint32_t n_thr = out.interior_nodes >= (1u << 18) ? std::min<uint32_t>(std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency())), n_trees) : 1u;
+            std::vector<uint32_t> cut(n_thr + 1, n_trees);   // cut the trees into runs of about equal node counts
+            cut[0] = 0;
+            for (uint32_t k = 1, t = 0; k < n_thr; k++) { const uint64_t want = (uint64_t)out.interior_nodes * k / n_thr; while (t < n_trees && plan.node_base[t] < want) t++; cut[k] = t; }
+            ThreadGroup th;
+            for (uint32_t k = 1; k < n_thr; k++) if (cut[k + 1] > cut[k]) th.run([&plan, &out, a = cut[k], e = cut[k + 1]]() { renumber_like_host(plan, out.nodes.data(), a, e); });
+            renumber_like_host(plan, out.nodes.data(), cut[0], cut[1]);
+            th.join();
+        }
+        lap("numbering");
+        out.root_ref = plan.trees[0].root_ref;
+        for (int k = 0; k < 3; k++) { out.root_lo[k] = plan.trees[0].lo[k]; out.root_hi[k] = plan.trees[0].hi[k]; }
+        if (trees_out) *trees_out = plan.trees;
+        out.leaf_nodes = plan.leaf_nodes; out.max_leaf_prims = plan.max_leaf_prims; out.max_depth = plan.max_depth;   // over all trees of the forest
+        out.total_nodes = out.interior_nodes + out.leaf_nodes;
+        out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        rc = 0;
+    }
+fail:
+    for (void* p : allocs) if (p) (void)hipFree(p);
+    return rc;
+}
+
+// Builds the HLBVH of `in` on the current device — or, with `forest`, the scene's aggregate and the aggregates of its instanced objects in one go.
+// Returns 0, -1 (bad arguments / device failure, `err` says which), -2 (one of the reference's HLBVH assertions fires on this input).
+int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, const ForestSpec* forest, std::vector<ForestTreeOut>* trees_out) {
     out = BuildOutput();
+    if (trees_out) trees_out->clear();
+    if (forest) return build_hlbvh_forest_device(in, max_prims_in_node, stream, out, err, *forest, trees_out);
     if (in.items || in.n_tris >= 0x3FFFFFFFu) { err = "device build: instanced scenes and more than 2^30 triangles take the host builder"; return -1; }
     const uint32_t n = (uint32_t)in.n_tris;
     if (n == 0) return 0;

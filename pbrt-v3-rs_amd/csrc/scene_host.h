@@ -124,7 +124,9 @@ int launch_traverse(PbrtHipScene* s, bool anyhit, const void* d_rays, void* d_ou
 void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p);  // 0 closest, 1 any hit, 2 both (MIXED)
 int ensure_traversal_workspace(PbrtHipScene* s);
 void free_wavefront(PbrtHipScene* s);
-int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err);   // bvh_device.hip
+// bvh_device.hip.  forest non-null: the forest form, as build_sah_device's below (the arrays come back on the host)
+int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, const ForestSpec* forest = nullptr,
+                       std::vector<ForestTreeOut>* trees_out = nullptr);
 // bvh_sah_device.hip.  keep_nodes / keep_tris non-null: the Node64 / TriRec arrays are not copied to `out` but handed over as device allocations (the caller frees them)
 // forest non-null: the scene's aggregate and its instanced objects' aggregates in one build, laid out as build_forest_host lays them out; trees_out: every tree's root
 int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, void** keep_nodes = nullptr, void** keep_tris = nullptr,
