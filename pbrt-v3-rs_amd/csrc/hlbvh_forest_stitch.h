@@ -1,10 +1,12 @@
-// The host's share of the HLBVH forest build on the device (bvh_device.hip): the kernels make every treelet of every tree of a forest [scene | object | object ..]; what is
-// left is per TREE — the SAH over that tree's treelet roots (hlbvh.rs:296-432, build_upper_sah), where each treelet's interior nodes and leaf records go in the forest's arrays,
-// the SAH nodes themselves, and the host builder's node numbering.  Plain C++, no device code: scripts/hlbvh_forest_stitch_check.cpp runs it on the CPU against build_forest_host.
+// The host's share of the HLBVH build on the device (bvh_device.hip): the kernels make every treelet of every tree of a forest [scene | object | object ..] — a scene without
+// object instances is a forest of one tree; what is left is per TREE — the SAH over that tree's treelet roots (hlbvh.rs:296-432, build_upper_sah), where each treelet's
+// interior nodes and leaf records go in the forest's arrays, the SAH nodes themselves, and, for a forest with objects, the host builder's node numbering.  Plain C++, no device
+// code: scripts/hlbvh_forest_stitch_check.cpp runs it on the CPU against build_forest_host.
 //
 // Numbering.  The kernels number a treelet's interior nodes in the recursion's creation order (a node, its whole first subtree, the second), a tree's nodes as
-// [SAH nodes | treelet 0's | treelet 1's ..].  build_bvh numbers a tree as it walks it depth first and gives BOTH interior children of a node their numbers when it visits
-// the node (bvh_build.cpp), so renumber_like_host walks every tree once more and permutes it: afterwards the arrays are build_forest_host's entry by entry.
+// [SAH nodes | treelet 0's | treelet 1's ..].  A scene of one tree ships in that numbering.  build_bvh numbers a tree as it walks it depth first and gives BOTH interior children
+// of a node their numbers when it visits the node (bvh_build.cpp), so for a forest renumber_like_host walks every tree once more and permutes it: afterwards the arrays are
+// build_forest_host's entry by entry.
 #pragma once
 #include "bvh_build.h"
 #include <algorithm>

@@ -2,6 +2,7 @@
 // tree's treelet roots, the offsets that make per-tree numbers forest-wide references, and the host builder's node numbering.  The kernels' share — bounds, Morton codes, the
 // stable sort by (tree, code), the treelets with their nodes in the recursion's creation order — is restated here in plain C++ (as bvh_device.hip does it, hlbvh.rs:62-294), so the
 // whole build runs without a GPU and is compared with build_forest_host(.., split_method = 1, ..) on the same input: roots, bounds, n_items, every node and every leaf record.
+// A scene without objects is a forest of one tree, which the device build ships in the kernels' numbering: for those the array BEFORE renumber_like_host is compared too.
 // Built with the address and undefined-behaviour sanitizers by hlbvh_forest_stitch_check.sh; prints one line per case, exit status 1 on any difference.
 #include "../pbrt-v3-rs_amd/csrc/hlbvh_forest_stitch.h"
 #include <cstdio>
@@ -86,6 +87,29 @@ struct Emit {
 
 static int g_bad = 0;
 #define EXPECT(c, ...) do { if (!(c)) { if (g_bad++ < 20) { std::printf("MISMATCH %s: ", name); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
+
+static bool same_boxes(const Node64& a, const Node64& b) {
+    bool same = true;
+    for (int q = 0; q < 2; q++) same = same && a.x0[q] == b.x0[q] && a.y0[q] == b.y0[q] && a.z0[q] == b.z0[q] && a.x1[q] == b.x1[q] && a.y1[q] == b.y1[q] && a.z1[q] == b.z1[q];
+    return same;
+}
+// two trees in different numberings, walked from their roots in step: boxes, axes and leaf references node for node (interior references are followed, not compared)
+static void walk_in_step(const char* name, const std::vector<Node64>& a, uint32_t root_a, const std::vector<Node64>& b, uint32_t root_b) {
+    std::vector<std::pair<uint32_t, uint32_t>> stack(1, std::make_pair(root_a, root_b));
+    size_t seen = 0;
+    while (!stack.empty() && seen <= a.size()) {
+        const std::pair<uint32_t, uint32_t> it = stack.back(); stack.pop_back();
+        if ((it.first | it.second) & PH_LEAF_BIT) { EXPECT(it.first == it.second, "in step: leaf reference %08x, host %08x", it.first, it.second); continue; }
+        EXPECT(it.first < a.size() && it.second < b.size(), "in step: reference %u / %u past the arrays", it.first, it.second);
+        if (it.first >= a.size() || it.second >= b.size()) continue;
+        seen++;
+        const Node64& p = a[it.first]; const Node64& q = b[it.second];
+        EXPECT(p.axis == q.axis, "in step: node %u axis %u, host node %u axis %u", it.first, p.axis, it.second, q.axis);
+        EXPECT(same_boxes(p, q), "in step: node %u and host node %u: child boxes differ", it.first, it.second);
+        stack.push_back({p.c1, q.c1}); stack.push_back({p.c0, q.c0});
+    }
+    EXPECT(seen == a.size() && seen == b.size(), "in step: %zu nodes reached of %zu, host %zu", seen, a.size(), b.size());
+}
 
 static void check(const char* name, Scene& sc, int max_prims, bool want_single_treelets, bool want_lone_object) {
     InstancedScene isc{sc.obj_tri0.data(), sc.obj_tri1.data(), sc.obj_tri0.size(), sc.inst_object.data(), sc.inst_i2w.data(), sc.inst_object.size(), sc.top_items.data(), sc.top_items.size()};
@@ -172,6 +196,10 @@ static void check(const char* name, Scene& sc, int max_prims, bool want_single_t
         for (uint32_t i = tl[t].first; i < tl[t].first + tl[t].n; i++) rec_prim[plan.out_base[t] + (i - tl[t].first)] = L.items[ids[i]];
     }
     place_upper_nodes(plan, nodes.data());
+    if (sc.obj_tri0.empty()) {   // one tree: this is the array the device build ships
+        EXPECT(n_trees == 1, "%u trees, the case wants one", n_trees);
+        walk_in_step(name, nodes, plan.trees[0].root_ref, want.nodes, want_trees[0].root_ref);
+    }
     renumber_like_host(plan, nodes.data(), 0, n_trees);
     // ---- against build_forest_host ----
     EXPECT(plan.interior_nodes == want.interior_nodes && plan.leaf_nodes == want.leaf_nodes && plan.max_leaf_prims == want.max_leaf_prims && plan.max_depth == want.max_depth,
@@ -185,9 +213,7 @@ static void check(const char* name, Scene& sc, int max_prims, bool want_single_t
     for (size_t v = 0; v < std::min(nodes.size(), want.nodes.size()); v++) {
         const Node64& a = nodes[v]; const Node64& b = want.nodes[v];
         EXPECT(a.c0 == b.c0 && a.c1 == b.c1 && a.axis == b.axis, "node %zu: children %08x %08x axis %u, host %08x %08x %u", v, a.c0, a.c1, a.axis, b.c0, b.c1, b.axis);
-        bool same = true;
-        for (int q = 0; q < 2; q++) same = same && a.x0[q] == b.x0[q] && a.y0[q] == b.y0[q] && a.z0[q] == b.z0[q] && a.x1[q] == b.x1[q] && a.y1[q] == b.y1[q] && a.z1[q] == b.z1[q];
-        EXPECT(same, "node %zu: child boxes differ", v);
+        EXPECT(same_boxes(a, b), "node %zu: child boxes differ", v);
     }
     for (uint32_t i = 0; i < n; i++) {
         const bool inst = (rec_prim[i] & PH_ITEM_INST) != 0;
@@ -241,6 +267,12 @@ int main() {
         s.obj_tri1.push_back((uint32_t)(s.idx.size() / 3));
         s.instance(0); s.top_tri(6.0f); s.instance(0, true);
         for (int mp : {1, 4}) check("deep treelets", s, mp, false, false);
+    }
+    for (int n : {1, 2, 3, 17, 300, 5000}) {   // no objects: one tree of scene-level triangles, as a scene without instances is built
+        Scene s;
+        for (int k = 0; k < n; k++) s.top_tri(10.0f);
+        const std::string name = "one tree of " + std::to_string(n);
+        for (int mp : {1, 4}) check(name.c_str(), s, mp, false, false);
     }
     if (g_bad) { std::printf("%d mismatches\n", g_bad); return 1; }
     std::printf("all equal\n");

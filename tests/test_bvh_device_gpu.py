@@ -1,6 +1,7 @@
 """-m gpu: the trees built on the device — HLBVH (csrc/bvh_device.hip: hlbvh.rs + morton.rs as kernels) and SAH, the reference's default (csrc/bvh_sah_device.hip: sah.rs one
 tree level per round of kernels) — against the host builder and the oracle.  Same leaves in the same depth-first order, same leaf ends, the same child boxes, the same root
-bound (for SAH: the same node array, entry by entry) — so hits cannot depend on where the tree was built."""
+bound and statistics (for SAH: the same node array, entry by entry; for HLBVH, whose single tree keeps the kernels' node numbering: the same tree node for node, both walked
+from their roots in step) — so hits cannot depend on where the tree was built."""
 import ctypes as C
 
 import numpy as np
@@ -13,7 +14,7 @@ from oracle_binding import OracleScene
 pytestmark = pytest.mark.gpu
 
 
-def _build(lib, which, P, idx, n_tris, max_prims, split=1):
+def _build(lib, which, P, idx, n_tris, max_prims, split=1, may_refuse=False):
     order = np.zeros(n_tris, np.uint32); last = np.zeros(n_tris, np.uint32)
     nodes = np.zeros((max(n_tris - 1, 1), 16), np.uint32); info = np.zeros(5, np.uint64); rb = np.zeros(6, np.float32)
     if which == "host":
@@ -22,25 +23,46 @@ def _build(lib, which, P, idx, n_tris, max_prims, split=1):
     else:
         lib.pbrt_hip_device_build_bvh.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         rc = lib.pbrt_hip_device_build_bvh(0, P.ctypes.data, idx.ctypes.data, n_tris, split, max_prims, order.ctypes.data, last.ctypes.data, nodes.ctypes.data, info.ctypes.data, rb.ctypes.data, None)
+    if may_refuse and rc != 0:
+        return dict(rc=rc)
     assert rc == 0, rc
     f = nodes.view(np.float32)
     n_int = int(info[0])
     boxes = {(f[k, c], f[k, c + 2], f[k, c + 4], f[k, c + 1], f[k, c + 3], f[k, c + 5]) for k in range(n_int) for c in (0, 6)}
     ends = np.flatnonzero(last); starts = np.concatenate([[0], ends[:-1] + 1]) if len(ends) else np.zeros(0, int)
     leaves = [tuple(order[a:b + 1]) for a, b in zip(starts, ends)]
-    return dict(order=order, last=last, info=info[:3].copy(), info5=info.copy(), rb=rb, boxes=boxes, leaves=leaves, nodes=nodes[:n_int].copy())
+    return dict(rc=rc, order=order, last=last, info=info[:3].copy(), info5=info.copy(), rb=rb, boxes=boxes, leaves=leaves, nodes=nodes[:n_int].copy())
 
 
-@pytest.mark.parametrize("n_tris,seed,max_prims", [(1, 1, 4), (2, 1, 4), (3, 5, 4), (17, 2, 4), (300, 8, 2), (5000, 3, 4), (5000, 4, 1), (20000, 6, 8), (300000, 7, 4)])
-def test_device_hlbvh_equals_host_and_oracle(host, product, n_tris, seed, max_prims):
-    P, idx = host.gen_random_tris(n_tris, seed)
-    h = _build(product.lib, "host", P, idx, n_tris, max_prims)
-    d = _build(product.lib, "device", P, idx, n_tris, max_prims)
+def _assert_same_tree(d, h):
+    """The two node arrays walked from their roots in step, a level at a time: every pair of nodes has the same twelve planes as floats, the same axis and the same leaf
+    references; interior references are followed, not compared (the numberings differ)."""
+    a, b = np.array([d["info5"][4]], np.uint32), np.array([h["info5"][4]], np.uint32)
+    seen = 0
+    while len(a):
+        leaf = ((a | b) & 0x80000000) != 0
+        assert np.array_equal(a[leaf], b[leaf]), "leaf references differ"
+        a, b = a[~leaf], b[~leaf]
+        seen += len(a)
+        assert seen <= len(d["nodes"]) and (a < len(d["nodes"])).all() and (b < len(h["nodes"])).all()
+        na, nb = d["nodes"][a], h["nodes"][b]
+        assert np.array_equal(na[:, :12].view(np.float32), nb[:, :12].view(np.float32)), "child boxes differ"
+        assert np.array_equal(na[:, 14], nb[:, 14]), "split axes differ"
+        a, b = np.concatenate([na[:, 12], na[:, 13]]), np.concatenate([nb[:, 12], nb[:, 13]])
+    assert seen == len(d["nodes"]) == len(h["nodes"])
+
+
+def _check_hlbvh(lib, P, idx, max_prims, h=None):
+    n_tris = len(idx) // 3
+    h = h or _build(lib, "host", P, idx, n_tris, max_prims)
+    d = _build(lib, "device", P, idx, n_tris, max_prims)
     assert np.array_equal(d["order"], h["order"]), "primitive order differs"
     assert np.array_equal(d["last"], h["last"]), "leaf ends differ"
     assert np.array_equal(d["info"], h["info"])          # interior nodes, leaves, largest leaf
+    assert np.array_equal(d["info5"], h["info5"])        # .. and depth, root reference
     assert np.array_equal(d["rb"], h["rb"])
     assert d["boxes"] == h["boxes"]
+    _assert_same_tree(d, h)
     if n_tris <= 20000:
         orc = OracleScene()
         m = orc.add_material_matte(); orc.add_mesh(P, idx, m); orc.build_accel(1, max_prims)
@@ -50,6 +72,35 @@ def test_device_hlbvh_equals_host_and_oracle(host, product, n_tris, seed, max_pr
         assert d["leaves"] == [tuple(oprims[l["offset"]:l["offset"] + l["n_primitives"]]) for l in ol]
         if len(onodes) > 1:
             assert d["boxes"] == {tuple(n["pmin"]) + tuple(n["pmax"]) for n in onodes[1:]}
+    return d
+
+
+# (256 / 257: a block of the treelet-head count exactly full, and one item into the second block; 255: leaves far larger than usual)
+@pytest.mark.parametrize("n_tris,seed,max_prims", [(1, 1, 4), (2, 1, 4), (3, 5, 4), (17, 2, 4), (300, 8, 2), (5000, 3, 4), (5000, 4, 1), (20000, 6, 8), (300000, 7, 4),
+                                                   (256, 1, 4), (257, 1, 4), (513, 2, 1), (20000, 9, 255)])
+def test_device_hlbvh_equals_host_and_oracle(host, product, n_tris, seed, max_prims):
+    P, idx = host.gen_random_tris(n_tris, seed)
+    _check_hlbvh(product.lib, P, idx, max_prims)
+
+
+@pytest.mark.parametrize("max_prims", [1, 4])
+def test_device_hlbvh_one_treelet_without_a_splitting_bit(product, max_prims):
+    """40 triangles that share one centroid (one triangle scaled about the centre of its bound): equal codes, one treelet, one leaf whatever max_prims is."""
+    base = np.array([[-1, -1, -1], [1, 1, 1], [0.25, -0.5, 0.125]], np.float32)      # bound (-1 .. 1)^3, centroid 0
+    P = np.concatenate([base * np.float32(0.1 + 0.02 * k) for k in range(40)]); idx = np.arange(120, dtype=np.uint32)
+    d = _check_hlbvh(product.lib, P, idx, max_prims)
+    assert list(d["info5"][:3]) == [0, 1, 40] and d["leaves"] == [tuple(range(40))]
+
+
+def test_device_hlbvh_one_deep_treelet(product):
+    """241 triangles in one treelet of many levels: the mesh's bound is the unit cube and the centroids are 0.5 + j * 2^-24 per axis, j < 64 — the scaled offsets 512 + j * 2^-14
+    differ in the low six bits of their bit patterns only (quirk B10), so the top 12 code bits agree; max_prims 1 splits the treelet down to its distinct codes."""
+    rng = np.random.default_rng(3)
+    ctr = (np.float32(0.5) + rng.integers(0, 64, (240, 3)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+    tris = np.stack([ctr - np.float32(0.125), ctr + np.float32(0.125), ctr], 1)
+    P = np.concatenate([np.array([[0, 0, 0], [1, 1, 1], [0.5, 0.25, 0.75]], np.float32), tris.reshape(-1, 3)]).astype(np.float32); idx = np.arange(3 * 241, dtype=np.uint32)
+    d = _check_hlbvh(product.lib, np.ascontiguousarray(P), idx, 1)
+    assert d["info5"][3] >= 8          # many levels of emit_lbvh below the one treelet root
 
 
 def _awkward_tris(n_tris, seed, mode):
@@ -75,6 +126,19 @@ def _awkward_tris(n_tris, seed, mode):
         return np.ascontiguousarray(P), idx
     P = (c[:, None, :] + d).reshape(-1, 3).astype(np.float32)
     return np.ascontiguousarray(P), np.arange(3 * n_tris, dtype=np.uint32)
+
+
+def test_device_hlbvh_refuses_what_the_host_refuses(product):
+    """A regular grid of quads in a plane: where the reference's HLBVH assertions fire in the SAH over the treelet roots the host builder returns -2 — then so does the device
+    build; where the host builds the tree, the device builds the same."""
+    P, idx = _awkward_tris(20000, 1, 3)
+    n_tris = len(idx) // 3
+    h = _build(product.lib, "host", P, idx, n_tris, 4, may_refuse=True)
+    if h["rc"] == -2:
+        assert _build(product.lib, "device", P, idx, n_tris, 4, may_refuse=True)["rc"] == -2
+    else:
+        assert h["rc"] == 0
+        _check_hlbvh(product.lib, P, idx, 4, h=h)
 
 
 @pytest.mark.parametrize("n_tris,seed,max_prims,mode", [(1, 1, 4, 0), (2, 1, 4, 0), (3, 5, 4, 0), (5, 2, 1, 0), (17, 2, 4, 0), (300, 8, 2, 0), (5000, 3, 4, 0), (5000, 4, 1, 0), (20000, 6, 8, 0),
