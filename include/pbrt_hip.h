@@ -168,9 +168,11 @@ int pbrt_hip_add_instance(PbrtHipScene*, uint32_t object_id, const float instanc
  *                             a, b = zmin, zmax), 3 Disk::new (disk.rs:21-40; a = height, b = innerradius)
  * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: a quadric between object_begin and object_end; a quadric right after pbrt_hip_add_light_diffuse_area lights that no mesh
  * has claimed (it would be the area light's shape; a sphere light is made by pbrt_hip_add_sphere_light, the other quadrics' Shape::sample is not provided); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a
- * quadric.  pbrt_hip_build_accel refuses a scene that holds quadrics together with object definitions or instances; pbrt_hip_build_accel_device refuses any scene
- * with a quadric (the host builders make its tree).  Quadrics and triangle meshes with alpha / shadow-alpha textures share a scene freely: the masks belong to the meshes'
- * triangles, a quadric in the same leaf is tested in its place in the leaf's order. */
+ * quadric.  Scene-level quadrics and object instances share a scene freely (instanced triangle objects, single-primitive and empty ones included; definitions that no instance
+ * uses are ignored, as in any instanced scene): a quadric stands in the scene-level tree next to the instances and is tested in its place in its leaf's order.  One leftover
+ * refusal, with no technical reason and kept only because older tests pin it: pbrt_hip_build_accel returns PBRT_HIP_ERR_UNSUPPORTED for a scene that holds a quadric and object
+ * definitions but NOT ONE instance.  pbrt_hip_build_accel_device refuses any scene with a quadric (the host builders make its tree, forest included).  Quadrics and triangle
+ * meshes with alpha / shadow-alpha textures share a scene freely: the masks belong to the meshes' triangles, a quadric in the same leaf is tested in its place in the leaf's order. */
 int pbrt_hip_add_sphere(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
                         uint32_t material_id, uint32_t flags);
 int pbrt_hip_add_hyperboloid(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], const float p1[3], const float p2[3], float phi_max_deg,

@@ -337,6 +337,10 @@ static __device__ __forceinline__ bool alpha_accept_lean(const DeviceScene& sc, 
 //   QUADRIC with ALPHA != 0 (quadrics beside alpha-masked meshes): a quadric record carries no PH_TRI_ALPHATEX (set_last_mesh_alpha_textures refuses a quadric), so a lane at one never sets
 //   alpha_wait and a waiting lane always stands at a triangle.  The leaf step has ONE test site for both (a second copy of the test gave wrong hits on this toolchain); a lane
 //   tests its leaf's records one at a time in the leaf's order, so a quadric accepted ahead of a masked triangle has shortened t_max before that triangle is tested (and re-tested).
+//   QUADRIC with INST (scene-level quadrics among object instances): a leaf record is an instance record, a quadric record or a triangle.  A quadric record exists only in the scene-level
+//   tree, so the lane that meets one is in no instance (in_inst == 0), its RayState is the world-space ray's and its direction is wdx, wdy, wdz — no second fetch from the queue.  Order along
+//   the ray is the leaf's: a quadric accepted ahead of an instance record has shortened t_max before xf_ray carries it into the instance, a hit inside an instance has shortened it before a
+//   later quadric of the leaf is tested; an accepted quadric leaves hit_inst = 0 (`in_inst & ...` at scene level), also after an earlier hit inside an instance.
 // WPE > 0 compiles the kernel for exactly that many waves per SIMD (= resident 256-thread blocks per CU): the register allocator then fits the budget
 // (7: 72 VGPRs, 8: 64) instead of taking what it likes; 0 leaves the choice to the compiler (same code as before).
 //
@@ -380,6 +384,12 @@ struct ShapeQuadric : ShapeFlat { static constexpr bool quadric = true; static c
 // LDS value stack and noise table beside the traversal stack (24 576 + 18 432 + 512 B = 43 520 B per block, as ShapeAlphaGeneral<false>) — DESIGN §4.4 has the numbers.
 struct ShapeQuadricAlphaLean : ShapeQuadric { static constexpr int alpha = 1, alpha_min = 12; };
 struct ShapeQuadricAlphaGeneral : ShapeQuadric { static constexpr int alpha = 2, alpha_min = 12; };
+// Quadrics in scenes with object instances: the instancing rows' loops (leaf / refill thresholds, node steps, the 11-entry LDS stack that keeps spill_lds_depth(true) at 11) with the
+// analytic test out of line and the occupancy left to the compiler, as in ShapeQuadric.  LDS per block: 11 x 256 x 8 B of stack + 9 x 256 x 4 B of inst_save = 31 744 B; the general-alpha
+// row adds the evaluator's value stack and noise table, 12 entries of stack as ShapeAlphaGeneral<true>: 24 576 + 9 216 + 18 432 + 512 = 52 736 B of the 65 536 a block may have.
+struct ShapeInstQuadric : ShapeInst { static constexpr bool quadric = true; static constexpr int wpe = 0; };
+struct ShapeInstQuadricAlphaLean : ShapeInstAlphaLean { static constexpr bool quadric = true; static constexpr int wpe = 0; };
+struct ShapeInstQuadricAlphaGeneral : ShapeAlphaGeneral<true> { static constexpr bool quadric = true; };
 // The counting builds (pbrt_hip_set_traversal_counting): the default loop with the scene's features.
 template <bool INST, int ALPHA, bool QUADRIC = false> struct ShapeCount : ShapeDefaults { static constexpr bool count = true, inst = INST, quadric = QUADRIC; static constexpr int alpha = ALPHA; };
 
@@ -392,10 +402,11 @@ template <class... S> struct ShapeTable {
 };
 using TravShapes = ShapeTable<ShapeFlat, ShapeInst, ShapeFlatAlphaLean, ShapeInstAlphaLean, ShapeAlphaGeneral<false>, ShapeAlphaGeneral<true>, ShapeQuadric,
                               ShapeCount<false, 0>, ShapeCount<true, 0>, ShapeCount<false, 1>, ShapeCount<true, 1>, ShapeCount<false, 2>, ShapeCount<true, 2>, ShapeCount<false, 0, true>,
-                              ShapeQuadricAlphaLean, ShapeQuadricAlphaGeneral, ShapeCount<false, 1, true>, ShapeCount<false, 2, true>>;
+                              ShapeQuadricAlphaLean, ShapeQuadricAlphaGeneral, ShapeCount<false, 1, true>, ShapeCount<false, 2, true>,
+                              ShapeInstQuadric, ShapeInstQuadricAlphaLean, ShapeInstQuadricAlphaGeneral, ShapeCount<true, 0, true>, ShapeCount<true, 1, true>, ShapeCount<true, 2, true>>;
 // The scene's row of TravShapes.  alpha: 0 no alpha-mask textures, 1 image-map masks only (the inlined test), 2 any texture class (the general evaluator out of line).
-// A scene with quadrics has no instances (build_accel refuses it otherwise); it may have alpha-mask textures on its triangle meshes, and its row follows their class.
-constexpr int pick_shape(bool inst, int alpha, bool quadric, bool count) { return quadric ? TravShapes::find(false, alpha, true, count) : TravShapes::find(inst, alpha, false, count); }
+// Every combination of (instances, alpha class, quadrics, counting) has its row: a scene with quadrics may hold object instances and alpha-mask textures on its triangle meshes.
+constexpr int pick_shape(bool inst, int alpha, bool quadric, bool count) { return TravShapes::find(inst, alpha, quadric, count); }
 constexpr bool every_scene_has_a_shape() {
     for (int k = 0; k < 24; k++) if (pick_shape(k & 1, (k >> 1) % 3, k >= 12, k % 12 >= 6) < 0) return false;
     return true;
@@ -410,7 +421,6 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
     static_assert(MODE == TRAV_CLOSEST || MODE == TRAV_ANY || MODE == TRAV_MIXED, "no such mode");
     static_assert(LDS_DEPTH >= TravShapes::spill_lds_depth(INST), "the spill region starts at the shallowest LDS stack of the table's rows: a shape outside the table would write past it");
     static_assert(ALPHA_MIN == 0 || ALPHA != 0, "the alpha phase needs an alpha test");
-    static_assert(!QUADRIC || !INST, "build_accel refuses quadrics together with instances: no such kernel");
     __shared__ uint2 lds_stack[LDS_DEPTH][PH_TRAV_BLOCK];
     // INST: the scene-level ray's origin and what ray_setup derived from it (six IEEE divides), parked while the lane walks an instance: leaving an instance is then nine LDS reads instead of
     // a reload of the ray and a second ray_setup.  The direction is not parked — the scene-level one stays in three registers of its own (re-reading it from the ray queue at every instance cost 4 %:
@@ -671,10 +681,15 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                         if (COUNT) c_tris[(MIXED && ah) ? 1 : 0]++;
                         const bool second_meeting = ALPHA && ALPHA_MIN > 0 && alpha_wait;   // the lane waited at this record for its alpha mask's verdict: the test below is the one it already passed
                         alpha_wait = false;
-                        // Shape::intersect / intersect_p of a quadric (quadric.h): the ray's direction comes from the queue again.  (With QUADRIC = false the condition below IS the triangle test.)
+                        // Shape::intersect / intersect_p of a quadric (quadric.h).  (With QUADRIC = false the condition below IS the triangle test.)  The ray's direction: the flat rows read it from
+                        // the queue again (RayState keeps none).  INST: a quadric record exists only in the scene-level tree (add_quadric refuses one inside an object definition), so a lane that
+                        // meets one has in_inst == 0, its RayState is the world-space ray's and wdx, wdy, wdz — the direction the instancing kernel keeps in registers anyway — are the bits the
+                        // queue holds: no second fetch.
                         auto quadric_leaf = [&]() -> bool {
-                            const float4 rdq = reinterpret_cast<const float4*>((MIXED && ah) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index)[1];
-                            t = quadric_test(sc.self, __float_as_uint(a.x), r.ox, r.oy, r.oz, r.t_max, rdq.x, rdq.y, rdq.z);
+                            float qdx, qdy, qdz;
+                            if constexpr (INST && QUADRIC) { qdx = wdx; qdy = wdy; qdz = wdz; }   // (a discarded statement otherwise: the other instantiations capture what they did)
+                            else { const float4 rdq = reinterpret_cast<const float4*>((MIXED && ah) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index)[1]; qdx = rdq.x; qdy = rdq.y; qdz = rdq.z; }
+                            t = quadric_test(sc.self, __float_as_uint(a.x), r.ox, r.oy, r.oz, r.t_max, qdx, qdy, qdz);
                             b0 = b1 = b2 = 0.0f;
                             return t > 0.0f;
                         };
@@ -695,7 +710,7 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                                 else {
                                     r.t_max = t; hit_tri = ti;
                                     if (!LEAN) { hit_prim = __float_as_uint(a.w); hb0 = b0; hb1 = b1; hb2 = b2; hit_cls = (flags >> PH_TRI_CLASS_SHIFT) & PH_TRI_KEY_MASK; }
-                                    if (INST) { hit_inst = in_inst & 0x3FFFFFFFu; inst_hit = true; }
+                                    if (INST) { hit_inst = in_inst & 0x3FFFFFFFu; inst_hit = true; }   // (a scene-level hit, triangle or quadric: in_inst == 0, so hit_inst = 0; inst_hit is set too, harmlessly — it is reset on entering an instance and read only on leaving one)
                                 }
                             }
                         }
