@@ -430,6 +430,27 @@ int pbrt_hip_film_to_rgb(const PbrtHipScene*, const float* xyz, const float* wei
 int pbrt_hip_generate_camera_rays(PbrtHipScene*, const int pixel_bounds[4], uint32_t sample_index,
                                   PbrtHipRay* out_rays, float* out_pfilm_xy);
 
+/* Test aids for a-M and a-S: the device's BSDF and sampler code on explicit inputs.  A binding does not need them.  Both need an uploaded scene only (no accelerator), launch a
+ * kernel that calls the functions the render kernels call, and leave the handle usable after a refusal.
+ *
+ * pbrt_hip_bsdf_probe_batch: `material`'s BSDF (BSDF::new, core/src/reflection/bsdf.rs:100-116) in the frame `frame` = {shading normal ns, geometric normal ng, shading dpdu}
+ * (9 floats; NULL: ns = ng = +z, dpdu = +x), n probes, 8 floats out each, world-space directions:
+ *   op 0  out[0..2] = BSDF::f(wo, wi, flags) (bsdf.rs:133-158), out[3] = BSDF::pdf(wo, wi, flags) (bsdf.rs:331-356)
+ *   op 1  BSDF::sample_f(wo, u, flags) (bsdf.rs:160-292): out[0..2] = f, out[3] = pdf, out[4..6] = wi, out[7] = the sampled BxDFType (0 for a failed sample)
+ *   op 2  out[0] = BSDF::num_components(flags), out[1] = number of BxDFs, out[2] = BSDF::eta
+ * path 0: the general lobe list, as the shade pass makes it for scenes that hold more than MatteMaterial.  path 1: the one-lobe BSDF of scenes made of MatteMaterial alone, which has
+ * neither flags nor a sampled type: every flags[i] must hold REFLECTION | DIFFUSE (PBRT_HIP_ERR_INVALID_ARG otherwise), and out[7] is the lobe's type where pdf != 0.
+ * PBRT_HIP_ERR_UNSUPPORTED: the material takes any parameter from a texture (bump map included); path 1 for a material not made by pbrt_hip_add_material_matte.
+ * PBRT_HIP_ERR_INVALID_ARG: unknown material, op or path; a null array with n > 0. */
+int pbrt_hip_bsdf_probe_batch(PbrtHipScene*, uint32_t material, int op, int path, uint64_t n, const float* wo /*3n*/, const float* wi /*3n*/, const float* u /*2n*/,
+                              const uint32_t* flags /*n*/, const float* frame /*9 or NULL*/, float* out /*8n*/);
+/* pbrt_hip_sampler_value_batch: out[i] = the configured sampler's value for pixel xy[i], sample number sample[i], dimension dim[i] — GlobalSampler::get_index_for_sample followed by
+ * sample_dimension (samplers/src/halton.rs:118-160, samplers/src/sobol.rs:65-93).  use_lds != 0: under Halton the block first stages the tables of the first 54 dimensions in LDS,
+ * as the shade pass does, and reads those dimensions from there.  PBRT_HIP_ERR_STATE: no sampler, or Sobol without tables.  PBRT_HIP_ERR_UNSUPPORTED: Sobol beyond the tables given
+ * (dimension, sample-bounds resolution, or a sample number whose index needs more than the 52 columns of a matrix).  PBRT_HIP_ERR_INVALID_ARG: a Halton dimension >= 1000
+ * (PRIME_TABLE_SIZE); a Sobol pixel outside the sampler's power-of-two square. */
+int pbrt_hip_sampler_value_batch(PbrtHipScene*, uint64_t n, const int* xy /*2n*/, const uint32_t* sample /*n*/, const uint32_t* dim /*n*/, int use_lds, float* out /*n*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -977,6 +977,36 @@ int oracle_bsdf_probe(OracleScene* s, uint32_t material, int op, const float wo[
     return 0;
 }
 
+// The same contract over n probes in one call, in the frame {ns, ng, shading dpdu} (9 floats; NULL: the canonical frame above).  BSDF::new normalises dpdu and takes
+// ts = cross(ns, ss) (bsdf.rs:100-116), as Renderer::make_bsdf does.  `path` belongs to the product's probe (its two BSDF code paths) and is ignored here.
+int oracle_bsdf_probe_batch(OracleScene* s, uint32_t material, int op, int /*path*/, uint64_t n, const float* wo, const float* wi, const float* u, const uint32_t* flags, const float* frame,
+                            float* out) {
+    if (!s || material >= s->sc.materials.size() || op < 0 || op > 2 || (n && (!wo || !wi || !u || !flags || !out))) return -1;
+    const Material& m = s->sc.materials[material];
+    if (m.textured) { s->err = "bsdf_probe_batch: the material takes a parameter from a texture"; return -5; }
+    Renderer::BSDF b; b.ns = b.ng = V3(0, 0, 1); b.ss = V3(1, 0, 0);
+    if (frame) { b.ns = V3(frame[0], frame[1], frame[2]); b.ng = V3(frame[3], frame[4], frame[5]); b.ss = normalize(V3(frame[6], frame[7], frame[8])); }
+    b.ts = cross(b.ns, b.ss);
+    b.lobes = m.lobes.data(); b.n = (int)m.lobes.size(); b.eta = m.bsdf_eta;
+    for (uint64_t i = 0; i < n; i++) {
+        float* o = out + 8 * i;
+        for (int k = 0; k < 8; k++) o[k] = 0.0f;
+        const V3 vo(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), vi(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+        const int fl = (int)flags[i];
+        if (op == 0) {
+            Spec f = b.f(vo, vi, fl);
+            o[0] = f.c[0]; o[1] = f.c[1]; o[2] = f.c[2]; o[3] = b.pdf(vo, vi, fl);
+        } else if (op == 1) {
+            Spec f; Float pdf; V3 w; int st = 0;
+            b.sample_f(vo, V2(u[2 * i], u[2 * i + 1]), f, pdf, w, fl, &st);
+            o[0] = f.c[0]; o[1] = f.c[1]; o[2] = f.c[2]; o[3] = pdf; o[4] = w.x; o[5] = w.y; o[6] = w.z; o[7] = (float)st;
+        } else {
+            o[0] = (float)b.num_components(fl); o[1] = (float)b.n; o[2] = b.eta;
+        }
+    }
+    return 0;
+}
+
 // SpatialLightDistribution of the last render: out[0..2] voxel resolution, out[3] distributions created
 // ("SpatialLightDistribution/Distributions created", spatial.rs:17-21).
 int oracle_spatial_stats(OracleScene* s, uint64_t out[4]) {
@@ -1059,6 +1089,32 @@ float oracle_scrambled_radical_inverse(int base_index, uint64_t a) { const auto&
 float oracle_sampler_value(OracleScene* s, int x, int y, uint32_t sample, uint32_t dim) {
     HaltonSampler sp(s->r.scfg); sp.start_pixel(x, y); sp.set_sample_number(sample);
     return sp.sample_dimension(sp.interval_index, dim);
+}
+
+// The configured sampler's value — Halton or Sobol — per (pixel, sample number, dimension): start_pixel, set_sample_number, sample_dimension.  `use_lds` belongs to the
+// product's probe and is ignored.  A Sobol draw beyond the tables given is refused like a render beyond them.
+int oracle_sampler_value_batch(OracleScene* s, uint64_t n, const int* xy, const uint32_t* sample, const uint32_t* dim, int /*use_lds*/, float* out) {
+    if (!s || (n && (!xy || !sample || !dim || !out))) return -1;
+    if (!s->have_sampler) return -2;
+    auto run = [&](auto& sp) {
+        for (uint64_t i = 0; i < n; i++) { sp.start_pixel(xy[2 * i], xy[2 * i + 1]); sp.set_sample_number(sample[i]); out[i] = sp.sample_dimension(sp.interval_index, dim[i]); }
+    };
+    if (s->r.scfg.kind == 0) {
+        for (uint64_t i = 0; i < n; i++) if (dim[i] >= (uint32_t)PRIME_TABLE_SIZE) return -1;
+        HaltonSampler sp(s->r.scfg); run(sp);
+    } else if (s->r.scfg.kind == 1) {
+        if (!s->r.scfg.sobol.m32) { s->err = "sobol tables not set"; return -2; }
+        SobolSampler sp(s->r.scfg);
+        if (sp.log2_res > (int)(s->vdc.size() / 52)) { s->err = "sampler_value_batch: sample-bounds resolution exceeds the Sobol tables given"; return -5; }
+        for (uint64_t i = 0; i < n; i++) {
+            if (dim[i] >= s->r.scfg.sobol.n_dims) { s->err = "sampler_value_batch: dimension beyond the Sobol tables given"; return -5; }
+            const long long dx = (long long)xy[2 * i] - sp.bounds[0], dy = (long long)xy[2 * i + 1] - sp.bounds[1];
+            if (dx < 0 || dy < 0 || dx >= sp.resolution || dy >= sp.resolution) return -1;
+            if (2 * sp.log2_res >= 52 ? sample[i] != 0 : ((uint64_t)sample[i] >> (52 - 2 * sp.log2_res)) != 0) { s->err = "sampler_value_batch: sample number beyond the 52 columns of the Sobol matrices"; return -5; }
+        }
+        run(sp);
+    } else return -5;
+    return 0;
 }
 
 // geometry probes that replay the reference's proptests (core/src/geometry/*.rs #[cfg(test)])

@@ -484,6 +484,7 @@ int pbrt_hip_add_material_matte(PbrtHipScene* s, const float kd[3], float sigma_
         lobes.push_back(l);
     }
     const int rc = push_material(s, m, lobes, false, out_id);
+    if (rc == PBRT_HIP_OK) s->material_params.back().made_as = 6;
     if (rc == PBRT_HIP_OK && m.has_bxdf) s->material_params.back().lobe[0] = 0;
     return rc;
     });

@@ -157,6 +157,8 @@ class Binding:
             "selftest_rccl_gather": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint64)]),
             "set_sample_record_budget": (C.c_int, [vp, C.c_uint64]),
             "get_render_footprint": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+            "bsdf_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, u32p, fp, fp]),
+            "sampler_value_batch": (C.c_int, [vp, C.c_uint64, ip, u32p, u32p, C.c_int, fp]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -673,6 +675,31 @@ class Scene:
         inp = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype=np.float32)
         out = np.zeros((len(uv), 3), np.float32)
         self._chk(self.b.fn("texture_eval_batch_nodiff" if nodiff else "texture_eval_batch")(self.h, texture, len(uv), _ptr(inp, C.c_float), _ptr(out, C.c_float)))
+        return out
+
+    def bsdf_probe_batch(self, material, op, wo, wi, u, flags, frame=None, path=0):
+        """The BSDF of `material` on explicit inputs (pbrt_hip_bsdf_probe_batch), a probe for the parity tests: wo, wi (n,3), u (n,2), flags (n,), frame = (ns, ng, dpdu) or
+        None for the canonical one.  Returns (n,8): op 0 -> f rgb, pdf; op 1 -> sample_f's f rgb, pdf, wi xyz, sampled type; op 2 -> num_components, lobe count, eta.
+        path 1: the one-lobe matte BSDF."""
+        wo = _f32(wo, (-1, 3)); wi = _f32(wi, (-1, 3)); u = _f32(u, (-1, 2))
+        flags = np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+        n = len(wo)
+        assert len(wi) == n and len(u) == n and len(flags) == n
+        fr = None if frame is None else _f32(frame, (9,))
+        out = np.zeros((n, 8), np.float32)
+        self._chk(self.b.fn("bsdf_probe_batch")(self.h, material, op, path, n, _ptr(wo, C.c_float), _ptr(wi, C.c_float), _ptr(u, C.c_float), _ptr(flags, C.c_uint32),
+                                                _ptr(fr, C.c_float), _ptr(out, C.c_float)))
+        return out
+
+    def sampler_value_batch(self, xy, sample, dim, use_lds=False):
+        """The configured sampler's value per (pixel, sample number, dimension) (pbrt_hip_sampler_value_batch), a probe for the parity tests.  use_lds: read the first 54
+        Halton dimensions from the LDS copy of their tables, as the shade pass does."""
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32).reshape(-1); dim = np.ascontiguousarray(dim, dtype=np.uint32).reshape(-1)
+        n = len(xy)
+        assert len(sample) == n and len(dim) == n
+        out = np.zeros(n, np.float32)
+        self._chk(self.b.fn("sampler_value_batch")(self.h, n, _ptr(xy, C.c_int), _ptr(sample, C.c_uint32), _ptr(dim, C.c_uint32), 1 if use_lds else 0, _ptr(out, C.c_float)))
         return out
 
     def mipmap_pyramid(self, mipmap):
