@@ -450,6 +450,22 @@ int pbrt_hip_bsdf_probe_batch(PbrtHipScene*, uint32_t material, int op, int path
  * (dimension, sample-bounds resolution, or a sample number whose index needs more than the 52 columns of a matrix).  PBRT_HIP_ERR_INVALID_ARG: a Halton dimension >= 1000
  * (PRIME_TABLE_SIZE); a Sobol pixel outside the sampler's power-of-two square. */
 int pbrt_hip_sampler_value_batch(PbrtHipScene*, uint64_t n, const int* xy /*2n*/, const uint32_t* sample /*n*/, const uint32_t* dim /*n*/, int use_lds, float* out /*n*/);
+/* pbrt_hip_light_probe_batch (a-Li, a-T2, f6): light number `light` (the order of the add_light_* / add_sphere_light calls) of a scene whose accelerator is built, on n reference points.
+ * ref = per probe {p[3], p_error[3], n[3], time}: the fields of the Interaction the light code reads; u = the 2D sample, wi = a world-space direction.
+ * Layout 1 of the output: PBRT_HIP_LIGHT_PROBE_STRIDE = 28 floats per probe, zeroed first, then
+ *   op 0  Light::sample_li(ref, u): out[0..2] wi, [3] pdf, [4..6] radiance, [7] 1 where a sample was made, [8..10] / [11..13] / [14..16] the point, error and normal of the
+ *         VisibilityTester's far end, and the ray Interaction::spawn_ray_to_hit (core/src/interaction/mod.rs:212-223) makes towards it: [17..19] origin, [20..22] direction, [23] t_max.
+ *         Where no sample was made ([7] = 0) the record is as sample_li initialised it and the ray slots stay zero.  [24..27] are spare.
+ *   op 1  out[0] = Light::pdf_li(ref, wi)
+ *   op 2  out[0..2] = Light::le of a ray with direction wi
+ * variant 0: the code of scenes with textures (radiance, projection and goniometric maps are read); variant 1: the code of scenes without, PBRT_HIP_ERR_UNSUPPORTED for a light that
+ * holds such a map; variant 2: sample_li as pbrt_hip_render_whitted's light loop calls it (op 0 only), the one variant that admits a light made by pbrt_hip_add_sphere_light
+ * (PBRT_HIP_ERR_UNSUPPORTED under 0 and 1, as the path integrator refuses such a scene).
+ * PBRT_HIP_ERR_INVALID_ARG: unknown light, op or variant; op 1 or 2 under variant 2; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built; an area light
+ * without its mesh.  Nothing is launched on a refusal. */
+#define PBRT_HIP_LIGHT_PROBE_STRIDE 28
+int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int variant, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/,
+                               float* out /*28n*/);
 
 #ifdef __cplusplus
 }

@@ -1117,6 +1117,63 @@ int oracle_sampler_value_batch(OracleScene* s, uint64_t n, const int* xy, const 
     return 0;
 }
 
+// ORACLE ONLY: what an infinite light's Distribution2D holds, for the case sets that place samples on its CDF entries.  what 0: {dw, dh}; 1: the marginal cdf (dh + 1 floats);
+// 2: the conditional cdfs (dh rows of dw + 1).  Returns the number of floats written, or a negative error.
+int64_t oracle_light_distribution(OracleScene* s, uint32_t light, int what, float* out, uint64_t cap) {
+    if (!s || !out || light >= s->sc.lights.size() || s->sc.lights[light].type != L_INFINITE || what < 0 || what > 2) return -1;
+    const Light& l = s->sc.lights[light];
+    std::vector<Float> v;
+    const bool map = l.map_mip >= 0;
+    const size_t dw = map ? (size_t)l.dw : 2, dh = map ? (size_t)l.dh : 2;
+    if (what == 0) v = {(Float)dw, (Float)dh};
+    else if (what == 1) { if (map) v = l.d_marg_cdf; else v.assign(l.marg_cdf, l.marg_cdf + 3); }
+    else if (map) v = l.d_cond_cdf;
+    else for (int r = 0; r < 2; r++) v.insert(v.end(), l.cond_cdf[r], l.cond_cdf[r] + 3);
+    if (v.size() > cap) return -1;
+    std::memcpy(out, v.data(), v.size() * sizeof(Float));
+    return (int64_t)v.size();
+}
+
+// Light probe, with the contract and the 28-float record of pbrt_hip_light_probe_batch (include/pbrt_hip.h): light_sample_li followed by spawn_ray_to_hit (op 0), light_pdf_li (op 1),
+// light_le (op 2) on explicit reference points {p, p_error, n, time}.  The variants are the product's code paths: here they only decide what is refused — a light with a map under
+// variant 1, a spherical light under 0 and 1 (Renderer::light_sample_li samples it for every caller; the product's path integrator refuses the scene), ops 1 and 2 under variant 2.
+int oracle_light_probe_batch(OracleScene* s, uint32_t light, int op, int variant, uint64_t n, const float* ref, const float* u, const float* wi, float* out) {
+    if (!s) return -1;
+    if (n && (!ref || !u || !wi || !out)) { s->err = "light_probe_batch: null argument"; return -1; }
+    if (light >= s->sc.lights.size()) { s->err = "light_probe_batch: unknown light"; return -1; }
+    if (op < 0 || op > 2 || variant < 0 || variant > 2 || (variant == 2 && op != 0)) { s->err = "light_probe_batch: unknown op or variant"; return -1; }
+    if (n > 0xFFFFFFFFull) { s->err = "light_probe_batch: too many probes"; return -1; }
+    if (!s->built) { s->err = "light_probe_batch: build_accel first"; return -2; }
+    const Light& l = s->sc.lights[light];
+    if (l.type == L_AREA && l.prim >= s->sc.n_tris()) { s->err = "light_probe_batch: the area light has no shape yet"; return -2; }
+    if (l.type == L_AREA && l.sphere >= 0 && variant != 2) { s->err = "light_probe_batch: a spherical area light belongs to variant 2"; return -5; }
+    if (variant == 1 && l.map_mip >= 0) { s->err = "light_probe_batch: variant 1 has no maps"; return -5; }
+    const int stride = 28;
+    for (uint64_t i = 0; i < n; i++) {
+        const float* rf = ref + 10 * i;
+        float* o = out + (size_t)stride * i;
+        for (int k = 0; k < stride; k++) o[k] = 0.0f;
+        SurfaceHit hit;
+        hit.p = V3(rf[0], rf[1], rf[2]); hit.p_error = V3(rf[3], rf[4], rf[5]); hit.n = V3(rf[6], rf[7], rf[8]); hit.time = rf[9];
+        hit.ns = hit.n; hit.prim = 0;
+        const V3 w(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+        if (op == 0) {
+            const LiSample r = s->r.light_sample_li(l, hit, V2(u[2 * i], u[2 * i + 1]));
+            if (!r.valid) continue;   // the record as sample_li initialises it: zeros
+            o[0] = r.wi.x; o[1] = r.wi.y; o[2] = r.wi.z; o[3] = r.pdf; o[4] = r.value.c[0]; o[5] = r.value.c[1]; o[6] = r.value.c[2]; o[7] = 1.0f;
+            o[8] = r.vp.x; o[9] = r.vp.y; o[10] = r.vp.z; o[11] = r.vperr.x; o[12] = r.vperr.y; o[13] = r.vperr.z; o[14] = r.vn.x; o[15] = r.vn.y; o[16] = r.vn.z;
+            const Ray sr = spawn_ray_to_hit(hit.p, hit.p_error, hit.n, hit.time, r.vp, r.vperr, r.vn);
+            o[17] = sr.o.x; o[18] = sr.o.y; o[19] = sr.o.z; o[20] = sr.d.x; o[21] = sr.d.y; o[22] = sr.d.z; o[23] = sr.t_max;
+        } else if (op == 1) {
+            o[0] = s->r.light_pdf_li(l, hit, w);
+        } else {
+            const Spec le = s->r.light_le(l, Ray(V3(0, 0, 0), w, INF, 0.0f));
+            o[0] = le.c[0]; o[1] = le.c[1]; o[2] = le.c[2];
+        }
+    }
+    return 0;
+}
+
 // geometry probes that replay the reference's proptests (core/src/geometry/*.rs #[cfg(test)])
 // op: 0 dot 1 cross 2 normalize 3 length 4 abs 5 min/max component 6 max_dimension 7 permute(xyz->a[3..6]) 8 ray.at
 //     9 coordinate_system 10 matrix inverse (16 in, 16 out) 11 face_forward 12 distance_squared 13 box test

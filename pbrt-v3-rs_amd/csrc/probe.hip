@@ -1,10 +1,12 @@
-// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch): the device's BSDF and sampler code on explicit inputs.
-// Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h); no formula lives here.
+// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch): the device's BSDF, sampler and light code on explicit inputs.
+// Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
 #include "pt_device.h"
 #include "bsdf_general.h"
 #include "wf_device.h"
+#include "texture.h"
+#include "sphere_light.h"
 #include <cstring>
 
 namespace ph {
@@ -64,6 +66,39 @@ __global__ __launch_bounds__(256) void sampler_value_kernel(DeviceScene sc, Samp
     if (i >= n) return;
     const SamplerCursor c = cursor_for(sc, sp, xy[2 * (size_t)i], xy[2 * (size_t)i + 1], sample[i], dim[i], hl);
     out[i] = sampler_dim(sc, sp, c, c.dim);
+}
+
+// VARIANT 0: light_le / light_sample_li / light_pdf_li<true>, as the textured shade kernels and spatial_compute_kernel instantiate them; 1: the <false> instantiations of the
+// texture-free kernels; 2: wh_light_sample_li<true>, the Whitted light loop's (op 0 only).  The reference point is a SurfHit that holds what the light code reads: p, p_error, n, time.
+// PBRT_HIP_LIGHT_PROBE_STRIDE floats out per probe, zeroed first (include/pbrt_hip.h gives the layout)
+template <int VARIANT>
+__global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene sc, uint32_t light, int op, uint32_t n, const float* ref_in, const float* u_in, const float* wi_in, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr bool MAP = VARIANT != 1;
+    const float* rf = ref_in + 10 * (size_t)i;
+    SurfHit hit;
+    hit.p = ld3(rf); hit.p_error = ld3(rf + 3); hit.n = ld3(rf + 6); hit.time = rf[9];
+    hit.wo = mk3(0.0f, 0.0f, 0.0f); hit.ns = hit.n; hit.dpdu_s = hit.wo; hit.prim = 0u;
+    const f2 u = mk2(u_in[2 * (size_t)i], u_in[2 * (size_t)i + 1]);
+    const f3 wi = ld3(wi_in + 3 * (size_t)i);
+    const LightRec& l = sc.lights[light];
+    float* o = out + PBRT_HIP_LIGHT_PROBE_STRIDE * (size_t)i;
+    for (int k = 0; k < PBRT_HIP_LIGHT_PROBE_STRIDE; k++) o[k] = 0.0f;
+    if (op == 0) {
+        const LiSample r = VARIANT == 2 ? wh_light_sample_li<true>(sc, l, hit, u) : light_sample_li<MAP>(sc, l, hit, u);
+        o[0] = r.wi.x; o[1] = r.wi.y; o[2] = r.wi.z; o[3] = r.pdf; o[4] = r.value.r; o[5] = r.value.g; o[6] = r.value.b; o[7] = r.valid ? 1.0f : 0.0f;
+        o[8] = r.vp.x; o[9] = r.vp.y; o[10] = r.vp.z; o[11] = r.vperr.x; o[12] = r.vperr.y; o[13] = r.vperr.z; o[14] = r.vn.x; o[15] = r.vn.y; o[16] = r.vn.z;
+        if (r.valid) {   // the shadow ray shade_kernel makes next
+            const RayIn sr = spawn_ray_to_hit(hit, r.vp, r.vperr, r.vn);
+            o[17] = sr.ox; o[18] = sr.oy; o[19] = sr.oz; o[20] = sr.dx; o[21] = sr.dy; o[22] = sr.dz; o[23] = sr.t_max;
+        }
+    } else if (op == 1) {
+        o[0] = light_pdf_li<MAP>(sc, l, hit, wi);
+    } else {
+        const spec le = light_le<MAP>(sc, l, wi);
+        o[0] = le.r; o[1] = le.g; o[2] = le.b;
+    }
 }
 
 }  // namespace ph
@@ -163,6 +198,47 @@ int pbrt_hip_sampler_value_batch(PbrtHipScene* s, uint64_t n, const int* xy, con
                        (const uint32_t*)(d + o_d), use_lds ? 1 : 0, (float*)(d + o_out));
     PH_CHECK(s, hipGetLastError());
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * 4, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, int variant, uint64_t n, const float* ref, const float* u, const float* wi, float* out) {
+    return ph_guard(s, "pbrt_hip_light_probe_batch", [&]() -> int {
+    if (!s || (n && (!ref || !u || !wi || !out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "light_probe_batch: null argument");
+    if (light >= s->lights.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "light_probe_batch: unknown light");
+    if (op < 0 || op > 2 || variant < 0 || variant > 2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "light_probe_batch: op must be 0, 1 or 2 and variant 0, 1 or 2");
+    if (variant == 2 && op != 0) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "light_probe_batch: variant 2 is the Whitted light loop's sample_li; it has op 0 only");
+    if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "light_probe_batch: too many probes");
+    if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "light_probe_batch: build_accel first (the world radius and the degenerate-triangle flags come from it)");
+    const LightRec& l = s->lights[light];
+    if (l.type == PH_L_AREA) {
+        if (l.prim >= s->tri_mesh.size()) return set_err(s, PBRT_HIP_ERR_STATE, "light_probe_batch: the area light has no shape yet");
+        if ((s->meshes[s->tri_mesh[l.prim]].flags & PH_MESH_QUADRIC) && variant != 2)
+            return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: a spherical area light is sampled by the Whitted light loop alone (variant 2)");
+    }
+    if (variant == 1 && l.map_mip1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: variant 1 is the code of scenes without textures; this light holds a radiance, projection or goniometric map");
+    if (n == 0) return PBRT_HIP_OK;
+    PH_CHECK(s, hipSetDevice(s->device));
+    int rc;
+    if ((rc = upload_scene(s))) return rc;
+    const size_t stride = PBRT_HIP_LIGHT_PROBE_STRIDE * sizeof(float);
+    const size_t o_ref = 0, o_u = o_ref + up256(n * 40), o_wi = o_u + up256(n * 8), o_out = o_wi + up256(n * 12), total = o_out + up256(n * stride);
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    PH_CHECK(s, hipMemcpyAsync(d + o_ref, ref, n * 40, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 8, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_wi, wi, n * 12, hipMemcpyHostToDevice, s->stream));
+    const dim3 grid((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), block(PH_PROBE_BLOCK);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, light, op, (uint32_t)n, (const float*)(d + o_ref), (const float*)(d + o_u), (const float*)(d + o_wi), (float*)(d + o_out));
+    };
+    if (variant == 0) launch(ph::light_probe_kernel<0>);
+    else if (variant == 1) launch(ph::light_probe_kernel<1>);
+    else launch(ph::light_probe_kernel<2>);
+    PH_CHECK(s, hipGetLastError());
+    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
     return PBRT_HIP_OK;
     });

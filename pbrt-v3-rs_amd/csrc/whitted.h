@@ -9,6 +9,7 @@
 #include "bsdf_general.h"
 #include "texture.h"
 #include "wf_device.h"
+#include "sphere_light.h"
 
 namespace ph {
 
@@ -274,72 +275,7 @@ PH_DEV void wh_sample_specular(const WhBsdf& b, f3 wo_w, f2 u, bool transmit, sp
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// DiffuseAreaLight::sample_li (lights/src/diffuse.rs:114-129) on a Sphere: Sphere::sample_solid_angle (shapes/src/sphere.rs:344-410) — uniform over the cone the sphere
-// subtends from the reference point, or uniform over the FULL sphere's area (Sphere::sample) where the point lies inside it — and the light's tail.  The z and phi cuts
-// of a partial sphere enter through `area` alone: a sample may land on the part that is cut away, as in the reference.  `rev` = the shape's reverse_orientation (not
-// QuadricRec::flip: the reference flips the sampled normal for reverse_orientation only, whatever the transform's handedness).
-PH_DEV LiSample sphere_light_sample_li(const LightRec& l, const QuadricRec& q, bool rev, const SurfHit& hit, f2 u) {
-    LiSample r;
-    r.valid = false; r.pdf = 0.0f; r.wi = mk3(0, 0, 0); r.value = mks1(0.0f);
-    r.vp = mk3(0, 0, 0); r.vperr = mk3(0, 0, 0); r.vn = mk3(0, 0, 0);
-    const float* m = q.o2w;   // p_center = object_to_world.transform_point(Point3f::ZERO) (transform.rs:288-302)
-    const float xc = m[0] * 0.0f + m[1] * 0.0f + m[2] * 0.0f + m[3], yc = m[4] * 0.0f + m[5] * 0.0f + m[6] * 0.0f + m[7];
-    const float zc = m[8] * 0.0f + m[9] * 0.0f + m[10] * 0.0f + m[11], wc_ = m[12] * 0.0f + m[13] * 0.0f + m[14] * 0.0f + m[15];
-    const f3 p_center = (wc_ == 1.0f) ? mk3(xc, yc, zc) : mk3(xc, yc, zc) / wc_;
-    f3 p, n, p_error;
-    float pdf;
-    const float phi = kTwoPi * u.y;
-    float sin_phi_, cos_phi_;
-    d_sincos(phi, sin_phi_, cos_phi_);
-    const f3 p_origin = offset_origin(hit.p, hit.p_error, hit.n, p_center - hit.p);
-    if (distance_squared(p_origin, p_center) <= q.radius * q.radius) {   // inside: Sphere::sample, then the area pdf as a solid-angle one (shape.rs:64-84)
-        const float z = 1.0f - 2.0f * u.x, rr = ph_sqrt(pmaxf(0.0f, 1.0f - z * z));   // uniform_sample_sphere
-        f3 p_obj = q.radius * mk3(rr * cos_phi_, rr * sin_phi_, z);
-        n = normalize(q_xf_normal(q.w2o, p_obj));
-        if (rev) n = n * -1.0f;
-        p_obj = p_obj * ph_div(q.radius, length(p_obj));
-        f3 pe;
-        p = xf_point_abs_err(q.o2w, p_obj, kGamma5 * vabs(p_obj), pe); p_error = pe;
-        pdf = ph_div(1.0f, l.area);
-        f3 wi = p - hit.p;
-        if (length_squared(wi) == 0.0f) pdf = 0.0f;
-        else { wi = normalize(wi); pdf *= ph_div(distance_squared(hit.p, p), abs_dot(n, -wi)); }
-        if (__builtin_isinf(pdf)) pdf = 0.0f;
-    } else {
-        const float dc = length(hit.p - p_center), inv_dc = ph_div(1.0f, dc);
-        const f3 wc = (p_center - hit.p) * inv_dc;
-        f3 wc_x, wc_y;
-        coordinate_system(wc, wc_x, wc_y);
-        const float sin_theta_max = q.radius * inv_dc, sin_theta_max2 = sin_theta_max * sin_theta_max, inv_sin_theta_max = ph_div(1.0f, sin_theta_max);
-        const float cos_theta_max = ph_sqrt(pmaxf(0.0f, 1.0f - sin_theta_max2));
-        float cos_theta = (cos_theta_max - 1.0f) * u.x + 1.0f, sin_theta2 = 1.0f - cos_theta * cos_theta;
-        if (sin_theta_max2 < 0.00068523f) { sin_theta2 = sin_theta_max2 * u.x; cos_theta = ph_sqrt(1.0f - sin_theta2); }   // sin^2(1.5 deg): the Taylor form
-        const float cos_alpha = sin_theta2 * inv_sin_theta_max + cos_theta * ph_sqrt(pmaxf(0.0f, 1.0f - sin_theta2 * inv_sin_theta_max * inv_sin_theta_max));
-        const float sin_alpha = ph_sqrt(pmaxf(0.0f, 1.0f - cos_alpha * cos_alpha));
-        const f3 n_world = (sin_alpha * cos_phi_) * (-wc_x) + (sin_alpha * sin_phi_) * (-wc_y) + cos_alpha * (-wc);   // spherical_direction_in_coord_frame
-        p = p_center + q.radius * n_world;
-        p_error = kGamma5 * vabs(p);
-        n = n_world;
-        if (rev) n = n * -1.0f;
-        pdf = ph_div(1.0f, kTwoPi * (1.0f - cos_theta_max));   // uniform_cone_pdf
-    }
-    f3 wi2 = p - hit.p;
-    const float l2 = length_squared(wi2);
-    if (pdf == 0.0f || l2 == 0.0f) return r;
-    wi2 = wi2 / ph_sqrt(l2);
-    r.wi = wi2; r.pdf = pdf; r.value = area_L(l, n, -wi2); r.vp = p; r.vperr = p_error; r.vn = n; r.valid = true;
-    return r;
-}
-// Light::sample_li as the Whitted light loop calls it.  Only the QUADRIC instantiation knows that an area light's shape may be a sphere (pbrt_hip_add_sphere_light): the light's
-// primitive slot then leads to a PH_MESH_QUADRIC record whose vert_base is the QuadricRec.  light_sample_li itself (pt_device.h) stays as the path integrator's kernels inline it.
-template <bool QUADRIC> PH_DEV LiSample wh_light_sample_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f2 u) {
-    if (QUADRIC && l.type == PH_L_AREA) {
-        const MeshRec m = sc.meshes[sc.tri_mesh[l.prim]];
-        if (m.flags & PH_MESH_QUADRIC) return sphere_light_sample_li(l, sc.quadrics[m.vert_base], (m.flags & PH_MESH_REV) != 0u, hit, u);
-    }
-    return light_sample_li<true>(sc, l, hit, u);
-}
-
+// Light::sample_li as the light loop calls it: wh_light_sample_li (sphere_light.h).
 // The state kernel: one thread per running sample and round.  It adds last round's unoccluded light samples to their frame, then advances the sample's recursion until it
 // has a closest-hit ray to send, has sent PH_WH_SLICE occlusion rays, or frame 0 has returned.  A vertex is rebuilt from the frame (ray, hit, vertex record) whenever the
 // sample comes back to it: its light loop's next slice, the refracted ray once the reflected subtree has returned.

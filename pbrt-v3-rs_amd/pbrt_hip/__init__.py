@@ -159,6 +159,7 @@ class Binding:
             "get_render_footprint": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
             "bsdf_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, u32p, fp, fp]),
             "sampler_value_batch": (C.c_int, [vp, C.c_uint64, ip, u32p, u32p, C.c_int, fp]),
+            "light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, fp]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -700,6 +701,20 @@ class Scene:
         assert len(sample) == n and len(dim) == n
         out = np.zeros(n, np.float32)
         self._chk(self.b.fn("sampler_value_batch")(self.h, n, _ptr(xy, C.c_int), _ptr(sample, C.c_uint32), _ptr(dim, C.c_uint32), 1 if use_lds else 0, _ptr(out, C.c_float)))
+        return out
+
+    LIGHT_PROBE_STRIDE = 28
+
+    def light_probe_batch(self, light, op, ref, u=None, wi=None, variant=0):
+        """Light number `light` on explicit reference points (pbrt_hip_light_probe_batch), a probe for the parity tests: ref (n,10) = p, p_error, n, time; u (n,2); wi (n,3).
+        Returns (n,28): op 0 -> sample_li's wi, pdf, radiance, valid, far point / error / normal, shadow ray origin / direction / t_max; op 1 -> pdf_li; op 2 -> le.
+        variant 0 / 1: the code of scenes with / without textures; 2: the Whitted light loop's sample_li (spherical lights)."""
+        ref = _f32(ref, (-1, 10)); n = len(ref)
+        u = _f32(u, (-1, 2)) if u is not None else np.full((n, 2), 0.5, np.float32)
+        wi = _f32(wi, (-1, 3)) if wi is not None else np.tile(np.array([0, 0, 1], np.float32), (n, 1))
+        assert len(u) == n and len(wi) == n
+        out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
+        self._chk(self.b.fn("light_probe_batch")(self.h, light, op, variant, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
         return out
 
     def mipmap_pyramid(self, mipmap):

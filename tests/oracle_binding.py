@@ -66,8 +66,8 @@ def oracle_binding():
 
 
 class OracleScene(pbrt_hip.Scene):
-    """pbrt_hip.Scene driven against liboracle.so, plus the oracle-only extras.  The batch probes (bsdf_probe_batch, sampler_value_batch) are the inherited
-    methods: oracle_bsdf_probe_batch / oracle_sampler_value_batch have the product's signatures."""
+    """pbrt_hip.Scene driven against liboracle.so, plus the oracle-only extras.  The batch probes (bsdf_probe_batch, sampler_value_batch, light_probe_batch) are the
+    inherited methods: oracle_bsdf_probe_batch / oracle_sampler_value_batch / oracle_light_probe_batch have the product's signatures."""
 
     def __init__(self):
         super().__init__(oracle_binding(), 0)
