@@ -29,6 +29,7 @@ struct BuildInput {
     // quad_bounds[6q..6q+5] = Shape::world_bound = object_to_world(object_bound) (core/src/geometry/shape.rs), computed by the caller.  Its TriRec carries PH_TRI_QUADRIC and q.
     const uint32_t* prim_quadric = nullptr;
     const float* quad_bounds = nullptr;
+    size_t n_quadrics = 0;   // the quadrics quad_bounds covers; the device builder checks prim_quadric against it before a kernel follows one
 };
 #define PH_ITEM_INST 0x80000000u
 

@@ -209,16 +209,22 @@ __global__ __launch_bounds__(256) void f_tree_of_kernel(const uint32_t* tree_sta
     while (lo + 1 < hi) { const uint32_t mid = (lo + hi) >> 1; if (tree_start[mid] <= i) lo = mid; else hi = mid; }
     tree_of[i] = lo;
 }
-// K1: bounds of the items at positions [i0, i1) (a triangle, or PH_ITEM_INST | k with the bound inst_bounds[6k ..]; no item list: item i is triangle i) and, per tree, the union of them
-__global__ __launch_bounds__(256) void f_bounds_kernel(const float* P, const uint32_t* idx, const uint32_t* items, const float* inst_bounds, const uint32_t* tree_of, uint32_t i0, uint32_t i1,
-                                                       float* blo, float* bhi, uint32_t* tb /*[n_trees][6]: ord(min xyz), ord(max xyz)*/) {
+// K1: bounds of the items at positions [i0, i1) (a primitive slot, or PH_ITEM_INST | k with the bound inst_bounds[6k ..]; no item list: item i is slot i) and, per tree, the union of them.
+// A slot holds a triangle or, where prim_quadric[slot] = 1 + q, a quadric whose bound quad_bounds[6q ..] the caller computed (bvh_build.cpp:421-423); its index triple is never followed.
+// prim_quadric is null in a scene without quadrics.
+__global__ __launch_bounds__(256) void f_bounds_kernel(const float* P, const uint32_t* idx, const uint32_t* items, const float* inst_bounds, const uint32_t* prim_quadric, const float* quad_bounds,
+                                                       const uint32_t* tree_of, uint32_t i0, uint32_t i1, float* blo, float* bhi, uint32_t* tb /*[n_trees][6]: ord(min xyz), ord(max xyz)*/) {
     const uint32_t first = i0 + blockIdx.x * blockDim.x, i = first + threadIdx.x;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     const bool ok = i < i1;
     if (ok) {
         const uint32_t item = items ? items[i] : i;
+        const uint32_t quad = (prim_quadric && !(item & PH_ITEM_INST)) ? prim_quadric[item] : 0u;
         if (item & PH_ITEM_INST) {
             const float* bb = inst_bounds + 6 * (size_t)(item & ~PH_ITEM_INST);
+            for (int k = 0; k < 3; k++) { lo[k] = bb[k]; hi[k] = bb[3 + k]; }
+        } else if (quad) {
+            const float* bb = quad_bounds + 6 * (size_t)(quad - 1u);
             for (int k = 0; k < 3; k++) { lo[k] = bb[k]; hi[k] = bb[3 + k]; }
         } else {
             const float* a = P + 3 * (size_t)idx[3 * (size_t)item];
@@ -341,20 +347,26 @@ __global__ __launch_bounds__(256) void f_convert_kernel(const DNode* pool, uint3
     o.c0 = ref(a); o.c1 = ref(b); o.axis = nd.axis; o.pad = 0;
     nodes[tl_dense_base[t] + nd.dense] = o;
 }
-// K6b: leaf records in the final order; an instance's record is what build_bvh writes (prim, PH_TRI_INSTANCE, the rest zero until the scene is uploaded)
+// K6b: leaf records in the final order; an instance's record is what build_bvh writes (prim, PH_TRI_INSTANCE, the rest zero until the scene is uploaded), and so is a quadric's
+// (bvh_build.cpp:451-455: the quadric's index as the bit pattern of p0[0], the slot, PH_TRI_QUADRIC, the slot's flags and mesh, the rest zero)
 __global__ __launch_bounds__(256) void f_gather_kernel(const uint32_t* ids, const uint32_t* leaf_last, const uint32_t* tl_of_pos, const uint32_t* tl_first, const uint32_t* tl_out_base, uint32_t n, const uint32_t* items,
-                                                       const float* P, const uint32_t* idx, const uint32_t* tri_flags, const uint32_t* tri_mesh, TriRec* tris) {
+                                                       const float* P, const uint32_t* idx, const uint32_t* tri_flags, const uint32_t* tri_mesh, const uint32_t* prim_quadric, TriRec* tris) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t t = tl_of_pos[i];
     const uint32_t q = tl_out_base[t] + (i - tl_first[t]);
     const uint32_t id = items ? items[ids[i]] : ids[i];
     const uint32_t last = leaf_last[i] ? PH_TRI_LAST : 0u;
+    const uint32_t quad = (prim_quadric && !(id & PH_ITEM_INST)) ? prim_quadric[id] : 0u;
     TriRec r;
     if (id & PH_ITEM_INST) {
         r.p0[0] = r.p0[1] = r.p0[2] = 0.0f; r.prim = id & ~PH_ITEM_INST;
         r.p1[0] = r.p1[1] = r.p1[2] = 0.0f; r.flags = PH_TRI_INSTANCE | last;
         r.p2[0] = r.p2[1] = r.p2[2] = 0.0f; r.mesh = 0u;
+    } else if (quad) {
+        r.p0[0] = __uint_as_float(quad - 1u); r.p0[1] = r.p0[2] = 0.0f; r.prim = id;
+        r.p1[0] = r.p1[1] = r.p1[2] = 0.0f; r.flags = ((tri_flags ? tri_flags[id] : 0u) & ~PH_TRI_LAST) | PH_TRI_QUADRIC | last;
+        r.p2[0] = r.p2[1] = r.p2[2] = 0.0f; r.mesh = tri_mesh ? tri_mesh[id] : 0u;
     } else {
         const float* p0 = P + 3 * (size_t)idx[3 * (size_t)id]; const float* p1 = P + 3 * (size_t)idx[3 * (size_t)id + 1]; const float* p2 = P + 3 * (size_t)idx[3 * (size_t)id + 2];
         r.p0[0] = p0[0]; r.p0[1] = p0[1]; r.p0[2] = p0[2]; r.prim = id;
@@ -399,16 +411,25 @@ int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t 
         const uint32_t it = h_items[i];
         if ((it & PH_ITEM_INST) ? (i >= top_end || (size_t)(it & ~PH_ITEM_INST) >= n_inst) : (size_t)it >= in.n_tris) { err = "device build: an item names no triangle or instance"; return -1; }
     }
+    const uint32_t* pq = in.prim_quadric;   // null: every slot holds a triangle
+    if (pq && !in.quad_bounds) { err = "device build: quadric slots without their bounds"; return -1; }
+    if (pq) for (uint32_t i = 0; i < n; i++) {   // a quadric stands in the scene's own tree only (object definitions hold none), and names one of the n_quadrics bounds
+        const uint32_t it = h_items ? h_items[i] : i;
+        if ((it & PH_ITEM_INST) || !pq[it]) continue;
+        if ((forest && i >= top_end) || (size_t)(pq[it] - 1u) >= in.n_quadrics) { err = "device build: a quadric slot inside an object's tree, or one that names no quadric"; return -1; }
+    }
     const uint32_t max_prims = (uint32_t)(max_prims_in_node & 0xff);   // bvh/mod.rs:357 `as u8`
     auto t0 = std::chrono::steady_clock::now();
     const bool prof = std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr;
     auto lap = [&](const char* what) { if (prof) { (void)hipStreamSynchronize(stream); std::fprintf(stderr, "build_hlbvh_forest_device n=%u trees=%u: %-28s at %.3f s\n", n, n_trees, what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } };
     std::vector<void*> allocs;
     auto dalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; } allocs.push_back(p); return p; };
-    size_t n_verts = 0;
-    for (size_t i = 0; i < 3 * in.n_tris; i++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[i] + 1);
+    size_t n_verts = 0;   // over the triangle slots: a quadric slot's index triple is {0, 0, 0} and stands for no vertex (a scene of quadrics only has none: nothing of P is read)
+    if (!pq) for (size_t i = 0; i < 3 * in.n_tris; i++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[i] + 1);
+    else for (size_t t = 0; t < in.n_tris; t++) if (!pq[t]) for (int k = 0; k < 3; k++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[3 * t + k] + 1);
     float* dP = (float*)dalloc(n_verts * 12); uint32_t* dIdx = (uint32_t*)dalloc(in.n_tris * 12);
     uint32_t* d_items = h_items ? (uint32_t*)dalloc((size_t)n * 4) : nullptr; uint32_t* d_tree_start = (uint32_t*)dalloc(((size_t)n_trees + 1) * 4); uint32_t* tree_of = (uint32_t*)dalloc((size_t)n * 4);
+    uint32_t* d_pq = pq ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr; float* d_qb = pq ? (float*)dalloc(in.n_quadrics * 24) : nullptr;
     uint32_t* d_inst_tree = (uint32_t*)dalloc(n_inst * 4); float* d_i2w = (float*)dalloc(n_inst * 64); float* d_inst_bounds = (float*)dalloc(n_inst * 24);
     float* blo = (float*)dalloc((size_t)n * 12); float* bhi = (float*)dalloc((size_t)n * 12);
     uint32_t* tb = (uint32_t*)dalloc((size_t)n_trees * 24);
@@ -436,11 +457,15 @@ int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t 
     for (void* p : allocs) if (!p) { err = "device build: out of device memory"; goto fail; }
     {
         for (uint32_t t = 0; t < n_trees; t++) for (int k = 0; k < 3; k++) { tb_init[6 * (size_t)t + k] = 0xFFFFFFFFu; tb_init[6 * (size_t)t + 3 + k] = 0u; }
-        PHD_CHECK(hipMemcpyAsync(dP, in.P, n_verts * 12, hipMemcpyHostToDevice, stream));
+        if (n_verts) PHD_CHECK(hipMemcpyAsync(dP, in.P, n_verts * 12, hipMemcpyHostToDevice, stream));
         PHD_CHECK(hipMemcpyAsync(dIdx, in.idx, in.n_tris * 12, hipMemcpyHostToDevice, stream));
         if (d_items) PHD_CHECK(hipMemcpyAsync(d_items, h_items, (size_t)n * 4, hipMemcpyHostToDevice, stream));
         PHD_CHECK(hipMemcpyAsync(d_tree_start, tree_start, ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, stream));
         PHD_CHECK(hipMemcpyAsync(tb, tb_init.data(), (size_t)n_trees * 24, hipMemcpyHostToDevice, stream));
+        if (d_pq) {
+            PHD_CHECK(hipMemcpyAsync(d_pq, pq, in.n_tris * 4, hipMemcpyHostToDevice, stream));
+            if (in.n_quadrics) PHD_CHECK(hipMemcpyAsync(d_qb, in.quad_bounds, in.n_quadrics * 24, hipMemcpyHostToDevice, stream));
+        }
         if (n_inst) {
             PHD_CHECK(hipMemcpyAsync(d_inst_tree, inst_tree, n_inst * 4, hipMemcpyHostToDevice, stream));
             PHD_CHECK(hipMemcpyAsync(d_i2w, inst_i2w, n_inst * 64, hipMemcpyHostToDevice, stream));
@@ -455,9 +480,9 @@ int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t 
         lap("allocations and uploads");
         hipLaunchKernelGGL(phd::f_tree_of_kernel, g, b, 0, stream, d_tree_start, n_trees, n, tree_of);
         // K1: the objects' trees first — the scene's tree holds TransformedPrimitives, whose bounds are the objects' tree bounds carried to world space
-        if (n > top_end) hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((n - top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, tree_of, top_end, n, blo, bhi, tb);
+        if (n > top_end) hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((n - top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, d_pq, d_qb, tree_of, top_end, n, blo, bhi, tb);
         if (n_inst) hipLaunchKernelGGL(phd::f_inst_bounds_kernel, dim3((uint32_t)((n_inst + 255u) / 256u)), b, 0, stream, tb, d_inst_tree, d_i2w, (uint32_t)n_inst, d_inst_bounds);
-        hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, tree_of, 0u, top_end, blo, bhi, tb);
+        hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, d_pq, d_qb, tree_of, 0u, top_end, blo, bhi, tb);
         hipLaunchKernelGGL(phd::f_morton_kernel, g, b, 0, stream, blo, bhi, n, tb, tree_of, keys[0], codes_keep, vals[0]);
         int cur = 0;
         auto sort_pass = [&](int shift) {
@@ -519,7 +544,7 @@ int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t 
         PHD_CHECK(hipMemcpyAsync(d_tl_dense, plan.dense_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
         PHD_CHECK(hipMemcpyAsync(d_tl_out, plan.out_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(phd::f_convert_kernel, dim3((uint32_t)(((uint64_t)2 * n + 255u) / 256u)), b, 0, stream, pool, n, tl_of_pos, d_tl_first, d_tl_dense, d_tl_out, d_nodes);
-        hipLaunchKernelGGL(phd::f_gather_kernel, g, b, 0, stream, ids, leaf_last, tl_of_pos, d_tl_first, d_tl_out, n, d_items, dP, dIdx, d_flags, d_mesh, d_tris);
+        hipLaunchKernelGGL(phd::f_gather_kernel, g, b, 0, stream, ids, leaf_last, tl_of_pos, d_tl_first, d_tl_out, n, d_items, dP, dIdx, d_flags, d_mesh, d_pq, d_tris);
         PHD_CHECK(hipGetLastError());
         out.nodes.resize(out.interior_nodes);
         out.tris.resize(n);
@@ -528,7 +553,8 @@ int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t 
         PHD_CHECK(hipStreamSynchronize(stream));
         lap("nodes, records, downloads");
         place_upper_nodes(plan, out.nodes.data());
-        if (forest) {   // a single tree keeps the kernels' numbering.  A forest takes the host builder's, tree by tree (trees are independent: spread them over a few threads where there is much to do)
+        if (forest || pq) {   // a single tree of triangles keeps the kernels' numbering.  A forest takes the host builder's, tree by tree (trees are independent: spread them over a few threads where there is much to do),
+                              // and so does the single tree of a scene with quadrics: such a scene's arrays are the host builder's entry by entry, with or without instances
             const uint32_t n_thr = out.interior_nodes >= (1u << 18) ? std::min<uint32_t>(std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency())), n_trees) : 1u;
             std::vector<uint32_t> cut(n_thr + 1, n_trees);   // cut the trees into runs of about equal node counts
             cut[0] = 0;

@@ -870,7 +870,7 @@ int Api::pbrt_world_end(RenderReport& rep) {
     auto t0 = clk::now();
     // "sah" and "hlbvh" trees are made on the GPU, scenes with object instances included (same trees: csrc/bvh_sah_device.hip, bvh_device.hip); everything else by the library's host builder
     int brc = PBRT_HIP_ERR_UNSUPPORTED;
-    if ((split == 0 || split == 1) && !check_only_) brc = pbrt_hip_build_accel_device(scene_, split, max_prims);   // UNSUPPORTED for scenes with quadric shapes: the host builder makes the same tree
+    if ((split == 0 || split == 1) && !check_only_) brc = pbrt_hip_build_accel_device(scene_, split, max_prims);   // UNSUPPORTED for the SAH tree of a scene with quadric shapes: the host builder makes the same tree
     if (brc == PBRT_HIP_ERR_UNSUPPORTED) brc = ABI(pbrt_hip_build_accel(scene_, split, max_prims));
     if (!check(brc, "build_accel")) return PBRT_HIP_ERR_DEVICE;
     rep.build_seconds = std::chrono::duration<double>(clk::now() - t0).count();

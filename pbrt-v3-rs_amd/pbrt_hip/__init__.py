@@ -538,7 +538,7 @@ class Scene:
         self._chk(self.b.fn("build_accel")(self.h, split_method, max_prims_in_node))
 
     def build_accel_best(self, split_method=0, max_prims_in_node=4):
-        """build_accel_device where it applies (SAH / HLBVH trees, scenes with object instances included; not EqualCounts, not scenes with quadrics — with or without object instances), build_accel elsewhere: the same tree either way."""
+        """build_accel_device where it applies (SAH / HLBVH trees, scenes with object instances included; scenes with quadrics with HLBVH only; not EqualCounts, not the SAH tree of a scene with quadrics), build_accel elsewhere: the same tree either way."""
         if split_method in (0, 1) and self.b.has("build_accel_device"):
             try:
                 return self.build_accel_device(split_method, max_prims_in_node)
