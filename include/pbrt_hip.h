@@ -467,6 +467,12 @@ int pbrt_hip_sampler_value_batch(PbrtHipScene*, uint64_t n, const int* xy /*2n*/
 #define PBRT_HIP_LIGHT_PROBE_STRIDE 28
 int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int variant, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/,
                                float* out /*28n*/);
+/* pbrt_hip_raysort_probe: the ray binning between wavefront rounds (csrc/raysort.h) on explicit keys, through the launch the path integrator's rounds use.  keys_cl / keys_sh = the
+ * bin keys (< 4096) of n_cl closest-hit and n_sh any-hit rays; the keys and the two counts are uploaded and read from device memory, as in a render.  order_out[0 .. n_cl + n_sh) =
+ * the queue positions (closest-hit rays 0 .. n_cl, any-hit rays behind them) grouped by bin, closest-hit rays first; the order inside a bin is unspecified.  sort_blocks = the grid
+ * of the two passes over the keys (a render uses 1024).  Needs a handle only: no geometry, no accelerator.
+ * PBRT_HIP_ERR_INVALID_ARG: a null handle; sort_blocks 0 or above 65536; a null array with a non-zero count; a key >= 4096; n_cl + n_sh >= 0x7FFF0000.  Nothing is launched on a refusal. */
+int pbrt_hip_raysort_probe(PbrtHipScene*, uint32_t n_cl, uint32_t n_sh, const uint32_t* keys_cl, const uint32_t* keys_sh, uint32_t sort_blocks, uint32_t* order_out /* n_cl + n_sh */);
 
 #ifdef __cplusplus
 }

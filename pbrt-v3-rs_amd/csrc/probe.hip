@@ -1,4 +1,5 @@
-// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch): the device's BSDF, sampler and light code on explicit inputs.
+// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_raysort_probe): the device's BSDF, sampler and light
+// code and the ray binning between wavefront rounds on explicit inputs.
 // Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
@@ -240,6 +241,33 @@ int pbrt_hip_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, int vari
     PH_CHECK(s, hipGetLastError());
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_raysort_probe(PbrtHipScene* s, uint32_t n_cl, uint32_t n_sh, const uint32_t* keys_cl, const uint32_t* keys_sh, uint32_t sort_blocks, uint32_t* order_out) {
+    return ph_guard(s, "pbrt_hip_raysort_probe", [&]() -> int {
+    if (!s || (n_cl && !keys_cl) || (n_sh && !keys_sh) || ((n_cl || n_sh) && !order_out)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: null argument");
+    if (sort_blocks == 0 || sort_blocks > 65536u) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: sort_blocks must be 1 .. 65536");
+    const uint64_t n = (uint64_t)n_cl + n_sh;
+    if (n >= 0x7FFF0000ull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: more rays than a round's queues hold");
+    for (uint32_t i = 0; i < n_cl; i++) if (keys_cl[i] >= PH_SORT_BINS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a key is not below 4096");
+    for (uint32_t i = 0; i < n_sh; i++) if (keys_sh[i] >= PH_SORT_BINS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a key is not below 4096");
+    PH_CHECK(s, hipSetDevice(s->device));
+    const size_t o_cl = 0, o_sh = o_cl + up256((size_t)n_cl * 4), o_n = o_sh + up256((size_t)n_sh * 4), o_order = o_n + 256, o_ws = o_order + up256(n * 4),
+                 total = o_ws + up256(raysort_workspace_bytes(sort_blocks));
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    const uint32_t counts[2] = {n_cl, n_sh};
+    if (n_cl) PH_CHECK(s, hipMemcpyAsync(d + o_cl, keys_cl, (size_t)n_cl * 4, hipMemcpyHostToDevice, s->stream));
+    if (n_sh) PH_CHECK(s, hipMemcpyAsync(d + o_sh, keys_sh, (size_t)n_sh * 4, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_n, counts, 8, hipMemcpyHostToDevice, s->stream));
+    launch_raysort(s, (const uint32_t*)(d + o_cl), (const uint32_t*)(d + o_sh), (const uint32_t*)(d + o_n), (const uint32_t*)(d + o_n) + 1, (uint32_t*)(d + o_order), (uint32_t*)(d + o_ws),
+                   sort_blocks);
+    PH_CHECK(s, hipGetLastError());
+    if (n) PH_CHECK(s, hipMemcpyAsync(order_out, d + o_order, n * 4, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));   // (`counts` and the caller's arrays are pageable: the copies above have left them by now)
     return PBRT_HIP_OK;
     });
 }

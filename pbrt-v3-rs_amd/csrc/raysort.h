@@ -8,26 +8,30 @@
 // the traversal kernel walks the queue through it.  Rays are not moved: the kernel that writes a ray (shade) also writes its 4-byte bin key, the two
 // passes here read the keys and write 4 B of `order` per ray.
 //
-// A counting sort without global atomics per ray: every block histograms its contiguous slice of the queue in LDS and adds the
-// non-empty bins to the global tallies (one atomic per block and bin), a single block scans the 8192 tallies, and the second
-// pass repeats the LDS histogram, claims the block's share of each bin with one atomic per bin and ranks its rays inside LDS.
-// The order inside a bin is whatever the atomics give; it does not matter.  (Tried and dropped: one LDS atomic per distinct key of a wave, found with a
+// A counting sort without global atomics per ray, in two passes over the keys.  Every block owns a contiguous slice of the queue (raysort_plan.h: the same slice in
+// both passes).  The first pass histograms the slice in LDS and adds the non-empty bins to the global tallies, one atomic per block and bin; what the atomic
+// returns is where the block's share of that bin starts inside the bin, and the block keeps it: one row of `block_share` per block.  A single block scans the
+// 8192 tallies.  The second pass starts a cursor per bin at bin_start + block_share in LDS and ranks its rays with LDS atomics, one per run of equal keys in a lane.  (Until the shares were
+// kept, the second pass histogrammed its slice again only to claim them with a second round of global atomics: a third read of the keys, a third LDS-atomic pass
+// and a second 32 KB LDS array, which held the kernel to two blocks per CU.)  Keys are read 16 bytes per lane and several loads deep (PH_SORT_DEPTH) before the
+// first LDS atomic that depends on them: with one 4-byte load in flight per lane the passes were bound by load latency, at 0.9 - 1.5 TB/s.
+// The order inside a bin is whatever the atomics give; no result depends on it.  The time of the traversal kernel does, by about 2 %: neighbours in the queue are mostly
+// rays of one pixel in one cell, and it pays to leave them neighbours inside a block's share of a bin (raysort_scatter_kernel).  (Tried and dropped: one LDS atomic per distinct key of a wave, found with a
 // ballot loop — a wave of the path-ordered queue holds many distinct keys, the loop cost more than the plain atomics: binning 28 -> 70 ms per configs[2] frame.)
 #pragma once
+#include "raysort_plan.h"
 #include "traverse.h"
 
 namespace ph {
 
-#define PH_SORT_BINS 4096u            // per ray kind
-#define PH_SORT_KEYS (2u * PH_SORT_BINS)
-#define PH_SORT_BLOCK 256
+#define PH_SORT_DEPTH 4               // 16-byte key loads a lane issues before it uses the first
 
 struct RaySortParams {
     const uint32_t* keys_cl; const uint32_t* keys_sh;   // one key per queue slot, written by the kernel that wrote the ray (ray_sort_key)
     const uint32_t* n_cl; const uint32_t* n_sh;
     uint32_t* order;        // out: [n_cl + n_sh]
     uint32_t* bin_start;    // [PH_SORT_KEYS] tallies -> exclusive starts (scan kernel)
-    uint32_t* bin_cursor;   // [PH_SORT_KEYS] zeroed by the scan kernel
+    uint32_t* block_share;  // [gridDim.x][PH_SORT_KEYS] where each block's rays start inside each bin; 0 for a bin the block has no ray in
 };
 struct RaySortGrid {        // how a ray is binned: by the cell of its origin in a 16^3 grid over the scene bound
     float lo[3], scale[3];  // cell coordinate = (o - lo) * scale in [0, 1)
@@ -49,31 +53,67 @@ PH_DEV uint32_t ray_sort_key(const RaySortGrid& g, float ox, float oy, float oz)
     const uint32_t cz = (uint32_t)pmini(pmaxi((int)(fz * 16.0f), 0), 15);
     return part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
 }
-PH_DEV uint32_t raysort_key_at(const RaySortParams& p, uint32_t i, uint32_t n_cl) {
-    return i < n_cl ? p.keys_cl[i] : PH_SORT_BINS + p.keys_sh[i - n_cl];
+// The keys of one run of a slice (raysort_plan.h), each handed on by exactly one thread of the block with its joint key (key + key_add) and its joint queue position (position
+// in the run's array + pos_add): scalar head, 16-byte body, scalar tail.  The body goes PH_SORT_DEPTH vectors per lane at a time while that many are left, all loads issued
+// before `fv` sees them (fv(v, i0): v[d] holds the keys of positions i0 + 4 * d * PH_SORT_BLOCK + 0 .. 3), and one vector at a time through `f1(key, position)` after that.
+template <class FV, class F1>
+PH_DEV void raysort_walk_run(const uint32_t* keys, const RaySortRun& r, uint32_t key_add, uint32_t pos_add, FV&& fv, F1&& f1) {
+    if (r.head + threadIdx.x < r.body) f1(keys[r.head + threadIdx.x] + key_add, r.head + threadIdx.x + pos_add);
+    const uint4* body = reinterpret_cast<const uint4*>(keys + r.body);
+    const uint32_t n_vec = (r.tail - r.body) >> 2;
+    uint32_t j = threadIdx.x;
+    for (; j + (PH_SORT_DEPTH - 1) * PH_SORT_BLOCK < n_vec; j += PH_SORT_DEPTH * PH_SORT_BLOCK) {
+        uint4 v[PH_SORT_DEPTH];
+#pragma unroll
+        for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) v[d] = body[j + d * PH_SORT_BLOCK];
+        __builtin_amdgcn_sched_barrier(0);   // (left alone, the scheduler sinks each load to just above its first use: one in flight again)
+#pragma unroll
+        for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) { v[d].x += key_add; v[d].y += key_add; v[d].z += key_add; v[d].w += key_add; }
+        fv(v, r.body + 4u * j + pos_add);
+    }
+    for (; j < n_vec; j += PH_SORT_BLOCK) {
+        const uint4 v = body[j];
+        const uint32_t i = r.body + 4u * j + pos_add;
+        f1(v.x + key_add, i); f1(v.y + key_add, i + 1u); f1(v.z + key_add, i + 2u); f1(v.w + key_add, i + 3u);
+    }
+    if (r.tail + threadIdx.x < r.end) f1(keys[r.tail + threadIdx.x] + key_add, r.tail + threadIdx.x + pos_add);
 }
-
-PH_DEV void raysort_slice(const RaySortParams& p, uint32_t n, uint32_t& lo, uint32_t& hi) {
-    const uint32_t per = (((n + gridDim.x - 1u) / gridDim.x) + PH_SORT_BLOCK - 1u) & ~(uint32_t)(PH_SORT_BLOCK - 1u);
-    lo = blockIdx.x * per; hi = lo + per < n ? lo + per : n;
-    if (lo > n) lo = n;
+// every ray of the slice; an any-hit ray's key lies PH_SORT_BINS up, its position n_cl up
+template <class FV, class F1>
+PH_DEV void raysort_walk_slice(const RaySortParams& p, const RaySortSlice& s, uint32_t n_cl, FV&& fv, F1&& f1) {
+    raysort_walk_run(p.keys_cl, s.cl, 0u, 0u, fv, f1);
+    raysort_walk_run(p.keys_sh, s.sh, PH_SORT_BINS, n_cl, fv, f1);
 }
+PH_DEV RaySortSlice raysort_slice(const RaySortParams& p, uint32_t n_cl, uint32_t n_sh) {
+    return raysort_plan(n_cl, n_sh, gridDim.x, PH_SORT_BLOCK, PH_SORT_FLOOR, blockIdx.x, (uint32_t)((uintptr_t)p.keys_cl >> 2) & 3u, (uint32_t)((uintptr_t)p.keys_sh >> 2) & 3u);
+}
+// a key outside the table (the shade pass writes none) must not reach past the LDS array
+PH_DEV uint32_t raysort_bin(uint32_t key) { return key & (PH_SORT_KEYS - 1u); }
 
 __global__ __launch_bounds__(PH_SORT_BLOCK) void raysort_hist_kernel(RaySortParams p) {
     __shared__ uint32_t h[PH_SORT_KEYS];
-    const uint32_t n_cl = *p.n_cl, n = n_cl + *p.n_sh;
-    uint32_t lo, hi;
-    raysort_slice(p, n, lo, hi);
-    if (lo >= hi) return;
+    const uint32_t n_cl = *p.n_cl, n_sh = *p.n_sh;
+    const RaySortSlice s = raysort_slice(p, n_cl, n_sh);
+    if (s.lo >= s.hi) return;
     for (uint32_t k = threadIdx.x; k < PH_SORT_KEYS; k += PH_SORT_BLOCK) h[k] = 0u;
     __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += PH_SORT_BLOCK) atomicAdd(&h[raysort_key_at(p, i, n_cl)], 1u);
+    raysort_walk_slice(p, s, n_cl,
+        [&](const uint4 (&v)[PH_SORT_DEPTH], uint32_t) {
+#pragma unroll
+            for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) {
+                atomicAdd(&h[raysort_bin(v[d].x)], 1u); atomicAdd(&h[raysort_bin(v[d].y)], 1u); atomicAdd(&h[raysort_bin(v[d].z)], 1u); atomicAdd(&h[raysort_bin(v[d].w)], 1u);
+            }
+        },
+        [&](uint32_t key, uint32_t) { atomicAdd(&h[raysort_bin(key)], 1u); });
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < PH_SORT_KEYS; k += PH_SORT_BLOCK)
-        if (h[k]) atomicAdd(&p.bin_start[k], h[k]);
+    uint32_t* share = p.block_share + (size_t)blockIdx.x * PH_SORT_KEYS;
+    for (uint32_t k = threadIdx.x; k < PH_SORT_KEYS; k += PH_SORT_BLOCK) {
+        const uint32_t c = h[k];
+        share[k] = c ? atomicAdd(&p.bin_start[k], c) : 0u;
+    }
 }
 
-// one block: exclusive scan of the PH_SORT_KEYS tallies in place, cursors cleared
+// one block: exclusive scan of the PH_SORT_KEYS tallies in place
 __global__ __launch_bounds__(1024) void raysort_scan_kernel(RaySortParams p) {
     __shared__ uint32_t part[1024];
     constexpr uint32_t PER = PH_SORT_KEYS / 1024u;
@@ -88,30 +128,45 @@ __global__ __launch_bounds__(1024) void raysort_scan_kernel(RaySortParams p) {
         __syncthreads();
     }
     uint32_t run = part[threadIdx.x] - sum;
-    for (uint32_t k = 0; k < PER; k++) { p.bin_start[threadIdx.x * PER + k] = run; p.bin_cursor[threadIdx.x * PER + k] = 0u; run += v[k]; }
+    for (uint32_t k = 0; k < PER; k++) { p.bin_start[threadIdx.x * PER + k] = run; run += v[k]; }
 }
 
 __global__ __launch_bounds__(PH_SORT_BLOCK) void raysort_scatter_kernel(RaySortParams p) {
-    __shared__ uint32_t h[PH_SORT_KEYS];     // tallies of the slice, then the running rank inside each bin
-    __shared__ uint32_t base[PH_SORT_KEYS];  // where the slice's share of each bin starts in `order`
-    const uint32_t n_cl = *p.n_cl, n = n_cl + *p.n_sh;
-    uint32_t lo, hi;
-    raysort_slice(p, n, lo, hi);
-    if (lo >= hi) return;
-    for (uint32_t k = threadIdx.x; k < PH_SORT_KEYS; k += PH_SORT_BLOCK) h[k] = 0u;
+    __shared__ uint32_t base[PH_SORT_KEYS];  // where the slice's next ray of each bin goes in `order`
+    const uint32_t n_cl = *p.n_cl, n_sh = *p.n_sh;
+    const RaySortSlice s = raysort_slice(p, n_cl, n_sh);
+    if (s.lo >= s.hi) return;
+    const uint32_t* share = p.block_share + (size_t)blockIdx.x * PH_SORT_KEYS;
+    for (uint32_t k = threadIdx.x; k < PH_SORT_KEYS; k += PH_SORT_BLOCK) base[k] = p.bin_start[k] + share[k];
     __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += PH_SORT_BLOCK) atomicAdd(&h[raysort_key_at(p, i, n_cl)], 1u);
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < PH_SORT_KEYS; k += PH_SORT_BLOCK) {
-        const uint32_t c = h[k];
-        base[k] = c ? p.bin_start[k] + atomicAdd(&p.bin_cursor[k], c) : 0u;
-        h[k] = 0u;
-    }
-    __syncthreads();
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += PH_SORT_BLOCK) {
-        const uint32_t key = raysort_key_at(p, i, n_cl);
-        p.order[base[key] + atomicAdd(&h[key], 1u)] = i;
-    }
+    raysort_walk_slice(p, s, n_cl,
+        [&](const uint4 (&v)[PH_SORT_DEPTH], uint32_t i0) {
+            // A lane holds four consecutive queue positions.  Equal keys among them take one atomic (at the first of them) and consecutive ranks, in position order: the queue is
+            // in path order, the rays of one pixel follow each other and mostly share a cell, and the traversal kernel is faster by 2 % of its time when such rays stay neighbours in
+            // `order` (one atomic per key, four passes over the lanes, deals them out four ways: traversal 652 -> 666 ms per configs[2] frame).
+            // All ranks first, then all stores: an LDS atomic that returns is as slow as a load, and a store behind each would make them take turns.
+            uint4 at[PH_SORT_DEPTH];
+#pragma unroll
+            for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) {
+                const uint32_t x = raysort_bin(v[d].x), y = raysort_bin(v[d].y), z = raysort_bin(v[d].z), w = raysort_bin(v[d].w);
+                const uint32_t yx = y == x, zx = z == x, wx = w == x, zy = z == y, wy = w == y, wz = w == z;
+                at[d].x = atomicAdd(&base[x], 1u + yx + zx + wx);
+                at[d].y = yx ? 0u : atomicAdd(&base[y], 1u + zy + wy);
+                at[d].z = (zx | zy) ? 0u : atomicAdd(&base[z], 1u + wz);
+                at[d].w = (wx | wy | wz) ? 0u : atomicAdd(&base[w], 1u);
+            }
+#pragma unroll
+            for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) {
+                const uint32_t x = raysort_bin(v[d].x), y = raysort_bin(v[d].y), z = raysort_bin(v[d].z), w = raysort_bin(v[d].w);
+                const uint32_t yx = y == x, zx = z == x, wx = w == x, zy = z == y, wy = w == y, wz = w == z;
+                const uint32_t rx = at[d].x, ry = yx ? rx + 1u : at[d].y;
+                const uint32_t rz = zx ? rx + 1u + yx : zy ? ry + 1u : at[d].z;
+                const uint32_t rw = wx ? rx + 1u + yx + zx : wy ? ry + 1u + zy : wz ? rz + 1u : at[d].w;
+                const uint32_t i = i0 + 4u * d * PH_SORT_BLOCK;
+                p.order[rx] = i; p.order[ry] = i + 1u; p.order[rz] = i + 2u; p.order[rw] = i + 3u;
+            }
+        },
+        [&](uint32_t key, uint32_t i) { p.order[atomicAdd(&base[raysort_bin(key)], 1u)] = i; });
 }
 
 }  // namespace ph

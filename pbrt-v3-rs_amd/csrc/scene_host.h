@@ -4,6 +4,7 @@
 #include "band_plan.h"
 #include "bvh_build.h"
 #include "guard.h"
+#include "raysort_plan.h"
 #include "scene_types.h"
 #include <hip/hip_runtime.h>
 namespace ph { struct TravParams; }
@@ -123,6 +124,10 @@ int upload_light_distribution(PbrtHipScene* s, int light_strategy);
 int launch_traverse(PbrtHipScene* s, bool anyhit, const void* d_rays, void* d_out, uint32_t n, float* kernel_ms);
 void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p);  // 0 closest, 1 any hit, 2 both (MIXED)
 int ensure_traversal_workspace(PbrtHipScene* s);
+// wavefront.hip: the ray binning between rounds (raysort.h) on device arrays, for callers that do not see the kernels; workspace = raysort_workspace_bytes(sort_blocks) bytes
+inline size_t raysort_workspace_bytes(uint32_t sort_blocks) { return ((size_t)sort_blocks + 1) * PH_SORT_KEYS * 4; }
+void launch_raysort(PbrtHipScene* s, const uint32_t* keys_cl, const uint32_t* keys_sh, const uint32_t* n_cl, const uint32_t* n_sh, uint32_t* order, uint32_t* workspace,
+                    uint32_t sort_blocks);
 void free_wavefront(PbrtHipScene* s);
 // bvh_device.hip.  forest non-null: the forest form, as build_sah_device's below (the arrays come back on the host)
 int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, const ForestSpec* forest = nullptr,

@@ -823,6 +823,18 @@ void free_wavefront(PbrtHipScene* s) {
     s->wf = nullptr;
 }
 
+// The ray binning of one round (raysort.h) on the scene's stream: `order` from the keys and the two counts, all in device memory; workspace = raysort_workspace_bytes(sort_blocks)
+// bytes, the tallies and behind them one row of shares per block.  The hist and the scatter pass run on the same grid, which is what gives a block the same slice in both.
+void launch_raysort(PbrtHipScene* s, const uint32_t* keys_cl, const uint32_t* keys_sh, const uint32_t* n_cl, const uint32_t* n_sh, uint32_t* order, uint32_t* workspace,
+                    uint32_t sort_blocks) {
+    ph::RaySortParams p{};
+    p.keys_cl = keys_cl; p.keys_sh = keys_sh; p.n_cl = n_cl; p.n_sh = n_sh; p.order = order; p.bin_start = workspace; p.block_share = workspace + PH_SORT_KEYS;
+    (void)hipMemsetAsync(p.bin_start, 0, PH_SORT_KEYS * 4, s->stream);
+    hipLaunchKernelGGL(ph::raysort_hist_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, p);
+    hipLaunchKernelGGL(ph::raysort_scan_kernel, dim3(1), dim3(1024), 0, s->stream, p);
+    hipLaunchKernelGGL(ph::raysort_scatter_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, p);
+}
+
 size_t path_chunk_bytes_per_path(bool general, bool textured) { Wavefront w; return chunk_bytes_per_path(w.chunk_table(textured, general || textured)); }
 static int sat_i(float v) { if (v != v) return 0; if (v >= 2147483648.0f) return 2147483647; if (v <= -2147483648.0f) return (int)0x80000000; return (int)v; }
 
@@ -1004,12 +1016,10 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
 
     if ((rc = ensure_traversal_workspace(s))) return rc;
     // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h): 8 heads, served in chunks of 49 152 rays (a multiple of every batch size); 1 024 blocks per sort pass
+    // (the three raysort kernels per configs[2] frame: 512 blocks 9.40 ms, 1 024: 9.18, 2 048: 9.19)
     const uint32_t n_heads = 8, head_chunk = 49152, sort_blocks = 1024;
-    ph::RaySortParams sortp{};
     ph::RaySortGrid sort_grid{};
-    if ((rc = ensure_buf(s, w.d_sort_bins, 2 * PH_SORT_KEYS * 4))) return rc;
-    sortp.order = (uint32_t*)w.d_order.p; sortp.bin_start = (uint32_t*)w.d_sort_bins.p; sortp.bin_cursor = sortp.bin_start + PH_SORT_KEYS;
-    sortp.keys_cl = (const uint32_t*)w.d_keys_cl.p; sortp.keys_sh = (const uint32_t*)w.d_keys_sh.p;
+    if ((rc = ensure_buf(s, w.d_sort_bins, raysort_workspace_bytes(sort_blocks)))) return rc;   // the tallies and one row of shares per block: 32 MB, outside the chunk table
     for (int k = 0; k < 3; k++) {
         const float ext = s->bvh.root_hi[k] - s->bvh.root_lo[k];
         sort_grid.lo[k] = s->bvh.root_lo[k]; sort_grid.scale[k] = ext > 0.0f ? 1.0f / ext : 0.0f;
@@ -1106,14 +1116,9 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
                 if (it > 0) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
                     tp.rays2 = wp.rays_sh; tp.out2 = wp.occ; tp.n2_ptr = &c->n_sh;
                     // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
-                    sortp.n_cl = &c->n_cl; sortp.n_sh = &c->n_sh;
-                    if ((rc = timed(3, [&]() {
-                            (void)hipMemsetAsync(sortp.bin_start, 0, PH_SORT_KEYS * 4, s->stream);
-                            hipLaunchKernelGGL(ph::raysort_hist_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
-                            hipLaunchKernelGGL(ph::raysort_scan_kernel, dim3(1), dim3(1024), 0, s->stream, sortp);
-                            hipLaunchKernelGGL(ph::raysort_scatter_kernel, dim3(sort_blocks), dim3(PH_SORT_BLOCK), 0, s->stream, sortp);
-                        }))) return rc;
-                    tp.order = sortp.order;
+                    uint32_t* const order = (uint32_t*)w.d_order.p;
+                    if ((rc = timed(3, [&]() { launch_raysort(s, wp.keys_cl, wp.keys_sh, &c->n_cl, &c->n_sh, order, (uint32_t*)w.d_sort_bins.p, sort_blocks); }))) return rc;
+                    tp.order = order;
                     if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 2, s->trav_blocks, tp); }))) return rc;
                 } else if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 0, s->trav_blocks, tp); }))) return rc;
                 // the shade side's work queues: this round's list regrouped by what has to be done for each path (matsort.h)

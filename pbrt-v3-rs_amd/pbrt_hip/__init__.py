@@ -160,6 +160,7 @@ class Binding:
             "bsdf_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, u32p, fp, fp]),
             "sampler_value_batch": (C.c_int, [vp, C.c_uint64, ip, u32p, u32p, C.c_int, fp]),
             "light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, fp]),
+            "raysort_probe": (C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
