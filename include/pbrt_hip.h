@@ -171,8 +171,8 @@ int pbrt_hip_add_instance(PbrtHipScene*, uint32_t object_id, const float instanc
  * quadric.  Scene-level quadrics and object instances share a scene freely (instanced triangle objects, single-primitive and empty ones included; definitions that no instance
  * uses are ignored, as in any instanced scene): a quadric stands in the scene-level tree next to the instances and is tested in its place in its leaf's order.  One leftover
  * refusal, with no technical reason and kept only because older tests pin it: pbrt_hip_build_accel returns PBRT_HIP_ERR_UNSUPPORTED for a scene that holds a quadric and object
- * definitions but NOT ONE instance.  pbrt_hip_build_accel_device builds the HLBVH tree (split_method 1) of a scene with quadrics, forest included; with split_method 0 (SAH) it still refuses such a scene, because
- * older tests pin that answer and the SAH device builder was not taught quadrics (the host builders make that tree).  Quadrics and triangle
+ * definitions but NOT ONE instance.  Both device builders take a scene with quadrics, forest included: pbrt_hip_build_accel_device builds its HLBVH tree (split_method 1) and, because
+ * older tests pin that answer, still refuses its SAH tree (split_method 0) with PBRT_HIP_ERR_UNSUPPORTED; pbrt_hip_build_accel_device_shapes builds either.  Quadrics and triangle
  * meshes with alpha / shadow-alpha textures share a scene freely: the masks belong to the meshes' triangles, a quadric in the same leaf is tested in its place in the leaf's order. */
 int pbrt_hip_add_sphere(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
                         uint32_t material_id, uint32_t flags);
@@ -333,8 +333,13 @@ int pbrt_hip_build_accel(PbrtHipScene*, int split_method, int max_prims_in_node)
  * split_method 0 (SAH, the reference's default; accelerators/src/bvh/sah.rs:26-367): one level of the tree per round of kernels — bucket boxes by atomics,
  * the reference's cost loop per node, itertools::partition's element order from a prefix sum.  split_method 1 (HLBVH; hlbvh.rs:33-449, morton.rs:33-120):
  * Morton codes, radix sort, the treelets emitted side by side one tree LEVEL per launch, SAH over the treelet roots on the host.  EqualCounts (3) is a host build: UNSUPPORTED here.  Scenes with object
- * instances (SAH and HLBVH): the scene's aggregate and every instanced object's are built side by side as one forest.  Scenes with quadric shapes: HLBVH only (above). */
+ * instances (SAH and HLBVH): the scene's aggregate and every instanced object's are built side by side as one forest.  Scenes with quadric shapes: HLBVH only (above); the next call builds their SAH tree. */
 int pbrt_hip_build_accel_device(PbrtHipScene*, int split_method, int max_prims_in_node);
+
+/* pbrt_hip_build_accel_device in every respect, except that split_method 0 (SAH; sah.rs:26-367) also takes a scene with quadric shapes: a quadric enters the build with its
+ * Shape::world_bound (core/src/geometry/shape.rs) as a triangle does with Triangle::world_bound (triangle.rs:427-431), in the flat tree and, at scene level, in a forest.  The tree
+ * is the one pbrt_hip_build_accel(scene, 0, ..) makes, array for array, and stays on the GPU.  Every refusal of pbrt_hip_build_accel holds here as well. */
+int pbrt_hip_build_accel_device_shapes(PbrtHipScene*, int split_method, int max_prims_in_node);
 
 /* World bound of the built aggregate (BVHAccel::world_bound, bvh/mod.rs:161-167): {pmin[3], pmax[3]}. */
 int pbrt_hip_world_bound(const PbrtHipScene*, float out_bounds[6]);

@@ -134,6 +134,7 @@ namespace phost {
     do { hipError_t e__ = (call); if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); (void)hipGetLastError(); goto fail; } } while (0)
 
 // Builds the SAH tree of `in` on the current device — or, with `forest`, the scene's aggregate and the aggregates of its instanced objects in one go (bvh_sah_steps.h: Ctx).
+// A primitive slot may hold a quadric (in.prim_quadric, bvh_build.h:28-32) — in the flat tree or in the scene's own tree of a forest, not inside an object's tree.
 // Returns 0, or -1 (bad arguments / device failure, `err` says which).
 int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, void** keep_nodes, void** keep_tris,
                      const ForestSpec* forest, std::vector<ForestTreeOut>* trees_out) {
@@ -150,19 +151,28 @@ int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t st
     const uint32_t* tree_start = forest ? forest->tree_start : one_tree;
     for (uint32_t t = 0; t < n_trees; t++) if (tree_start[t] >= tree_start[t + 1] || tree_start[t + 1] > n) { err = "device build: empty or unordered tree range"; return -1; }
     if (tree_start[0] != 0 || tree_start[n_trees] != n) { err = "device build: tree ranges do not cover the items"; return -1; }
+    const uint32_t* pq = in.prim_quadric;   // null: every slot holds a triangle
+    if (pq && !in.quad_bounds) { err = "device build: quadric slots without their bounds"; return -1; }
+    if (pq) for (uint32_t i = 0; i < n; i++) {   // a quadric stands in the scene's own tree only (object definitions hold none), and names one of the n_quadrics bounds
+        const uint32_t it = forest ? forest->items[i] : i;
+        if ((it & PH_ITEM_INST) || (size_t)it >= in.n_tris || !pq[it]) continue;
+        if ((forest && i >= tree_start[1]) || (size_t)(pq[it] - 1u) >= in.n_quadrics) { err = "device build: a quadric slot inside an object's tree, or one that names no quadric"; return -1; }
+    }
     auto t0 = std::chrono::steady_clock::now();
     const bool prof = std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr;
     auto lap = [&](const char* what) { if (prof) { (void)hipStreamSynchronize(stream); std::fprintf(stderr, "build_sah_device n=%u: %-28s at %.3f s\n", n, what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } };
     std::vector<void*> allocs;
     auto dalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; } allocs.push_back(p); return p; };
-    size_t n_verts = 0;
-    for (size_t i = 0; i < 3 * in.n_tris; i++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[i] + 1);
+    size_t n_verts = 0;   // over the triangle slots: a quadric slot's index triple is {0, 0, 0} and stands for no vertex (a scene of quadrics only has none: nothing of P is read)
+    if (!pq) for (size_t i = 0; i < 3 * in.n_tris; i++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[i] + 1);
+    else for (size_t t = 0; t < in.n_tris; t++) if (!pq[t]) for (int k = 0; k < 3; k++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[3 * t + k] + 1);
     const uint32_t n_chunks = (n + PHS_CHUNK - 1u) / PHS_CHUNK;
     const size_t n_inst = forest ? forest->n_inst : 0;
     float* dP = (float*)dalloc(n_verts * 12); uint32_t* dIdx = (uint32_t*)dalloc(in.n_tris * 12);
     uint32_t* d_flags = in.tri_flags ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr; uint32_t* d_mesh = in.tri_mesh ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr;
     uint32_t* d_items = forest ? (uint32_t*)dalloc((size_t)n * 4) : nullptr;
     float* d_inst_bounds = n_inst ? (float*)dalloc(n_inst * 24) : nullptr;
+    uint32_t* d_pq = pq ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr; float* d_qb = pq ? (float*)dalloc(in.n_quadrics * 24) : nullptr;
     uint32_t* d_tree_start = (uint32_t*)dalloc(((size_t)n_trees + 1) * 4);
     uint32_t* d_root_words = (uint32_t*)dalloc((size_t)n_trees * 48);
     uint32_t* d_bases = (uint32_t*)dalloc((size_t)n_trees * 4);
@@ -170,6 +180,7 @@ int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t st
     c.n = n; c.max_prims = (uint32_t)(max_prims_in_node & 0xff);   // bvh/mod.rs:357 `as u8`
     c.P = dP; c.idx = dIdx; c.tri_flags = d_flags; c.tri_mesh = d_mesh;
     c.items = d_items; c.inst_bounds = d_inst_bounds; c.tree_start = d_tree_start; c.n_trees = n_trees; c.root_words = d_root_words;
+    c.prim_quadric = d_pq; c.quad_bounds = d_qb;
     c.e_lo = (Elem*)dalloc((size_t)n * sizeof(Elem)); c.e_hi = (Elem*)dalloc((size_t)n * sizeof(Elem));
     c.seg = (uint32_t*)dalloc((size_t)n * 4); c.bkt = (uint8_t*)dalloc(n);
     c.nodes = (SNode*)dalloc(((size_t)2 * n + 2) * sizeof(SNode));
@@ -190,7 +201,7 @@ int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t st
     {
         uint32_t init[16] = {0};
         for (uint32_t t = 0; t < n_trees; t++) init_bounds_words(root_words.data() + 12 * (size_t)t);
-        PHS_CHECK(hipMemcpyAsync(dP, in.P, n_verts * 12, hipMemcpyHostToDevice, stream));
+        if (n_verts) PHS_CHECK(hipMemcpyAsync(dP, in.P, n_verts * 12, hipMemcpyHostToDevice, stream));
         PHS_CHECK(hipMemcpyAsync(dIdx, in.idx, in.n_tris * 12, hipMemcpyHostToDevice, stream));
         PHS_CHECK(hipMemcpyAsync(c.counters, init, 64, hipMemcpyHostToDevice, stream));
         PHS_CHECK(hipMemcpyAsync(d_tree_start, tree_start, ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, stream));
@@ -198,6 +209,10 @@ int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t st
         if (d_items) PHS_CHECK(hipMemcpyAsync(d_items, forest->items, (size_t)n * 4, hipMemcpyHostToDevice, stream));
         if (d_flags) PHS_CHECK(hipMemcpyAsync(d_flags, in.tri_flags, in.n_tris * 4, hipMemcpyHostToDevice, stream));
         if (d_mesh) PHS_CHECK(hipMemcpyAsync(d_mesh, in.tri_mesh, in.n_tris * 4, hipMemcpyHostToDevice, stream));
+        if (d_pq) {
+            PHS_CHECK(hipMemcpyAsync(d_pq, pq, in.n_tris * 4, hipMemcpyHostToDevice, stream));
+            if (in.n_quadrics) PHS_CHECK(hipMemcpyAsync(d_qb, in.quad_bounds, in.n_quadrics * 24, hipMemcpyHostToDevice, stream));
+        }
         PHS_CHECK(hipMemsetAsync(c.leaf_last, 0, (size_t)n * 4, stream));
         const dim3 per_elem((n + 255u) / 256u), per_chunk(n_chunks), b(256);
         lap("allocations and uploads");

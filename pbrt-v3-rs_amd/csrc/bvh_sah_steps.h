@@ -105,6 +105,9 @@ struct Ctx {
     uint32_t* lf; uint32_t* lb;      // per segment, from its start: positions of the k-th misplaced failing / passing element
     uint32_t* leaf_last;
     Node64* out_nodes; TriRec* out_tris;
+    // quadric shapes, null in a scene without them (bvh_build.h:28-32): prim_quadric[id] = 0, or 1 + q for a slot that holds quadric q, whose Shape::world_bound is quad_bounds[6q ..].
+    // (At the end: Ctx goes to every kernel by value, and the members above keep their offsets.)
+    const uint32_t* prim_quadric; const float* quad_bounds;
 };
 
 PHS_HD float box_area(const float* lo, const float* hi) {   // bounds3.rs:95-107
@@ -135,12 +138,18 @@ PHS_HD uint32_t tree_of(const Ctx& c, uint32_t i) {   // the tree whose range ho
     while (hi - lo > 1u) { const uint32_t m = (lo + hi) >> 1; if (c.tree_start[m] <= i) lo = m; else hi = m; }
     return lo;
 }
-// ---- pass 0: Triangle::world_bound (triangle.rs:427-431) — or the TransformedPrimitive's, handed in — per primitive, and its tree's two bounds into dst[12] --------------
+// the quadric in primitive slot `id`, 1-based; 0: the slot holds a triangle (or `id` names an instance)
+PHS_HD uint32_t quadric_of(const Ctx& c, uint32_t id) { return (c.prim_quadric && !(id & PHS_ITEM_INST)) ? c.prim_quadric[id] : 0u; }
+// ---- pass 0: Triangle::world_bound (triangle.rs:427-431) — or the TransformedPrimitive's or the quadric's, handed in — per primitive, and its tree's two bounds into dst[12] --
 PHS_HD void init_elem(const Ctx& c, uint32_t i, uint32_t tree, uint32_t* dst) {
     const uint32_t id = c.items ? c.items[i] : i;
+    const uint32_t quad = quadric_of(c, id);
     float lo[3], hi[3];
     if (id & PHS_ITEM_INST) {
         const float* bb = c.inst_bounds + 6 * (size_t)(id & ~PHS_ITEM_INST);
+        for (int k = 0; k < 3; k++) { lo[k] = bb[k]; hi[k] = bb[3 + k]; }
+    } else if (quad) {   // the caller's Shape::world_bound as given (bvh_build.cpp:421-423); the slot's index triple {0, 0, 0} is not followed, P may be null
+        const float* bb = c.quad_bounds + 6 * (size_t)(quad - 1u);
         for (int k = 0; k < 3; k++) { lo[k] = bb[k]; hi[k] = bb[3 + k]; }
     } else {
         const float* a = c.P + 3 * (size_t)c.idx[3 * (size_t)id];
@@ -356,6 +365,15 @@ PHS_HD void emit_tri(const Ctx& c, uint32_t i) {
         TriRec r;
         memset(&r, 0, sizeof r);
         r.prim = id & ~PHS_ITEM_INST; r.flags = PH_TRI_INSTANCE | (c.leaf_last[i] ? PH_TRI_LAST : 0u);
+        c.out_tris[i] = r;
+        return;
+    }
+    if (const uint32_t quad = quadric_of(c, id)) {   // a quadric: zeros, its index in the quadric table in the first word of p0 (bvh_build.cpp:451-455)
+        TriRec r;
+        memset(&r, 0, sizeof r);
+        r.p0[0] = bitsf(quad - 1u); r.prim = id;
+        r.flags = ((c.tri_flags ? c.tri_flags[id] : 0u) & ~PH_TRI_LAST) | PH_TRI_QUADRIC | (c.leaf_last[i] ? PH_TRI_LAST : 0u);
+        r.mesh = c.tri_mesh ? c.tri_mesh[id] : 0u;
         c.out_tris[i] = r;
         return;
     }

@@ -83,7 +83,8 @@ struct PbrtHipScene : SceneHostState {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    bool build_on_device = false;    // set for the duration of pbrt_hip_build_accel_device
+    bool build_on_device = false;    // set for the duration of pbrt_hip_build_accel_device / pbrt_hip_build_accel_device_shapes
+    bool build_sah_quadrics_on_device = false;   // ... of pbrt_hip_build_accel_device_shapes only: the SAH device builder takes the scene's quadrics
     MultiDevice* multi = nullptr;    // non-null on a handle made by pbrt_hip_scene_create_multi: the other devices' contexts and the exchange state
 
     // ---- device residency ---------------------------------------------------------------------------------------------

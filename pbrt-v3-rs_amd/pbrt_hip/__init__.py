@@ -152,6 +152,7 @@ class Binding:
             "accel_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
             "accel_copy": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
             "build_accel_device": (C.c_int, [vp, C.c_int, C.c_int]),
+            "build_accel_device_shapes": (C.c_int, [vp, C.c_int, C.c_int]),
             "scene_create_multi": (vp, [ip, C.c_int]),
             "scene_devices": (C.c_int, [vp, ip, C.c_int]),
             "selftest_rccl_gather": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -535,17 +536,28 @@ class Scene:
         """The SAH (0) or HLBVH (1) tree constructed on the GPU: same tree as build_accel(split_method, ..)."""
         self._chk(self.b.fn("build_accel_device")(self.h, split_method, max_prims_in_node))
 
+    def build_accel_device_shapes(self, split_method=0, max_prims_in_node=4):
+        """build_accel_device, except that the SAH tree (0) of a scene with quadric shapes is built on the GPU as well."""
+        self._chk(self.b.fn("build_accel_device_shapes")(self.h, split_method, max_prims_in_node))
+
     def build_accel(self, split_method=0, max_prims_in_node=4):
         self._chk(self.b.fn("build_accel")(self.h, split_method, max_prims_in_node))
 
     def build_accel_best(self, split_method=0, max_prims_in_node=4):
-        """build_accel_device where it applies (SAH / HLBVH trees, scenes with object instances included; scenes with quadrics with HLBVH only; not EqualCounts, not the SAH tree of a scene with quadrics), build_accel elsewhere: the same tree either way."""
+        """build_accel_device where it applies (SAH / HLBVH trees, scenes with object instances included; not EqualCounts), build_accel_device_shapes for the SAH tree of a scene with
+        quadrics, which build_accel_device refuses, build_accel elsewhere: the same tree either way."""
         if split_method in (0, 1) and self.b.has("build_accel_device"):
             try:
                 return self.build_accel_device(split_method, max_prims_in_node)
             except PbrtHipError as e:
                 if e.code != ERR_UNSUPPORTED:
                     raise
+            if split_method == 0 and self.b.has("build_accel_device_shapes"):
+                try:
+                    return self.build_accel_device_shapes(split_method, max_prims_in_node)
+                except PbrtHipError as e:
+                    if e.code != ERR_UNSUPPORTED:
+                        raise
         self.build_accel(split_method, max_prims_in_node)
 
     def world_bound(self):
