@@ -88,6 +88,7 @@ PbrtHipScene* pbrt_hip_scene_create(int device_ordinal);  /* NULL if no usable d
  * per-tile film buffers on the first device — ncclSend / ncclRecv over xGMI, the path's one exchange step; RCCL is loaded when first needed — and merges
  * them there in increasing tile index (Film::merge_film_tile, core/src/film/mod.rs:220-248): the film equals the one-device film bit for bit.
  * An ordinal may repeat (contexts sharing a GPU, device-to-device copies instead of RCCL): a rehearsal aid for boxes with one GPU.
+ * pbrt_hip_render_whitted_devices drives the Whitted integrator over the same handle in the same way.
  * The batch and *_tiles_device entry points of such a handle act on its first device only. */
 PbrtHipScene* pbrt_hip_scene_create_multi(const int* device_ordinals, int n_devices);
 int pbrt_hip_scene_devices(const PbrtHipScene*, int* out_ordinals, int capacity);   /* returns the number of devices behind the handle */
@@ -395,10 +396,19 @@ int pbrt_hip_render_path(PbrtHipScene*, int max_depth, float rr_threshold, int l
  * max_depth in [0, 16], INVALID_ARG beyond.  UNSUPPORTED, before any work: a render whose recursion COULD draw more sampler dimensions than the tables hold —
  * 5 + V * 2 * n_lights + I * 4 must stay below 1000 (Halton, halton.rs:106-110) / 1024 (Sobol) and within the n32 / 52 dimensions given to pbrt_hip_set_sobol_tables,
  * where, with d = max(max_depth, 1), the recursion tree has V = 2^d - 1 vertices of which I = 2^(d-1) - 1 lie above the last level if the scene's materials hold specular
- * reflection AND specular transmission lobes, V = d and I = d - 1 with one of the two kinds, V = 1 and I = min(d - 1, 1) with neither; and a handle made by pbrt_hip_scene_create_multi (several devices render with pbrt_hip_render_path only).
+ * reflection AND specular transmission lobes, V = d and I = d - 1 with one of the two kinds, V = 1 and I = min(d - 1, 1) with neither; and a handle made by pbrt_hip_scene_create_multi (several devices render with pbrt_hip_render_whitted_devices).
  * out_stats: camera_rays, regular_rays, shadow_rays and render_seconds are filled, the rest is zero. */
 int pbrt_hip_render_whitted(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                             float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
+/* pbrt_hip_render_whitted for a handle over any number of devices: the reference's tile loop over worker threads (core/src/integrator/sampler_integrator.rs:254-296) with one
+ * device per worker.  On a one-device handle it is pbrt_hip_render_whitted, call for call.  On a handle over n devices (pbrt_hip_scene_create_multi) device k renders the tiles t
+ * with t % (tile_parts * n) == tile_part + tile_parts * k, with its own workspace, chunk plan and film bands (the handle's sample-record budget applies to each); the tile buffers
+ * are gathered on the first device and merged there in increasing tile index (Film::merge_film_tile, core/src/film/mod.rs:220-279), as pbrt_hip_render_path does on such a handle:
+ * the film equals the one-device film bit for bit.  out_stats: camera_rays, regular_rays and shadow_rays are summed over the devices, render_seconds is the largest of theirs, the
+ * rest is zero; pbrt_hip_get_render_footprint reports per entry the largest value of any device.  Refusals are pbrt_hip_render_whitted's (checked on the handle's state, before any
+ * device is touched) and INVALID_ARG where tile_parts * n exceeds 64; all of them before any work, the outputs untouched and the handle usable. */
+int pbrt_hip_render_whitted_devices(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                                    float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
 
 /* Memory for the sample records.  A render keeps one 20-byte record {L.rgb, p_film} per camera sample until the film pass has replayed FilmTile::add_sample over it
  * (core/src/film/film_tile.rs:62-108).  The reference holds O(pixels): every worker thread adds its samples to its FilmTile as they are made and Film::merge_film_tile
@@ -424,6 +434,11 @@ int pbrt_hip_tile_buffer_floats(PbrtHipScene*, int tile_size, int tile_part, int
 int pbrt_hip_render_path_tiles_device(PbrtHipScene*, int max_depth, float rr_threshold, int light_strategy,
                                       const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                                       void* d_tile_buffer, PbrtHipStats* out_stats);
+/* The same for the Whitted integrator: pbrt_hip_render_whitted's arguments and refusals (then INVALID_ARG for a null buffer), this rank's FilmTiles (the tiles t with
+ * t % tile_parts == tile_part, sampler_integrator.rs:254-296) into the caller's device buffer of pbrt_hip_tile_buffer_floats floats, ready for pbrt_hip_merge_tiles_device
+ * (Film::merge_film_tile, core/src/film/mod.rs:220-279).  One process per GPU renders a Whitted frame with it as with the path form. */
+int pbrt_hip_render_whitted_tiles_device(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                                         void* d_tile_buffer, PbrtHipStats* out_stats);
 /* Film::merge_film_tile (core/src/film/mod.rs:220-279) in increasing tile order over tile_parts device buffers. */
 int pbrt_hip_merge_tiles_device(PbrtHipScene*, int tile_size, int tile_parts, const void* const* d_tile_buffers,
                                 float* out_xyz, float* out_weight);

@@ -5,7 +5,8 @@
 // round-robin to the devices (tile t of the handle's share -> device (t / tile_parts) % n, the reference's tile enumeration :254-259, :314-336), every device renders
 // its tiles with the scene replicated in its own HBM, the per-tile film buffers are gathered on the first device — the path's ONE exchange step, RCCL
 // send / receive over xGMI — and merged there in increasing tile index (Film::merge_film_tile, core/src/film/mod.rs:220-248), so the film equals the
-// one-device film bit for bit.
+// one-device film bit for bit.  render_on_devices is that frame for either integrator: pbrt_hip_render_path (render_path_multi) and pbrt_hip_render_whitted_devices
+// (render_whitted_multi) hand it their own tile renderer and tally the per-device stats their own way.
 //
 // The capture calls (add_mesh, add_light_*, set_film ...) act on the handle itself; the other devices' contexts receive a copy of the captured state
 // when a render finds it changed, upload it and drop the bulky host arrays again.  RCCL is loaded at the first exchange (dlopen), so single-device use
@@ -16,6 +17,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <thread>
 
@@ -159,10 +161,15 @@ static int exchange(PbrtHipScene* s, const std::vector<PbrtHipScene*>& devs, con
     return PBRT_HIP_OK;
 }
 
-int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
-                      float* out_xyz, float* out_weight, PbrtHipStats* out_stats) {
+// The frame of a handle over several devices, whatever the integrator: the handle's share of the tiles dealt round-robin, the replicas brought up to date, one host thread
+// per device running `render` (the integrator's own tile renderer, on that device's context, into that context's tile buffer), the exchange step, zeroed stand-ins for the
+// parts other ranks hold, and Film::merge_film_tile on the first device.  devs / stats come back for the caller's own tally of the per-device stats.
+using DeviceRender = std::function<int(PbrtHipScene* d, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats)>;
+
+static int render_on_devices(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight, const DeviceRender& render,
+                             std::vector<PbrtHipScene*>& devs, std::vector<PbrtHipStats>& stats) {
     MultiDevice& m = *s->multi;
-    std::vector<PbrtHipScene*> devs{s};
+    devs.assign(1, s);
     devs.insert(devs.end(), m.replicas.begin(), m.replicas.end());
     const int n = (int)devs.size();
     const int parts = tile_parts * n;   // device k renders the tiles t with t % parts == tile_part + tile_parts * k: the handle's share, dealt round-robin
@@ -183,12 +190,12 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
 
     // ---- every device renders its tiles, one host thread per device ------------------------------------------------------------------------
     std::vector<int> rcs((size_t)n, PBRT_HIP_OK);
-    std::vector<PbrtHipStats> stats((size_t)n);
+    stats.assign((size_t)n, PbrtHipStats{});
     auto work = [&](int k) {
         PbrtHipScene* d = devs[k];
         if (hipSetDevice(d->device) != hipSuccess) { rcs[k] = set_err(d, PBRT_HIP_ERR_DEVICE, "hipSetDevice failed"); return; }
         rcs[k] = ph_guard(d, "render (device worker)", [&]() -> int {
-            return render_tiles(d, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, tile_part + tile_parts * k, parts, tile_buffer_of(d).p, &stats[k]);
+            return render(d, tile_part + tile_parts * k, parts, tile_buffer_of(d).p, &stats[k]);
         });
     };
     {
@@ -218,7 +225,19 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
             bufs[(size_t)p] = m.zeros[p].p;
         }
     }
-    if ((rc = merge_tiles(s, tile_size, parts, bufs.data(), out_xyz, out_weight))) return rc;
+    return merge_tiles(s, tile_size, parts, bufs.data(), out_xyz, out_weight);
+}
+
+int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                      float* out_xyz, float* out_weight, PbrtHipStats* out_stats) {
+    std::vector<PbrtHipScene*> devs;
+    std::vector<PbrtHipStats> stats;
+    int rc = render_on_devices(s, tile_size, tile_part, tile_parts, out_xyz, out_weight,
+                               [&](PbrtHipScene* d, int part, int parts, void* d_tile_buffer, PbrtHipStats* st) {
+                                   return render_tiles(d, max_depth, rr_threshold, light_strategy, pixel_bounds, tile_size, part, parts, d_tile_buffer, st);
+                               }, devs, stats);
+    if (rc) return rc;
+    const int n = (int)devs.size();
     if (out_stats) {
         *out_stats = stats[0];
         for (int k = 1; k < n; k++) {
@@ -244,6 +263,27 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
             if (any) out_stats->light_distributions_created = count;
         }
         PH_CHECK(s, hipSetDevice(s->device));
+    }
+    return PBRT_HIP_OK;
+}
+
+// The Whitted integrator's frame on the same driver (pbrt_hip_render_whitted_devices): every device runs render_whitted_tiles with its own workspace, chunk plan and bands.
+int render_whitted_multi(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                         PbrtHipStats* out_stats) {
+    std::vector<PbrtHipScene*> devs;
+    std::vector<PbrtHipStats> stats;
+    int rc = render_on_devices(s, tile_size, tile_part, tile_parts, out_xyz, out_weight,
+                               [&](PbrtHipScene* d, int part, int parts, void* d_tile_buffer, PbrtHipStats* st) {
+                                   return render_whitted_tiles(d, max_depth, pixel_bounds, tile_size, part, parts, d_tile_buffer, st);
+                               }, devs, stats);
+    if (rc) return rc;
+    if (out_stats) {
+        *out_stats = stats[0];   // camera_rays, regular_rays, shadow_rays and render_seconds; render_whitted_tiles leaves the rest zero
+        for (size_t k = 1; k < stats.size(); k++) {
+            const PbrtHipStats& t = stats[k];
+            out_stats->camera_rays += t.camera_rays; out_stats->regular_rays += t.regular_rays; out_stats->shadow_rays += t.shadow_rays;
+            out_stats->render_seconds = std::max(out_stats->render_seconds, t.render_seconds);   // the devices run side by side
+        }
     }
     return PBRT_HIP_OK;
 }

@@ -164,11 +164,15 @@ size_t path_chunk_bytes_per_path(bool general_materials, bool textured_materials
 // whitted.hip
 void free_whitted(PbrtHipScene* s);
 size_t whitted_chunk_bytes_per_sample(uint32_t n_frames);   // ... and the Whitted driver's
+// the Whitted driver itself: this context's tiles of the part into d_tile_buffer, as render_tiles does for the path integrator (arguments checked by the caller)
+int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats);
 // ORs the voxels whose light distribution the context's last spatial render filled into `touched` (one byte per voxel, sized on first use); *count = voxels set so far
 int spatial_voxels_touched(PbrtHipScene* s, std::vector<uint8_t>& touched, uint64_t* count);
 // multi.hip
 int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                       float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
+int render_whitted_multi(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                         PbrtHipStats* out_stats);
 void free_multi(PbrtHipScene* s);
 }  // namespace phost
 

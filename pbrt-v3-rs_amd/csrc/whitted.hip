@@ -70,7 +70,7 @@ static int check_whitted_args(PbrtHipScene* s, int max_depth, const int* pixel_b
     return PBRT_HIP_OK;
 }
 
-static int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats) {
+int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats) {
     int rc;
     PH_CHECK(s, hipSetDevice(s->device));
     if ((rc = upload_scene(s))) return rc;
@@ -173,16 +173,48 @@ static int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_
 
 using namespace phost;
 
-extern "C" int pbrt_hip_render_whitted(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
-                                       PbrtHipStats* out_stats) {
-    return ph_guard(s, "pbrt_hip_render_whitted", [&]() -> int {
-    int rc = check_whitted_args(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts);
-    if (rc) return rc;
-    if (!out_xyz || !out_weight) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render_whitted: null output");
-    if (s->multi) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render_whitted: a handle over several devices renders with pbrt_hip_render_path only");
+// one device: this handle's tiles into its own tile buffer, then the film
+static int render_whitted_one(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                              PbrtHipStats* out_stats) {
+    int rc;
     DevBuf& tiles = tile_buffer_of(s);
     if ((rc = ensure_buf(s, tiles, tile_buffer_floats_for(s, tile_size, tile_part, tile_parts) * 4))) return rc;
     if ((rc = render_whitted_tiles(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, tiles.p, out_stats))) return rc;
     return merge_own_tiles(s, tile_size, tile_part, tile_parts, out_xyz, out_weight);
+}
+
+extern "C" {
+
+int pbrt_hip_render_whitted(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                            PbrtHipStats* out_stats) {
+    return ph_guard(s, "pbrt_hip_render_whitted", [&]() -> int {
+    int rc = check_whitted_args(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts);
+    if (rc) return rc;
+    if (!out_xyz || !out_weight) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render_whitted: null output");
+    if (s->multi) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render_whitted: a handle over several devices renders with pbrt_hip_render_whitted_devices");
+    return render_whitted_one(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
     });
 }
+
+int pbrt_hip_render_whitted_devices(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                                    PbrtHipStats* out_stats) {
+    return ph_guard(s, "pbrt_hip_render_whitted_devices", [&]() -> int {
+    int rc = check_whitted_args(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts);   // on the handle's state: no replica is touched before the refusals are through
+    if (rc) return rc;
+    if (!out_xyz || !out_weight) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render_whitted: null output");
+    if (s->multi) return render_whitted_multi(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
+    return render_whitted_one(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
+    });
+}
+
+int pbrt_hip_render_whitted_tiles_device(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, void* d_tile_buffer,
+                                         PbrtHipStats* out_stats) {
+    return ph_guard(s, "pbrt_hip_render_whitted_tiles_device", [&]() -> int {
+    int rc = check_whitted_args(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts);
+    if (rc) return rc;
+    if (!d_tile_buffer) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render_whitted: null tile buffer");
+    return render_whitted_tiles(s, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, d_tile_buffer, out_stats);
+    });
+}
+
+}  // extern "C"

@@ -878,7 +878,6 @@ int Api::pbrt_world_end(RenderReport& rep) {
     // ---- integrator (path.rs:287-327, whitted.rs:121-150: "maxdepth" 5 and "pixelbounds", read the same way)
     const bool whitted = integrator_name_ == "whitted";
     if (integrator_name_ != "path" && !whitted) { error = "Integrator \"" + integrator_name_ + "\" is outside the hot-path scope (supported: path, whitted)"; return PBRT_HIP_ERR_UNSUPPORTED; }
-    if (whitted && n_devices_ > 1) { error = "Integrator \"whitted\" renders on one device (--devices with more than one GPU: path only)"; return PBRT_HIP_ERR_UNSUPPORTED; }
     const int max_depth = integrator_p_.find_one_int("maxdepth", 5);
     int pb[4] = {sb[0], sb[1], sb[2], sb[3]};
     if (const std::vector<int>* v = integrator_p_.find_ints("pixelbounds")) {
@@ -903,9 +902,9 @@ int Api::pbrt_world_end(RenderReport& rep) {
     const size_t npix = (size_t)std::max(0, cb[2] - cb[0]) * (size_t)std::max(0, cb[3] - cb[1]);
     std::vector<float> xyz(npix * 3), wt(npix), rgb(npix * 3);
     if (!check(pbrt_hip_set_sample_record_budget(scene_, sample_record_budget), "set_sample_record_budget")) return PBRT_HIP_ERR_INVALID_ARG;
-    int rc = whitted ? pbrt_hip_render_whitted(scene_, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
+    int rc = whitted ? pbrt_hip_render_whitted_devices(scene_, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
                      : pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
-    if (!check(rc, whitted ? "render_whitted" : "render_path")) return rc;
+    if (!check(rc, whitted ? "render_whitted_devices" : "render_path")) return rc;
     if (!check(pbrt_hip_film_to_rgb(scene_, xyz.data(), wt.data(), rgb.data()), "film_to_rgb")) return PBRT_HIP_ERR_DEVICE;
     std::string err;
     if (!write_image(filename, rgb.data(), cb[2] - cb[0], cb[3] - cb[1], err)) { error = err; return PBRT_HIP_ERR_INVALID_ARG; }

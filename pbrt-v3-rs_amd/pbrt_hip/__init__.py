@@ -104,6 +104,8 @@ class Binding:
             "occluded_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, fp]),
             "tile_buffer_floats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
             "render_whitted": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
+            "render_whitted_devices": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
+            "render_whitted_tiles_device": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Stats)]),
             "render_path_tiles_device": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Stats)]),
             "merge_tiles_device": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), fp, fp]),
             "add_material_none": (C.c_int, [vp, u32p]),
@@ -805,6 +807,16 @@ class Scene:
         self._chk(self.b.fn("render_whitted")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
         return xyz, wt, st
 
+    def render_whitted_devices(self, max_depth=5, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1):
+        """render_whitted on a handle over any number of devices (pbrt_hip_render_whitted_devices): the handle's tiles dealt round-robin to its devices, gathered on the first
+        and merged in tile order.  On a one-device handle it is render_whitted."""
+        h, w = self._film_hw()
+        xyz = np.zeros((h, w, 3), np.float32); wt = np.zeros((h, w), np.float32)
+        pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
+        st = Stats()
+        self._chk(self.b.fn("render_whitted_devices")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
+        return xyz, wt, st
+
     def set_sample_record_budget(self, nbytes=0):
         """Bound on the bytes of sample records resident at once (pbrt_hip_set_sample_record_budget): the frame renders in bands of whole tiles, bit for bit the
         one-band film.  0 = automatic.  Holds until changed."""
@@ -838,6 +850,13 @@ class Scene:
         st = Stats()
         self._chk(self.b.fn("render_path_tiles_device")(self.h, max_depth, C.c_float(rr_threshold), light_strategy, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts,
                                                         d_tile_buffer_ptr, C.byref(st)))
+        return st
+
+    def render_whitted_tiles_device(self, d_tile_buffer_ptr, max_depth=5, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1):
+        """The Whitted integrator's rank form (pbrt_hip_render_whitted_tiles_device): this part's FilmTiles into a device buffer of tile_buffer_floats floats."""
+        pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
+        st = Stats()
+        self._chk(self.b.fn("render_whitted_tiles_device")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, d_tile_buffer_ptr, C.byref(st)))
         return st
 
     def merge_tiles_device(self, d_ptrs, tile_size=16, out=None):
