@@ -184,6 +184,11 @@ int upload_scene(PbrtHipScene* s) {
         if ((rc = upload_vec(s, s->texels, &d.texels))) return rc;
         if ((rc = upload_vec(s, lut, &d.ewa_lut))) return rc;
     }
+    s->lights_infinite = s->lights_delta = false; s->lights_area = !s->emission_only.empty();
+    for (LightRec& l : s->lights) {   // which kinds of light the shade pass will meet (shade_shapes.h), and whether light_pdf_li needs phi for this light
+        if (l.type == PH_L_INFINITE) s->lights_infinite = true; else if (l.type == PH_L_AREA) s->lights_area = true; else s->lights_delta = true;
+        if (l.type == PH_L_INFINITE) l.cond_flat = (!l.map_mip1 && std::memcmp(&l.cond_func[0], &l.cond_func[1], 4) == 0 && std::memcmp(&l.cond_func[2], &l.cond_func[3], 4) == 0) ? 1 : 0;
+    }
     if (s->emission_only.empty()) { if ((rc = upload_vec(s, s->lights, &d.lights))) return rc; }
     else {
         std::vector<LightRec> all(s->lights);

@@ -3,6 +3,7 @@
 #pragma once
 #include "dmath.h"
 #include "scene_types.h"
+#include "shade_shapes.h"
 #include "traverse.h"
 
 namespace ph {
@@ -137,8 +138,10 @@ struct SamplerCursor {
     int px, py;
     const HaltonLds* lds;  // LDS-staged Halton tables, or null
 };
-PH_DEV float sampler_dim(const DeviceScene& sc, const SamplerRec& sp, const SamplerCursor& c, uint32_t dim) {
-    return sp.kind == 0 ? halton_sample(sc, sp, (uint32_t)c.index, dim, c.lds) : sobol_sample(sc, sp, c.index, dim, c.px, c.py);
+// Row (shade_shapes.h): a row without the Sobol sampler is picked for Halton scenes only and compiles no test of sp.kind
+template <class Row = ShadeRowFull> PH_DEV float sampler_dim(const DeviceScene& sc, const SamplerRec& sp, const SamplerCursor& c, uint32_t dim) {
+    if constexpr (!Row::sobol) return halton_sample(sc, sp, (uint32_t)c.index, dim, c.lds);
+    else return sp.kind == 0 ? halton_sample(sc, sp, (uint32_t)c.index, dim, c.lds) : sobol_sample(sc, sp, c.index, dim, c.px, c.py);
 }
 PH_DEV float get_1d(const DeviceScene& sc, const SamplerRec& sp, SamplerCursor& c) {  // halton.rs:226-235 (no sample arrays on this path)
     float p = sampler_dim(sc, sp, c, c.dim);
@@ -522,11 +525,14 @@ PH_DEV float dist2_sample_continuous(const float* func, const float* cdf, float 
 
 struct LiSample { f3 wi; float pdf; spec value; f3 vp, vperr, vn; bool valid; };
 // Triangle::area-light sampling record, shared by sample_li
-template <bool MAP = true> PH_DEV LiSample light_sample_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f2 u) {
+// Row (shade_shapes.h) names the light kinds that are compiled: a kind the row leaves out is the type of no light of the scenes the row is picked for, and a row with
+// infinite lights only does not read the type at all.
+template <bool MAP = true, class Row = ShadeRowFull> PH_DEV LiSample light_sample_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f2 u) {
     LiSample r;
     r.valid = false; r.pdf = 0.0f; r.wi = mk3(0, 0, 0); r.value = mks1(0.0f);
     r.vp = mk3(0, 0, 0); r.vperr = mk3(0, 0, 0); r.vn = mk3(0, 0, 0);
-    if (l.type == PH_L_INFINITE) {  // infinite.rs:133-173
+    constexpr bool ONLY_INFINITE = Row::infinite && !Row::area && !Row::delta;
+    if (Row::infinite && (ONLY_INFINITE || l.type == PH_L_INFINITE)) {  // infinite.rs:133-173
         float d0, d1, map_pdf;
         if (MAP && l.map_mip1) map_pdf = envmap_sample(sc.self, l.dist_off, l.dw, l.dh, u.x, u.y, &d0, &d1);
         else {
@@ -546,10 +552,10 @@ template <bool MAP = true> PH_DEV LiSample light_sample_li(const DeviceScene& sc
         r.vp = hit.p + r.wi * (2.0f * sc.world_radius);
         r.value = (MAP && l.map_mip1) ? envmap_lookup(sc.self, l.map_mip1 - 1u, d0, d1) : infinite_lookup(l, mk2(d0, d1));
         r.valid = true;
-    } else if (l.type == PH_L_DISTANT) {  // distant.rs:87-96
+    } else if (Row::delta && l.type == PH_L_DISTANT) {  // distant.rs:87-96
         f3 w = mk3(l.v[0], l.v[1], l.v[2]);
         r.wi = w; r.pdf = 1.0f; r.vp = hit.p + w * (2.0f * sc.world_radius); r.value = mks(l.L[0], l.L[1], l.L[2]); r.valid = true;
-    } else if (l.type == PH_L_SPOT) {  // spot.rs:75-84, falloff :52-66
+    } else if (Row::delta && l.type == PH_L_SPOT) {  // spot.rs:75-84, falloff :52-66
         f3 pl = mk3(l.v[0], l.v[1], l.v[2]);
         r.wi = normalize(pl - hit.p); r.pdf = 1.0f; r.vp = pl;
         const f3 wl = normalize(xf_vec(l.w2l, -r.wi));
@@ -559,7 +565,7 @@ template <bool MAP = true> PH_DEV LiSample light_sample_li(const DeviceScene& sc
         else if (cos_theta >= l.cos_falloff_start) fall = 1.0f;
         else { const float delta = ph_div(cos_theta - l.cos_total_width, l.cos_falloff_start - l.cos_total_width); fall = (delta * delta) * (delta * delta); }
         r.value = mks(l.L[0], l.L[1], l.L[2]) * fall / distance_squared(pl, hit.p); r.valid = true;
-    } else if (l.type == PH_L_PROJECTION) {  // projection.rs:180-191, projection() :145-168
+    } else if (Row::delta && l.type == PH_L_PROJECTION) {  // projection.rs:180-191, projection() :145-168
         f3 pl = mk3(l.v[0], l.v[1], l.v[2]);
         r.wi = normalize(pl - hit.p); r.pdf = 1.0f; r.vp = pl;
         spec pr = mks1(0.0f);
@@ -580,7 +586,7 @@ template <bool MAP = true> PH_DEV LiSample light_sample_li(const DeviceScene& sc
             }
         }
         r.value = mks(l.L[0], l.L[1], l.L[2]) * pr / distance_squared(pl, hit.p); r.valid = true;
-    } else if (l.type == PH_L_GONIO) {  // goniometric.rs:102-113, scale() :82-96
+    } else if (Row::delta && l.type == PH_L_GONIO) {  // goniometric.rs:102-113, scale() :82-96
         f3 pl = mk3(l.v[0], l.v[1], l.v[2]);
         r.wi = normalize(pl - hit.p); r.pdf = 1.0f; r.vp = pl;
         f3 wp = normalize(xf_vec(l.w2l, -r.wi));
@@ -588,11 +594,11 @@ template <bool MAP = true> PH_DEV LiSample light_sample_li(const DeviceScene& sc
         const float theta = spherical_theta(wp), phi = spherical_phi(wp);
         const spec scl = (MAP && l.map_mip1) ? envmap_lookup(sc.self, l.map_mip1 - 1u, phi * kInvTwoPi, theta * kInvPi) : mks1(1.0f);
         r.value = mks(l.L[0], l.L[1], l.L[2]) * scl / distance_squared(pl, hit.p); r.valid = true;
-    } else if (l.type == PH_L_POINT) {  // point.rs:83-93
+    } else if (Row::delta && l.type == PH_L_POINT) {  // point.rs:83-93
         f3 pl = mk3(l.v[0], l.v[1], l.v[2]);
         r.wi = normalize(pl - hit.p); r.pdf = 1.0f; r.vp = pl;
         r.value = mks(l.L[0], l.L[1], l.L[2]) / distance_squared(pl, hit.p); r.valid = true;
-    } else {  // DiffuseAreaLight::sample_li (diffuse.rs:114-129) -> sample_solid_angle (shape.rs:64-84) -> Triangle::sample (triangle.rs:918-949)
+    } else if (Row::area) {  // DiffuseAreaLight::sample_li (diffuse.rs:114-129) -> sample_solid_angle (shape.rs:64-84) -> Triangle::sample (triangle.rs:918-949)
         const MeshRec m = sc.meshes[sc.tri_mesh[l.prim]];
         const TriVerts t = load_tri(sc, l.prim);
         f2 b = uniform_sample_triangle(u);
@@ -620,10 +626,14 @@ template <bool MAP = true> PH_DEV LiSample light_sample_li(const DeviceScene& sc
     }
     return r;
 }
-template <bool MAP = true> PH_DEV float light_pdf_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f3 wi) {
-    if (l.type == PH_L_INFINITE) {  // infinite.rs:201-211 + Distribution2D::pdf (distribution_2d.rs:51-65)
+// Row::phi_skip: without a radiance map phi (an f64 atan2) only chooses between cond_func[2 * iv] and cond_func[2 * iv + 1]; where the host found the two equal bit for bit in both
+// rows (LightRec::cond_flat, set at upload) it is not computed and entry 2 * iv is read — the entry a NaN phi selects anyway.  light_le needs both angles: its blend weights come from them.
+template <bool MAP = true, class Row = ShadeRowFull> PH_DEV float light_pdf_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f3 wi) {
+    constexpr bool ONLY_INFINITE = Row::infinite && !Row::area && !Row::delta;
+    if (Row::infinite && (ONLY_INFINITE || l.type == PH_L_INFINITE)) {  // infinite.rs:201-211 + Distribution2D::pdf (distribution_2d.rs:51-65)
         f3 w = xf_vec(l.w2l, wi);
-        float theta = spherical_theta(w), phi = spherical_phi(w), sin_theta = d_sin(theta);
+        const bool need_phi = !Row::phi_skip || (MAP && l.map_mip1) || !l.cond_flat;
+        float theta = spherical_theta(w), phi = need_phi ? spherical_phi(w) : 0.0f, sin_theta = d_sin(theta);
         if (sin_theta == 0.0f) return 0.0f;
         if (MAP && l.map_mip1) return ph_div(envmap_pdf(sc.self, l.dist_off, l.dw, l.dh, phi * kInvTwoPi, theta * kInvPi), kTwoPi * kPi * sin_theta);
         uint32_t iu = f2u_sat(phi * kInvTwoPi * 2.0f), iv = f2u_sat(theta * kInvPi * 2.0f);
@@ -631,7 +641,7 @@ template <bool MAP = true> PH_DEV float light_pdf_li(const DeviceScene& sc, cons
         if (iv > 1) iv = 1;
         return ph_div(ph_div(l.cond_func[2 * iv + iu], l.marg_int), kTwoPi * kPi * sin_theta);
     }
-    if (l.type == PH_L_AREA) {  // Shape::pdf_solid_angle (core/src/geometry/shape.rs:86-107): one Triangle::intersect, no BVH
+    if (Row::area && l.type == PH_L_AREA) {  // Shape::pdf_solid_angle (core/src/geometry/shape.rs:86-107): one Triangle::intersect, no BVH
         RayIn ray = spawn_ray(hit, wi);
         RayState rs;
         ray_setup(rs, ray);

@@ -6,6 +6,7 @@
 #include "guard.h"
 #include "raysort_plan.h"
 #include "scene_types.h"
+#include "shade_shapes.h"
 #include <hip/hip_runtime.h>
 namespace ph { struct TravParams; }
 #include <string>
@@ -93,6 +94,9 @@ struct PbrtHipScene : SceneHostState {
     // a tree pbrt_hip_build_accel_device(0, ..) left where it was built: `bvh.nodes` / `bvh.tris` stay empty on the host (accel_copy reads them back on request; the multi-device driver replicates by hipMemcpyPeer)
     void* tree_dev_nodes = nullptr; void* tree_dev_tris = nullptr; size_t tree_dev_n_tris = 0;
     bool uploaded = false;
+    // the light side of the scene's shade-pass features (shade_shapes.h), derived by upload_scene from the light list it uploads: every call that changes a light clears `uploaded`,
+    // so the next render derives them again.  The sampler and the light strategy are read when the row is picked (wavefront.hip, shade_row_of).
+    bool lights_infinite = false, lights_area = false, lights_delta = false;
     int light_strategy_uploaded = -1;
     DevBuf d_ld_func, d_ld_cdf;
 

@@ -179,7 +179,10 @@ struct MipRec {  // MIPMap<T> (core/src/mipmap/mod.rs:76-96): pyramid levels in 
 enum { PH_L_INFINITE = 0, PH_L_DISTANT = 1, PH_L_POINT = 2, PH_L_AREA = 3, PH_L_SPOT = 4, PH_L_PROJECTION = 5, PH_L_GONIO = 6 };
 struct LightRec {
     int32_t type;
-    int32_t two_sided;
+    union {
+        int32_t two_sided;   // area
+        int32_t cond_flat;   // infinite without a radiance map: cond_func[0] == cond_func[1] and cond_func[2] == cond_func[3] bit for bit (checked at upload): light_pdf_li may skip phi
+    };
     uint32_t prim;       // area: bound triangle
     float area;          // area: Triangle::area()
     float L[3];          // radiance / intensity

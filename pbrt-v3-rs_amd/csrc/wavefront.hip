@@ -298,20 +298,54 @@ template <> struct BsdfOps<true> {
 // Waves per SIMD the shade kernels are compiled for.  40 KB of LDS per block allow 4 blocks per CU; the one-lobe kernel fits 128 VGPRs with
 // 51 spilled registers and gains 6 % from the fourth wave, the general-BSDF kernel would spill 181 and loses, so it stays at 3; so do the
 // texture variants, whose out-of-line calls keep many values live (textured matte: 279 spilled registers at 4 waves, 45 at 3; 19.5 -> 15.9 ms).
+// The lean row of the one-lobe kernel (shade_shapes.h, ShadeRowSky: infinite lights only, Halton, no spatial distribution; 20 480 B of staged rays and sampler rows, 27 504 B of LDS
+// in all) would hold FIVE blocks per CU and loses at five: same box, configs[2], three runs each, alternating —
+//   every light kind, 4 waves (before the rows):  128 VGPRs, 144 B scratch (20 loads / 17 stores), 114 SGPR spills, 47.8 KB, 39 792 B LDS: shade pass 160.1 ms per frame, frame 813.0 ms
+//   lean row, 5 waves:                             96 VGPRs, 128 B scratch (39 loads / 25 stores),  60 SGPR spills, 29.4 KB, 27 504 B LDS:            169.8 ms,              825.1 ms
+//   lean row, 4 waves:                            128 VGPRs,   no scratch,                          60 SGPR spills, 28.4 KB, 27 504 B LDS:            146.1 ms,              799.9 ms
+// so it stays at 4.  (Of the 14 ms, 10.5 are the lean LDS layout's: the lean row with the full row's stage / s_u arrays measures 157.6 / 810.9 ms.)  DESIGN §4.2 has the kernel times.
 #ifndef PH_SHADE_GEN_TEX_WAVES
 #define PH_SHADE_GEN_TEX_WAVES 3
 #endif
 #define PH_SHADE_WAVES(GEN, TEX) ((GEN) && (TEX) ? PH_SHADE_GEN_TEX_WAVES : (((GEN) || (TEX)) ? 3 : 4))
 #define PH_SHADE_ATTR __attribute__((amdgpu_waves_per_eu(PH_SHADE_WAVES(GEN, TEX), PH_SHADE_WAVES(GEN, TEX))))
+// The block's per-thread LDS columns: the rays a vertex makes, staged for the block-aggregated append (`stage`), and the sampler dimensions it draws (`su`).  Every thread touches
+// column `tid` only.  The full form: stage[3][2] of {origin, t_max}, {direction, time} and 8 rows of su, 24 576 + 8 192 B.
+template <bool LEAN> struct ShadeLds {
+    static constexpr int stage_rays = 3, su_rows = 8;
+    typedef float4 (*Stage)[2][PH_SHADE_BLOCK];
+    typedef float (*Su)[PH_SHADE_BLOCK];
+    static PH_DEV void put(Stage stage, Su, int q, uint32_t tid, const RayIn& r) { stage[q][0][tid] = make_float4(r.ox, r.oy, r.oz, r.t_max); stage[q][1][tid] = make_float4(r.dx, r.dy, r.dz, r.time); }
+    static PH_DEV void get(Stage stage, Su, int q, uint32_t tid, float, float, float4& ro, float4& rdv) { ro = stage[q][0][tid]; rdv = stage[q][1][tid]; }
+};
+// Lean (ShadeRow*::lean_lds): origin and direction only, in rows of `su` behind the sampler's — t_max is the queue's (kInf for an extension or MIS ray, 1 - kShadowEps for a shadow
+// ray: spawn_ray / spawn_ray_to_hit) and time the incoming ray's, both in registers at the append.  The extension ray is staged after the vertex has read its last sampler value (or,
+// at a null BSDF, instead of drawing any), so it lies over the first six sampler rows: 20 rows x 1 KB = 20 480 B, and `stage` is not referenced at all.
+template <> struct ShadeLds<true> {
+    static constexpr int stage_rays = 1, su_rows = 20;   // sampler dimensions 0..7; rays: ext 0..5, mis 8..13, shadow 14..19
+    typedef float4 (*Stage)[2][PH_SHADE_BLOCK];
+    typedef float (*Su)[PH_SHADE_BLOCK];
+    static PH_DEV int base(int q) { return q == 0 ? 0 : (q == 1 ? 8 : 14); }
+    static PH_DEV void put(Stage, Su su, int q, uint32_t tid, const RayIn& r) {
+        const int b = base(q);
+        su[b][tid] = r.ox; su[b + 1][tid] = r.oy; su[b + 2][tid] = r.oz; su[b + 3][tid] = r.dx; su[b + 4][tid] = r.dy; su[b + 5][tid] = r.dz;
+    }
+    static PH_DEV void get(Stage, Su su, int q, uint32_t tid, float t_max, float time, float4& ro, float4& rdv) {
+        const int b = base(q);
+        ro = make_float4(su[b][tid], su[b + 1][tid], su[b + 2][tid], t_max); rdv = make_float4(su[b + 3][tid], su[b + 4][tid], su[b + 5][tid], time);
+    }
+};
 // QUADRIC: the scene may hold quadric shapes (instantiated with GEN and TEX only: api.hip, add_quadric_common): a new vertex on one takes its interaction from the shape's own test
-template <bool GEN, bool TEX = false, bool QUADRIC = false>
+// Row (shade_shapes.h): the light kinds, samplers and light distribution the kernel is compiled for; the rows leaner than ShadeRowFull exist for the texture-free matte kernel only
+template <bool GEN, bool TEX = false, bool QUADRIC = false, class Row = ShadeRowFull>
 __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(DeviceScene sc, WfParams w, int it) {
     using BO = BsdfOps<GEN>;
-    __shared__ float4 stage[3][2][PH_SHADE_BLOCK];           // [ext, mis, shadow][ray halves][thread]
+    using LDS = ShadeLds<Row::lean_lds>;
+    __shared__ float4 stage[LDS::stage_rays][2][PH_SHADE_BLOCK];           // [ext, mis, shadow][ray halves][thread]
     __shared__ uint32_t wave_cnt[3][PH_SHADE_BLOCK / 64];   // [cl, sh, live][wave]
     __shared__ uint32_t q_base[3];
     __shared__ HaltonLds halton_lds;
-    __shared__ float s_u[8][PH_SHADE_BLOCK];  // the (up to) 8 sampler dimensions a vertex can consume, drawn by ONE loop
+    __shared__ float s_u[LDS::su_rows][PH_SHADE_BLOCK];  // the (up to) 8 sampler dimensions a vertex can consume, drawn by ONE loop
     const uint32_t n_live = w.ctr[it].n_live;
 #if PH_PHASE_CLOCK && defined(__HIP_DEVICE_COMPILE__)
     __shared__ unsigned long long phc_lds[3 * PHC_N];
@@ -320,7 +354,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
 #endif
     PHC_BEGIN(10);
     const HaltonLds* hl = nullptr;
-    if (w.sp.kind == 0 && blockIdx.x * blockDim.x < n_live) { halton_lds_fill(&halton_lds, sc); hl = &halton_lds; }
+    if ((!Row::sobol || w.sp.kind == 0) && blockIdx.x * blockDim.x < n_live) { halton_lds_fill(&halton_lds, sc); hl = &halton_lds; }
     __syncthreads();
     const RayIn* rays_in = w.rays_cl[it & 1];
     RayIn* rays_out = w.rays_cl[(it + 1) & 1];
@@ -340,7 +374,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
         const bool active = i < n_live;
         uint32_t pid = 0, flags = 0, bounces = 0, dim = 0;
         spec L = mks1(0.0f), beta = mks1(1.0f);
-        float pick_pdf = 0.0f, eta_scale = 1.0f;
+        float pick_pdf = 0.0f, eta_scale = 1.0f, ray_time = 0.0f;   // ray_time: the incoming ray's, which every ray of the new vertex carries on
         bool want_ext = false, want_mis = false, want_sh = false;
 
         if (active) {
@@ -375,11 +409,13 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                     spec li2 = mks1(0.0f);
                     if (hprim != 0xFFFFFFFFu) {
                         const LightRec& lt = sc.lights[light_num];
-                        if (lt.type == PH_L_AREA && lt.prim == hprim) {  // the hit primitive's area light IS the sampled light
-                            const float4 h1 = hp[1];
-                            MeshRec m;
-                            SurfHit lh = make_surface_hit_any(sc, wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
-                            li2 = area_L(lt, lh.n, -wi);  // SurfaceInteraction::le (surface_interaction.rs:283-289)
+                        if constexpr (Row::area) {
+                            if (lt.type == PH_L_AREA && lt.prim == hprim) {  // the hit primitive's area light IS the sampled light
+                                const float4 h1 = hp[1];
+                                MeshRec m;
+                                SurfHit lh = make_surface_hit_any(sc, wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
+                                li2 = area_L(lt, lh.n, -wi);  // SurfaceInteraction::le (surface_interaction.rs:283-289)
+                            }
                         }
                     } else li2 = light_le<TEX>(sc, sc.lights[light_num], wi);
                     if (!is_black(li2)) est = est + mks(F4.x, F4.y, F4.z) * li2 * mks1(1.0f) * A4.w / O4.w;  // f*li*tr*weight/scattering_pdf
@@ -395,6 +431,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
             if (flags & F_EXT) {
                 flags &= ~F_EXT;
                 const RayIn ray = load_ray(rays_in + idx4.x);
+                if constexpr (Row::lean_lds) ray_time = ray.time;
                 const float4* hp = reinterpret_cast<const float4*>(w.hits_cl + idx4.x);
                 const float4 h0 = hp[0];
                 const uint32_t hprim = __float_as_uint(h0.y);
@@ -412,7 +449,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                     SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs)
                                          : make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
                     if (emit) {
-                        if (m.first_light >= 0) L = L + beta * area_L(sc.lights[(uint32_t)m.first_light + (hprim - m.tri_base)], si.n, -rd);
+                        if (Row::area && m.first_light >= 0) L = L + beta * area_L(sc.lights[(uint32_t)m.first_light + (hprim - m.tri_base)], si.n, -rd);
                         else L = L + beta * mks1(0.0f);
                     }
                     PHC_END(1);
@@ -423,8 +460,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                         // specular flag stay as they are (path.rs:142-150)
                         const RayIn re = spawn_ray(si, rd);
                         flags |= F_EXT | F_NODIFF; want_ext = true;
-                        stage[0][0][tid] = make_float4(re.ox, re.oy, re.oz, re.t_max);
-                        stage[0][1][tid] = make_float4(re.dx, re.dy, re.dz, re.time);
+                        LDS::put(stage, s_u, 0, tid, re);
                     } else if ((int)bounces < w.max_depth) {
                         const uint32_t ppix = pid / w.chunk_spp;
                         const int2 xy = w.px_xy[ppix];
@@ -447,13 +483,13 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                         }
                         PHC_END(2);
                         PHC_BEGIN(3);
-                        SamplerCursor cur = cursor_for(sc, w.sp, xy.x, xy.y, w.s0 + (pid - ppix * w.chunk_spp), dim, hl);
+                        SamplerCursor cur = cursor_for<Row>(sc, w.sp, xy.x, xy.y, w.s0 + (pid - ppix * w.chunk_spp), dim, hl);
                         // Draw the next 8 dimensions in one (not unrolled) loop: light pick 1D, u_light 2D, u_scattering 2D, BSDF 2D,
                         // Russian roulette 1D.  li consumes a prefix of them that depends on the vertex (A4 ledger); which VALUE lands in
                         // which role is decided below exactly as get_1d/get_2d would, only the evaluation is hoisted (one copy of the
                         // radical-inverse code instead of ten keeps the kernel inside the instruction cache).
 #pragma unroll 1
-                        for (uint32_t k = 0; k < 8; k++) s_u[k][tid] = sampler_dim(sc, w.sp, cur, dim + k);
+                        for (uint32_t k = 0; k < 8; k++) s_u[k][tid] = sampler_dim<Row>(sc, w.sp, cur, dim + k);
                         PHC_END(3);
                         uint32_t c = 0;  // dimensions consumed so far at this vertex
                         if (BO::has_non_specular(bsdf)) {  // num_components(all & !SPECULAR) > 0 (path.rs:161-172)
@@ -465,7 +501,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                 // sample_discrete; with a single light the CDF is {0, 1} and the answer is 0 for every sample in [0,1):
                                 // keeping that case wave-uniform lets the light record be fetched with scalar loads
                                 const float* ld_func = sc.ld_func; const float* ld_cdf = sc.ld_cdf; float ld_func_int = sc.ld_func_int;
-                                if (w.spatial.enabled) {  // light_distribution.lookup(&isect.hit.p) (path.rs:156-157)
+                                if (Row::spatial && w.spatial.enabled) {  // light_distribution.lookup(&isect.hit.p) (path.rs:156-157)
                                     const int32_t slot = w.spatial.vox_slot[spatial_voxel_of(w.spatial, si.p)];
                                     if (slot >= 0) {
                                         ld_func = w.spatial.pool + (size_t)slot * w.spatial.stride;
@@ -478,13 +514,13 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                 if (pick_pdf != 0.0f) {
                                     const LightRec& light = sc.lights[light_num];
                                     const f2 u_light = mk2(s_u[1][tid], s_u[2][tid]), u_scatter = mk2(s_u[3][tid], s_u[4][tid]); c = 5;
-                                    const bool is_delta = light.type == PH_L_DISTANT || light.type == PH_L_POINT || light.type == PH_L_SPOT || light.type == PH_L_PROJECTION || light.type == PH_L_GONIO;
+                                    const bool is_delta = Row::delta && (light.type == PH_L_DISTANT || light.type == PH_L_POINT || light.type == PH_L_SPOT || light.type == PH_L_PROJECTION || light.type == PH_L_GONIO);
                                     float w2 = 0.0f, spdf_store = 0.0f;
                                     spec A = mks1(0.0f);
                                     // estimate_direct (integrator/common.rs:146-299), specular = false, handle_media = false
                                     {
                                         PHC_BEGIN(5);
-                                        const LiSample ls = light_sample_li<TEX>(sc, light, si, u_light);
+                                        const LiSample ls = light_sample_li<TEX, Row>(sc, light, si, u_light);
                                         PHC_END(5);
                                         PHC_BEGIN(6);
                                         if (ls.valid && ls.pdf > 0.0f && !is_black(ls.value)) {
@@ -492,8 +528,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                             const float scattering_pdf = BO::pdf_ns(bsdf, si.wo, ls.wi);
                                             if (!is_black(f)) {
                                                 const RayIn rs = spawn_ray_to_hit(si, ls.vp, ls.vperr, ls.vn);  // VisibilityTester::unoccluded
-                                                stage[2][0][tid] = make_float4(rs.ox, rs.oy, rs.oz, rs.t_max);
-                                                stage[2][1][tid] = make_float4(rs.dx, rs.dy, rs.dz, rs.time);
+                                                LDS::put(stage, s_u, 2, tid, rs);
                                                 want_sh = true;
                                                 if (is_delta) A = f * ls.value / ls.pdf;
                                                 else A = f * ls.value * power_heuristic1(ls.pdf, scattering_pdf) / ls.pdf;
@@ -508,13 +543,12 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                         BO::sample_ns(bsdf, si.wo, u_scatter, f1, spdf, wi2);  // never specular with these flags: sampled_specular = false
                                         const spec f = f1 * abs_dot(wi2, si.ns);
                                         if (!is_black(f) && spdf > 0.0f) {
-                                            const float lp = light_pdf_li<TEX>(sc, light, si, wi2);
+                                            const float lp = light_pdf_li<TEX, Row>(sc, light, si, wi2);
                                             if (lp != 0.0f) {  // lp == 0 -> `return ld` with the light-sampling part only
                                                 w2 = power_heuristic1(spdf, lp);
                                                 spdf_store = spdf;
                                                 const RayIn rm = spawn_ray(si, wi2);
-                                                stage[1][0][tid] = make_float4(rm.ox, rm.oy, rm.oz, rm.t_max);
-                                                stage[1][1][tid] = make_float4(rm.dx, rm.dy, rm.dz, rm.time);
+                                                LDS::put(stage, s_u, 1, tid, rm);
                                                 want_mis = true;
                                                 w.s_f2[(it + 1) & 1][i] = make_float4(f.r, f.g, f.b, __uint_as_float(light_num));
                                                 flags |= F_PMIS;
@@ -556,8 +590,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                             }
                             if (cont) {
                                 bounces += 1; flags |= F_EXT; want_ext = true;
-                                stage[0][0][tid] = make_float4(re.ox, re.oy, re.oz, re.t_max);
-                                stage[0][1][tid] = make_float4(re.dx, re.dy, re.dz, re.time);
+                                LDS::put(stage, s_u, 0, tid, re);
                             }
                         }
                         cur.dim = dim + c;
@@ -596,20 +629,20 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
             if (want_ext) {
                 ext_slot = cl_slot;
                 float4* d = reinterpret_cast<float4*>(rays_out + ext_slot);
-                const float4 ro = stage[0][0][tid], rdv = stage[0][1][tid];
+                float4 ro, rdv; LDS::get(stage, s_u, 0, tid, kInf, ray_time, ro, rdv);
                 d[0] = ro; d[1] = rdv;
                 w.keys_cl[ext_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
             }
             if (want_mis) {
                 mis_slot = cl_slot + (want_ext ? 1u : 0u);
                 float4* d = reinterpret_cast<float4*>(rays_out + mis_slot);
-                const float4 ro = stage[1][0][tid], rdv = stage[1][1][tid];
+                float4 ro, rdv; LDS::get(stage, s_u, 1, tid, kInf, ray_time, ro, rdv);
                 d[0] = ro; d[1] = rdv;
                 w.keys_cl[mis_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
             }
             if (want_sh) {
                 float4* d = reinterpret_cast<float4*>(w.rays_sh + sh_slot);
-                const float4 ro = stage[2][0][tid], rdv = stage[2][1][tid];
+                float4 ro, rdv; LDS::get(stage, s_u, 2, tid, 1.0f - kShadowEps, ray_time, ro, rdv);
                 d[0] = ro; d[1] = rdv;
                 w.keys_sh[sh_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
             }
@@ -974,6 +1007,15 @@ static int setup_spatial(PbrtHipScene* s, ph::SpatialRec& sr) {
     return PBRT_HIP_OK;
 }
 
+// The row of ph::ShadeRows this render's shade launches take: the lights' kinds as upload_scene found them, the sampler and the strategy as they are now.  The rows leaner
+// than the full one are compiled for the texture-free matte kernel; the general, textured and quadric kernels keep the full row.  PBRT_HIP_SHADE_ROW=full: the full row for every scene.
+static int shade_row_of(const PbrtHipScene* s, bool spatial) {
+    if (s->general_materials || s->textured_materials || !s->quadrics.empty()) return ph::kShadeRowFull;
+    const char* e = std::getenv("PBRT_HIP_SHADE_ROW");
+    const ph::ShadeFeatures f{s->lights_infinite, s->lights_area, s->lights_delta, s->sampler.kind != 0, spatial};
+    return ph::pick_shade_row(f, e && std::strcmp(e, "full") == 0);
+}
+
 // renders this rank's tiles into d_tile_buffer (device)
 int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int part,
                         int parts, void* d_tile_buffer, PbrtHipStats* out_stats) {
@@ -1007,6 +1049,7 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
     const int kMaxNullSkips = 1024;
     const int n_iter_cap = s->has_none_material ? n_iter + kMaxNullSkips : n_iter;
     const bool has_quadrics = !s->quadrics.empty();   // the QUADRIC instantiations of the texture, light-distribution and shade passes
+    const int shade_row = shade_row_of(s, spatial);
     if ((rc = ensure_buf(s, w.d_ctr, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters)))) return rc;
     if ((rc = ensure_buf(s, w.d_stats, 64 + 6 * PHC_N * 8))) return rc;   // DevStats (+ the shade kernel's phase tallies in measurement builds)
     if ((rc = samples_alloc(s, &rec))) return rc;
@@ -1155,7 +1198,8 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
                         }))) return rc;
                 }
                 if ((rc = timed(2, [&]() {
-                        if (has_quadrics) hipLaunchKernelGGL((ph::shade_kernel<true, true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);   // (quadrics set both flags)
+                        if (shade_row == ph::kShadeRowSky) hipLaunchKernelGGL((ph::shade_kernel<false, false, false, ph::ShadeRowSky>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                        else if (has_quadrics) hipLaunchKernelGGL((ph::shade_kernel<true, true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);   // (quadrics set both flags)
                         else if (s->textured_materials) {
                             if (s->general_materials) hipLaunchKernelGGL((ph::shade_kernel<true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
                             else hipLaunchKernelGGL((ph::shade_kernel<false, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);

@@ -17,9 +17,9 @@ PH_DEV uint32_t wave_alloc(uint32_t* ctr, bool want) {
     return base + (uint32_t)__popcll(m & lt);
 }
 
-PH_DEV SamplerCursor cursor_for(const DeviceScene& sc, const SamplerRec& sp, int px, int py, uint32_t s, uint32_t dim, const HaltonLds* lds = nullptr) {
+template <class Row = ShadeRowFull> PH_DEV SamplerCursor cursor_for(const DeviceScene& sc, const SamplerRec& sp, int px, int py, uint32_t s, uint32_t dim, const HaltonLds* lds = nullptr) {
     SamplerCursor c; c.px = px; c.py = py; c.dim = dim; c.lds = lds;
-    if (sp.kind == 0) c.index = (uint64_t)halton_pixel_offset(sp, px, py) + (uint64_t)s * sp.sample_stride;  // halton.rs:143
+    if (!Row::sobol || sp.kind == 0) c.index = (uint64_t)halton_pixel_offset(sp, px, py) + (uint64_t)s * sp.sample_stride;  // halton.rs:143
     else c.index = sobol_interval_to_index(sc, (uint32_t)sp.log2_resolution, s, px - sp.bounds[0], py - sp.bounds[1]);
     return c;
 }
