@@ -190,7 +190,8 @@ int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const f
  * pbrt_hip_render_whitted renders such a scene; pbrt_hip_render_path and pbrt_hip_render_path_tiles_device return PBRT_HIP_ERR_UNSUPPORTED before any work (message: "sphere light"), because
  * PathIntegrator::li also needs Sphere::pdf_solid_angle for its MIS weight; the handle stays usable.  The batch intersection entry points treat the sphere as ordinary geometry.
  * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: between object_begin and object_end, as for any quadric; while pbrt_hip_add_light_diffuse_area lights that no mesh has claimed are pending.
- * The other five quadrics cannot be lights, and the pbrt_hip_render front end does not read Shape "sphere". */
+ * The other five quadrics cannot be lights.  The pbrt_hip_render front end makes this call for Shape "sphere" under AreaLightSource "diffuse" when run with --quadrics (without the
+ * option it refuses the six quadric Shape directives), and refuses such a scene under Integrator "path" itself. */
 int pbrt_hip_add_sphere_light(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
                               uint32_t material_id, uint32_t flags, const float L_rgb[3], int two_sided);
 

@@ -662,8 +662,67 @@ uint32_t Api::material_id_for(const MaterialDesc& m) {
     return id;
 }
 
+// material: shape parameters override the material's (TextureParams looks in the shape's set first, graphics_state.rs:147-165)
+MaterialDesc Api::material_for_shape(const ParamSet& p) const {
+    MaterialDesc eff = gs_.material;
+    static const char* kMatParams[] = {"Kd", "Ks", "Kr", "Kt", "sigma", "roughness", "uroughness", "vroughness", "eta", "index", "k", "opacity", "bumpmap", "reflect", "transmit", "amount"};
+    for (const char* name : kMatParams) {
+        auto f = p.floats.find(name); auto tx = p.textures.find(name);
+        if (tx != p.textures.end()) { eff.params.textures[name] = tx->second; eff.params.floats.erase(name); }
+        else if (f != p.floats.end()) { eff.params.floats[name] = f->second; eff.params.textures.erase(name); }
+    }
+    { auto b = p.bools.find("remaproughness"); if (b != p.bools.end()) eff.params.bools["remaproughness"] = b->second; }
+    return eff;
+}
+
+static bool is_quadric_shape(const std::string& name) {
+    return name == "sphere" || name == "cylinder" || name == "cone" || name == "paraboloid" || name == "disk" || name == "hyperboloid";
+}
+
+// The six quadric shapes (Api::quadrics): parameters and defaults as each shape's From<(&ParamSet, ..)> reads them; object_to_world is the CTM with the inverse it accumulated
+// (api/src/lib.rs:760-773), flags bit 0 the graphics state's reverse orientation (the library takes swaps_handedness from the matrix).
+void Api::quadric_shape(const std::string& name, const ParamSet& p) {
+    // what the library refuses is refused here as well: check mode calls nothing in it
+    if (!current_object_.empty()) { error = "Shape \"" + name + "\" between ObjectBegin and ObjectEnd: quadric shapes inside object definitions are not supported"; return; }
+    const bool light = !gs_.area_light.empty();
+    if (light) {
+        if (gs_.area_light != "diffuse" && gs_.area_light != "area") { error = "AreaLightSource \"" + gs_.area_light + "\" unknown"; return; }
+        if (name != "sphere") { error = "AreaLightSource \"" + gs_.area_light + "\" on Shape \"" + name + "\": of the quadric shapes only the sphere can be an area light"; return; }
+        for (auto& u : gs_.area_light_params.unsupported) { error = "AreaLightSource: parameter '" + u + "' has a spectral type this host cannot evaluate"; return; }
+    }
+    for (const char* an : {"alpha", "shadowalpha"})   // only the triangle mesh reads them (triangle.rs:278-312)
+        if (p.floats.count(an) || p.textures.count(an)) warn("Shape \"" + name + "\": the reference's quadric shapes read no '" + an + "'; ignoring it");
+    const uint32_t mat = material_id_for(material_for_shape(p));
+    if (!error.empty()) return;
+    const uint32_t flags = gs_.reverse_orientation ? 1u : 0u;
+    const float phi_max = p.find_one_float("phimax", 360.0f);
+    if (name == "sphere") {  // shapes/src/sphere.rs:494-520
+        const float radius = p.find_one_float("radius", 1.0f);
+        const float z_min = p.find_one_float("zmin", -radius), z_max = p.find_one_float("zmax", radius);
+        if (light) {  // one DiffuseAreaLight around the shape, numbered where the Shape directive stands (lib.rs:783-812; lights/src/diffuse.rs:230-250)
+            const ParamSet& ap = gs_.area_light_params;
+            auto L = mul3(ap.find_one_rgb("L", {1.0f, 1.0f, 1.0f}), ap.find_one_rgb("scale", {1.0f, 1.0f, 1.0f}));
+            if (!check(ABI(pbrt_hip_add_sphere_light(scene_, ctm_.m, ctm_.mi, radius, z_min, z_max, phi_max, mat, flags, L.data(), ap.find_one_bool("twosided", false) ? 1 : 0)), "add_sphere_light")) return;
+            n_lights_++; sphere_light_ = true;
+        } else if (!check(ABI(pbrt_hip_add_sphere(scene_, ctm_.m, ctm_.mi, radius, z_min, z_max, phi_max, mat, flags)), "add_sphere")) return;
+    } else if (name == "hyperboloid") {  // hyperboloid.rs:425-447: the defaults are the file's own, not pbrt's (0 0 0) and (1 1 1)
+        const std::array<float, 3> p1 = p.find_one_rgb("p1", {3.0f, 1.2f, 1.0f}), p2 = p.find_one_rgb("p2", {1.0f, -0.5f, -1.0f});
+        if (!check(ABI(pbrt_hip_add_hyperboloid(scene_, ctm_.m, ctm_.mi, p1.data(), p2.data(), phi_max, mat, flags)), "add_hyperboloid")) return;
+    } else {
+        const float radius = p.find_one_float("radius", 1.0f);
+        int kind; float a, b;
+        if (name == "cylinder") { kind = 0; a = p.find_one_float("zmin", -1.0f); b = p.find_one_float("zmax", 1.0f); }        // cylinder.rs:351-375
+        else if (name == "cone") { kind = 1; a = p.find_one_float("height", 1.0f); b = 0.0f; }                                // cone.rs:321-343
+        else if (name == "paraboloid") { kind = 2; a = p.find_one_float("zmin", 0.0f); b = p.find_one_float("zmax", 1.0f); }  // paraboloid.rs:337-361
+        else { kind = 3; a = p.find_one_float("height", 0.0f); b = p.find_one_float("innerradius", 0.0f); }                   // disk.rs:237-261
+        if (!check(ABI(pbrt_hip_add_quadric(scene_, kind, ctm_.m, ctm_.mi, radius, a, b, phi_max, mat, flags)), "add_quadric")) return;
+    }
+    n_quadrics_++;
+}
+
 void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::string& scene_dir) {
     if (!verify_world("Shape") || !error.empty() || (!scene_ && !check_only_)) return;
+    if (quadrics && is_quadric_shape(name)) { quadric_shape(name, p); return; }
     std::vector<float> P, N, S, UV;
     std::vector<uint32_t> idx;
     if (name == "trianglemesh") {  // shapes/src/triangle.rs:184-330
@@ -699,7 +758,7 @@ void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::stri
         if (mesh.P.empty() || mesh.indices.empty()) { warn("PLY file '" + fn + "' is invalid! No face/vertex elements found!"); return; }
         P.swap(mesh.P); N.swap(mesh.N); UV.swap(mesh.UV); idx.swap(mesh.indices);
     } else {
-        error = "Shape \"" + name + "\" is outside the hot-path scope (supported: trianglemesh, plymesh)";
+        error = "Shape \"" + name + "\" is outside the hot-path scope (supported: trianglemesh, plymesh" + (is_quadric_shape(name) ? "; the six quadric shapes are read with --quadrics)" : ")");
         return;
     }
     // alpha / shadowalpha (triangle.rs:278-312): a float texture by name (constant ones fold to the constant, the others are evaluated per candidate hit) or a float
@@ -720,16 +779,7 @@ void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::stri
     const float alpha = alpha_of("alpha"), shadow_alpha = alpha_of("shadowalpha");
     if (!error.empty()) return;
 
-    // material: shape parameters override the material's (TextureParams looks in the shape's set first, graphics_state.rs:147-165)
-    MaterialDesc eff = gs_.material;
-    static const char* kMatParams[] = {"Kd", "Ks", "Kr", "Kt", "sigma", "roughness", "uroughness", "vroughness", "eta", "index", "k", "opacity", "bumpmap", "reflect", "transmit", "amount"};
-    for (const char* name : kMatParams) {
-        auto f = p.floats.find(name); auto tx = p.textures.find(name);
-        if (tx != p.textures.end()) { eff.params.textures[name] = tx->second; eff.params.floats.erase(name); }
-        else if (f != p.floats.end()) { eff.params.floats[name] = f->second; eff.params.textures.erase(name); }
-    }
-    { auto b = p.bools.find("remaproughness"); if (b != p.bools.end()) eff.params.bools["remaproughness"] = b->second; }
-    const uint32_t mat = material_id_for(eff);
+    const uint32_t mat = material_id_for(material_for_shape(p));
     if (!error.empty()) return;
 
     // TriangleMesh::new moves the vertices to world space once (triangle.rs:93-99)
@@ -768,6 +818,8 @@ int Api::pbrt_world_end(RenderReport& rep) {
     if (!verify_world("WorldEnd")) { error = "WorldEnd outside a world block"; return PBRT_HIP_ERR_STATE; }
     while (!gs_stack_.empty()) { warn("Missing end to AttributeBegin"); pbrt_attribute_end(); }
     while (!ctm_stack_.empty()) { warn("Missing end to TransformBegin"); ctm_stack_.pop_back(); }
+    // PathIntegrator::li weights a hit on an emitter by the light's pdf, and Sphere::pdf_solid_angle is not provided: the library refuses at render time, check mode has to here
+    if (sphere_light_ && integrator_name_ == "path") { error = "Shape \"sphere\" under AreaLightSource \"diffuse\" (a sphere light) is rendered by Integrator \"whitted\" only, not by \"path\""; return PBRT_HIP_ERR_UNSUPPORTED; }
 
     // ---- filter + film (make_filter / make_film, graphics_state.rs:600-690; film/mod.rs:420-487)
     int fkind = -1; float rad[2] = {0.5f, 0.5f}, fparams[2] = {0.0f, 0.0f};
@@ -870,7 +922,8 @@ int Api::pbrt_world_end(RenderReport& rep) {
     auto t0 = clk::now();
     // "sah" and "hlbvh" trees are made on the GPU, scenes with object instances included (same trees: csrc/bvh_sah_device.hip, bvh_device.hip); everything else by the library's host builder
     int brc = PBRT_HIP_ERR_UNSUPPORTED;
-    if ((split == 0 || split == 1) && !check_only_) brc = pbrt_hip_build_accel_device(scene_, split, max_prims);   // UNSUPPORTED for the SAH tree of a scene with quadric shapes: the host builder makes the same tree
+    if ((split == 0 || split == 1) && !check_only_)   // pbrt_hip_build_accel_device refuses the SAH tree of a scene with quadric shapes; the _shapes entry builds either
+        brc = n_quadrics_ ? pbrt_hip_build_accel_device_shapes(scene_, split, max_prims) : pbrt_hip_build_accel_device(scene_, split, max_prims);
     if (brc == PBRT_HIP_ERR_UNSUPPORTED) brc = ABI(pbrt_hip_build_accel(scene_, split, max_prims));
     if (!check(brc, "build_accel")) return PBRT_HIP_ERR_DEVICE;
     rep.build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
@@ -895,7 +948,7 @@ int Api::pbrt_world_end(RenderReport& rep) {
     else { warn("Light sample distribution type \"" + lss + "\" unknown. Using \"spatial\"."); strategy = 2; }
 
     rep.xres = xres; rep.yres = yres; std::memcpy(rep.crop, cb, sizeof cb);
-    rep.n_triangles = n_tris_; rep.n_lights = n_lights_; rep.n_instances = n_instances_; rep.warnings = warnings;
+    rep.n_triangles = n_tris_; rep.n_lights = n_lights_; rep.n_instances = n_instances_; rep.n_quadrics = n_quadrics_; rep.warnings = warnings;
     rep.integrator = integrator_name_;
     rep.spp = spp; rep.max_depth = max_depth; rep.light_strategy = strategy; std::memcpy(rep.pixel_bounds, pb, sizeof pb);
     if (check_only_) { rep.out_file = filename; return PBRT_HIP_OK; }

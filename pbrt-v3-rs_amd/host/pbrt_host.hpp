@@ -53,6 +53,7 @@ struct RenderReport {
     std::string out_file;
     double build_seconds = 0, load_seconds = 0;
     uint64_t n_triangles = 0, n_lights = 0, n_instances = 0;  // n_triangles counts instanced triangles once per instance
+    uint64_t n_quadrics = 0;  // sphere, cylinder, cone, paraboloid, disk, hyperboloid (read with Api::quadrics)
     std::string integrator;  // "path" or "whitted"
     int spp = 0, max_depth = 0, light_strategy = 0, pixel_bounds[4] = {0, 0, 0, 0};
     std::vector<std::string> warnings;
@@ -109,6 +110,7 @@ class Api {
     std::string sobol_tables_file;  // raw little-endian: u32[1024*52], u64[25*52], u64[26*52]
     int tile_size = 16;
     unsigned long long sample_record_budget = 0;   // --sample-record-budget BYTES (pbrt_hip_set_sample_record_budget); 0 = automatic
+    bool quadrics = false;   // --quadrics: Shape "sphere" / "cylinder" / "cone" / "paraboloid" / "disk" / "hyperboloid" are read; without it they are refused as out of scope
     bool quiet = false;
     std::vector<std::string> warnings;
     std::string error;
@@ -134,11 +136,15 @@ class Api {
     std::map<std::string, uint64_t> object_tris_;
     std::string current_object_;                // "" outside ObjectBegin/ObjectEnd
     uint64_t n_instances_ = 0;
+    uint64_t n_quadrics_ = 0;
+    bool sphere_light_ = false;   // a Shape "sphere" stood under AreaLightSource "diffuse": only the Whitted integrator renders it
     int n_devices_ = 1;   // GPUs behind scene_ (--devices)
     bool verify_options(const char* func);
     bool verify_world(const char* func);
     void concat(const Xform& t);
     uint32_t material_id_for(const MaterialDesc& m);
+    MaterialDesc material_for_shape(const ParamSet& shape_params) const;
+    void quadric_shape(const std::string& name, const ParamSet& p);
     bool check(int rc, const char* what);
 };
 
