@@ -304,6 +304,17 @@ int ensure_traversal_workspace(PbrtHipScene* s) {
     return PBRT_HIP_OK;
 }
 
+// The traversal kernels' error flag, read once the stream has drained and cleared for the next call: shared by the ray batches below and the two render drivers.
+int traversal_overflow_check(PbrtHipScene* s) {
+    uint32_t flag = 0;
+    PH_CHECK(s, hipMemcpy(&flag, s->d_error.p, 4, hipMemcpyDeviceToHost));
+    if (flag) {
+        (void)hipMemset(s->d_error.p, 0, 4);
+        return set_err(s, PBRT_HIP_ERR_DEVICE, "traversal stack exceeded 64 entries (the reference panics here, bvh/mod.rs:185)");
+    }
+    return PBRT_HIP_OK;
+}
+
 // One traversal kernel shape, launched for mode 0 closest hit, 1 any hit or 2 both queues in one launch (ph::TravMode)
 template <class Shape>
 static void launch_traverse_shape(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p) {
@@ -1546,16 +1557,6 @@ int pbrt_hip_accel_copy(PbrtHipScene* s, void* out_nodes, uint64_t node_capacity
     });
 }
 
-static int check_error_flag(PbrtHipScene* s) {
-    uint32_t flag = 0;
-    PH_CHECK(s, hipMemcpy(&flag, s->d_error.p, 4, hipMemcpyDeviceToHost));
-    if (flag) {
-        (void)hipMemset(s->d_error.p, 0, 4);
-        return set_err(s, PBRT_HIP_ERR_DEVICE, "traversal stack exceeded 64 entries (the reference panics here, bvh/mod.rs:185)");
-    }
-    return PBRT_HIP_OK;
-}
-
 static int batch_common(PbrtHipScene* s, bool anyhit, const void* rays, void* out, uint64_t n, bool device_ptrs, float* kernel_ms) {
     if (!s) return PBRT_HIP_ERR_INVALID_ARG;
     if (n && (!rays || !out)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "batch: null buffer");
@@ -1576,7 +1577,7 @@ static int batch_common(PbrtHipScene* s, bool anyhit, const void* rays, void* ou
     if ((rc = launch_traverse(s, anyhit, d_rays, d_out, (uint32_t)n, kernel_ms))) return rc;
     if (!device_ptrs) PH_CHECK(s, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return check_error_flag(s);
+    return traversal_overflow_check(s);
 }
 
 int pbrt_hip_intersect_batch(PbrtHipScene* s, const PbrtHipRay* rays, PbrtHipHit* hits, uint64_t n) { return ph_guard(s, "pbrt_hip_intersect_batch", [&]() -> int { return batch_common(s, false, rays, hits, n, false, nullptr); }); }

@@ -95,7 +95,7 @@ struct PbrtHipScene : SceneHostState {
     void* tree_dev_nodes = nullptr; void* tree_dev_tris = nullptr; size_t tree_dev_n_tris = 0;
     bool uploaded = false;
     // the light side of the scene's shade-pass features (shade_shapes.h), derived by upload_scene from the light list it uploads: every call that changes a light clears `uploaded`,
-    // so the next render derives them again.  The sampler and the light strategy are read when the row is picked (wavefront.hip, shade_row_of).
+    // so the next render derives them again.  The sampler and the light strategy are read when the variant is picked (wavefront.hip, plan_path_frame).
     bool lights_infinite = false, lights_area = false, lights_delta = false;
     int light_strategy_uploaded = -1;
     DevBuf d_ld_func, d_ld_cdf;
@@ -129,6 +129,7 @@ int upload_light_distribution(PbrtHipScene* s, int light_strategy);
 int launch_traverse(PbrtHipScene* s, bool anyhit, const void* d_rays, void* d_out, uint32_t n, float* kernel_ms);
 void launch_traverse_kernel(PbrtHipScene* s, int mode, uint32_t blocks, const ph::TravParams& p);  // 0 closest, 1 any hit, 2 both (MIXED)
 int ensure_traversal_workspace(PbrtHipScene* s);
+int traversal_overflow_check(PbrtHipScene* s);   // after the stream has drained: reads the traversal kernels' error flag, clears it, and reports a stack that ran over
 // wavefront.hip: the ray binning between rounds (raysort.h) on device arrays, for callers that do not see the kernels; workspace = raysort_workspace_bytes(sort_blocks) bytes
 inline size_t raysort_workspace_bytes(uint32_t sort_blocks) { return ((size_t)sort_blocks + 1) * PH_SORT_KEYS * 4; }
 void launch_raysort(PbrtHipScene* s, const uint32_t* keys_cl, const uint32_t* keys_sh, const uint32_t* n_cl, const uint32_t* n_sh, uint32_t* order, uint32_t* workspace,
@@ -160,6 +161,8 @@ int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_part
 // one band at a time (samples_band): n_px, px_xy and `band` are then that band's, and a record's pixel index counts from the band's first pixel.
 struct SampleRecords { uint32_t n_px; const int2* px_xy; float4* rec_L; float* rec_py; uint8_t* px_rounded; SampleBand band; uint32_t band_px; std::vector<SampleBand> bands; };
 int samples_begin(PbrtHipScene* s, int tile_size, int part, int parts, SampleRecords* out);   // tile and pixel lists; n_px == 0: nothing to render
+// a driver's first step: device, upload_scene, samples_begin, *out_stats zeroed; n_px == 0: the tile buffer is cleared, the driver returns
+int frame_begin(PbrtHipScene* s, int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats, SampleRecords* rec);
 int samples_plan_bands(PbrtHipScene* s, SampleRecords* out, size_t chunk_held, size_t chunk_per_path);   // the bands, under the handle's budget or the automatic one
 int samples_alloc(PbrtHipScene* s, SampleRecords* out);                                        // the records of the largest band
 int samples_band(PbrtHipScene* s, const SampleRecords& r, size_t band, SampleRecords* out);   // one band of them, px_rounded cleared

@@ -930,12 +930,6 @@ size_t tile_buffer_floats_for(const PbrtHipScene* s, int tile_size, int part, in
     return std::max<size_t>(local, 1) * (size_t)g.slot_w * g.slot_h * 4;
 }
 
-static hipEvent_t get_event(PbrtHipScene* s, size_t i) {
-    Wavefront& w = *s->wf;
-    while (w.events.size() <= i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; w.events.push_back(e); }
-    return w.events[i];
-}
-
 int check_render_args(PbrtHipScene* s, int max_depth, int light_strategy, const int* pixel_bounds, int tile_size, int part, int parts) {
     if (!s || !pixel_bounds) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "render: null argument");
     if (!s->built || !s->have_camera || !s->have_film || !s->have_sampler)
@@ -1007,88 +1001,109 @@ static int setup_spatial(PbrtHipScene* s, ph::SpatialRec& sr) {
     return PBRT_HIP_OK;
 }
 
-// The row of ph::ShadeRows this render's shade launches take: the lights' kinds as upload_scene found them, the sampler and the strategy as they are now.  The rows leaner
-// than the full one are compiled for the texture-free matte kernel; the general, textured and quadric kernels keep the full row.  PBRT_HIP_SHADE_ROW=full: the full row for every scene.
-static int shade_row_of(const PbrtHipScene* s, bool spatial) {
-    if (s->general_materials || s->textured_materials || !s->quadrics.empty()) return ph::kShadeRowFull;
-    const char* e = std::getenv("PBRT_HIP_SHADE_ROW");
-    const ph::ShadeFeatures f{s->lights_infinite, s->lights_area, s->lights_delta, s->sampler.kind != 0, spatial};
-    return ph::pick_shade_row(f, e && std::strcmp(e, "full") == 0);
+// ---- what the shade side launches ------------------------------------------------------------------------------------------------------------------------------------------
+// shade_shapes.h's two tables expanded into launchers, as api.hip's dispatch_traverse_shape does with TravShapes: the pickers give an index, the kernel is named here once.
+template <class V> static void launch_shade_variant(PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
+    hipLaunchKernelGGL((ph::shade_kernel<V::gen, V::tex, V::quadric, typename V::Row>), dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+}
+template <class... V> static void dispatch_shade_variant(ph::ShadeVariantTable<V...>, int variant, PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
+    static constexpr void (*launchers[])(PbrtHipScene*, uint32_t, const ph::WfParams&, int) = {&launch_shade_variant<V>...};
+    launchers[variant](s, blocks, wp, it);
+}
+// (the launchers of the table's two anchors are what instantiates them: compiled with the others, picked by nothing)
+template <class V> static void launch_tex_variant(PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
+    hipLaunchKernelGGL((ph::texture_kernel<V::simple, V::camera, V::waves, V::quadric>), dim3(blocks), dim3(PH_TEX_LDS_THREADS), 0, s->stream, s->ds, wp, it);
+}
+template <class... V> static void dispatch_tex_variant(ph::TexVariantTable<V...>, int variant, PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
+    static constexpr void (*launchers[])(PbrtHipScene*, uint32_t, const ph::WfParams&, int) = {&launch_tex_variant<V>...};
+    launchers[variant](s, blocks, wp, it);
 }
 
-// renders this rank's tiles into d_tile_buffer (device)
-int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int part,
-                        int parts, void* d_tile_buffer, PbrtHipStats* out_stats) {
+// ---- one frame of the path driver, step by step: plan, bind, the rounds of a chunk, finish ---------------------------------------------------------------------------------
+// Everything a frame decides before its first launch.
+struct PathPlan {
+    bool spatial;        // the spatial light distribution is live: strategy 2 with more than one light (one light -> uniform, light_distrib/mod.rs:59-64)
+    bool mat_queues;     // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
+    bool has_quadrics;   // the QUADRIC instantiations of the texture, light-distribution and shade passes
+    int shade_variant;   // of ph::ShadeVariants: the lights' kinds as upload_scene found them, the sampler and the strategy as they are now; PBRT_HIP_SHADE_ROW=full: the full row for every scene
+    int tex_variant[2];  // of ph::TexVariants: [1] the camera round's, [0] the later rounds'
+    // Material "none" surfaces are passed through without counting a bounce, so a path may need more rounds than n_iter = max_depth + 1: those are
+    // run one at a time while paths remain (host reads the live count), up to kMaxNullSkips more (n_iter_cap).
+    static constexpr int kMaxNullSkips = 1024;
+    int n_iter, n_iter_cap;
+    uint32_t chunk_spp;  // samples per pixel of a chunk; B = paths the chunk's buffers are sized for (the largest band's pixels * chunk_spp)
+    size_t B;
+    uint32_t shade_blocks;
+    bool identity;       // does pixel_bounds cover every pixel of this rank's tiles?
+    // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h): 8 heads, served in chunks of 49 152 rays (a multiple of every batch size); 1 024 blocks per sort pass
+    // (the three raysort kernels per configs[2] frame: 512 blocks 9.40 ms, 1 024: 9.18, 2 048: 9.19)
+    static constexpr uint32_t n_heads = 8, head_chunk = 49152, sort_blocks = 1024;
+};
+
+// The plan, and the workspace for it: the bands of the sample records, the chunk, every buffer whose size the plan fixes.  The order of the allocations (and of the look at the
+// free memory among them) is part of the result: the chunk size and the reported footprint follow from it.
+static int plan_path_frame(PbrtHipScene* s, int max_depth, int light_strategy, const int pixel_bounds[4], SampleRecords& rec, PathPlan& p) {
     int rc;
-    PH_CHECK(s, hipSetDevice(s->device));
-    if ((rc = upload_scene(s))) return rc;
-    const bool spatial = light_strategy == 2 && s->lights.size() > 1;  // one light -> uniform (light_distrib/mod.rs:59-64)
-    if ((rc = upload_light_distribution(s, light_strategy == 2 ? 0 : light_strategy))) return rc;
-    if (out_stats) std::memset(out_stats, 0, sizeof(*out_stats));
-    SampleRecords rec{};
-    if ((rc = samples_begin(s, tile_size, part, parts, &rec))) return rc;
     Wavefront& w = *s->wf;
     const uint32_t spp = s->sampler.spp;
-    if (rec.n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
-
+    p.spatial = light_strategy == 2 && s->lights.size() > 1;
     // ---- chunking: B = n_px * chunk_spp paths in flight ----------------------------------------------------------------------
     // 128 Mi paths per chunk where the card has room for them (463 B of queues and path state per path, 591 B with a texture pass: 62 – 79 GB of the MI355X's 288 GB):
     // large chunks bin better (more rays per origin cell and round) and pay fewer launch tails — configs[2] 913 -> 878 ms per frame, configs[3] 934 -> 898 ms against the 32 Mi of round 1 (256 Mi, the whole frame at once, adds nothing: 875 / 899 ms).
     static const ChunkPolicy kChunks{128u << 20, 1u << 20, 0x7FFF0000ull, "render"};
-    // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
-    const bool mat_queues = s->general_materials || s->textured_materials;
-    const ChunkTable chunk = w.chunk_table(s->textured_materials, mat_queues);
+    p.mat_queues = s->general_materials || s->textured_materials;
+    const ChunkTable chunk = w.chunk_table(s->textured_materials, p.mat_queues);
     // the bands of tiles whose sample records are resident together (band_plan.h); every size below is the largest band's, and the buffers serve all bands
     if ((rc = samples_plan_bands(s, &rec, chunk_bytes_held(chunk), chunk_bytes_per_path(chunk)))) return rc;
     const uint32_t n_px = rec.band_px;
     const size_t rec_need = (size_t)n_px * spp * 20, rec_have = w.d_recL.bytes + w.d_recpy.bytes;   // planned before the sample records are allocated: what they still need is set aside
-    uint32_t chunk_spp = plan_chunk_spp_now(kChunks, chunk, rec_need > rec_have ? rec_need - rec_have : 0, n_px, spp);
-    const int n_iter = max_depth + 1;
-    // Material "none" surfaces are passed through without counting a bounce, so a path may need more rounds than max_depth + 1: those are
-    // run one at a time while paths remain (host reads the live count), up to kMaxNullSkips more.
-    const int kMaxNullSkips = 1024;
-    const int n_iter_cap = s->has_none_material ? n_iter + kMaxNullSkips : n_iter;
-    const bool has_quadrics = !s->quadrics.empty();   // the QUADRIC instantiations of the texture, light-distribution and shade passes
-    const int shade_row = shade_row_of(s, spatial);
-    if ((rc = ensure_buf(s, w.d_ctr, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters)))) return rc;
+    p.chunk_spp = plan_chunk_spp_now(kChunks, chunk, rec_need > rec_have ? rec_need - rec_have : 0, n_px, spp);
+    p.n_iter = max_depth + 1;
+    p.n_iter_cap = s->has_none_material ? p.n_iter + PathPlan::kMaxNullSkips : p.n_iter;
+    p.has_quadrics = !s->quadrics.empty();
+    const char* e = std::getenv("PBRT_HIP_SHADE_ROW");
+    p.shade_variant = ph::pick_shade_variant(ph::ShadeTraits{s->general_materials, s->textured_materials, p.has_quadrics},
+                                             ph::ShadeFeatures{s->lights_infinite, s->lights_area, s->lights_delta, s->sampler.kind != 0, p.spatial}, e && std::strcmp(e, "full") == 0);
+    for (int camera = 0; camera < 2; camera++) p.tex_variant[camera] = ph::pick_tex_variant(camera != 0, s->simple_textures, p.has_quadrics);
+    if ((rc = ensure_buf(s, w.d_ctr, (size_t)(p.n_iter_cap + 2) * sizeof(ph::IterCounters)))) return rc;
     if ((rc = ensure_buf(s, w.d_stats, 64 + 6 * PHC_N * 8))) return rc;   // DevStats (+ the shade kernel's phase tallies in measurement builds)
     if ((rc = samples_alloc(s, &rec))) return rc;
-    if ((rc = chunk_alloc_or_halve(s, kChunks, chunk, n_px, chunk_spp))) return rc;
-    const size_t B = (size_t)n_px * chunk_spp;
-    chunk_note_footprint(s, B, chunk);
-
+    if ((rc = chunk_alloc_or_halve(s, kChunks, chunk, n_px, p.chunk_spp))) return rc;
+    p.B = (size_t)n_px * p.chunk_spp;
+    chunk_note_footprint(s, p.B, chunk);
     if ((rc = ensure_traversal_workspace(s))) return rc;
-    // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h): 8 heads, served in chunks of 49 152 rays (a multiple of every batch size); 1 024 blocks per sort pass
-    // (the three raysort kernels per configs[2] frame: 512 blocks 9.40 ms, 1 024: 9.18, 2 048: 9.19)
-    const uint32_t n_heads = 8, head_chunk = 49152, sort_blocks = 1024;
-    ph::RaySortGrid sort_grid{};
-    if ((rc = ensure_buf(s, w.d_sort_bins, raysort_workspace_bytes(sort_blocks)))) return rc;   // the tallies and one row of shares per block: 32 MB, outside the chunk table
-    for (int k = 0; k < 3; k++) {
-        const float ext = s->bvh.root_hi[k] - s->bvh.root_lo[k];
-        sort_grid.lo[k] = s->bvh.root_lo[k]; sort_grid.scale[k] = ext > 0.0f ? 1.0f / ext : 0.0f;
-    }
-    if ((rc = ensure_buf(s, w.d_heads, (size_t)(n_iter_cap + 2) * n_heads * 64))) return rc;
-    ph::MatSortParams msp{};
-    if (mat_queues) {
-        if ((rc = ensure_buf(s, w.d_mbins, (size_t)(2 * PH_MS_BINS + 1) * 4))) return rc;
+    if ((rc = ensure_buf(s, w.d_sort_bins, raysort_workspace_bytes(PathPlan::sort_blocks)))) return rc;   // the tallies and one row of shares per block: 32 MB, outside the chunk table
+    if ((rc = ensure_buf(s, w.d_heads, (size_t)(p.n_iter_cap + 2) * PathPlan::n_heads * 64))) return rc;
+    if (p.mat_queues && (rc = ensure_buf(s, w.d_mbins, (size_t)(2 * PH_MS_BINS + 1) * 4))) return rc;
+    p.shade_blocks = (uint32_t)std::min<size_t>((p.B + 255) / 256, 256 * 16);
+    p.identity = true;
+    for (const ph::TileInfo& t : w.tiles)
+        if (t.tb[0] < pixel_bounds[0] || t.tb[1] < pixel_bounds[1] || t.tb[2] > pixel_bounds[2] || t.tb[3] > pixel_bounds[3]) { p.identity = false; break; }
+    return PBRT_HIP_OK;
+}
+
+// The kernels' parameter blocks from the workspace and the plan; the per-frame device state (camera copy, the spatial tables, the statistics) is reset on the stream.
+static int bind_path_frame(PbrtHipScene* s, const PathPlan& p, int max_depth, float rr_threshold, const int pixel_bounds[4], ph::WfParams& wp, ph::MatSortParams& msp) {
+    int rc;
+    Wavefront& w = *s->wf;
+    const size_t B = p.B;
+    if (p.mat_queues) {
         msp.max_depth = max_depth; msp.mat_key = s->ds.mat_key; msp.key_emit = s->ds.ms_key_emit; msp.key_idle = s->ds.ms_key_idle;
         msp.tris = s->ds.tris; msp.meshes = s->ds.meshes; msp.hits = (const ph::HitOut*)w.d_hits.p;
         msp.keys = (uint16_t*)w.d_mkeys.p; msp.order = (uint32_t*)w.d_morder.p;
         msp.bin_start = (uint32_t*)w.d_mbins.p; msp.bin_cursor = msp.bin_start + PH_MS_BINS + 1;
     }
-
-    ph::WfParams wp{};
     wp.cam = s->cam; wp.sp = s->sampler;
-    wp.textured = s->textured_materials ? 1u : 0u; wp.cam_dev = nullptr;
+    wp.textured = s->textured_materials ? 1u : 0u; wp.cam_dev = nullptr; wp.tex_out = nullptr;
     wp.any_rt = 0u;
     for (const MaterialRec& mr : s->materials) if (mr.rt_mode) wp.any_rt = 1u;
     if (s->textured_materials) {
         if ((rc = ensure_buf(s, w.d_cam, sizeof(CameraRec)))) return rc;
         PH_CHECK(s, hipMemcpyAsync(w.d_cam.p, &s->cam, sizeof(CameraRec), hipMemcpyHostToDevice, s->stream));
-        wp.cam_dev = (const CameraRec*)w.d_cam.p;
+        wp.cam_dev = (const CameraRec*)w.d_cam.p; wp.tex_out = (TexOut*)w.d_tex_out.p;
     }
     for (int i = 0; i < 4; i++) wp.pixel_bounds[i] = pixel_bounds[i];
-    wp.max_depth = max_depth; wp.rr_threshold = rr_threshold;
+    wp.max_depth = max_depth; wp.rr_threshold = rr_threshold; wp.identity_slots = p.identity ? 1u : 0u;
     wp.rays_cl[0] = (ph::RayIn*)w.d_rays_cl[0].p; wp.rays_cl[1] = (ph::RayIn*)w.d_rays_cl[1].p;
     wp.hits_cl = (ph::HitOut*)w.d_hits.p; wp.rays_sh = (ph::RayIn*)w.d_rays_sh.p; wp.occ = (uint8_t*)w.d_occ.p;
     wp.live[0] = (uint32_t*)w.d_live[0].p; wp.live[1] = (uint32_t*)w.d_live[1].p;
@@ -1098,22 +1113,47 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         wp.s_f2[k] = (float4*)w.d_sf2.p + (size_t)k * B; wp.s_bold[k] = (float4*)w.d_sbold.p + (size_t)k * B; wp.s_idx[k] = (uint4*)w.d_sidx.p + (size_t)k * B;
         wp.s_prev[k] = (uint32_t*)w.d_sprev.p + (size_t)k * B;
     }
-    wp.sort_grid = sort_grid; wp.keys_cl = (uint32_t*)w.d_keys_cl.p; wp.keys_sh = (uint32_t*)w.d_keys_sh.p;
-    wp.m_order = mat_queues ? (const uint32_t*)w.d_morder.p : nullptr; wp.m_bins = mat_queues ? (const uint32_t*)w.d_mbins.p : nullptr;
-
-    if (spatial) { if ((rc = setup_spatial(s, wp.spatial))) return rc; }
+    for (int k = 0; k < 3; k++) {
+        const float ext = s->bvh.root_hi[k] - s->bvh.root_lo[k];
+        wp.sort_grid.lo[k] = s->bvh.root_lo[k]; wp.sort_grid.scale[k] = ext > 0.0f ? 1.0f / ext : 0.0f;
+    }
+    wp.keys_cl = (uint32_t*)w.d_keys_cl.p; wp.keys_sh = (uint32_t*)w.d_keys_sh.p;
+    wp.m_order = p.mat_queues ? (const uint32_t*)w.d_morder.p : nullptr; wp.m_bins = p.mat_queues ? (const uint32_t*)w.d_mbins.p : nullptr;
+    if (p.spatial) { if ((rc = setup_spatial(s, wp.spatial))) return rc; }
     PH_CHECK(s, hipMemsetAsync(w.d_stats.p, 0, 64 + 6 * PHC_N * 8, s->stream));
     wp.phase = PH_PHASE_CLOCK ? (unsigned long long*)((char*)w.d_stats.p + 64) : nullptr;
-    bool identity = true;  // does pixel_bounds cover every pixel of this rank's tiles?
-    for (const ph::TileInfo& t : w.tiles)
-        if (t.tb[0] < pixel_bounds[0] || t.tb[1] < pixel_bounds[1] || t.tb[2] > pixel_bounds[2] || t.tb[3] > pixel_bounds[3]) { identity = false; break; }
-    size_t ev = 0;
-    hipEvent_t e_begin = get_event(s, ev++), e_end = get_event(s, ev++);
-    if (!e_begin || !e_end) return set_err(s, PBRT_HIP_ERR_DEVICE, "hipEventCreate failed");
-    struct Span { hipEvent_t a, b; int kind; };
+    return PBRT_HIP_OK;
+}
+
+// The frame's clock on the scene's stream: one pair of events around the whole render and one pair around every timed span, from the workspace's pool (Wavefront::events).
+struct SpanTimer {
+    // EXTEND: the traversal launches; SHADOW: none any more — shadow rays travel in the mixed launch, so its fields stay 0 —; SHADE: raygen, the shade side's passes and the
+    // film pass; BIN: the ray binning between rounds, reported as shade time (ray binning counts as non-traversal time)
+    enum Kind { EXTEND, SHADOW, SHADE, BIN, N_KINDS };
+    struct Span { hipEvent_t a, b; Kind kind; };
+    PbrtHipScene* s;
+    size_t next = 0;
+    hipEvent_t e_begin = nullptr, e_end = nullptr;
     std::vector<Span> spans;
-    auto timed = [&](int kind, auto&& launch) -> int {
-        hipEvent_t a = get_event(s, ev++), b = get_event(s, ev++);
+
+    hipEvent_t event() {
+        std::vector<hipEvent_t>& pool = s->wf->events;
+        while (pool.size() <= next) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; pool.push_back(e); }
+        return pool[next++];
+    }
+    int begin() {
+        e_begin = event(); e_end = event();
+        if (!e_begin || !e_end) return set_err(s, PBRT_HIP_ERR_DEVICE, "hipEventCreate failed");
+        PH_CHECK(s, hipEventRecord(e_begin, s->stream));
+        return PBRT_HIP_OK;
+    }
+    int end() {
+        PH_CHECK(s, hipEventRecord(e_end, s->stream));
+        PH_CHECK(s, hipStreamSynchronize(s->stream));
+        return PBRT_HIP_OK;
+    }
+    template <class Launch> int timed(Kind kind, Launch&& launch) {
+        hipEvent_t a = event(), b = event();
         if (!a || !b) return set_err(s, PBRT_HIP_ERR_DEVICE, "hipEventCreate failed");
         PH_CHECK(s, hipEventRecord(a, s->stream));
         launch();
@@ -1121,145 +1161,175 @@ int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_s
         PH_CHECK(s, hipEventRecord(b, s->stream));
         spans.push_back({a, b, kind});
         return PBRT_HIP_OK;
-    };
-    PH_CHECK(s, hipEventRecord(e_begin, s->stream));
-    uint64_t regular = 0, shadow = 0;
-    std::vector<ph::IterCounters> hctr((size_t)n_iter_cap + 2);
-    const uint32_t shade_blocks = (uint32_t)std::min<size_t>((B + 255) / 256, 256 * 16);
-    wp.tex_out = nullptr;
-    if (s->textured_materials) wp.tex_out = (TexOut*)w.d_tex_out.p;
-
-    // band by band: the per-spp chunk loop over the band's pixels, then the film pass over its tiles.  Counters, statistics, time spans and the spatial light distribution's
-    // voxel tables run on through the bands.
-    for (size_t band = 0; band < rec.bands.size(); band++) {
-        SampleRecords br{};
-        if ((rc = samples_band(s, rec, band, &br))) return rc;
-        wp.n_px = br.n_px; wp.px_xy = br.px_xy; wp.rec_L = br.rec_L; wp.rec_py = br.rec_py; wp.px_rounded = br.px_rounded;
-        for (uint32_t s0 = 0; s0 < spp; s0 += chunk_spp) {
-            const uint32_t cs = std::min(chunk_spp, spp - s0);
-            wp.chunk_spp = cs; wp.s0 = s0; wp.B = br.n_px * cs; wp.identity_slots = identity ? 1u : 0u;
-            PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, (size_t)(n_iter_cap + 2) * sizeof(ph::IterCounters), s->stream));
-            PH_CHECK(s, hipMemsetAsync(w.d_heads.p, 0, (size_t)(n_iter_cap + 2) * n_heads * 64, s->stream));
-            if (identity) hipLaunchKernelGGL(ph::preset_counters_kernel, dim3(1), dim3(1), 0, s->stream, wp.ctr, wp.stats, wp.B);
-            if ((rc = timed(2, [&]() { hipLaunchKernelGGL(ph::raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp); }))) return rc;
-            int iters_run = 0;
-            for (int it = 0; it < n_iter_cap; it++) {
-                ph::IterCounters* c = (ph::IterCounters*)w.d_ctr.p + it;
-                if (it >= n_iter) {  // only with "none" materials: go on while some path is still alive
-                    uint32_t live = 0;
-                    PH_CHECK(s, hipMemcpyAsync(&live, &c->n_live, 4, hipMemcpyDeviceToHost, s->stream));
-                    PH_CHECK(s, hipStreamSynchronize(s->stream));
-                    if (live == 0) break;
-                    if (it == n_iter_cap - 1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: a path crossed more than 1024 'none' surfaces");
-                }
-                iters_run = it + 1;
-                ph::TravParams tp{};
-                tp.rays = wp.rays_cl[it & 1]; tp.out = wp.hits_cl; tp.n = 0; tp.n_ptr = &c->n_cl; tp.counter = &c->head_cl;
-                tp.heads = (uint32_t*)w.d_heads.p + (size_t)it * n_heads * 16; tp.n_heads = n_heads; tp.head_chunk = head_chunk;
-                if (it > 0) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
-                    tp.rays2 = wp.rays_sh; tp.out2 = wp.occ; tp.n2_ptr = &c->n_sh;
-                    // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
-                    uint32_t* const order = (uint32_t*)w.d_order.p;
-                    if ((rc = timed(3, [&]() { launch_raysort(s, wp.keys_cl, wp.keys_sh, &c->n_cl, &c->n_sh, order, (uint32_t*)w.d_sort_bins.p, sort_blocks); }))) return rc;
-                    tp.order = order;
-                    if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 2, s->trav_blocks, tp); }))) return rc;
-                } else if ((rc = timed(0, [&]() { launch_traverse_kernel(s, 0, s->trav_blocks, tp); }))) return rc;
-                // the shade side's work queues: this round's list regrouped by what has to be done for each path (matsort.h)
-                if (mat_queues) {
-                    msp.s_idx = wp.s_idx[it & 1]; msp.n_live = &c->n_live;
-                    if ((rc = timed(2, [&]() {
-                            (void)hipMemsetAsync(msp.bin_start, 0, (PH_MS_BINS + 1) * 4, s->stream);
-                            hipLaunchKernelGGL(ph::matsort_hist_kernel, dim3(sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
-                            hipLaunchKernelGGL(ph::matsort_scan_kernel, dim3(1), dim3(PH_MS_BINS), 0, s->stream, msp);
-                            hipLaunchKernelGGL(ph::matsort_scatter_kernel, dim3(sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
-                        }))) return rc;
-                }
-                // the texture pass first: besides colours and bumped frames it finds the hits that have no BSDF at all (TexOut::bumped, PH_TEXOUT_NULL_BSDF), which the
-                // light-distribution pass must skip as the reference's `continue` does (path.rs:142-157)
-                if (s->textured_materials) {
-                    if ((rc = timed(2, [&]() {
-                            const dim3 g(shade_blocks), b(PH_TEX_LDS_THREADS);
-                            if (it == 0) {   // camera rays: differentials, filtered look-ups
-                                if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, true, 2, true>), g, b, 0, s->stream, s->ds, wp, it);
-                                else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, true, 3>), g, b, 0, s->stream, s->ds, wp, it);
-                                else hipLaunchKernelGGL((ph::texture_kernel<false, true, 2>), g, b, 0, s->stream, s->ds, wp, it);
-                            } else {
-                                if (has_quadrics) hipLaunchKernelGGL((ph::texture_kernel<false, false, 3, true>), g, b, 0, s->stream, s->ds, wp, it);
-                                else if (s->simple_textures) hipLaunchKernelGGL((ph::texture_kernel<true, false, 4>), g, b, 0, s->stream, s->ds, wp, it);
-                                else hipLaunchKernelGGL((ph::texture_kernel<false, false, 3>), g, b, 0, s->stream, s->ds, wp, it);
-                            }
-                        }))) return rc;
-                }
-                if (spatial && (it < max_depth || s->has_none_material)) {  // vertices reached at bounce == max_depth sample no light (path.rs:136-139)
-                    if ((rc = timed(2, [&]() {
-                            if (has_quadrics) hipLaunchKernelGGL(ph::spatial_mark_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                            else hipLaunchKernelGGL(ph::spatial_mark_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                            hipLaunchKernelGGL(ph::spatial_compute_kernel, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, wp.spatial);
-                        }))) return rc;
-                }
-                if ((rc = timed(2, [&]() {
-                        if (shade_row == ph::kShadeRowSky) hipLaunchKernelGGL((ph::shade_kernel<false, false, false, ph::ShadeRowSky>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                        else if (has_quadrics) hipLaunchKernelGGL((ph::shade_kernel<true, true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);   // (quadrics set both flags)
-                        else if (s->textured_materials) {
-                            if (s->general_materials) hipLaunchKernelGGL((ph::shade_kernel<true, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                            else hipLaunchKernelGGL((ph::shade_kernel<false, true>), dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                        } else if (s->general_materials) hipLaunchKernelGGL(ph::shade_kernel<true>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                        else hipLaunchKernelGGL(ph::shade_kernel<false>, dim3(shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                    }))) return rc;
-            }
-            PH_CHECK(s, hipMemcpyAsync(hctr.data(), w.d_ctr.p, (size_t)(iters_run + 1) * sizeof(ph::IterCounters), hipMemcpyDeviceToHost, s->stream));
-            PH_CHECK(s, hipStreamSynchronize(s->stream));
-            for (int it = 0; it < iters_run; it++) { regular += hctr[it].n_cl; shadow += hctr[it].n_sh; }
-        }
-
-        // ---- film: per-tile accumulation in reference order ---------------------------------------------------------------------------
-        int film_rc = PBRT_HIP_OK;
-        if ((rc = timed(2, [&]() { film_rc = samples_to_tiles(s, br, d_tile_buffer); })) || (rc = film_rc)) return rc;
     }
-    PH_CHECK(s, hipEventRecord(e_end, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    // render_seconds, the three *_seconds and the two *_launches of the stats, after end()
+    int fold(PbrtHipStats* out) const {
+        float ms = 0;
+        PH_CHECK(s, hipEventElapsedTime(&ms, e_begin, e_end));
+        out->render_seconds = ms * 1e-3;
+        double acc[N_KINDS] = {};
+        uint64_t launches[N_KINDS] = {};
+        for (const Span& sp : spans) { float m = 0; if (hipEventElapsedTime(&m, sp.a, sp.b) == hipSuccess) acc[sp.kind] += m * 1e-3; launches[sp.kind]++; }
+        out->extend_seconds = acc[EXTEND]; out->shadow_seconds = acc[SHADOW]; out->shade_seconds = acc[SHADE] + acc[BIN];
+        out->extend_launches = launches[EXTEND]; out->shadow_launches = launches[SHADOW];
+        return PBRT_HIP_OK;
+    }
+};
 
-    uint32_t flag = 0;
-    PH_CHECK(s, hipMemcpy(&flag, s->d_error.p, 4, hipMemcpyDeviceToHost));
-    if (flag) { (void)hipMemset(s->d_error.p, 0, 4); return set_err(s, PBRT_HIP_ERR_DEVICE, "traversal stack exceeded 64 entries (the reference panics here, bvh/mod.rs:185)"); }
+// What the steps of one render_tiles call hand on to each other.
+struct PathFrame {
+    PathPlan plan{};
+    ph::WfParams wp{};
+    ph::MatSortParams msp{};
+    SpanTimer timer;
+    uint64_t regular = 0, shadow = 0;    // rays of the chunks so far, read back chunk by chunk
+};
+
+// Round `it` of a chunk: the round's rays through the traversal kernel, then the shade side over the hits — work queues, texture pass, light distributions, shade pass.
+static int run_round(PbrtHipScene* s, PathFrame& f, int it) {
+    int rc;
+    Wavefront& w = *s->wf;
+    const PathPlan& p = f.plan;
+    const ph::WfParams& wp = f.wp;
+    SpanTimer& t = f.timer;
+    ph::IterCounters* c = (ph::IterCounters*)w.d_ctr.p + it;
+    ph::TravParams tp{};
+    tp.rays = wp.rays_cl[it & 1]; tp.out = wp.hits_cl; tp.n = 0; tp.n_ptr = &c->n_cl; tp.counter = &c->head_cl;
+    tp.heads = (uint32_t*)w.d_heads.p + (size_t)it * p.n_heads * 16; tp.n_heads = p.n_heads; tp.head_chunk = p.head_chunk;
+    if (it > 0) {  // this round's extension rays and the shadow rays of the previous vertices: one launch, one tail
+        tp.rays2 = wp.rays_sh; tp.out2 = wp.occ; tp.n2_ptr = &c->n_sh;
+        // regroup the round's rays by origin cell; camera rays (round 0) leave raygen in pixel order already
+        uint32_t* const order = (uint32_t*)w.d_order.p;
+        if ((rc = t.timed(SpanTimer::BIN, [&]() { launch_raysort(s, wp.keys_cl, wp.keys_sh, &c->n_cl, &c->n_sh, order, (uint32_t*)w.d_sort_bins.p, p.sort_blocks); }))) return rc;
+        tp.order = order;
+    }
+    if ((rc = t.timed(SpanTimer::EXTEND, [&]() { launch_traverse_kernel(s, it > 0 ? 2 : 0, s->trav_blocks, tp); }))) return rc;
+    // the shade side's work queues: this round's list regrouped by what has to be done for each path (matsort.h)
+    if (p.mat_queues) {
+        ph::MatSortParams& msp = f.msp;
+        msp.s_idx = wp.s_idx[it & 1]; msp.n_live = &c->n_live;
+        if ((rc = t.timed(SpanTimer::SHADE, [&]() {
+                (void)hipMemsetAsync(msp.bin_start, 0, (PH_MS_BINS + 1) * 4, s->stream);
+                hipLaunchKernelGGL(ph::matsort_hist_kernel, dim3(p.sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
+                hipLaunchKernelGGL(ph::matsort_scan_kernel, dim3(1), dim3(PH_MS_BINS), 0, s->stream, msp);
+                hipLaunchKernelGGL(ph::matsort_scatter_kernel, dim3(p.sort_blocks), dim3(PH_MS_BLOCK), 0, s->stream, msp);
+            }))) return rc;
+    }
+    // the texture pass first: besides colours and bumped frames it finds the hits that have no BSDF at all (TexOut::bumped, PH_TEXOUT_NULL_BSDF), which the
+    // light-distribution pass must skip as the reference's `continue` does (path.rs:142-157)
+    if (s->textured_materials) {
+        if ((rc = t.timed(SpanTimer::SHADE, [&]() { dispatch_tex_variant(ph::TexVariants{}, p.tex_variant[it == 0], s, p.shade_blocks, wp, it); }))) return rc;
+    }
+    if (p.spatial && (it < wp.max_depth || s->has_none_material)) {  // vertices reached at bounce == max_depth sample no light (path.rs:136-139)
+        if ((rc = t.timed(SpanTimer::SHADE, [&]() {
+                if (p.has_quadrics) hipLaunchKernelGGL(ph::spatial_mark_kernel<true>, dim3(p.shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                else hipLaunchKernelGGL(ph::spatial_mark_kernel<false>, dim3(p.shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+                hipLaunchKernelGGL(ph::spatial_compute_kernel, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, wp.spatial);
+            }))) return rc;
+    }
+    return t.timed(SpanTimer::SHADE, [&]() { dispatch_shade_variant(ph::ShadeVariants{}, p.shade_variant, s, p.shade_blocks, wp, it); });
+}
+
+// One chunk: samples [s0, s0 + chunk_spp) of every pixel of the band bound in f.wp — counters cleared, raygen, the rounds, the ray counts read back.
+static int run_chunk(PbrtHipScene* s, PathFrame& f, uint32_t s0) {
+    int rc;
+    Wavefront& w = *s->wf;
+    const PathPlan& p = f.plan;
+    ph::WfParams& wp = f.wp;
+    wp.chunk_spp = std::min(p.chunk_spp, s->sampler.spp - s0); wp.s0 = s0; wp.B = wp.n_px * wp.chunk_spp;
+    PH_CHECK(s, hipMemsetAsync(w.d_ctr.p, 0, (size_t)(p.n_iter_cap + 2) * sizeof(ph::IterCounters), s->stream));
+    PH_CHECK(s, hipMemsetAsync(w.d_heads.p, 0, (size_t)(p.n_iter_cap + 2) * p.n_heads * 64, s->stream));
+    if (p.identity) hipLaunchKernelGGL(ph::preset_counters_kernel, dim3(1), dim3(1), 0, s->stream, wp.ctr, wp.stats, wp.B);
+    if ((rc = f.timer.timed(SpanTimer::SHADE, [&]() { hipLaunchKernelGGL(ph::raygen_kernel, dim3((wp.B + 255) / 256), dim3(256), 0, s->stream, s->ds, wp); }))) return rc;
+    int iters_run = 0;
+    for (int it = 0; it < p.n_iter_cap; it++) {
+        if (it >= p.n_iter) {  // only with "none" materials: go on while some path is still alive
+            uint32_t live = 0;
+            PH_CHECK(s, hipMemcpyAsync(&live, &wp.ctr[it].n_live, 4, hipMemcpyDeviceToHost, s->stream));
+            PH_CHECK(s, hipStreamSynchronize(s->stream));
+            if (live == 0) break;
+            if (it == p.n_iter_cap - 1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: a path crossed more than 1024 'none' surfaces");
+        }
+        iters_run = it + 1;
+        if ((rc = run_round(s, f, it))) return rc;
+    }
+    std::vector<ph::IterCounters> hctr((size_t)iters_run + 1);
+    PH_CHECK(s, hipMemcpyAsync(hctr.data(), w.d_ctr.p, hctr.size() * sizeof(ph::IterCounters), hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    for (int it = 0; it < iters_run; it++) { f.regular += hctr[it].n_cl; f.shadow += hctr[it].n_sh; }
+    return PBRT_HIP_OK;
+}
+
+#if PH_PHASE_CLOCK
+// measurement build: the shade and texture kernels' phase clocks of this render, to stderr
+static int dump_phase_clocks(PbrtHipScene* s) {
+    Wavefront& w = *s->wf;
+    unsigned long long ph_[3 * PHC_N];
+    PH_CHECK(s, hipMemcpy(ph_, (const char*)w.d_stats.p + 64, sizeof ph_, hipMemcpyDeviceToHost));
+    static const char* names[11] = {"state+resolve", "surface+emission", "bsdf+textures", "sampler_dims", "light_pick", "light_sample_li", "f/pdf+shadow_ray", "mis_half", "bsdf_sample+rr", "queue_append", "whole_kernel"};
+    for (int k = 0; k < 11; k++)
+        std::fprintf(stderr, "SHADE_PHASE %-17s cycles %14llu (%5.1f %% of the kernel)  executions %12llu  mean active lanes %5.1f\n", names[k], ph_[k], ph_[10] ? 100.0 * (double)ph_[k] / (double)ph_[10] : 0.0,
+                     ph_[PHC_N + k], ph_[PHC_N + k] ? (double)ph_[2 * PHC_N + k] / (double)ph_[PHC_N + k] : 0.0);
+    unsigned long long pt_[3 * PHC_N];
+    PH_CHECK(s, hipMemcpy(pt_, (const char*)w.d_stats.p + 64 + 3 * PHC_N * 8, sizeof pt_, hipMemcpyDeviceToHost));
+    static const char* tnames[4] = {"hit+context", "bump", "lobe_colours", "whole_kernel"};
+    for (int k = 0; k < 4; k++)
+        std::fprintf(stderr, "TEXTURE_PHASE %-13s cycles %14llu (%5.1f %% of the kernel)  executions %12llu  mean active lanes %5.1f\n", tnames[k], pt_[k], pt_[3] ? 100.0 * (double)pt_[k] / (double)pt_[3] : 0.0,
+                     pt_[PHC_N + k], pt_[PHC_N + k] ? (double)pt_[2 * PHC_N + k] / (double)pt_[PHC_N + k] : 0.0);
+    return PBRT_HIP_OK;
+}
+#endif
+
+// After the last band: the device's complaints (traversal stack, spatial pool), then the statistics.
+static int finish_path_frame(PbrtHipScene* s, const PathFrame& f, PbrtHipStats* out_stats) {
+    int rc;
+    Wavefront& w = *s->wf;
+    if ((rc = traversal_overflow_check(s))) return rc;
     uint32_t sp_ctr[4] = {0, 0, 0, 0};
-    if (spatial) {
+    if (f.plan.spatial) {
         PH_CHECK(s, hipMemcpy(sp_ctr, w.d_sp_ctr.p, sizeof sp_ctr, hipMemcpyDeviceToHost));
         if (sp_ctr[ph::SP_OVERFLOW])
             return set_err(s, PBRT_HIP_ERR_OOM, "render: SpatialLightDistribution pool exhausted (" + std::to_string(sp_ctr[ph::SP_CLAIMED]) + " voxels x " +
                                                 std::to_string(s->lights.size()) + " lights); use lightsamplestrategy power/uniform or a larger GPU memory budget");
     }
 #if PH_PHASE_CLOCK
-    {   // measurement build: the shade kernel's phase clocks of this render, to stderr
-        unsigned long long ph_[3 * PHC_N];
-        PH_CHECK(s, hipMemcpy(ph_, (const char*)w.d_stats.p + 64, sizeof ph_, hipMemcpyDeviceToHost));
-        static const char* names[11] = {"state+resolve", "surface+emission", "bsdf+textures", "sampler_dims", "light_pick", "light_sample_li", "f/pdf+shadow_ray", "mis_half", "bsdf_sample+rr", "queue_append", "whole_kernel"};
-        for (int k = 0; k < 11; k++)
-            std::fprintf(stderr, "SHADE_PHASE %-17s cycles %14llu (%5.1f %% of the kernel)  executions %12llu  mean active lanes %5.1f\n", names[k], ph_[k], ph_[10] ? 100.0 * (double)ph_[k] / (double)ph_[10] : 0.0,
-                         ph_[PHC_N + k], ph_[PHC_N + k] ? (double)ph_[2 * PHC_N + k] / (double)ph_[PHC_N + k] : 0.0);
-        unsigned long long pt_[3 * PHC_N];
-        PH_CHECK(s, hipMemcpy(pt_, (const char*)w.d_stats.p + 64 + 3 * PHC_N * 8, sizeof pt_, hipMemcpyDeviceToHost));
-        static const char* tnames[4] = {"hit+context", "bump", "lobe_colours", "whole_kernel"};
-        for (int k = 0; k < 4; k++)
-            std::fprintf(stderr, "TEXTURE_PHASE %-13s cycles %14llu (%5.1f %% of the kernel)  executions %12llu  mean active lanes %5.1f\n", tnames[k], pt_[k], pt_[3] ? 100.0 * (double)pt_[k] / (double)pt_[3] : 0.0,
-                         pt_[PHC_N + k], pt_[PHC_N + k] ? (double)pt_[2 * PHC_N + k] / (double)pt_[PHC_N + k] : 0.0);
-    }
+    if ((rc = dump_phase_clocks(s))) return rc;
 #endif
-    if (out_stats) {
-        out_stats->light_distributions_created = sp_ctr[ph::SP_DONE];
-        ph::DevStats ds;
-        PH_CHECK(s, hipMemcpy(&ds, w.d_stats.p, sizeof(ds), hipMemcpyDeviceToHost));
-        out_stats->camera_rays = ds.camera_rays; out_stats->regular_rays = regular; out_stats->shadow_rays = shadow;
-        out_stats->paths_total = ds.paths_total; out_stats->paths_zero_radiance = ds.paths_zero;
-        float ms = 0;
-        PH_CHECK(s, hipEventElapsedTime(&ms, e_begin, e_end));
-        out_stats->render_seconds = ms * 1e-3;
-        double acc[4] = {0, 0, 0, 0};
-        for (const Span& sp : spans) { float m = 0; if (hipEventElapsedTime(&m, sp.a, sp.b) == hipSuccess) acc[sp.kind] += m * 1e-3; }
-        out_stats->extend_seconds = acc[0]; out_stats->shadow_seconds = acc[1]; out_stats->shade_seconds = acc[2] + acc[3];  // ray binning counts as non-traversal time
-        for (const Span& sp : spans) { if (sp.kind == 0) out_stats->extend_launches++; else if (sp.kind == 1) out_stats->shadow_launches++; }
+    if (!out_stats) return PBRT_HIP_OK;
+    out_stats->light_distributions_created = sp_ctr[ph::SP_DONE];
+    ph::DevStats ds;
+    PH_CHECK(s, hipMemcpy(&ds, w.d_stats.p, sizeof(ds), hipMemcpyDeviceToHost));
+    out_stats->camera_rays = ds.camera_rays; out_stats->regular_rays = f.regular; out_stats->shadow_rays = f.shadow;
+    out_stats->paths_total = ds.paths_total; out_stats->paths_zero_radiance = ds.paths_zero;
+    return f.timer.fold(out_stats);
+}
+
+// renders this rank's tiles into d_tile_buffer (device): plan -> bind -> for each band { for each chunk { rounds }; film } -> finish
+int render_tiles(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int part,
+                        int parts, void* d_tile_buffer, PbrtHipStats* out_stats) {
+    int rc;
+    SampleRecords rec{};
+    if ((rc = frame_begin(s, tile_size, part, parts, d_tile_buffer, out_stats, &rec)) || rec.n_px == 0) return rc;
+    if ((rc = upload_light_distribution(s, light_strategy == 2 ? 0 : light_strategy))) return rc;
+    PathFrame f{};
+    f.timer.s = s;
+    if ((rc = plan_path_frame(s, max_depth, light_strategy, pixel_bounds, rec, f.plan))) return rc;
+    if ((rc = bind_path_frame(s, f.plan, max_depth, rr_threshold, pixel_bounds, f.wp, f.msp))) return rc;
+    if ((rc = f.timer.begin())) return rc;
+    // band by band: the per-spp chunk loop over the band's pixels, then the film pass over its tiles.  Counters, statistics, time spans and the spatial light distribution's
+    // voxel tables run on through the bands.
+    for (size_t band = 0; band < rec.bands.size(); band++) {
+        SampleRecords br{};
+        if ((rc = samples_band(s, rec, band, &br))) return rc;
+        f.wp.n_px = br.n_px; f.wp.px_xy = br.px_xy; f.wp.rec_L = br.rec_L; f.wp.rec_py = br.rec_py; f.wp.px_rounded = br.px_rounded;
+        for (uint32_t s0 = 0; s0 < s->sampler.spp; s0 += f.plan.chunk_spp)
+            if ((rc = run_chunk(s, f, s0))) return rc;
+        // ---- film: per-tile accumulation in reference order ---------------------------------------------------------------------------
+        int film_rc = PBRT_HIP_OK;
+        if ((rc = f.timer.timed(SpanTimer::SHADE, [&]() { film_rc = samples_to_tiles(s, br, d_tile_buffer); })) || (rc = film_rc)) return rc;
     }
-    return PBRT_HIP_OK;
+    if ((rc = f.timer.end())) return rc;
+    return finish_path_frame(s, f, out_stats);
 }
 
 int merge_tiles(PbrtHipScene* s, int tile_size, int parts, const void* const* d_bufs, float* out_xyz, float* out_weight) {
@@ -1327,6 +1397,21 @@ int merge_own_tiles(PbrtHipScene* s, int tile_size, int tile_part, int tile_part
     rc = merge_tiles(s, tile_size, tile_parts, bufs.data(), out_xyz, out_weight);
     for (auto& z : zeros) if (z.p) (void)hipFree(z.p);
     return rc;
+}
+
+// The start of a frame on this context, the same for every integrator: the device, the scene as it is now, the rank's tile and pixel lists, *out_stats zeroed.
+// rec->n_px == 0 on return: the rank has no pixel; its tile buffer is cleared and the driver has nothing to render.
+int frame_begin(PbrtHipScene* s, int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats, SampleRecords* rec) {
+    int rc;
+    PH_CHECK(s, hipSetDevice(s->device));
+    if ((rc = upload_scene(s))) return rc;
+    if ((rc = samples_begin(s, tile_size, part, parts, rec))) return rc;
+    if (out_stats) std::memset(out_stats, 0, sizeof(*out_stats));
+    if (rec->n_px == 0) {
+        PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream));
+        PH_CHECK(s, hipStreamSynchronize(s->stream));
+    }
+    return PBRT_HIP_OK;
 }
 
 // The sample side of a frame, the same for every integrator: the rank's tile and pixel lists ...
@@ -1489,9 +1574,3 @@ int pbrt_hip_generate_camera_rays(PbrtHipScene* s, const int pb[4], uint32_t sam
 }
 
 }  // extern "C"
-
-// Compiled, never launched: they fix the register budget of the out-of-line evaluator the launched forms call (TexEval::run, texture.h).  The backend compiles
-// a device function for the largest waves per SIMD among its callers, so these two keep it at 4 waves without differentials and 3 with them — the budget the
-// texture pass was tuned with.  Without them the later-round general pass spills 356 VGPRs instead of 48 and configs[4] loses 1.2 % (texture pass + 3.4 %).
-template __global__ void ph::texture_kernel<false, false, 4>(DeviceScene, ph::WfParams, int);
-template __global__ void ph::texture_kernel<false, true, 3>(DeviceScene, ph::WfParams, int);

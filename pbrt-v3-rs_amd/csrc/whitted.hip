@@ -72,12 +72,8 @@ static int check_whitted_args(PbrtHipScene* s, int max_depth, const int* pixel_b
 
 int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats) {
     int rc;
-    PH_CHECK(s, hipSetDevice(s->device));
-    if ((rc = upload_scene(s))) return rc;
     SampleRecords rec{};
-    if ((rc = samples_begin(s, tile_size, part, parts, &rec))) return rc;
-    if (out_stats) std::memset(out_stats, 0, sizeof(*out_stats));
-    if (rec.n_px == 0) { PH_CHECK(s, hipMemsetAsync(d_tile_buffer, 0, tile_buffer_floats_for(s, tile_size, part, parts) * 4, s->stream)); PH_CHECK(s, hipStreamSynchronize(s->stream)); return PBRT_HIP_OK; }
+    if ((rc = frame_begin(s, tile_size, part, parts, d_tile_buffer, out_stats, &rec)) || rec.n_px == 0) return rc;
     if (!s->wh) s->wh = new WhittedWorkspace();
     WhittedWorkspace& w = *s->wh;
     const uint32_t spp = s->sampler.spp, n_frames = (uint32_t)std::max(max_depth, 1);
@@ -155,9 +151,7 @@ int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_bounds[
     PH_CHECK(s, hipEventRecord(s->ev1, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
 
-    uint32_t flag = 0;
-    PH_CHECK(s, hipMemcpy(&flag, s->d_error.p, 4, hipMemcpyDeviceToHost));
-    if (flag) { (void)hipMemset(s->d_error.p, 0, 4); return set_err(s, PBRT_HIP_ERR_DEVICE, "traversal stack exceeded 64 entries (the reference panics here, bvh/mod.rs:185)"); }
+    if ((rc = traversal_overflow_check(s))) return rc;
     if (out_stats) {
         ph::WhDevStats ds;
         PH_CHECK(s, hipMemcpy(&ds, w.d_stats.p, sizeof ds, hipMemcpyDeviceToHost));
