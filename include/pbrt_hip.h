@@ -494,6 +494,19 @@ int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int varian
  * of the two passes over the keys (a render uses 1024).  Needs a handle only: no geometry, no accelerator.
  * PBRT_HIP_ERR_INVALID_ARG: a null handle; sort_blocks 0 or above 65536; a null array with a non-zero count; a key >= 4096; n_cl + n_sh >= 0x7FFF0000.  Nothing is launched on a refusal. */
 int pbrt_hip_raysort_probe(PbrtHipScene*, uint32_t n_cl, uint32_t n_sh, const uint32_t* keys_cl, const uint32_t* keys_sh, uint32_t sort_blocks, uint32_t* order_out /* n_cl + n_sh */);
+/* pbrt_hip_texture_probe_batch (a-SI, f3): texture number `texture` at n explicit contexts (the 15 floats per point of pbrt_hip_texture_eval_batch), through each piece of code the
+ * renderer evaluates textures with; 3 floats out per probe.
+ *   variant 0  the general evaluator with differentials (camera rays of scenes with procedural textures)      variant 1  the same without: the derivative fields are ignored as if zero
+ *   variant 2  the evaluator of scenes whose programs hold only constants, uv-mapped image maps, scale and mix, with differentials      variant 3  the same without
+ *   variant 4  the lean alpha test's evaluator on the context's (u, v): red channel in out[0], out[1] = out[2] = 0
+ * Variants 2 and 3 must equal 0 and 1; 1 must equal 0 on zero derivatives; 4 must equal the red channel of 1.
+ * pbrt_hip_bump_probe_batch: Material::bump (core/src/material.rs:62-101) with `texture` as the displacement, on an explicit shading frame.  in = per probe the 15 context floats (the
+ * hit point is the context's p), then n, ns, dpdu_s, dpdv_s, dndu, dndv (33 floats); out = the new shading normal and shading dp/du (6 floats).  variant 0 .. 3 as above.
+ * Both need an uploaded scene only (no accelerator) and leave the handle usable after a refusal.
+ * PBRT_HIP_ERR_INVALID_ARG: unknown texture or variant; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_UNSUPPORTED: variant 2, 3 or 4 on a program that holds any other
+ * operation than constant, uv-mapped image map, scale and mix.  Nothing is launched on a refusal. */
+int pbrt_hip_texture_probe_batch(PbrtHipScene*, uint32_t texture, int variant, uint64_t n, const float* contexts /*15n*/, float* out /*3n*/);
+int pbrt_hip_bump_probe_batch(PbrtHipScene*, uint32_t texture, int variant, uint64_t n, const float* in /*33n*/, float* out /*6n*/);
 
 #ifdef __cplusplus
 }

@@ -567,6 +567,60 @@ int oracle_texture_eval_batch(OracleScene* s, uint32_t tex, uint64_t n, const fl
     }
     return 0;
 }
+// Texture probes, with the contract of pbrt_hip_texture_probe_batch / pbrt_hip_bump_probe_batch (include/pbrt_hip.h).  The variants are the product's code paths; here they decide
+// what is refused (2, 3, 4: a program with another operation than constant, uv-mapped image map, scale, mix) and whether the derivative fields are read (1, 3, 4: as if zero).
+static TexCtx probe_tex_ctx(const float* q, bool nodiff) {
+    TexCtx c; c.uv = V2(q[0], q[1]); c.p = V3(q[6], q[7], q[8]);
+    if (!nodiff) { c.dudx = q[2]; c.dvdx = q[3]; c.dudy = q[4]; c.dvdy = q[5]; c.dpdx = V3(q[9], q[10], q[11]); c.dpdy = V3(q[12], q[13], q[14]); }
+    return c;
+}
+static bool tex_tree_is_simple(const std::vector<Texture>& tex, int id) {
+    const Texture& t = tex[(size_t)id];
+    if (t.kind == TK_CONST) return true;
+    if (t.kind == TK_IMAGE) return t.mapping == 0;
+    if (t.kind == TK_SCALE) return tex_tree_is_simple(tex, t.t1) && tex_tree_is_simple(tex, t.t2);
+    if (t.kind == TK_MIX) return tex_tree_is_simple(tex, t.t1) && tex_tree_is_simple(tex, t.t2) && tex_tree_is_simple(tex, t.amount);
+    return false;
+}
+static int texture_probe_refusal(OracleScene* s, const char* who, uint32_t tex, int variant, int n_variants, uint64_t n, const void* in, const void* out) {
+    if (!s) return -1;
+    const std::string w(who);
+    if (n && (!in || !out)) { s->err = w + ": null argument"; return -1; }
+    if (tex >= s->sc.textures.size()) { s->err = w + ": unknown texture"; return -1; }
+    if (variant < 0 || variant >= n_variants) { s->err = w + ": unknown variant"; return -1; }
+    if (n > 0xFFFFFFFFull) { s->err = w + ": too many probes"; return -1; }
+    if (variant >= 2 && !tex_tree_is_simple(s->sc.textures, (int)tex)) { s->err = w + ": variants 2 and above admit constants, uv-mapped image maps, scale and mix only"; return -5; }
+    return 0;
+}
+int oracle_texture_probe_batch(OracleScene* s, uint32_t tex, int variant, uint64_t n, const float* in, float* out) {
+    if (int rc = texture_probe_refusal(s, "texture_probe_batch", tex, variant, 5, n, in, out)) return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        const Spec v = tex_eval(s->sc.textures, s->sc.mipmaps, (int)tex, probe_tex_ctx(in + 15 * i, (variant & 1) != 0 || variant == 4));
+        out[3 * i] = v.c[0]; out[3 * i + 1] = variant == 4 ? 0.0f : v.c[1]; out[3 * i + 2] = variant == 4 ? 0.0f : v.c[2];
+    }
+    return 0;
+}
+// oracle only: per probe, the footprint texels ewa() visits and the noise_3d calls of variant 0's evaluation (2 uint64 per probe)
+int oracle_texture_probe_work(OracleScene* s, uint32_t tex, uint64_t n, const float* in, uint64_t* out_work) {
+    if (int rc = texture_probe_refusal(s, "texture_probe_work", tex, 0, 1, n, in, out_work)) return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        tex_work() = TexWork();
+        (void)tex_eval(s->sc.textures, s->sc.mipmaps, (int)tex, probe_tex_ctx(in + 15 * i, false));
+        out_work[2 * i] = tex_work().texels; out_work[2 * i + 1] = tex_work().noise;
+    }
+    return 0;
+}
+int oracle_bump_probe_batch(OracleScene* s, uint32_t tex, int variant, uint64_t n, const float* in, float* out) {
+    if (int rc = texture_probe_refusal(s, "bump_probe_batch", tex, variant, 4, n, in, out)) return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        const float* q = in + 33 * i;
+        Renderer::BumpFrame f{V3(q[15], q[16], q[17]), V3(q[18], q[19], q[20]), V3(q[21], q[22], q[23]), V3(q[24], q[25], q[26]), V3(q[27], q[28], q[29]), V3(q[30], q[31], q[32])};
+        Renderer::bump_frame(s->sc.textures, s->sc.mipmaps, (int)tex, probe_tex_ctx(q, (variant & 1) != 0), f);
+        float* o = out + 6 * i;
+        o[0] = f.ns.x; o[1] = f.ns.y; o[2] = f.ns.z; o[3] = f.dpdu_s.x; o[4] = f.dpdu_s.y; o[5] = f.dpdu_s.z;
+    }
+    return 0;
+}
 int oracle_mipmap_levels(OracleScene* s, uint32_t mip, int* out_levels, int* out_wh /*2 per level, up to 32 levels*/) {
     if (!s || mip >= s->sc.mipmaps.size()) return -1;
     const MipMap& m = s->sc.mipmaps[mip];

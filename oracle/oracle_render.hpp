@@ -1155,24 +1155,31 @@ struct Renderer {
             return true;
         }
     };
-    // Material::bump (core/src/material.rs:62-101) + set_shading_geometry(.., false) (surface_interaction.rs:152-173)
+    // Material::bump (core/src/material.rs:62-101) + set_shading_geometry(.., false) (surface_interaction.rs:152-173) on a displacement texture, a context and a shading frame
+    // (the hit point is the context's p): bump() below and the bump probe (oracle_capi.cpp: oracle_bump_probe_batch) both call it
+    struct BumpFrame { V3 n, ns, dpdu_s, dpdv_s, dndu_s, dndv_s; };
+    static void bump_frame(const std::vector<Texture>& textures, const std::vector<MipMap>& mipmaps, int bump_tex, const TexCtx& c, BumpFrame& f) {
+        Float du = 0.5f * (std::fabs(c.dudx) + std::fabs(c.dudy));
+        if (du == 0.0f) du = 0.0005f;
+        TexCtx cu = c; cu.p = c.p + du * f.dpdu_s; cu.uv = V2(c.uv.x + du, c.uv.y + 0.0f);
+        Float u_displace = tex_eval(textures, mipmaps, bump_tex, cu).c[0];
+        Float dv = 0.5f * (std::fabs(c.dvdx) + std::fabs(c.dvdy));
+        if (dv == 0.0f) dv = 0.0005f;
+        TexCtx cv = c; cv.p = c.p + dv * f.dpdv_s; cv.uv = V2(c.uv.x + 0.0f, c.uv.y + dv);
+        Float v_displace = tex_eval(textures, mipmaps, bump_tex, cv).c[0];
+        Float displace = tex_eval(textures, mipmaps, bump_tex, c).c[0];
+        V3 dpdu = f.dpdu_s + (u_displace - displace) / du * f.ns + displace * f.dndu_s;
+        V3 dpdv = f.dpdv_s + (v_displace - displace) / dv * f.ns + displace * f.dndv_s;
+        f.ns = face_forward(normalize(cross(dpdu, dpdv)), f.n);
+        f.dpdu_s = dpdu; f.dpdv_s = dpdv;
+    }
     void bump(SurfaceHit& si) const {
         const Material& m = sc->materials[sc->mesh_of(si.prim).material];
         if (m.bump_tex < 0) return;
         TexCtx c; c.uv = si.uv; c.dudx = si.dudx; c.dvdx = si.dvdx; c.dudy = si.dudy; c.dvdy = si.dvdy; c.p = si.p; c.dpdx = si.dpdx; c.dpdy = si.dpdy;
-        Float du = 0.5f * (std::fabs(si.dudx) + std::fabs(si.dudy));
-        if (du == 0.0f) du = 0.0005f;
-        TexCtx cu = c; cu.p = si.p + du * si.dpdu_s; cu.uv = V2(si.uv.x + du, si.uv.y + 0.0f);
-        Float u_displace = tex_eval(sc->textures, sc->mipmaps, m.bump_tex, cu).c[0];
-        Float dv = 0.5f * (std::fabs(si.dvdx) + std::fabs(si.dvdy));
-        if (dv == 0.0f) dv = 0.0005f;
-        TexCtx cv = c; cv.p = si.p + dv * si.dpdv_s; cv.uv = V2(si.uv.x + 0.0f, si.uv.y + dv);
-        Float v_displace = tex_eval(sc->textures, sc->mipmaps, m.bump_tex, cv).c[0];
-        Float displace = tex_eval(sc->textures, sc->mipmaps, m.bump_tex, c).c[0];
-        V3 dpdu = si.dpdu_s + (u_displace - displace) / du * si.ns + displace * si.dndu_s;
-        V3 dpdv = si.dpdv_s + (v_displace - displace) / dv * si.ns + displace * si.dndv_s;
-        si.ns = face_forward(normalize(cross(dpdu, dpdv)), si.n);
-        si.dpdu_s = dpdu; si.dpdv_s = dpdv;
+        BumpFrame f{si.n, si.ns, si.dpdu_s, si.dpdv_s, si.dndu_s, si.dndv_s};
+        bump_frame(sc->textures, sc->mipmaps, m.bump_tex, c, f);
+        si.ns = f.ns; si.dpdu_s = f.dpdu_s; si.dpdv_s = f.dpdv_s;
     }
     // `local` receives the per-hit lobe list of a textured material; the returned BSDF points at it, so it must outlive the BSDF
     BSDF make_bsdf(const SurfaceHit& si, Lobe* local) const {

@@ -26,6 +26,10 @@ inline int64_t f2isize(Float f) {  // `as isize`: saturating, NaN -> 0
     if (f <= -9223372036854775808.0f) return INT64_MIN;
     return (int64_t)f;
 }
+inline int64_t wrap_inc(int64_t v) { return (int64_t)((uint64_t)v + 1u); }  // v + 1 in two's complement, defined at INT64_MAX
+// work counters of oracle_texture_probe_work (oracle_capi.cpp): footprint texels visited by ewa() and noise_3d calls, per thread
+struct TexWork { uint64_t texels = 0, noise = 0; };
+inline TexWork& tex_work() { static thread_local TexWork w; return w; }
 inline Float lanczos(Float x, Float tau) {  // texture/common.rs:216-228 (host-side f32 sin: libm's, like the reference's)
     x = std::fabs(x);
     if (x < 1e-5f) return 1.0f;
@@ -158,8 +162,9 @@ struct MipMap {
         Float s = st.x * (Float)pyr[level].w - 0.5f, t = st.y * (Float)pyr[level].h - 0.5f;
         int64_t s0 = f2isize(std::floor(s)), t0 = f2isize(std::floor(t));
         Float ds = s - (Float)s0, dt = t - (Float)t0;
-        return texel(level, s0, t0) * (1.0f - ds) * (1.0f - dt) + texel(level, s0, t0 + 1) * (1.0f - ds) * dt + texel(level, s0 + 1, t0) * ds * (1.0f - dt) +
-               texel(level, s0 + 1, t0 + 1) * ds * dt;
+        const int64_t s0n = wrap_inc(s0), t0n = wrap_inc(t0);  // `s0 + 1` wraps at isize::MAX as the reference's release build does; a signed add would be undefined there
+        return texel(level, s0, t0) * (1.0f - ds) * (1.0f - dt) + texel(level, s0, t0n) * (1.0f - ds) * dt + texel(level, s0n, t0) * ds * (1.0f - dt) +
+               texel(level, s0n, t0n) * ds * dt;
     }
     Spec ewa(size_t level, V2 st, V2 dst0, V2 dst1) const {  // mipmap/mod.rs:320-371
         if (level >= pyr.size()) return texel(pyr.size() - 1, 0, 0);
@@ -177,19 +182,24 @@ struct MipMap {
         int64_t s0 = f2isize(std::ceil(s - 2.0f * inv_det * u_sqrt)), s1 = f2isize(std::floor(s + 2.0f * inv_det * u_sqrt));
         int64_t t0 = f2isize(std::ceil(t - 2.0f * inv_det * v_sqrt)), t1 = f2isize(std::floor(t + 2.0f * inv_det * v_sqrt));
         Spec sum(0.0f); Float sum_wts = 0.0f;
-        for (int64_t it = t0; it <= t1; it++) {
-            Float tt = (Float)it - t;
-            for (int64_t is = s0; is <= s1; is++) {
-                Float ss = (Float)is - s;
-                Float r2 = a * ss * ss + b * ss * tt + c * tt * tt;
-                if (r2 < 1.0f) {
-                    size_t index = pmin<size_t>(f2usize(r2 * (Float)WEIGHT_LUT_SIZE), WEIGHT_LUT_SIZE - 1);
-                    Float weight = weight_lut[index];
-                    sum += texel(level, is, it) * weight;
-                    sum_wts += weight;
+        // `t0..=t1`, `s0..=s1` (:355-357): the bounds saturate at isize::MAX, so the loops leave at the last index and never form t1 + 1 or s1 + 1
+        if (t0 <= t1 && s0 <= s1)
+            for (int64_t it = t0;; it++) {
+                Float tt = (Float)it - t;
+                for (int64_t is = s0;; is++) {
+                    Float ss = (Float)is - s;
+                    Float r2 = a * ss * ss + b * ss * tt + c * tt * tt;
+                    tex_work().texels++;
+                    if (r2 < 1.0f) {
+                        size_t index = pmin<size_t>(f2usize(r2 * (Float)WEIGHT_LUT_SIZE), WEIGHT_LUT_SIZE - 1);
+                        Float weight = weight_lut[index];
+                        sum += texel(level, is, it) * weight;
+                        sum_wts += weight;
+                    }
+                    if (is >= s1) break;
                 }
+                if (it >= t1) break;
             }
-        }
         if (is_float) return Spec(sum.c[0] / sum_wts);
         return sum / sum_wts;
     }
@@ -247,6 +257,7 @@ inline Float noise_grad(int64_t x, int64_t y, int64_t z, Float dx, Float dy, Flo
 }
 inline Float noise_weight(Float t) { Float t3 = t * t * t, t4 = t3 * t; return 6.0f * t4 * t - 15.0f * t4 + 10.0f * t3; }
 inline Float noise_3d(Float x, Float y, Float z) {
+    tex_work().noise++;
     int64_t ix = f2isize(std::floor(x)), iy = f2isize(std::floor(y)), iz = f2isize(std::floor(z));
     Float dx = x - (Float)ix, dy = y - (Float)iy, dz = z - (Float)iz;
     ix &= 255; iy &= 255; iz &= 255;

@@ -141,13 +141,10 @@ int upload_scene(PbrtHipScene* s) {
         s->alpha_lean = s->alpha_textures;
         for (const MeshRec& m : s->meshes)
             for (uint32_t t1 : {m.alpha_tex1, m.shadow_alpha_tex1})
-                if (t1)
-                    for (const TexOp& op : s->textures[t1 - 1u].prog)
-                        if (!(op.op == PH_TOP_CONST || op.op == PH_TOP_MUL || op.op == PH_TOP_MIX || (op.op == PH_TOP_IMAGE && op.mapping == 0u))) s->alpha_lean = false;
+                if (t1 && !tex_prog_is_simple(s->textures[t1 - 1u].prog)) s->alpha_lean = false;
         s->simple_textures = true;
         for (const PbrtHipScene::TextureHost& t : s->textures)
-            for (const TexOp& op : t.prog)
-                if (!(op.op == PH_TOP_CONST || op.op == PH_TOP_MUL || op.op == PH_TOP_MIX || (op.op == PH_TOP_IMAGE && op.mapping == 0u))) s->simple_textures = false;
+            if (!tex_prog_is_simple(t.prog)) s->simple_textures = false;
     }
     if ((rc = upload_vec(s, s->materials, &d.materials))) return rc;
     if ((rc = upload_vec(s, s->lobes, &d.lobes))) return rc;

@@ -1,5 +1,5 @@
-// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_raysort_probe): the device's BSDF, sampler and light
-// code and the ray binning between wavefront rounds on explicit inputs.
+// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_raysort_probe, pbrt_hip_texture_probe_batch,
+// pbrt_hip_bump_probe_batch): the device's BSDF, sampler, light and texture code and the ray binning between wavefront rounds on explicit inputs.
 // Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
@@ -102,6 +102,43 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene
     }
 }
 
+
+// the 15 floats of pbrt_hip_texture_eval_batch.  NODIFF: the context of every ray but a camera ray, as tex_ctx_from and alpha_accept make it — the nine derivative fields are zero
+// (the NODIFF evaluator skips only the image maps' filtered look-up; the procedural classes and bump_shading read the fields)
+template <bool NODIFF>
+PH_DEV TexCtx probe_tex_ctx(const float* q) {
+    TexCtx c; c.uv = mk2(q[0], q[1]); c.p = mk3(q[6], q[7], q[8]);
+    c.dudx = c.dvdx = c.dudy = c.dvdy = 0.0f; c.dpdx = mk3(0.0f, 0.0f, 0.0f); c.dpdy = c.dpdx;
+    if (!NODIFF) { c.dudx = q[2]; c.dvdx = q[3]; c.dudy = q[4]; c.dvdy = q[5]; c.dpdx = mk3(q[9], q[10], q[11]); c.dpdy = mk3(q[12], q[13], q[14]); }
+    return c;
+}
+// VARIANT 0 .. 3: tex_eval<SIMPLE, NODIFF> with SIMPLE = VARIANT >> 1, NODIFF = VARIANT & 1, the four instantiations of the texture pass and the alpha test; 4: alpha_prog_r, the lean
+// alpha test's evaluator (red channel).  One kernel per variant: each instantiation of the evaluator owns an LDS value stack
+template <int VARIANT>
+__global__ __launch_bounds__(PH_TEX_LDS_THREADS) void texture_probe_kernel(DeviceScene sc, uint32_t tex, uint32_t n, const float* in, float* out) {
+    noise_lds_fill();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const TexCtx c = probe_tex_ctx<(VARIANT & 1) != 0 || VARIANT == 4>(in + 15 * (size_t)i);
+    spec v;
+    if (VARIANT == 4) v = mks(alpha_prog_r(sc, tex, c.uv), 0.0f, 0.0f);
+    else v = tex_eval<(VARIANT & 2) != 0, (VARIANT & 1) != 0>(sc.self, tex, c);
+    out[3 * (size_t)i] = v.r; out[3 * (size_t)i + 1] = v.g; out[3 * (size_t)i + 2] = v.b;
+}
+// bump_shading<SIMPLE, NODIFF> on an explicit context and shading frame: in = 15 context floats, then n, ns, dpdu_s, dpdv_s, dndu, dndv; out = the new ns and dpdu_s
+template <int VARIANT>
+__global__ __launch_bounds__(PH_TEX_LDS_THREADS) void bump_probe_kernel(DeviceScene sc, uint32_t tex, uint32_t n, const float* in, float* out) {
+    noise_lds_fill();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in + 33 * (size_t)i;
+    const TexCtx c = probe_tex_ctx<(VARIANT & 1) != 0>(q);
+    BumpOut b;
+    bump_shading<(VARIANT & 2) != 0, (VARIANT & 1) != 0>(sc.self, tex, c, c.p, ld3(q + 15), ld3(q + 18), ld3(q + 21), ld3(q + 24), ld3(q + 27), ld3(q + 30), &b);
+    float* o = out + 6 * (size_t)i;
+    o[0] = b.ns.x; o[1] = b.ns.y; o[2] = b.ns.z; o[3] = b.dpdu_s.x; o[4] = b.dpdu_s.y; o[5] = b.dpdu_s.z;
+}
+
 }  // namespace ph
 
 using namespace phost;
@@ -117,6 +154,35 @@ bool material_reads_a_texture(const MaterialRec& m) {
     return m.textured || m.kd_tex1 || m.bump_tex1 || m.sigma_tex1 || m.opacity_tex1 || m.amount_tex1 || m.rt_mode || m.refl_tex1 || m.trans_tex1 || m.index_tex1;
 }
 }  // namespace
+
+// the two texture probes share their checks and their launch: `in_stride` floats in and `out_stride` floats out per probe
+namespace {
+template <class Launch>
+int texture_probe_common(PbrtHipScene* s, const char* who, uint32_t tex, int variant, int n_variants, uint64_t n, const float* in, size_t in_stride, float* out, size_t out_stride, Launch launch) {
+    const std::string w(who);
+    if (!s || (n && (!in || !out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, w + ": null argument");
+    if (tex >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, w + ": unknown texture");
+    if (variant < 0 || variant >= n_variants) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, w + ": unknown variant");
+    if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, w + ": too many probes");
+    if (variant >= 2 && !tex_prog_is_simple(s->textures[tex].prog))
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, w + ": variants 2 and above are the code of programs made of constants, uv-mapped image maps, scale and mix; this texture holds another operation");
+    if (n == 0) return PBRT_HIP_OK;
+    PH_CHECK(s, hipSetDevice(s->device));
+    int rc;
+    if ((rc = upload_scene(s))) return rc;   // textures do not need the accelerator: an empty one is fine
+    const size_t o_in = 0, o_out = o_in + up256(n * in_stride * 4), total = o_out + up256(n * out_stride * 4);
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    PH_CHECK(s, hipMemcpyAsync(d + o_in, in, n * in_stride * 4, hipMemcpyHostToDevice, s->stream));
+    launch(dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), (const float*)(d + o_in), (float*)(d + o_out));
+    PH_CHECK(s, hipGetLastError());
+    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * out_stride * 4, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+}
+}  // namespace
+static_assert(PH_PROBE_BLOCK <= PH_TEX_LDS_THREADS, "the texture probes evaluate textures: their blocks must fit the evaluator's LDS stack");
 
 extern "C" {
 
@@ -242,6 +308,31 @@ int pbrt_hip_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, int vari
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
     return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_texture_probe_batch(PbrtHipScene* s, uint32_t texture, int variant, uint64_t n, const float* contexts, float* out) {
+    return ph_guard(s, "pbrt_hip_texture_probe_batch", [&]() -> int {
+    return texture_probe_common(s, "texture_probe_batch", texture, variant, 5, n, contexts, 15, out, 3, [&](dim3 grid, dim3 block, const float* d_in, float* d_out) {
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, texture, (uint32_t)n, d_in, d_out); };
+        if (variant == 0) launch(ph::texture_probe_kernel<0>);
+        else if (variant == 1) launch(ph::texture_probe_kernel<1>);
+        else if (variant == 2) launch(ph::texture_probe_kernel<2>);
+        else if (variant == 3) launch(ph::texture_probe_kernel<3>);
+        else launch(ph::texture_probe_kernel<4>);
+    });
+    });
+}
+
+int pbrt_hip_bump_probe_batch(PbrtHipScene* s, uint32_t texture, int variant, uint64_t n, const float* in, float* out) {
+    return ph_guard(s, "pbrt_hip_bump_probe_batch", [&]() -> int {
+    return texture_probe_common(s, "bump_probe_batch", texture, variant, 4, n, in, 33, out, 6, [&](dim3 grid, dim3 block, const float* d_in, float* d_out) {
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, texture, (uint32_t)n, d_in, d_out); };
+        if (variant == 0) launch(ph::bump_probe_kernel<0>);
+        else if (variant == 1) launch(ph::bump_probe_kernel<1>);
+        else if (variant == 2) launch(ph::bump_probe_kernel<2>);
+        else launch(ph::bump_probe_kernel<3>);
+    });
     });
 }
 

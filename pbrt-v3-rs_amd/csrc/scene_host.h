@@ -122,6 +122,12 @@ int set_err(PbrtHipScene* s, int code, const std::string& msg);
 int hip_fail(PbrtHipScene* s, hipError_t e, const char* what);
 int ensure_buf(PbrtHipScene* s, DevBuf& b, size_t bytes);
 int upload_scene(PbrtHipScene* s);
+// a texture program of constants, uv-mapped image maps, scale and mix only: what the lean alpha test (alpha_prog_r), the texture pass's SIMPLE evaluator and the texture probes' variants 2 to 4 admit
+inline bool tex_prog_is_simple(const std::vector<TexOp>& prog) {
+    for (const TexOp& op : prog)
+        if (!(op.op == PH_TOP_CONST || op.op == PH_TOP_MUL || op.op == PH_TOP_MIX || (op.op == PH_TOP_IMAGE && op.mapping == 0u))) return false;
+    return true;
+}
 void projection_light_setup(float fov_deg, float aspect, float out_proj[16], float out_screen[4], float* out_cos_total_width);   // host_setup.cpp
 // MIPMap::lookup_triangle on the host copy of the texel pool (textures_api.hip), for what InfiniteAreaLight computes at construction time
 void hmip_lookup_triangle(const PbrtHipScene* s, const MipRec& m, float u, float v, float width, float out[3]);

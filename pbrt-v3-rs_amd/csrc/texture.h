@@ -45,8 +45,9 @@ PH_DEV spec mip_triangle(const DeviceScene& sc, const MipRec& m, uint32_t level,
     const float s = st.x * (float)m.level_w[level] - 0.5f, t = st.y * (float)m.level_h[level] - 0.5f;
     const long long s0 = f2ll_sat(floorf(s)), t0 = f2ll_sat(floorf(t));
     const float ds = s - (float)s0, dt = t - (float)t0;
-    return mip_texel(sc, m, level, s0, t0) * (1.0f - ds) * (1.0f - dt) + mip_texel(sc, m, level, s0, t0 + 1) * (1.0f - ds) * dt +
-           mip_texel(sc, m, level, s0 + 1, t0) * ds * (1.0f - dt) + mip_texel(sc, m, level, s0 + 1, t0 + 1) * ds * dt;
+    const long long s0n = (long long)((unsigned long long)s0 + 1ull), t0n = (long long)((unsigned long long)t0 + 1ull);   // `s0 + 1` wraps at isize::MAX, as the reference's release build does
+    return mip_texel(sc, m, level, s0, t0) * (1.0f - ds) * (1.0f - dt) + mip_texel(sc, m, level, s0, t0n) * (1.0f - ds) * dt +
+           mip_texel(sc, m, level, s0n, t0) * ds * (1.0f - dt) + mip_texel(sc, m, level, s0n, t0n) * ds * dt;
 }
 PH_DEV spec mip_ewa(const DeviceScene& sc, const MipRec& m, uint32_t level, f2 st, f2 dst0, f2 dst1) {
     if (level >= m.n_levels) return mip_texel(sc, m, m.n_levels - 1u, 0, 0);
@@ -66,34 +67,42 @@ PH_DEV spec mip_ewa(const DeviceScene& sc, const MipRec& m, uint32_t level, f2 s
     spec sum = mks1(0.0f);
     float sum_wts = 0.0f;
     const long long lim = 1ll << 30;
-    if (s0 > -lim && s1 < lim && t0 > -lim && t1 < lim) {   // the ellipse's box in 32-bit counters (always, short of degenerate differentials): (float)(int) == (float)(long long) here
-        for (int it = (int)t0; it <= (int)t1; it++) {
-            const float tt = (float)it - t;
-            for (int is = (int)s0; is <= (int)s1; is++) {
-                const float ss = (float)is - s;
-                const float r2 = a * ss * ss + b * ss * tt + c * tt * tt;
-                if (r2 < 1.0f) {
-                    uint32_t index = f2u_sat(r2 * (float)PH_EWA_LUT_SIZE);
-                    if (index > PH_EWA_LUT_SIZE - 1u) index = PH_EWA_LUT_SIZE - 1u;
-                    const float weight = sc.ewa_lut[index];
-                    sum = sum + mip_texel_i(sc, m, level, is, it) * weight;
-                    sum_wts += weight;
+    // `t0..=t1`, `s0..=s1` (mipmap/mod.rs:355-357): the bounds saturate at isize::MAX, so both forms of the loops leave at the last index and never form t1 + 1 or s1 + 1
+    if (t0 <= t1 && s0 <= s1) {
+        if (s0 > -lim && s1 < lim && t0 > -lim && t1 < lim) {   // the ellipse's box in 32-bit counters (always, short of degenerate differentials): (float)(int) == (float)(long long) here
+            const int is0 = (int)s0, is1 = (int)s1, it1 = (int)t1;
+            for (int it = (int)t0;; it++) {
+                const float tt = (float)it - t;
+                for (int is = is0;; is++) {
+                    const float ss = (float)is - s;
+                    const float r2 = a * ss * ss + b * ss * tt + c * tt * tt;
+                    if (r2 < 1.0f) {
+                        uint32_t index = f2u_sat(r2 * (float)PH_EWA_LUT_SIZE);
+                        if (index > PH_EWA_LUT_SIZE - 1u) index = PH_EWA_LUT_SIZE - 1u;
+                        const float weight = sc.ewa_lut[index];
+                        sum = sum + mip_texel_i(sc, m, level, is, it) * weight;
+                        sum_wts += weight;
+                    }
+                    if (is >= is1) break;
                 }
+                if (it >= it1) break;
             }
-        }
-    } else {
-        for (long long it = t0; it <= t1; it++) {
-            const float tt = (float)it - t;
-            for (long long is = s0; is <= s1; is++) {
-                const float ss = (float)is - s;
-                const float r2 = a * ss * ss + b * ss * tt + c * tt * tt;
-                if (r2 < 1.0f) {
-                    uint32_t index = f2u_sat(r2 * (float)PH_EWA_LUT_SIZE);
-                    if (index > PH_EWA_LUT_SIZE - 1u) index = PH_EWA_LUT_SIZE - 1u;
-                    const float weight = sc.ewa_lut[index];
-                    sum = sum + mip_texel(sc, m, level, is, it) * weight;
-                    sum_wts += weight;
+        } else {
+            for (long long it = t0;; it++) {
+                const float tt = (float)it - t;
+                for (long long is = s0;; is++) {
+                    const float ss = (float)is - s;
+                    const float r2 = a * ss * ss + b * ss * tt + c * tt * tt;
+                    if (r2 < 1.0f) {
+                        uint32_t index = f2u_sat(r2 * (float)PH_EWA_LUT_SIZE);
+                        if (index > PH_EWA_LUT_SIZE - 1u) index = PH_EWA_LUT_SIZE - 1u;
+                        const float weight = sc.ewa_lut[index];
+                        sum = sum + mip_texel(sc, m, level, is, it) * weight;
+                        sum_wts += weight;
+                    }
+                    if (is >= s1) break;
                 }
+                if (it >= t1) break;
             }
         }
     }

@@ -164,6 +164,8 @@ class Binding:
             "sampler_value_batch": (C.c_int, [vp, C.c_uint64, ip, u32p, u32p, C.c_int, fp]),
             "light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, fp]),
             "raysort_probe": (C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p]),
+            "texture_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
+            "bump_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -730,6 +732,23 @@ class Scene:
         assert len(u) == n and len(wi) == n
         out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
         self._chk(self.b.fn("light_probe_batch")(self.h, light, op, variant, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
+        return out
+
+    def texture_probe_batch(self, texture, contexts, variant=0):
+        """`texture` at explicit contexts (n,15) = u v du/dx dv/dx du/dy dv/dy p dp/dx dp/dy (pbrt_hip_texture_probe_batch), a probe for the parity tests.  variant 0 / 1: the
+        general evaluator with / without differentials; 2 / 3: the evaluator of constant / image / scale / mix programs with / without; 4: the lean alpha test's (red channel in
+        column 0).  Returns (n,3)."""
+        ctx = _f32(contexts, (-1, 15)); n = len(ctx)
+        out = np.zeros((n, 3), np.float32)
+        self._chk(self.b.fn("texture_probe_batch")(self.h, texture, variant, n, _ptr(ctx, C.c_float), _ptr(out, C.c_float)))
+        return out
+
+    def bump_probe_batch(self, texture, inputs, variant=0):
+        """Material::bump with `texture` as displacement on explicit inputs (n,33) = the 15 context floats, then n, ns, dpdu_s, dpdv_s, dndu, dndv (pbrt_hip_bump_probe_batch).
+        Returns (n,6): the new shading normal and shading dp/du.  variant 0 .. 3 as in texture_probe_batch."""
+        inp = _f32(inputs, (-1, 33)); n = len(inp)
+        out = np.zeros((n, 6), np.float32)
+        self._chk(self.b.fn("bump_probe_batch")(self.h, texture, variant, n, _ptr(inp, C.c_float), _ptr(out, C.c_float)))
         return out
 
     def mipmap_pyramid(self, mipmap):

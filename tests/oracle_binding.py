@@ -61,13 +61,15 @@ def oracle_binding():
         L.oracle_bsdf_probe.argtypes = [vp, C.c_uint32, C.c_int, fp, fp, fp, C.c_int, fp]
         L.oracle_spatial_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.oracle_spatial_voxel.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.oracle_texture_probe_work.argtypes = [vp, C.c_uint32, C.c_uint64, fp, C.POINTER(C.c_uint64)]
         _binding = b
     return _binding
 
 
 class OracleScene(pbrt_hip.Scene):
-    """pbrt_hip.Scene driven against liboracle.so, plus the oracle-only extras.  The batch probes (bsdf_probe_batch, sampler_value_batch, light_probe_batch) are the
-    inherited methods: oracle_bsdf_probe_batch / oracle_sampler_value_batch / oracle_light_probe_batch have the product's signatures."""
+    """pbrt_hip.Scene driven against liboracle.so, plus the oracle-only extras.  The batch probes (bsdf_probe_batch, sampler_value_batch, light_probe_batch, texture_probe_batch,
+    bump_probe_batch) are the inherited methods: oracle_bsdf_probe_batch / oracle_sampler_value_batch / oracle_light_probe_batch / oracle_texture_probe_batch /
+    oracle_bump_probe_batch have the product's signatures."""
 
     def __init__(self):
         super().__init__(oracle_binding(), 0)
@@ -102,6 +104,13 @@ class OracleScene(pbrt_hip.Scene):
         out = np.zeros(8, np.float32)
         f = lambda a: np.ascontiguousarray(a, dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float))
         self._chk(self.b.lib.oracle_bsdf_probe(self.h, material, op, f(wo), f(wi), f(u), flags, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def texture_probe_work(self, texture, contexts):
+        """per probe (n,2): the footprint texels MIPMap::ewa visits and the noise_3d calls of the evaluation with differentials (oracle_texture_probe_work)"""
+        ctx = np.ascontiguousarray(contexts, dtype=np.float32).reshape(-1, 15)
+        out = np.zeros((len(ctx), 2), np.uint64)
+        self._chk(self.b.lib.oracle_texture_probe_work(self.h, texture, len(ctx), ctx.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out
 
     def spatial_stats(self):
