@@ -187,13 +187,24 @@ int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const f
  * (z_max - z_min) of the constructor's clamped values — so a partial sphere emits and is sampled as the reference does it: Sphere::sample_solid_angle (shapes/src/sphere.rs:344-410)
  * draws from the cone the FULL sphere subtends, or from the full sphere's area where the reference point lies inside it, and DiffuseAreaLight::sample_li (diffuse.rs:114-129) takes the point
  * as it comes.  A ray that meets the sphere sees L on the side its normal faces (reverse orientation and the transform's handedness included), on both sides if two_sided (diffuse.rs:220-226).
- * pbrt_hip_render_whitted renders such a scene; pbrt_hip_render_path and pbrt_hip_render_path_tiles_device return PBRT_HIP_ERR_UNSUPPORTED before any work (message: "sphere light"), because
- * PathIntegrator::li also needs Sphere::pdf_solid_angle for its MIS weight; the handle stays usable.  The batch intersection entry points treat the sphere as ordinary geometry.
+ * pbrt_hip_render_whitted renders such a scene.  pbrt_hip_render_path and pbrt_hip_render_path_tiles_device render it on a handle that asked for it with
+ * pbrt_hip_set_path_sphere_lights (below); on any other they return PBRT_HIP_ERR_UNSUPPORTED before any work (message: "sphere light") and the handle stays usable.
+ * PathIntegrator::li needs Sphere::pdf_solid_angle (shapes/src/sphere.rs:462-475) for its MIS weight.  Outside the sphere that is the cone's uniform pdf, as the reference computes it.
+ * INSIDE (the reference point, offset towards the centre, lies in or on the sphere) the reference calls `Shape::pdf_solid_angle(self, hit, wi)` from inside `impl Shape for Sphere`,
+ * which resolves to the same function: it recurses until its stack ends and has no answer.  A documented departure from a reference that crashes: the library evaluates the trait's
+ * default there (core/src/geometry/shape.rs:86-107, the counterpart of sample_solid_angle's inside branch and what upstream pbrt-v3 does) — the ray hit.spawn_ray(wi) against the cut
+ * sphere, alpha ignored, distance^2 / (|n . -wi| * area), 0 for a miss or an infinite value.  The batch intersection entry points treat the sphere as ordinary geometry.
  * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: between object_begin and object_end, as for any quadric; while pbrt_hip_add_light_diffuse_area lights that no mesh has claimed are pending.
  * The other five quadrics cannot be lights.  The pbrt_hip_render front end makes this call for Shape "sphere" under AreaLightSource "diffuse" when run with --quadrics (without the
- * option it refuses the six quadric Shape directives), and refuses such a scene under Integrator "path" itself. */
+ * option it refuses the six quadric Shape directives), and refuses such a scene under Integrator "path" itself unless it is also run with --path-sphere-lights. */
 int pbrt_hip_add_sphere_light(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
                               uint32_t material_id, uint32_t flags, const float L_rgb[3], int two_sided);
+/* on != 0: pbrt_hip_render_path and pbrt_hip_render_path_tiles_device sample the lights made by pbrt_hip_add_sphere_light (DiffuseAreaLight::sample_li / pdf_li on a Sphere, in
+ * uniform_sample_one_light and, under light strategy 2, in the spatial light distribution) instead of refusing the scene.  0, the default: every answer is as before the switch
+ * existed.  Legal at any time before a render; holds until it is changed; applies to every device of a handle made by pbrt_hip_scene_create_multi, to tile parts, chunks and
+ * sample-record bands.  A scene without a sphere light launches the same kernels whatever the switch says.  A sphere light draws the 5 sampler dimensions per vertex of any
+ * non-delta light.  PBRT_HIP_ERR_INVALID_ARG: null handle. */
+int pbrt_hip_set_path_sphere_lights(PbrtHipScene*, int on);
 
 /* Alpha masks: the float textures behind a mesh's `alpha` / `shadowalpha` parameters (TriangleMesh::alpha_mask, shadow_alpha_mask: shapes/src/triangle.rs:291-312),
  * for the mesh added last; 0xFFFFFFFF keeps the constant given to add_mesh.  A candidate hit is rejected where the texture evaluates to exactly 0 at the hit's
@@ -488,6 +499,11 @@ int pbrt_hip_sampler_value_batch(PbrtHipScene*, uint64_t n, const int* xy /*2n*/
 #define PBRT_HIP_LIGHT_PROBE_STRIDE 28
 int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int variant, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/,
                                float* out /*28n*/);
+/* pbrt_hip_sphere_light_probe_batch: a light made by pbrt_hip_add_sphere_light as the path integrator's sphere-light shade pass calls it.  op 0: Light::sample_li — the function
+ * variant 2 of pbrt_hip_light_probe_batch runs; op 1: out[0] = Light::pdf_li(ref, wi), Sphere::pdf_solid_angle as described at pbrt_hip_add_sphere_light.  Inputs and the 28-float
+ * output layout are pbrt_hip_light_probe_batch's; the handle's pbrt_hip_set_path_sphere_lights switch is not consulted.  PBRT_HIP_ERR_UNSUPPORTED: the light is not a spherical
+ * area light.  PBRT_HIP_ERR_INVALID_ARG: unknown light or op; a null handle; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built. */
+int pbrt_hip_sphere_light_probe_batch(PbrtHipScene*, uint32_t light, int op, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/, float* out /*28n*/);
 /* pbrt_hip_raysort_probe: the ray binning between wavefront rounds (csrc/raysort.h) on explicit keys, through the launch the path integrator's rounds use.  keys_cl / keys_sh = the
  * bin keys (< 4096) of n_cl closest-hit and n_sh any-hit rays; the keys and the two counts are uploaded and read from device memory, as in a render.  order_out[0 .. n_cl + n_sh) =
  * the queue positions (closest-hit rays 0 .. n_cl, any-hit rays behind them) grouped by bin, closest-hit rays first; the order inside a bin is unspecified.  sort_blocks = the grid

@@ -180,6 +180,7 @@ static int render_on_devices(PbrtHipScene* s, int tile_size, int tile_part, int 
     for (int k = 0; k < n; k++) {
         floats[k] = tile_buffer_floats_for(s, tile_size, tile_part + tile_parts * k, parts);
         devs[k]->record_budget = s->record_budget;   // the sample-record budget (pbrt_hip_set_sample_record_budget) applies to every device
+        devs[k]->path_sphere_lights = s->path_sphere_lights;   // ... and so does the path integrator's sphere-light switch (pbrt_hip_set_path_sphere_lights)
         PH_CHECK(s, hipSetDevice(devs[k]->device));
         if ((rc = ensure_buf(devs[k], tile_buffer_of(devs[k]), floats[k] * 4))) { s->err = devs[k]->err; return rc; }
     }

@@ -1,4 +1,4 @@
-// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_raysort_probe, pbrt_hip_texture_probe_batch,
+// Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_sphere_light_probe_batch, pbrt_hip_raysort_probe, pbrt_hip_texture_probe_batch,
 // pbrt_hip_bump_probe_batch): the device's BSDF, sampler, light and texture code and the ray binning between wavefront rounds on explicit inputs.
 // Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
@@ -101,7 +101,30 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene
         o[0] = le.r; o[1] = le.g; o[2] = le.b;
     }
 }
-
+// Light::sample_li (op 0) and Light::pdf_li (op 1) as the path integrator's sphere-light shade pass calls them (wavefront.hip, ShadeRowSphereLights): wh_light_sample_li<true> and
+// sl_light_pdf_li (sphere_light.h).  Inputs and output layout are light_probe_kernel's.
+__global__ __launch_bounds__(PH_PROBE_BLOCK) void sphere_light_probe_kernel(DeviceScene sc, uint32_t light, int op, uint32_t n, const float* ref_in, const float* u_in, const float* wi_in, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* rf = ref_in + 10 * (size_t)i;
+    SurfHit hit;
+    hit.p = ld3(rf); hit.p_error = ld3(rf + 3); hit.n = ld3(rf + 6); hit.time = rf[9];
+    hit.wo = mk3(0.0f, 0.0f, 0.0f); hit.ns = hit.n; hit.dpdu_s = hit.wo; hit.prim = 0u;
+    const LightRec& l = sc.lights[light];
+    float* o = out + PBRT_HIP_LIGHT_PROBE_STRIDE * (size_t)i;
+    for (int k = 0; k < PBRT_HIP_LIGHT_PROBE_STRIDE; k++) o[k] = 0.0f;
+    if (op == 0) {
+        const LiSample r = wh_light_sample_li<true>(sc, l, hit, mk2(u_in[2 * (size_t)i], u_in[2 * (size_t)i + 1]));
+        o[0] = r.wi.x; o[1] = r.wi.y; o[2] = r.wi.z; o[3] = r.pdf; o[4] = r.value.r; o[5] = r.value.g; o[6] = r.value.b; o[7] = r.valid ? 1.0f : 0.0f;
+        o[8] = r.vp.x; o[9] = r.vp.y; o[10] = r.vp.z; o[11] = r.vperr.x; o[12] = r.vperr.y; o[13] = r.vperr.z; o[14] = r.vn.x; o[15] = r.vn.y; o[16] = r.vn.z;
+        if (r.valid) {   // the shadow ray shade_kernel makes next
+            const RayIn sr = spawn_ray_to_hit(hit, r.vp, r.vperr, r.vn);
+            o[17] = sr.ox; o[18] = sr.oy; o[19] = sr.oz; o[20] = sr.dx; o[21] = sr.dy; o[22] = sr.dz; o[23] = sr.t_max;
+        }
+    } else {
+        o[0] = sl_light_pdf_li(sc, l, hit, ld3(wi_in + 3 * (size_t)i));
+    }
+}
 
 // the 15 floats of pbrt_hip_texture_eval_batch.  NODIFF: the context of every ray but a camera ray, as tex_ctx_from and alpha_accept make it — the nine derivative fields are zero
 // (the NODIFF evaluator skips only the image maps' filtered look-up; the procedural classes and bump_shading read the fields)
@@ -304,6 +327,37 @@ int pbrt_hip_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, int vari
     if (variant == 0) launch(ph::light_probe_kernel<0>);
     else if (variant == 1) launch(ph::light_probe_kernel<1>);
     else launch(ph::light_probe_kernel<2>);
+    PH_CHECK(s, hipGetLastError());
+    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_sphere_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, uint64_t n, const float* ref, const float* u, const float* wi, float* out) {
+    return ph_guard(s, "pbrt_hip_sphere_light_probe_batch", [&]() -> int {
+    if (!s || (n && (!ref || !u || !wi || !out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "sphere_light_probe_batch: null argument");
+    if (light >= s->lights.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "sphere_light_probe_batch: unknown light");
+    if (op < 0 || op > 1) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "sphere_light_probe_batch: op must be 0 (sample_li) or 1 (pdf_li)");
+    if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "sphere_light_probe_batch: too many probes");
+    if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "sphere_light_probe_batch: build_accel first");
+    const LightRec& l = s->lights[light];
+    if (l.type != PH_L_AREA || l.prim >= s->tri_mesh.size() || !(s->meshes[s->tri_mesh[l.prim]].flags & PH_MESH_QUADRIC))
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "sphere_light_probe_batch: the light is not a spherical area light (pbrt_hip_add_sphere_light); pbrt_hip_light_probe_batch probes the others");
+    if (n == 0) return PBRT_HIP_OK;
+    PH_CHECK(s, hipSetDevice(s->device));
+    int rc;
+    if ((rc = upload_scene(s))) return rc;
+    const size_t stride = PBRT_HIP_LIGHT_PROBE_STRIDE * sizeof(float);
+    const size_t o_ref = 0, o_u = o_ref + up256(n * 40), o_wi = o_u + up256(n * 8), o_out = o_wi + up256(n * 12), total = o_out + up256(n * stride);
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    PH_CHECK(s, hipMemcpyAsync(d + o_ref, ref, n * 40, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 8, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_wi, wi, n * 12, hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(ph::sphere_light_probe_kernel, dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, light, op, (uint32_t)n,
+                       (const float*)(d + o_ref), (const float*)(d + o_u), (const float*)(d + o_wi), (float*)(d + o_out));
     PH_CHECK(s, hipGetLastError());
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));

@@ -51,7 +51,7 @@ struct SceneHostState {
     bool general_materials = false;  // some material is not matte: the renderer uses the general BSDF kernel
     bool simple_textures = false;    // every texture program is made of constants, image maps (uv mapping), scale and mix: the texture pass runs its lean instantiation (set at upload)
     std::vector<LightRec> lights;
-    uint32_t sphere_lights = 0;      // lights whose shape is a sphere (add_sphere_light): the Whitted driver samples them, the path integrator refuses the scene
+    uint32_t sphere_lights = 0;      // lights whose shape is a sphere (add_sphere_light): the Whitted driver samples them; the path integrator does on a handle with path_sphere_lights set and refuses the scene on any other
     // DiffuseAreaLights of shapes inside an object definition ("Area lights not supported with object instancing", api/src/lib.rs:877-881): the primitives keep their emission,
     // Scene::lights never sees them.  MeshRec::first_light = -2 - index on the host; uploaded behind the scene's lights (DeviceScene::n_lights does not count them).
     std::vector<LightRec> emission_only;
@@ -114,6 +114,7 @@ struct PbrtHipScene : SceneHostState {
     // sample records (band_plan.h): the caller's byte budget for them, 0 = automatic (pbrt_hip_set_sample_record_budget), and what the last render came to
     // (pbrt_hip_get_render_footprint: bands, tiles in the largest band, peak record bytes, the budget that applied, paths per chunk, chunk-scaled bytes, 0, 0)
     uint64_t record_budget = 0;
+    bool path_sphere_lights = false;   // pbrt_hip_set_path_sphere_lights: the path integrator samples sphere lights (SceneHostState::sphere_lights) instead of refusing the scene
     uint64_t footprint[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 

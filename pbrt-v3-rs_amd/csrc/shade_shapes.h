@@ -20,11 +20,19 @@ struct ShadeRowFull {
     static constexpr bool infinite = true, area = true, delta = true, halton = true, sobol = true, spatial = true;
     static constexpr bool phi_skip = false;   // light_pdf_li of a constant infinite light computes phi although both entries of its cond_func row are equal
     static constexpr bool lean_lds = false;   // the staged rays carry t_max and time; the drawn sampler dimensions have rows of their own
+    static constexpr bool sphere_lights = false;   // an area light's shape is a triangle
 };
 // Infinite lights only (any number, none included), Halton, no spatial distribution: the headline workload.
 struct ShadeRowSky {
     static constexpr bool infinite = true, area = false, delta = false, halton = true, sobol = false, spatial = false;
     static constexpr bool phi_skip = true, lean_lds = true;
+    static constexpr bool sphere_lights = false;
+};
+// The full row where an area light's shape may be a sphere (pbrt_hip_add_sphere_light with pbrt_hip_set_path_sphere_lights on): sample_li, pdf_li and the MIS resolve ask the light's
+// primitive whether it is a quadric (sphere_light.h).  NOT a row of ShadeRows and in no variant of ShadeVariants: wavefront.hip names the one kernel compiled on it next to its
+// launchers and the driver picks it before the table's picker, for such a scene alone, so every other scene launches what pick_shade_variant gives it.
+struct ShadeRowSphereLights : ShadeRowFull {
+    static constexpr bool sphere_lights = true;
 };
 
 template <class R> constexpr bool shade_row_covers(ShadeFeatures f) {

@@ -14,6 +14,7 @@
 // then samples uniformly: a data race that exists only with >1 thread.  This is the race-free behaviour.)
 #pragma once
 #include "pt_device.h"
+#include "sphere_light.h"
 
 namespace ph {
 
@@ -52,6 +53,8 @@ PH_DEV uint32_t spatial_voxel_of(const SpatialRec& sr, f3 p) {
 #define PH_SPATIAL_CHUNK 2048
 
 // One block per new voxel (grid-stride over the slots claimed since the last pass).
+// SPHERE: some light's shape may be a sphere (pbrt_hip_add_sphere_light under the path integrator): Light::sample_li is wh_light_sample_li (sphere_light.h), which asks the light's primitive
+template <bool SPHERE = false>
 __global__ __launch_bounds__(PH_SPATIAL_BLOCK) void spatial_compute_kernel(DeviceScene sc, SpatialRec sr) {
     __shared__ float buf[PH_SPATIAL_CHUNK];
     __shared__ float s_scalar[2];
@@ -86,7 +89,9 @@ __global__ __launch_bounds__(PH_SPATIAL_BLOCK) void spatial_compute_kernel(Devic
                 intr.p = mk3(sp_lerp(h[0], lo[0], hi[0]), sp_lerp(h[1], lo[1], hi[1]), sp_lerp(h[2], lo[2], hi[2]));
                 intr.p_error = mk3(0, 0, 0); intr.wo = mk3(0, 0, 0); intr.n = mk3(0, 0, 0); intr.ns = mk3(0, 0, 0); intr.dpdu_s = mk3(0, 0, 0);
                 intr.time = 0.0f; intr.prim = 0;
-                const LiSample ls = light_sample_li(sc, light, intr, mk2(h[3], h[4]));
+                LiSample ls;
+                if constexpr (SPHERE) ls = wh_light_sample_li<true>(sc, light, intr, mk2(h[3], h[4]));
+                else ls = light_sample_li(sc, light, intr, mk2(h[3], h[4]));
                 if (ls.valid && ls.pdf > 0.0f) acc += ph_div(lum_y(ls.value), ls.pdf);
             }
             func[j] = acc;

@@ -1,4 +1,5 @@
-// Light::sample_li where the light may be a spherical DiffuseAreaLight: what the Whitted state kernel (whitted.h) and the light probe (probe.hip) both call.
+// Light::sample_li and Light::pdf_li where the light may be a spherical DiffuseAreaLight: what the Whitted state kernel (whitted.h), the path integrator's sphere-light shade pass and
+// light-distribution pass (wavefront.hip, spatial.h) and the light probes (probe.hip) call.
 #pragma once
 #include "pt_device.h"
 
@@ -61,6 +62,35 @@ PH_DEV LiSample sphere_light_sample_li(const LightRec& l, const QuadricRec& q, b
     r.wi = wi2; r.pdf = pdf; r.value = area_L(l, n, -wi2); r.vp = p; r.vperr = p_error; r.vn = n; r.valid = true;
     return r;
 }
+// ---------------------------------------------------------------------------------------------------------------------------
+// DiffuseAreaLight::pdf_li (diffuse.rs:131-141) on a Sphere: Sphere::pdf_solid_angle (shapes/src/sphere.rs:462-475).  `qi`: the sphere's record in DeviceScene::quadrics.
+// Outside, the pdf of the cone the FULL sphere subtends from hit.p: it does not depend on wi and is not zero for a direction that misses the sphere, so estimate_direct traces the
+// BSDF-sampled ray in every case.  `radius` is the object-space radius against a world-space distance, whatever the transform scales, as in the reference.
+// Inside (the offset reference point lies in or on the sphere) the reference writes `Shape::pdf_solid_angle(self, hit, wi)` inside `impl Shape for Sphere`, which resolves to this very
+// function: it recurses until its stack ends and has no answer.  A DOCUMENTED DEPARTURE from a reference that crashes: what is built here is the counterpart of
+// sample_solid_angle's inside branch and what upstream pbrt-v3 does, the trait's default (core/src/geometry/shape.rs:86-107) — hit.spawn_ray(wi) against the sphere, test_alpha = false,
+// z and phi cuts included, then distance^2 / (|n . -wi| * area), 0 for a miss and for an infinite value.  The intersection is the shape's own leaf test and surface tail (quadric.h:
+// quadric_surface, what make_surface_hit_q calls), so the point and the normal are the ones a traced ray would report.
+PH_DEV float sphere_light_pdf_li(const DeviceScene& sc, const LightRec& l, uint32_t qi, const SurfHit& hit, f3 wi) {
+    const QuadricRec& q = sc.quadrics[qi];
+    const float* m = q.o2w;   // p_center = object_to_world.transform_point(Point3f::ZERO) (transform.rs:288-302)
+    const float xc = m[0] * 0.0f + m[1] * 0.0f + m[2] * 0.0f + m[3], yc = m[4] * 0.0f + m[5] * 0.0f + m[6] * 0.0f + m[7];
+    const float zc = m[8] * 0.0f + m[9] * 0.0f + m[10] * 0.0f + m[11], wc_ = m[12] * 0.0f + m[13] * 0.0f + m[14] * 0.0f + m[15];
+    const f3 p_center = (wc_ == 1.0f) ? mk3(xc, yc, zc) : mk3(xc, yc, zc) / wc_;
+    const f3 p_origin = offset_origin(hit.p, hit.p_error, hit.n, p_center - hit.p);
+    if (distance_squared(p_origin, p_center) <= q.radius * q.radius) {   // Shape::pdf_solid_angle (shape.rs:86-107)
+        const RayIn ray = spawn_ray(hit, wi);
+        float rod[6] = {ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz};
+        QSurf qs;
+        quadric_surface(sc.self, qi, rod, &qs);
+        if (!qs.hit) return 0.0f;
+        const float pdf = ph_div(distance_squared(hit.p, qs.p), abs_dot(qs.n, -wi) * l.area);
+        return __builtin_isinf(pdf) ? 0.0f : pdf;
+    }
+    const float sin_theta_max2 = ph_div(q.radius * q.radius, distance_squared(hit.p, p_center));
+    const float cos_theta_max = ph_sqrt(pmaxf(0.0f, 1.0f - sin_theta_max2));
+    return ph_div(1.0f, kTwoPi * (1.0f - cos_theta_max));   // uniform_cone_pdf
+}
 // Light::sample_li as the Whitted light loop calls it.  Only the QUADRIC instantiation knows that an area light's shape may be a sphere (pbrt_hip_add_sphere_light): the light's
 // primitive slot then leads to a PH_MESH_QUADRIC record whose vert_base is the QuadricRec.  light_sample_li itself (pt_device.h) stays as the path integrator's kernels inline it.
 template <bool QUADRIC> PH_DEV LiSample wh_light_sample_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f2 u) {
@@ -69,6 +99,15 @@ template <bool QUADRIC> PH_DEV LiSample wh_light_sample_li(const DeviceScene& sc
         if (m.flags & PH_MESH_QUADRIC) return sphere_light_sample_li(l, sc.quadrics[m.vert_base], (m.flags & PH_MESH_REV) != 0u, hit, u);
     }
     return light_sample_li<true>(sc, l, hit, u);
+}
+// Light::pdf_li as the path integrator's sphere-light shade pass calls it (wavefront.hip, ShadeRowSphereLights): the sphere's own pdf where the light's shape is one, else
+// light_pdf_li as every other shade kernel inlines it.  Its sample_li is wh_light_sample_li<true> above: the same function the Whitted light loop calls.
+PH_DEV float sl_light_pdf_li(const DeviceScene& sc, const LightRec& l, const SurfHit& hit, f3 wi) {
+    if (l.type == PH_L_AREA) {
+        const MeshRec m = sc.meshes[sc.tri_mesh[l.prim]];
+        if (m.flags & PH_MESH_QUADRIC) return sphere_light_pdf_li(sc, l, m.vert_base, hit, wi);
+    }
+    return light_pdf_li<true>(sc, l, hit, wi);
 }
 
 }  // namespace ph

@@ -18,6 +18,7 @@
 #include "host_math.h"
 #include "pt_device.h"
 #include "scene_host.h"
+#include "sphere_light.h"
 #include "spatial.h"
 #include "bsdf_general.h"
 #include "texture.h"
@@ -336,7 +337,8 @@ template <> struct ShadeLds<true> {
     }
 };
 // QUADRIC: the scene may hold quadric shapes (instantiated with GEN and TEX only: api.hip, add_quadric_common): a new vertex on one takes its interaction from the shape's own test
-// Row (shade_shapes.h): the light kinds, samplers and light distribution the kernel is compiled for; the rows leaner than ShadeRowFull exist for the texture-free matte kernel only
+// Row (shade_shapes.h): the light kinds, samplers and light distribution the kernel is compiled for; the rows leaner than ShadeRowFull exist for the texture-free matte kernel only;
+// ShadeRowSphereLights (instantiated with GEN, TEX and QUADRIC only) is the full row where an area light's shape may be a sphere: sample_li, pdf_li and the MIS resolve differ
 template <bool GEN, bool TEX = false, bool QUADRIC = false, class Row = ShadeRowFull>
 __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(DeviceScene sc, WfParams w, int it) {
     using BO = BsdfOps<GEN>;
@@ -413,7 +415,12 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                             if (lt.type == PH_L_AREA && lt.prim == hprim) {  // the hit primitive's area light IS the sampled light
                                 const float4 h1 = hp[1];
                                 MeshRec m;
-                                SurfHit lh = make_surface_hit_any(sc, wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
+                                SurfHit lh;
+                                if constexpr (Row::sphere_lights) {   // the sampled light may be a sphere: its interaction comes from the shape's own test on the MIS ray
+                                    QSurf lqs;
+                                    lh = make_surface_hit_q<true>(sc, mk3(mr.ox, mr.oy, mr.oz), wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &lqs);
+                                } else
+                                lh = make_surface_hit_any(sc, wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
                                 li2 = area_L(lt, lh.n, -wi);  // SurfaceInteraction::le (surface_interaction.rs:283-289)
                             }
                         }
@@ -520,7 +527,9 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                     // estimate_direct (integrator/common.rs:146-299), specular = false, handle_media = false
                                     {
                                         PHC_BEGIN(5);
-                                        const LiSample ls = light_sample_li<TEX, Row>(sc, light, si, u_light);
+                                        LiSample ls;
+                                        if constexpr (Row::sphere_lights) ls = wh_light_sample_li<true>(sc, light, si, u_light);
+                                        else ls = light_sample_li<TEX, Row>(sc, light, si, u_light);
                                         PHC_END(5);
                                         PHC_BEGIN(6);
                                         if (ls.valid && ls.pdf > 0.0f && !is_black(ls.value)) {
@@ -543,7 +552,9 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                         BO::sample_ns(bsdf, si.wo, u_scatter, f1, spdf, wi2);  // never specular with these flags: sampled_specular = false
                                         const spec f = f1 * abs_dot(wi2, si.ns);
                                         if (!is_black(f) && spdf > 0.0f) {
-                                            const float lp = light_pdf_li<TEX, Row>(sc, light, si, wi2);
+                                            float lp;
+                                            if constexpr (Row::sphere_lights) lp = sl_light_pdf_li(sc, light, si, wi2);
+                                            else lp = light_pdf_li<TEX, Row>(sc, light, si, wi2);
                                             if (lp != 0.0f) {  // lp == 0 -> `return ld` with the light-sampling part only
                                                 w2 = power_heuristic1(spdf, lp);
                                                 spdf_store = spdf;
@@ -946,10 +957,11 @@ int check_render_args(PbrtHipScene* s, int max_depth, int light_strategy, const 
     return PBRT_HIP_OK;
 }
 
-// PathIntegrator::li weights a light sample against Light::pdf_li, i.e. Shape::pdf_solid_angle of the light's shape (shape.rs:86-107).  For a sphere that is Sphere::pdf_solid_angle,
-// which nothing here can be checked against bit for bit, so a scene with a sphere light renders under the Whitted integrator only.  Before any work.
+// PathIntegrator::li weights a light sample against Light::pdf_li, i.e. Shape::pdf_solid_angle of the light's shape (shape.rs:86-107).  For a sphere that is Sphere::pdf_solid_angle
+// (sphere_light.h: sphere_light_pdf_li), whose inside branch departs from a reference that crashes there: the path integrator samples sphere lights only on a handle
+// that asked for it (pbrt_hip_set_path_sphere_lights); on any other the scene renders under the Whitted integrator only.  Before any work.
 static int refuse_sphere_lights(PbrtHipScene* s) {
-    if (s->sphere_lights == 0) return PBRT_HIP_OK;
+    if (s->sphere_lights == 0 || s->path_sphere_lights) return PBRT_HIP_OK;
     return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "render: the scene holds a sphere light (pbrt_hip_add_sphere_light), which the path integrator does not sample; render it with pbrt_hip_render_whitted");
 }
 
@@ -1010,6 +1022,15 @@ template <class... V> static void dispatch_shade_variant(ph::ShadeVariantTable<V
     static constexpr void (*launchers[])(PbrtHipScene*, uint32_t, const ph::WfParams&, int) = {&launch_shade_variant<V>...};
     launchers[variant](s, blocks, wp, it);
 }
+// The sphere-light forms (shade_shapes.h: ShadeRowSphereLights; spatial.h: spatial_compute_kernel<true>), outside the tables: one kernel each, named here, launched in place of the
+// table's pick / the triangle-light form for a scene that holds a sphere light (PathPlan::sphere_lights) and for no other.
+static void launch_shade_sphere_lights(PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
+    hipLaunchKernelGGL((ph::shade_kernel<true, true, true, ph::ShadeRowSphereLights>), dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, it);
+}
+static void launch_spatial_compute(PbrtHipScene* s, bool sphere_lights, const ph::SpatialRec& sr) {
+    if (sphere_lights) hipLaunchKernelGGL(ph::spatial_compute_kernel<true>, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, sr);
+    else hipLaunchKernelGGL(ph::spatial_compute_kernel<false>, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, sr);
+}
 // (the launchers of the table's two anchors are what instantiates them: compiled with the others, picked by nothing)
 template <class V> static void launch_tex_variant(PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
     hipLaunchKernelGGL((ph::texture_kernel<V::simple, V::camera, V::waves, V::quadric>), dim3(blocks), dim3(PH_TEX_LDS_THREADS), 0, s->stream, s->ds, wp, it);
@@ -1025,6 +1046,7 @@ struct PathPlan {
     bool spatial;        // the spatial light distribution is live: strategy 2 with more than one light (one light -> uniform, light_distrib/mod.rs:59-64)
     bool mat_queues;     // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
     bool has_quadrics;   // the QUADRIC instantiations of the texture, light-distribution and shade passes
+    bool sphere_lights;  // some light's shape is a sphere and the handle's switch is on (pbrt_hip_set_path_sphere_lights): the sphere-light forms of the shade and light-distribution passes
     int shade_variant;   // of ph::ShadeVariants: the lights' kinds as upload_scene found them, the sampler and the strategy as they are now; PBRT_HIP_SHADE_ROW=full: the full row for every scene
     int tex_variant[2];  // of ph::TexVariants: [1] the camera round's, [0] the later rounds'
     // Material "none" surfaces are passed through without counting a bounce, so a path may need more rounds than n_iter = max_depth + 1: those are
@@ -1061,6 +1083,7 @@ static int plan_path_frame(PbrtHipScene* s, int max_depth, int light_strategy, c
     p.n_iter = max_depth + 1;
     p.n_iter_cap = s->has_none_material ? p.n_iter + PathPlan::kMaxNullSkips : p.n_iter;
     p.has_quadrics = !s->quadrics.empty();
+    p.sphere_lights = s->sphere_lights != 0 && s->path_sphere_lights;
     const char* e = std::getenv("PBRT_HIP_SHADE_ROW");
     p.shade_variant = ph::pick_shade_variant(ph::ShadeTraits{s->general_materials, s->textured_materials, p.has_quadrics},
                                              ph::ShadeFeatures{s->lights_infinite, s->lights_area, s->lights_delta, s->sampler.kind != 0, p.spatial}, e && std::strcmp(e, "full") == 0);
@@ -1224,10 +1247,13 @@ static int run_round(PbrtHipScene* s, PathFrame& f, int it) {
         if ((rc = t.timed(SpanTimer::SHADE, [&]() {
                 if (p.has_quadrics) hipLaunchKernelGGL(ph::spatial_mark_kernel<true>, dim3(p.shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
                 else hipLaunchKernelGGL(ph::spatial_mark_kernel<false>, dim3(p.shade_blocks), dim3(256), 0, s->stream, s->ds, wp, it);
-                hipLaunchKernelGGL(ph::spatial_compute_kernel, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, wp.spatial);
+                launch_spatial_compute(s, p.sphere_lights, wp.spatial);
             }))) return rc;
     }
-    return t.timed(SpanTimer::SHADE, [&]() { dispatch_shade_variant(ph::ShadeVariants{}, p.shade_variant, s, p.shade_blocks, wp, it); });
+    return t.timed(SpanTimer::SHADE, [&]() {
+        if (p.sphere_lights) launch_shade_sphere_lights(s, p.shade_blocks, wp, it);
+        else dispatch_shade_variant(ph::ShadeVariants{}, p.shade_variant, s, p.shade_blocks, wp, it);
+    });
 }
 
 // One chunk: samples [s0, s0 + chunk_spp) of every pixel of the band bound in f.wp — counters cleared, raygen, the rounds, the ray counts read back.
@@ -1499,6 +1525,14 @@ int pbrt_hip_set_sample_record_budget(PbrtHipScene* s, uint64_t bytes) {
     return ph_guard(s, "pbrt_hip_set_sample_record_budget", [&]() -> int {
     if (!s) return PBRT_HIP_ERR_INVALID_ARG;
     s->record_budget = bytes;   // (a multi-device handle hands it to every device's context when it renders, multi.hip)
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_set_path_sphere_lights(PbrtHipScene* s, int on) {
+    return ph_guard(s, "pbrt_hip_set_path_sphere_lights", [&]() -> int {
+    if (!s) return PBRT_HIP_ERR_INVALID_ARG;
+    s->path_sphere_lights = on != 0;   // (a multi-device handle hands it to every device's context when it renders, multi.hip)
     return PBRT_HIP_OK;
     });
 }

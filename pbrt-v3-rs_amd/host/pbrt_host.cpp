@@ -818,8 +818,12 @@ int Api::pbrt_world_end(RenderReport& rep) {
     if (!verify_world("WorldEnd")) { error = "WorldEnd outside a world block"; return PBRT_HIP_ERR_STATE; }
     while (!gs_stack_.empty()) { warn("Missing end to AttributeBegin"); pbrt_attribute_end(); }
     while (!ctm_stack_.empty()) { warn("Missing end to TransformBegin"); ctm_stack_.pop_back(); }
-    // PathIntegrator::li weights a hit on an emitter by the light's pdf, and Sphere::pdf_solid_angle is not provided: the library refuses at render time, check mode has to here
-    if (sphere_light_ && integrator_name_ == "path") { error = "Shape \"sphere\" under AreaLightSource \"diffuse\" (a sphere light) is rendered by Integrator \"whitted\" only, not by \"path\""; return PBRT_HIP_ERR_UNSUPPORTED; }
+    // PathIntegrator::li weights a hit on an emitter by the light's pdf, Sphere::pdf_solid_angle, which the library evaluates only on a handle whose switch is on
+    // (pbrt_hip_set_path_sphere_lights: its inside branch departs from a reference that crashes there): the library refuses at render time, check mode has to here
+    if (sphere_light_ && integrator_name_ == "path" && !path_sphere_lights) {
+        error = "Shape \"sphere\" under AreaLightSource \"diffuse\" (a sphere light) is rendered by Integrator \"whitted\" only, not by \"path\" (unless run with --path-sphere-lights)";
+        return PBRT_HIP_ERR_UNSUPPORTED;
+    }
 
     // ---- filter + film (make_filter / make_film, graphics_state.rs:600-690; film/mod.rs:420-487)
     int fkind = -1; float rad[2] = {0.5f, 0.5f}, fparams[2] = {0.0f, 0.0f};
@@ -955,6 +959,7 @@ int Api::pbrt_world_end(RenderReport& rep) {
     const size_t npix = (size_t)std::max(0, cb[2] - cb[0]) * (size_t)std::max(0, cb[3] - cb[1]);
     std::vector<float> xyz(npix * 3), wt(npix), rgb(npix * 3);
     if (!check(pbrt_hip_set_sample_record_budget(scene_, sample_record_budget), "set_sample_record_budget")) return PBRT_HIP_ERR_INVALID_ARG;
+    if (!check(pbrt_hip_set_path_sphere_lights(scene_, path_sphere_lights ? 1 : 0), "set_path_sphere_lights")) return PBRT_HIP_ERR_INVALID_ARG;
     int rc = whitted ? pbrt_hip_render_whitted_devices(scene_, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
                      : pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
     if (!check(rc, whitted ? "render_whitted_devices" : "render_path")) return rc;

@@ -110,6 +110,7 @@ class Api {
     std::string sobol_tables_file;  // raw little-endian: u32[1024*52], u64[25*52], u64[26*52]
     int tile_size = 16;
     unsigned long long sample_record_budget = 0;   // --sample-record-budget BYTES (pbrt_hip_set_sample_record_budget); 0 = automatic
+    bool path_sphere_lights = false;   // --path-sphere-lights: a sphere light (Shape "sphere" under AreaLightSource "diffuse", read with `quadrics`) is rendered by Integrator "path" too
     bool quadrics = false;   // --quadrics: Shape "sphere" / "cylinder" / "cone" / "paraboloid" / "disk" / "hyperboloid" are read; without it they are refused as out of scope
     bool quiet = false;
     std::vector<std::string> warnings;
@@ -137,7 +138,7 @@ class Api {
     std::string current_object_;                // "" outside ObjectBegin/ObjectEnd
     uint64_t n_instances_ = 0;
     uint64_t n_quadrics_ = 0;
-    bool sphere_light_ = false;   // a Shape "sphere" stood under AreaLightSource "diffuse": only the Whitted integrator renders it
+    bool sphere_light_ = false;   // a Shape "sphere" stood under AreaLightSource "diffuse": the Whitted integrator renders it, the path integrator with path_sphere_lights
     int n_devices_ = 1;   // GPUs behind scene_ (--devices)
     bool verify_options(const char* func);
     bool verify_world(const char* func);

@@ -166,6 +166,8 @@ class Binding:
             "raysort_probe": (C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p]),
             "texture_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
             "bump_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
+            "set_path_sphere_lights": (C.c_int, [vp, C.c_int]),
+            "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -734,6 +736,17 @@ class Scene:
         self._chk(self.b.fn("light_probe_batch")(self.h, light, op, variant, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
         return out
 
+    def sphere_light_probe_batch(self, light, op, ref, u=None, wi=None):
+        """A spherical area light as the path integrator's sphere-light shade pass calls it (pbrt_hip_sphere_light_probe_batch): op 0 -> sample_li, op 1 -> pdf_li.  Inputs and the
+        (n,28) output are light_probe_batch's."""
+        ref = _f32(ref, (-1, 10)); n = len(ref)
+        u = _f32(u, (-1, 2)) if u is not None else np.full((n, 2), 0.5, np.float32)
+        wi = _f32(wi, (-1, 3)) if wi is not None else np.tile(np.array([0, 0, 1], np.float32), (n, 1))
+        assert len(u) == n and len(wi) == n
+        out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
+        self._chk(self.b.fn("sphere_light_probe_batch")(self.h, light, op, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
+        return out
+
     def texture_probe_batch(self, texture, contexts, variant=0):
         """`texture` at explicit contexts (n,15) = u v du/dx dv/dx du/dy dv/dy p dp/dx dp/dy (pbrt_hip_texture_probe_batch), a probe for the parity tests.  variant 0 / 1: the
         general evaluator with / without differentials; 2 / 3: the evaluator of constant / image / scale / mix programs with / without; 4: the lean alpha test's (red channel in
@@ -840,6 +853,11 @@ class Scene:
         """Bound on the bytes of sample records resident at once (pbrt_hip_set_sample_record_budget): the frame renders in bands of whole tiles, bit for bit the
         one-band film.  0 = automatic.  Holds until changed."""
         self._chk(self.b.fn("set_sample_record_budget")(self.h, int(nbytes)))
+
+    def set_path_sphere_lights(self, on=True):
+        """Let render_path / render_path_tiles_device sample spherical area lights (pbrt_hip_set_path_sphere_lights) instead of refusing such a scene.  Off by default;
+        holds until changed."""
+        self._chk(self.b.fn("set_path_sphere_lights")(self.h, 1 if on else 0))
 
     def render_footprint(self):
         """What the last render came to (pbrt_hip_get_render_footprint)."""
