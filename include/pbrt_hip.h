@@ -523,6 +523,19 @@ int pbrt_hip_raysort_probe(PbrtHipScene*, uint32_t n_cl, uint32_t n_sh, const ui
  * operation than constant, uv-mapped image map, scale and mix.  Nothing is launched on a refusal. */
 int pbrt_hip_texture_probe_batch(PbrtHipScene*, uint32_t texture, int variant, uint64_t n, const float* contexts /*15n*/, float* out /*3n*/);
 int pbrt_hip_bump_probe_batch(PbrtHipScene*, uint32_t texture, int variant, uint64_t n, const float* in /*33n*/, float* out /*6n*/);
+/* pbrt_hip_traverse_probe: the traversal kernel (csrc/traverse.h) on an explicit work queue, launched as a wavefront round launches it.  mode 0: n_cl closest-hit rays (n_sh = 0),
+ * mode 1: n_sh any-hit rays (n_cl = 0), mode 2: both queues in one launch — queue positions 0 .. n_cl are the closest-hit rays, n_cl .. n_cl + n_sh the any-hit rays; either count may
+ * be 0.  The rays and the two counts are uploaded and the counts read from device memory, as in a render.  order = NULL, or n_cl + n_sh queue positions: the queue is walked in that
+ * order (what the ray binning hands a round).  n_heads (1 .. 8) queue heads, head h serving the head_chunk-ray chunks c with c % n_heads == h; with n_heads = 1 the single counter
+ * is used and head_chunk is ignored.  blocks = the grid: 1 .. the resident grid the handle launches its renders with (6 blocks of 256 lanes per CU).  The kernel row is the scene's,
+ * the counting rows with pbrt_hip_set_traversal_counting on.  hits_out[n_cl] / occluded_out[n_sh] = what pbrt_hip_intersect_batch / pbrt_hip_occluded_batch give for the same rays:
+ * the result of a ray depends on nothing but the ray.  A result the kernel did not write comes back as 0xFF bytes.
+ * PBRT_HIP_ERR_INVALID_ARG: a null handle; a null array with a non-zero count; an unknown mode; mode 0 with n_sh > 0 or mode 1 with n_cl > 0; n_cl + n_sh >= 0x7FFF0000; n_heads 0 or
+ * above 8; n_heads > 1 with head_chunk 0 or no multiple of 64 (the kernel's precondition: a batch of 64 rays lies in one chunk); blocks 0 or above the resident grid; an order that
+ * is no permutation of 0 .. n_cl + n_sh (checked on the host).  PBRT_HIP_ERR_STATE: no accelerator built.  PBRT_HIP_ERR_DEVICE: a ray's traversal stack ran over, as in
+ * pbrt_hip_intersect_batch.  Nothing is launched on a refusal and the handle stays usable. */
+int pbrt_hip_traverse_probe(PbrtHipScene*, int mode, const PbrtHipRay* rays_cl, uint32_t n_cl, const PbrtHipRay* rays_sh, uint32_t n_sh, const uint32_t* order /* NULL or n_cl + n_sh */,
+                            uint32_t n_heads, uint32_t head_chunk, uint32_t blocks, PbrtHipHit* hits_out /* n_cl */, uint8_t* occluded_out /* n_sh */);
 
 #ifdef __cplusplus
 }

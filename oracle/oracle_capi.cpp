@@ -909,6 +909,26 @@ int oracle_occluded_batch_stats(OracleScene* s, const OracleRay* rays, uint8_t* 
 int oracle_occluded_batch(OracleScene* s, const OracleRay* rays, uint8_t* out, uint64_t n) {
     return oracle_occluded_batch_stats(s, rays, out, n, nullptr, 0);
 }
+// Per ray, what the counters of TraversalStats (oracle_scene.hpp) say about its walk: ORACLE_RAY_STATS_STRIDE u32 each —
+// [0] the device-style stack peak, scene-level and object-level entries together, [1] at scene level alone, [2] the peak under the counting rows' any-hit pushes, [3] the peak of the
+// reference's own to_visit, [4] candidate hits that need an alpha mask's verdict, [5] instance records entered, [6] ORC_SEQ_* bits, [7] nodes visited, [8] primitive tests,
+// [9] 1 where the ray hit / was occluded.  any_hit: intersect_p instead of intersect.  The results themselves are oracle_intersect_batch's.
+#define ORACLE_RAY_STATS_STRIDE 10
+int oracle_ray_stats_batch(OracleScene* s, const OracleRay* rays, uint64_t n, int any_hit, uint32_t* out) {
+    if (!s || (!rays && n) || (!out && n)) return -1;
+    if (!s->built) { s->err = "build_accel first"; return -2; }
+    for (uint64_t i = 0; i < n; i++) {
+        Ray r(V3(rays[i].o[0], rays[i].o[1], rays[i].o[2]), V3(rays[i].d[0], rays[i].d[1], rays[i].d[2]), rays[i].t_max, rays[i].time);
+        TraversalStats ts;
+        bool found;
+        if (any_hit) found = s->sc.intersect_p(r, &ts);
+        else { uint32_t prim = 0xffffffffu; TriHit h{0, 0, 0, 0}; found = s->sc.intersect(r, prim, h, &ts); }
+        uint32_t* o = out + ORACLE_RAY_STATS_STRIDE * i;
+        o[0] = ts.dev_peak; o[1] = ts.dev_peak_scene; o[2] = ts.dev_peak_count; o[3] = ts.ref_peak; o[4] = ts.alpha_candidates; o[5] = ts.inst_entered; o[6] = ts.leaf_seq;
+        o[7] = (uint32_t)ts.nodes_visited; o[8] = (uint32_t)ts.tri_tests; o[9] = found ? 1u : 0u;
+    }
+    return 0;
+}
 
 // The Sobol tables given must hold every dimension a path of max_depth draws (5 camera dimensions, then at most 8 per vertex) and the VdC
 // matrix for the sample bounds' log2 resolution; max_depth < 0 asks for the camera dimensions only.  The product's check_render_args keeps the

@@ -208,7 +208,27 @@ inline Bounds3 transform_bounds(const Transform& t, const Bounds3& b) {  // tran
         .union_p(t.point(V3(b.pmax.x, b.pmax.y, b.pmax.z)));
 }
 
-struct TraversalStats { uint64_t nodes_visited = 0, tri_tests = 0, rays = 0; };
+// Besides the three tallies: what a test needs to know which edges of the DEVICE's walk (csrc/traverse.h) a ray reaches.  Counters only, no result reads them.
+//  dev_sp / dev_peak / dev_peak_scene: the height of the device's traversal stack.  The device tests both children's boxes when their parent is visited and pushes the far child only
+//    when BOTH boxes were hit (`push` in traverse.h); the reference pushes the far child unconditionally and tests its box when it is popped.  An object's entries lie above the
+//    scene-level ones on one stack, so dev_sp runs on through the recursion into an instance; dev_peak_scene is the peak outside any instance.
+//  dev_sp_count / dev_peak_count: the same for an any-hit ray under the counting rows, which also push a far child whose box was missed whenever the near child's was hit.
+//  ref_peak: the peak of the reference's own to_visit (per aggregate: the recursion into an instance has a stack of its own).
+//  alpha_candidates: candidate hits (past the geometric test and the degenerate-triangle test) on a triangle whose mesh has an alpha or shadow-alpha texture: the device's alpha phase.
+//  inst_entered: instance records entered.  depth: 0 at scene level, 1 inside an instance.  leaf_seq: ORC_SEQ_* bits of the leaf-record sequences and instance forms met.
+enum : uint32_t { ORC_SEQ_INST_THEN_PRIM = 1u, ORC_SEQ_PRIM_THEN_INST = 2u, ORC_SEQ_INST_LAST = 4u, ORC_SEQ_INST_NOT_LAST = 8u, ORC_SEQ_INST_SINGLE = 16u, ORC_SEQ_INST_ROOT_LEAF = 32u,
+                ORC_SEQ_INST_TREE = 64u, ORC_SEQ_QUADRIC_WITH_INST = 128u, ORC_SEQ_HIT_IN_INST_THEN_NEARER = 256u, ORC_SEQ_ALPHA_LAST = 512u, ORC_SEQ_ALPHA_NOT_LAST = 1024u };
+struct TraversalStats {
+    uint64_t nodes_visited = 0, tri_tests = 0, rays = 0;
+    uint32_t dev_sp = 0, dev_peak = 0, dev_peak_scene = 0, dev_sp_count = 0, dev_peak_count = 0, ref_peak = 0, alpha_candidates = 0, inst_entered = 0, depth = 0, leaf_seq = 0;
+    bool hit_in_inst = false, alpha_is_last = false;
+    void dev_push(bool both, bool near_only) {
+        if (both) { dev_sp++; if (dev_sp > dev_peak) dev_peak = dev_sp; if (depth == 0 && dev_sp > dev_peak_scene) dev_peak_scene = dev_sp; }
+        if (both || near_only) { dev_sp_count++; if (dev_sp_count > dev_peak_count) dev_peak_count = dev_sp_count; }
+    }
+    void dev_pop(uint8_t f) { if (f & 1) dev_sp--; if (f & 2) dev_sp_count--; }
+    void ref_push(size_t to_visit) { if (to_visit > ref_peak) ref_peak = (uint32_t)to_visit; }
+};
 
 struct Scene {
     // geometry (all meshes concatenated)
@@ -408,7 +428,7 @@ struct Scene {
     // ---- Triangle::intersect up to the accept decision (triangle.rs:438-575 / 731-861).
     // Returns true and fills `h` iff the reference would return Some(..)/true, given constant alpha textures.
     // `test_alpha` mirrors test_alpha_texture; `shadow` selects intersect_p's extra shadow-alpha mask.
-    bool tri_intersect(const Ray& r, uint32_t prim, bool test_alpha, bool shadow, TriHit& h) const {
+    bool tri_intersect(const Ray& r, uint32_t prim, bool test_alpha, bool shadow, TriHit& h, TraversalStats* st = nullptr) const {
         V3 p0 = P[idx[3 * prim]], p1 = P[idx[3 * prim + 1]], p2 = P[idx[3 * prim + 2]];
         V3 p0t = p0 - r.o, p1t = p1 - r.o, p2t = p2 - r.o;
         int kz = max_dimension(vabs(r.d));
@@ -458,6 +478,7 @@ struct Scene {
             if (tri_is_bogus(prim)) return false;
         }
         if (test_alpha) {
+            if (st && (m.alpha_tex >= 0 || m.shadow_alpha_tex >= 0)) { st->alpha_candidates++; st->leaf_seq |= st->alpha_is_last ? ORC_SEQ_ALPHA_LAST : ORC_SEQ_ALPHA_NOT_LAST; }
             if (m.alpha_tex >= 0 || (shadow && m.shadow_alpha_tex >= 0)) {
                 // isect_local: p_hit, uv_hit, no differentials (SurfaceInteraction::new leaves der zero)
                 V2 uv[3]; tri_uvs(prim, uv);
@@ -524,16 +545,21 @@ struct Scene {
             TriHit h;
             if (st) st->tri_tests++;
             const Mesh& mm = mesh_of(ref);
-            const bool hit = mm.sphere >= 0 ? sphere_intersect(r, spheres[(size_t)mm.sphere], h) : (mm.hyper >= 0 ? hyperboloid_intersect(r, hyperboloids[(size_t)mm.hyper], h) : (mm.quadric >= 0 ? quadric_intersect(r, quadrics[(size_t)mm.quadric], h) : tri_intersect(r, ref, true, false, h)));
-            if (hit) { r.t_max = h.t; prim_out = ref; hit_out = h; return true; }
+            const bool hit = mm.sphere >= 0 ? sphere_intersect(r, spheres[(size_t)mm.sphere], h) : (mm.hyper >= 0 ? hyperboloid_intersect(r, hyperboloids[(size_t)mm.hyper], h) : (mm.quadric >= 0 ? quadric_intersect(r, quadrics[(size_t)mm.quadric], h) : tri_intersect(r, ref, true, false, h, st)));
+            if (hit) {
+                if (st && st->depth == 0 && st->hit_in_inst) st->leaf_seq |= ORC_SEQ_HIT_IN_INST_THEN_NEARER;
+                r.t_max = h.t; prim_out = ref; hit_out = h; return true;
+            }
             return false;
         }
         const uint32_t ii = ref & ~ORC_INST_BIT;
         const Instance& in = instances[ii]; const Object& ob = objects[in.object];
         Ray ray = transform_ray(in.i2w.inv(), r);
         bool hit;
+        if (st) { st->inst_entered++; st->depth++; st->leaf_seq |= inst_form(ob); }
         if (ob.tri1 - ob.tri0 == 1) hit = prim_intersect(ray, ob.tri0, prim_out, hit_out, st);
         else hit = intersect_in(ob.nodes, ob.ordered_prims, ray, prim_out, hit_out, st);
+        if (st) { st->depth--; if (hit) st->hit_in_inst = true; }
         if (!hit) return false;
         r.t_max = ray.t_max;
         hit_out.inst = ii + 1;
@@ -545,12 +571,40 @@ struct Scene {
             if (mesh_of(ref).sphere >= 0) return sphere_intersect(r, spheres[(size_t)mesh_of(ref).sphere], h);
             if (mesh_of(ref).hyper >= 0) return hyperboloid_intersect(r, hyperboloids[(size_t)mesh_of(ref).hyper], h);
             if (mesh_of(ref).quadric >= 0) return quadric_intersect(r, quadrics[(size_t)mesh_of(ref).quadric], h);
-            return tri_intersect(r, ref, true, true, h);
+            return tri_intersect(r, ref, true, true, h, st);
         }
         const Instance& in = instances[ref & ~ORC_INST_BIT]; const Object& ob = objects[in.object];
         Ray ray = transform_ray(in.i2w.inv(), r);
-        if (ob.tri1 - ob.tri0 == 1) return prim_intersect_p(ray, ob.tri0, st);
-        return intersect_p_in(ob.nodes, ob.ordered_prims, ray, st);
+        if (st) { st->inst_entered++; st->depth++; st->leaf_seq |= inst_form(ob); }
+        const bool hit = (ob.tri1 - ob.tri0 == 1) ? prim_intersect_p(ray, ob.tri0, st) : intersect_p_in(ob.nodes, ob.ordered_prims, ray, st);
+        if (st) st->depth--;
+        return hit;
+    }
+    // (counters) which of the device's three instance forms an object is: its lone primitive, an aggregate that is one leaf, a tree
+    static uint32_t inst_form(const Object& ob) {
+        if (ob.tri1 - ob.tri0 == 1) return ORC_SEQ_INST_SINGLE;
+        return (!ob.nodes.empty() && ob.nodes[0].n_primitives > 0) ? ORC_SEQ_INST_ROOT_LEAF : ORC_SEQ_INST_TREE;
+    }
+    // (counters) the record sequences of a leaf about to be tested from record `first` on
+    void note_leaf(const std::vector<uint32_t>& ordered_prims, const LinearBVHNode& node, uint32_t i, TraversalStats* st) const {
+        const uint32_t ref = ordered_prims[node.offset + i];
+        const bool last = i + 1 == node.n_primitives;
+        st->alpha_is_last = last;
+        if (ref & ORC_INST_BIT) {
+            st->leaf_seq |= last ? ORC_SEQ_INST_LAST : ORC_SEQ_INST_NOT_LAST;
+            if (!last && !(ordered_prims[node.offset + i + 1] & ORC_INST_BIT)) st->leaf_seq |= ORC_SEQ_INST_THEN_PRIM;
+            if (i > 0 && !(ordered_prims[node.offset + i - 1] & ORC_INST_BIT)) st->leaf_seq |= ORC_SEQ_PRIM_THEN_INST;
+            for (uint32_t k = 0; k < node.n_primitives; k++) {
+                const uint32_t o = ordered_prims[node.offset + k];
+                if (!(o & ORC_INST_BIT) && (mesh_of(o).sphere >= 0 || mesh_of(o).hyper >= 0 || mesh_of(o).quadric >= 0)) st->leaf_seq |= ORC_SEQ_QUADRIC_WITH_INST;
+            }
+        }
+    }
+    // (counters) the device's view of an interior node just entered: both children's boxes against the ray as it is now.  Returns the flags the pushed far child carries.
+    uint8_t note_interior(const std::vector<LinearBVHNode>& nodes, size_t near_i, size_t far_i, const Ray& r, V3 inv_dir, const int neg[3], TraversalStats* st) const {
+        const bool nh = box_hit(nodes[near_i].bounds, r, inv_dir, neg), fh = box_hit(nodes[far_i].bounds, r, inv_dir, neg);
+        st->dev_push(nh && fh, nh && !fh);
+        return (uint8_t)((nh && fh ? 1 : 0) | (nh ? 2 : 0));
     }
 
     // ---- BVHAccel::intersect (bvh/mod.rs:173-226)
@@ -562,22 +616,29 @@ struct Scene {
         int neg[3] = {inv_dir.x < 0.0f ? 1 : 0, inv_dir.y < 0.0f ? 1 : 0, inv_dir.z < 0.0f ? 1 : 0};
         size_t to_visit = 0, cur = 0;
         size_t stack[64];
+        uint8_t dev_flags[64];   // (counters) per entry of `stack`: what the device's stack holds for it
         for (;;) {
             const LinearBVHNode& node = nodes[cur];
             if (st) st->nodes_visited++;
             if (box_hit(node.bounds, r, inv_dir, neg)) {
                 if (node.n_primitives > 0) {
-                    for (uint32_t i = 0; i < node.n_primitives; i++)
+                    for (uint32_t i = 0; i < node.n_primitives; i++) {
+                        if (st) note_leaf(ordered_prims, node, i, st);
                         if (prim_intersect(r, ordered_prims[node.offset + i], prim_out, hit_out, st)) any = true;
+                    }
                     if (to_visit == 0) break;
                     cur = stack[--to_visit];
+                    if (st) st->dev_pop(dev_flags[to_visit]);
                 } else {
+                    const size_t near_i = neg[node.axis] == 1 ? node.offset : cur + 1, far_i = neg[node.axis] == 1 ? cur + 1 : node.offset;
+                    if (st) { dev_flags[to_visit] = note_interior(nodes, near_i, far_i, r, inv_dir, neg, st); st->ref_push(to_visit + 1); }
                     if (neg[node.axis] == 1) { stack[to_visit++] = cur + 1; cur = node.offset; }
                     else { stack[to_visit++] = node.offset; cur = cur + 1; }
                 }
             } else {
                 if (to_visit == 0) break;
                 cur = stack[--to_visit];
+                if (st) st->dev_pop(dev_flags[to_visit]);
             }
         }
         return any;
@@ -594,22 +655,29 @@ struct Scene {
         int neg[3] = {inv_dir.x < 0.0f ? 1 : 0, inv_dir.y < 0.0f ? 1 : 0, inv_dir.z < 0.0f ? 1 : 0};
         size_t to_visit = 0, cur = 0;
         size_t stack[64];
+        uint8_t dev_flags[64];   // (counters) as in intersect_in
         for (;;) {
             const LinearBVHNode& node = nodes[cur];
             if (st) st->nodes_visited++;
             if (box_hit(node.bounds, r, inv_dir, neg)) {
                 if (node.n_primitives > 0) {
-                    for (uint32_t i = 0; i < node.n_primitives; i++)
+                    for (uint32_t i = 0; i < node.n_primitives; i++) {
+                        if (st) note_leaf(ordered_prims, node, i, st);
                         if (prim_intersect_p(r, ordered_prims[node.offset + i], st)) return true;
+                    }
                     if (to_visit == 0) break;
                     cur = stack[--to_visit];
+                    if (st) st->dev_pop(dev_flags[to_visit]);
                 } else {
+                    const size_t near_i = neg[node.axis] == 1 ? node.offset : cur + 1, far_i = neg[node.axis] == 1 ? cur + 1 : node.offset;
+                    if (st) { dev_flags[to_visit] = note_interior(nodes, near_i, far_i, r, inv_dir, neg, st); st->ref_push(to_visit + 1); }
                     if (neg[node.axis] == 1) { stack[to_visit++] = cur + 1; cur = node.offset; }
                     else { stack[to_visit++] = node.offset; cur = cur + 1; }
                 }
             } else {
                 if (to_visit == 0) break;
                 cur = stack[--to_visit];
+                if (st) st->dev_pop(dev_flags[to_visit]);
             }
         }
         return false;

@@ -1,5 +1,5 @@
 // Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_sphere_light_probe_batch, pbrt_hip_raysort_probe, pbrt_hip_texture_probe_batch,
-// pbrt_hip_bump_probe_batch): the device's BSDF, sampler, light and texture code and the ray binning between wavefront rounds on explicit inputs.
+// pbrt_hip_bump_probe_batch, pbrt_hip_traverse_probe): the device's BSDF, sampler, light and texture code, the ray binning between wavefront rounds and the traversal kernel's queue on explicit inputs.
 // Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
@@ -9,6 +9,7 @@
 #include "texture.h"
 #include "sphere_light.h"
 #include <cstring>
+#include <vector>
 
 namespace ph {
 
@@ -414,6 +415,67 @@ int pbrt_hip_raysort_probe(PbrtHipScene* s, uint32_t n_cl, uint32_t n_sh, const 
     if (n) PH_CHECK(s, hipMemcpyAsync(order_out, d + o_order, n * 4, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));   // (`counts` and the caller's arrays are pageable: the copies above have left them by now)
     return PBRT_HIP_OK;
+    });
+}
+
+// The traversal kernel on an explicit queue: TravParams filled as run_round (wavefront.hip) fills them — counts in device memory, queue heads, head chunk, order — and the grid the caller
+// names.  No traversal logic here: the kernel row is the scene's (launch_traverse_kernel, pick_shape).
+#define PH_TRAVERSE_PROBE_HEADS 8u   // the heads buffer of a probe: what a path round uses (PathPlan::n_heads)
+int pbrt_hip_traverse_probe(PbrtHipScene* s, int mode, const PbrtHipRay* rays_cl, uint32_t n_cl, const PbrtHipRay* rays_sh, uint32_t n_sh, const uint32_t* order, uint32_t n_heads,
+                            uint32_t head_chunk, uint32_t blocks, PbrtHipHit* hits_out, uint8_t* occluded_out) {
+    return ph_guard(s, "pbrt_hip_traverse_probe", [&]() -> int {
+    if (!s) return PBRT_HIP_ERR_INVALID_ARG;
+    if ((n_cl && (!rays_cl || !hits_out)) || (n_sh && (!rays_sh || !occluded_out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: null array with a non-zero count");
+    if (mode < 0 || mode > 2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: mode must be 0 (closest hit), 1 (any hit) or 2 (mixed)");
+    if ((mode == 0 && n_sh) || (mode == 1 && n_cl)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: mode 0 takes closest-hit rays only (n_sh = 0), mode 1 any-hit rays only (n_cl = 0)");
+    const uint64_t n = (uint64_t)n_cl + n_sh;
+    if (n >= 0x7FFF0000ull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: more rays than a round's queues hold");
+    if (n_heads == 0 || n_heads > PH_TRAVERSE_PROBE_HEADS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: n_heads must be 1 .. 8");
+    if (n_heads > 1 && (head_chunk == 0 || head_chunk % PH_BATCH != 0)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: with several heads head_chunk must be a non-zero multiple of 64");
+    if (blocks == 0) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: blocks must be at least 1");
+    if (order) {   // a permutation of 0 .. n: any other list would leave a ray untraced or trace one twice
+        std::vector<bool> seen(n, false);
+        for (uint64_t i = 0; i < n; i++) {
+            if (order[i] >= n || seen[order[i]]) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: order is not a permutation of the queue positions");
+            seen[order[i]] = true;
+        }
+    }
+    if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "traverse_probe: call pbrt_hip_build_accel first");
+    PH_CHECK(s, hipSetDevice(s->device));
+    int rc;
+    if ((rc = upload_scene(s))) return rc;
+    if ((rc = ensure_traversal_workspace(s))) return rc;
+    if (blocks > s->trav_blocks) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: blocks exceeds the resident grid (the spill region is sized for it)");
+    const size_t ray_b = sizeof(PbrtHipRay), hit_b = sizeof(PbrtHipHit);
+    const size_t o_cl = 0, o_sh = o_cl + up256((size_t)n_cl * ray_b), o_n = o_sh + up256((size_t)n_sh * ray_b), o_heads = o_n + 256, o_order = o_heads + up256(PH_TRAVERSE_PROBE_HEADS * 64),
+                 o_hits = o_order + up256((size_t)n * 4), o_occ = o_hits + up256((size_t)n_cl * hit_b), total = o_occ + up256((size_t)n_sh) + 256;
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    const uint32_t counts[2] = {n_cl, n_sh};
+    if (n_cl) PH_CHECK(s, hipMemcpyAsync(d + o_cl, rays_cl, (size_t)n_cl * ray_b, hipMemcpyHostToDevice, s->stream));
+    if (n_sh) PH_CHECK(s, hipMemcpyAsync(d + o_sh, rays_sh, (size_t)n_sh * ray_b, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_n, counts, 8, hipMemcpyHostToDevice, s->stream));
+    if (order && n) PH_CHECK(s, hipMemcpyAsync(d + o_order, order, (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemsetAsync(d + o_heads, 0, PH_TRAVERSE_PROBE_HEADS * 64, s->stream));
+    PH_CHECK(s, hipMemsetAsync(s->d_counter.p, 0, 4, s->stream));
+    // results start as 0xFF bytes: a ray the queue never served is told from every answer the kernel writes
+    if (n_cl) PH_CHECK(s, hipMemsetAsync(d + o_hits, 0xFF, (size_t)n_cl * hit_b, s->stream));
+    if (n_sh) PH_CHECK(s, hipMemsetAsync(d + o_occ, 0xFF, (size_t)n_sh, s->stream));
+    ph::TravParams tp{};
+    const uint32_t* d_n = (const uint32_t*)(d + o_n);
+    tp.n = 0; tp.counter = (uint32_t*)s->d_counter.p;
+    if (mode == 1) { tp.rays = (const ph::RayIn*)(d + o_sh); tp.out = d + o_occ; tp.n_ptr = d_n + 1; }
+    else { tp.rays = (const ph::RayIn*)(d + o_cl); tp.out = d + o_hits; tp.n_ptr = d_n; }
+    if (mode == 2) { tp.rays2 = (const ph::RayIn*)(d + o_sh); tp.out2 = (uint8_t*)(d + o_occ); tp.n2_ptr = d_n + 1; }
+    tp.heads = (uint32_t*)(d + o_heads); tp.n_heads = n_heads; tp.head_chunk = head_chunk;
+    tp.order = order ? (const uint32_t*)(d + o_order) : nullptr;
+    launch_traverse_kernel(s, mode, blocks, tp);
+    PH_CHECK(s, hipGetLastError());
+    if (n_cl) PH_CHECK(s, hipMemcpyAsync(hits_out, d + o_hits, (size_t)n_cl * hit_b, hipMemcpyDeviceToHost, s->stream));
+    if (n_sh) PH_CHECK(s, hipMemcpyAsync(occluded_out, d + o_occ, (size_t)n_sh, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));   // (`counts` and the caller's arrays are pageable: the copies above have left them by now)
+    return traversal_overflow_check(s);
     });
 }
 

@@ -168,6 +168,7 @@ class Binding:
             "bump_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
             "set_path_sphere_lights": (C.c_int, [vp, C.c_int]),
             "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
+            "traverse_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -763,6 +764,19 @@ class Scene:
         out = np.zeros((n, 6), np.float32)
         self._chk(self.b.fn("bump_probe_batch")(self.h, texture, variant, n, _ptr(inp, C.c_float), _ptr(out, C.c_float)))
         return out
+
+    def traverse_probe(self, mode, rays_cl=None, rays_sh=None, order=None, n_heads=1, head_chunk=49152, blocks=1):
+        """The traversal kernel on an explicit queue (pbrt_hip_traverse_probe).  mode 0: rays_cl, 1: rays_sh, 2: both in one launch.  Returns (hits, occluded)."""
+        rays_cl = np.ascontiguousarray(rays_cl if rays_cl is not None else [], dtype=RAY_DTYPE)
+        rays_sh = np.ascontiguousarray(rays_sh if rays_sh is not None else [], dtype=RAY_DTYPE)
+        hits = np.zeros(len(rays_cl), HIT_DTYPE); occ = np.zeros(len(rays_sh), np.uint8)
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            assert len(order) == len(rays_cl) + len(rays_sh)
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        self._chk(self.b.fn("traverse_probe")(self.h, mode, ptr(rays_cl), len(rays_cl), ptr(rays_sh), len(rays_sh), order.ctypes.data if order is not None else None,
+                                              n_heads, head_chunk, blocks, ptr(hits), ptr(occ)))
+        return hits, occ
 
     def mipmap_pyramid(self, mipmap):
         """The pyramid the host built: list of (h, w, 3) float32 arrays, finest first (row 0 = t 0 = the image's bottom row)."""

@@ -62,6 +62,7 @@ def oracle_binding():
         L.oracle_spatial_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.oracle_spatial_voxel.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.oracle_texture_probe_work.argtypes = [vp, C.c_uint32, C.c_uint64, fp, C.POINTER(C.c_uint64)]
+        L.oracle_ray_stats_batch.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
         _binding = b
     return _binding
 
@@ -87,6 +88,21 @@ class OracleScene(pbrt_hip.Scene):
         st = TraversalStats()
         self._chk(self.b.lib.oracle_occluded_batch_stats(self.h, rays.ctypes.data, out.ctypes.data, len(rays), C.byref(st), threads))
         return out, st
+
+    RAY_STATS_DTYPE = np.dtype([("dev_peak", "<u4"), ("dev_peak_scene", "<u4"), ("dev_peak_count", "<u4"), ("ref_peak", "<u4"), ("alpha_candidates", "<u4"), ("inst_entered", "<u4"),
+                                ("leaf_seq", "<u4"), ("nodes_visited", "<u4"), ("tri_tests", "<u4"), ("found", "<u4")])
+    # leaf_seq bits (oracle_scene.hpp, ORC_SEQ_*)
+    SEQ_INST_THEN_PRIM, SEQ_PRIM_THEN_INST, SEQ_INST_LAST, SEQ_INST_NOT_LAST, SEQ_INST_SINGLE, SEQ_INST_ROOT_LEAF, SEQ_INST_TREE, SEQ_QUADRIC_WITH_INST = 1, 2, 4, 8, 16, 32, 64, 128
+    SEQ_HIT_IN_INST_THEN_NEARER, SEQ_ALPHA_LAST, SEQ_ALPHA_NOT_LAST = 256, 512, 1024
+
+    def ray_stats_batch(self, rays, any_hit=False):
+        """Per ray, the counters of the oracle's walk (oracle_ray_stats_batch): the stack height the device would reach (dev_peak: scene-level and object-level entries together,
+        dev_peak_scene: scene level alone, dev_peak_count: an any-hit ray under the counting rows), the reference's own to_visit peak, alpha-mask candidates, instances entered,
+        the SEQ_* bits of the leaf-record sequences met, nodes visited, primitive tests, and whether it hit."""
+        rays = np.ascontiguousarray(rays, dtype=pbrt_hip.RAY_DTYPE)
+        out = np.zeros(len(rays), self.RAY_STATS_DTYPE)
+        self._chk(self.b.lib.oracle_ray_stats_batch(self.h, rays.ctypes.data, len(rays), 1 if any_hit else 0, out.ctypes.data))
+        return out
 
     def render_path_ex(self, max_depth=5, rr_threshold=1.0, light_strategy=2, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1, threads=0,
                        count_traversal=False):
