@@ -168,7 +168,7 @@ int pbrt_hip_add_instance(PbrtHipScene*, uint32_t object_id, const float instanc
  *   pbrt_hip_add_quadric      kind 0 Cylinder::new (cylinder.rs:21-42; a, b = zmin, zmax), 1 Cone::new (cone.rs:21-40; a = height), 2 Paraboloid::new (paraboloid.rs:21-42;
  *                             a, b = zmin, zmax), 3 Disk::new (disk.rs:21-40; a = height, b = innerradius)
  * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: a quadric between object_begin and object_end; a quadric right after pbrt_hip_add_light_diffuse_area lights that no mesh
- * has claimed (it would be the area light's shape; a sphere light is made by pbrt_hip_add_sphere_light, the other quadrics' Shape::sample is not provided); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a
+ * has claimed (it would be the area light's shape; a sphere light is made by pbrt_hip_add_sphere_light, a cylinder or disk light by pbrt_hip_add_quadric_light; the reference's Shape::sample of the other three is todo!()); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a
  * quadric.  Scene-level quadrics and object instances share a scene freely (instanced triangle objects, single-primitive and empty ones included; definitions that no instance
  * uses are ignored, as in any instanced scene): a quadric stands in the scene-level tree next to the instances and is tested in its place in its leaf's order.  One leftover
  * refusal, with no technical reason and kept only because older tests pin it: pbrt_hip_build_accel returns PBRT_HIP_ERR_UNSUPPORTED for a scene that holds a quadric and object
@@ -195,7 +195,7 @@ int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const f
  * default there (core/src/geometry/shape.rs:86-107, the counterpart of sample_solid_angle's inside branch and what upstream pbrt-v3 does) — the ray hit.spawn_ray(wi) against the cut
  * sphere, alpha ignored, distance^2 / (|n . -wi| * area), 0 for a miss or an infinite value.  The batch intersection entry points treat the sphere as ordinary geometry.
  * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: between object_begin and object_end, as for any quadric; while pbrt_hip_add_light_diffuse_area lights that no mesh has claimed are pending.
- * The other five quadrics cannot be lights.  The pbrt_hip_render front end makes this call for Shape "sphere" under AreaLightSource "diffuse" when run with --quadrics (without the
+ * A cylinder or a disk becomes a light through pbrt_hip_add_quadric_light (below); cone, paraboloid and hyperboloid cannot be lights.  The pbrt_hip_render front end makes this call for Shape "sphere" under AreaLightSource "diffuse" when run with --quadrics (without the
  * option it refuses the six quadric Shape directives), and refuses such a scene under Integrator "path" itself unless it is also run with --path-sphere-lights. */
 int pbrt_hip_add_sphere_light(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], float radius, float z_min, float z_max, float phi_max_deg,
                               uint32_t material_id, uint32_t flags, const float L_rgb[3], int two_sided);
@@ -205,6 +205,20 @@ int pbrt_hip_add_sphere_light(PbrtHipScene*, const float o2w_m[16], const float 
  * sample-record bands.  A scene without a sphere light launches the same kernels whatever the switch says.  A sphere light draws the 5 sampler dimensions per vertex of any
  * non-delta light.  PBRT_HIP_ERR_INVALID_ARG: null handle. */
 int pbrt_hip_set_path_sphere_lights(PbrtHipScene*, int on);
+/* A cylinder (kind 0) or a disk (kind 3) that is the shape of a DiffuseAreaLight: pbrt_hip_add_quadric with the same arguments plus ONE light, numbered in call order among the
+ * add_light_* calls, with radiance L_rgb and `two_sided`.  area = Cylinder::area `(z_max - z_min) * radius * phi_max` (cylinder.rs:313-315) or Disk::area
+ * `phi_max * 0.5 * (radius^2 - inner_radius^2)` (disk.rs:205-207) of the constructor's values, whatever the transform scales.  Both shapes leave Shape::sample_solid_angle and
+ * Shape::pdf_solid_angle to the trait's defaults (core/src/geometry/shape.rs:64-107): sample_li draws Disk::sample (disk.rs:214-234) / Cylinder::sample (cylinder.rs:322-348) — uniform
+ * over the FULL shape's area; the disk's sample ignores inner_radius and phi_max, so a point may land on the part that is cut away, as in the reference — and turns 1/area into a
+ * solid-angle pdf, 0 (no sample) for a zero-length direction or an infinite value; pdf_li intersects spawn_ray(ref, wi) with the shape itself, cuts included, 0 for a miss.  The
+ * sampled normal is flipped for reverse orientation only; a ray that meets the shape sees L on the side its hit normal faces (reverse orientation XOR the transform's handedness),
+ * on both sides if two_sided.  The reference has an answer at every reference point, so pbrt_hip_render_path, _tiles_device, multi-device handles, chunks and bands render such a
+ * scene with no switch, and so do pbrt_hip_render_whitted, _devices and _tiles_device.  pbrt_hip_set_path_sphere_lights keeps its meaning for spheres only: a scene that also holds
+ * a sphere light is still refused by the path integrator on a handle whose switch is off.
+ * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: kind 1 (cone) or 2 (paraboloid), whose Shape::sample in the reference is todo!() (as is the hyperboloid's); between object_begin
+ * and object_end; while pbrt_hip_add_light_diffuse_area lights that no mesh has claimed are pending.  PBRT_HIP_ERR_INVALID_ARG: any other kind, a null argument, an unknown material. */
+int pbrt_hip_add_quadric_light(PbrtHipScene*, int kind, const float o2w_m[16], const float o2w_minv[16], float radius, float a, float b, float phi_max_deg,
+                               uint32_t material_id, uint32_t flags, const float L_rgb[3], int two_sided);
 
 /* Alpha masks: the float textures behind a mesh's `alpha` / `shadowalpha` parameters (TriangleMesh::alpha_mask, shadow_alpha_mask: shapes/src/triangle.rs:291-312),
  * for the mesh added last; 0xFFFFFFFF keeps the constant given to add_mesh.  A candidate hit is rejected where the texture evaluates to exactly 0 at the hit's
@@ -493,16 +507,17 @@ int pbrt_hip_sampler_value_batch(PbrtHipScene*, uint64_t n, const int* xy /*2n*/
  *   op 2  out[0..2] = Light::le of a ray with direction wi
  * variant 0: the code of scenes with textures (radiance, projection and goniometric maps are read); variant 1: the code of scenes without, PBRT_HIP_ERR_UNSUPPORTED for a light that
  * holds such a map; variant 2: sample_li as pbrt_hip_render_whitted's light loop calls it (op 0 only), the one variant that admits a light made by pbrt_hip_add_sphere_light
- * (PBRT_HIP_ERR_UNSUPPORTED under 0 and 1, as the path integrator refuses such a scene).
+ * or pbrt_hip_add_quadric_light (PBRT_HIP_ERR_UNSUPPORTED under 0 and 1: those are the forms whose area lights are triangles).
  * PBRT_HIP_ERR_INVALID_ARG: unknown light, op or variant; op 1 or 2 under variant 2; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built; an area light
  * without its mesh.  Nothing is launched on a refusal. */
 #define PBRT_HIP_LIGHT_PROBE_STRIDE 28
 int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int variant, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/,
                                float* out /*28n*/);
-/* pbrt_hip_sphere_light_probe_batch: a light made by pbrt_hip_add_sphere_light as the path integrator's sphere-light shade pass calls it.  op 0: Light::sample_li — the function
- * variant 2 of pbrt_hip_light_probe_batch runs; op 1: out[0] = Light::pdf_li(ref, wi), Sphere::pdf_solid_angle as described at pbrt_hip_add_sphere_light.  Inputs and the 28-float
- * output layout are pbrt_hip_light_probe_batch's; the handle's pbrt_hip_set_path_sphere_lights switch is not consulted.  PBRT_HIP_ERR_UNSUPPORTED: the light is not a spherical
- * area light.  PBRT_HIP_ERR_INVALID_ARG: unknown light or op; a null handle; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built. */
+/* pbrt_hip_sphere_light_probe_batch: a light made by pbrt_hip_add_sphere_light or pbrt_hip_add_quadric_light as the path integrator's sphere-light shade pass calls it.  op 0:
+ * Light::sample_li — the function variant 2 of pbrt_hip_light_probe_batch runs; op 1: out[0] = Light::pdf_li(ref, wi), Sphere::pdf_solid_angle as described at
+ * pbrt_hip_add_sphere_light, the trait's default Shape::pdf_solid_angle for a disk or a cylinder.  Inputs and the 28-float
+ * output layout are pbrt_hip_light_probe_batch's; the handle's pbrt_hip_set_path_sphere_lights switch is not consulted.  PBRT_HIP_ERR_UNSUPPORTED: the light's shape is not
+ * a quadric.  PBRT_HIP_ERR_INVALID_ARG: unknown light or op; a null handle; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built. */
 int pbrt_hip_sphere_light_probe_batch(PbrtHipScene*, uint32_t light, int op, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/, float* out /*28n*/);
 /* pbrt_hip_raysort_probe: the ray binning between wavefront rounds (csrc/raysort.h) on explicit keys, through the launch the path integrator's rounds use.  keys_cl / keys_sh = the
  * bin keys (< 4096) of n_cl closest-hit and n_sh any-hit rays; the keys and the two counts are uploaded and read from device memory, as in a render.  order_out[0 .. n_cl + n_sh) =

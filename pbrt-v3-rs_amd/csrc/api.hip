@@ -1075,6 +1075,31 @@ int pbrt_hip_add_quadric(PbrtHipScene* s, int kind, const float o2w_m[16], const
     return add_quadric_common(s, "add_quadric", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
     });
 }
+// pbrt_hip_add_quadric plus the DiffuseAreaLight whose shape is that cylinder or disk: one LightRec in call order, bound to the shape's primitive slot.  The reference's
+// Cone, Paraboloid and Hyperboloid ::sample are todo!(): such a light would panic at its first sample
+int pbrt_hip_add_quadric_light(PbrtHipScene* s, int kind, const float o2w_m[16], const float o2w_minv[16], float radius, float a, float b, float phi_max_deg, uint32_t material_id,
+                               uint32_t flags, const float L_rgb[3], int two_sided) {
+    return ph_guard(s, "pbrt_hip_add_quadric_light", [&]() -> int {
+    if (!s || !o2w_m || !o2w_minv || !L_rgb) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_quadric_light: null argument");
+    if (kind == PH_Q_CONE || kind == PH_Q_PARABOLOID)
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_quadric_light: a cone or a paraboloid cannot be an area light: the reference's Shape::sample for it is todo!()");
+    if (kind != PH_Q_CYLINDER && kind != PH_Q_DISK) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_quadric_light: kind must be 0 cylinder or 3 disk");
+    if (!s->lights.empty() && s->lights.back().type == PH_L_AREA && s->lights.back().prim == 0xFFFFFFFFu)
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_quadric_light: the diffuse area lights created last have no mesh yet; attach them first (the shape brings its own light)");
+    QuadricRec q{}; float lo[3], hi[3];
+    quadric_rec(kind, radius, a, b, phi_max_deg, q, lo, hi);
+    const int rc = add_quadric_common(s, "add_quadric_light", q, o2w_m, o2w_minv, lo, hi, material_id, flags);
+    if (rc) return rc;
+    LightRec l{}; l.type = PH_L_AREA; l.two_sided = two_sided ? 1 : 0; l.prim = s->meshes.back().tri_base;
+    if (kind == PH_Q_CYLINDER) l.area = (q.z_max - q.z_min) * q.radius * q.phi_max;                        // Cylinder::area (cylinder.rs:313-315)
+    else l.area = q.phi_max * 0.5f * (q.radius * q.radius - q.inner_radius * q.inner_radius);              // Disk::area (disk.rs:205-207)
+    for (int c = 0; c < 3; c++) l.L[c] = L_rgb[c];
+    s->meshes.back().first_light = (int32_t)s->lights.size();
+    s->lights.push_back(l);
+    s->quadric_lights++;
+    return PBRT_HIP_OK;
+    });
+}
 
 // Host-only run of the BVH builder over triangles AND quadric shapes (include/pbrt_hip_host.h), for inspection and tests; needs no GPU.  The shapes go through the same constructors
 // and the same world_bound as the capture calls above.

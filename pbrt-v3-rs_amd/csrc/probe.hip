@@ -102,7 +102,7 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene
         o[0] = le.r; o[1] = le.g; o[2] = le.b;
     }
 }
-// Light::sample_li (op 0) and Light::pdf_li (op 1) as the path integrator's sphere-light shade pass calls them (wavefront.hip, ShadeRowSphereLights): wh_light_sample_li<true> and
+// Light::sample_li (op 0) and Light::pdf_li (op 1) of a light whose shape is a quadric (sphere, disk, cylinder) as the path integrator's sphere-light shade pass calls them (wavefront.hip, ShadeRowSphereLights): wh_light_sample_li<true> and
 // sl_light_pdf_li (sphere_light.h).  Inputs and output layout are light_probe_kernel's.
 __global__ __launch_bounds__(PH_PROBE_BLOCK) void sphere_light_probe_kernel(DeviceScene sc, uint32_t light, int op, uint32_t n, const float* ref_in, const float* u_in, const float* wi_in, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -306,7 +306,7 @@ int pbrt_hip_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, int vari
     if (l.type == PH_L_AREA) {
         if (l.prim >= s->tri_mesh.size()) return set_err(s, PBRT_HIP_ERR_STATE, "light_probe_batch: the area light has no shape yet");
         if ((s->meshes[s->tri_mesh[l.prim]].flags & PH_MESH_QUADRIC) && variant != 2)
-            return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: a spherical area light is sampled by the Whitted light loop alone (variant 2)");
+            return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: a light whose shape is a quadric (a spherical, disk or cylinder area light) is sampled by variant 2, the Whitted light loop's sample_li, alone");
     }
     if (variant == 1 && l.map_mip1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: variant 1 is the code of scenes without textures; this light holds a radiance, projection or goniometric map");
     if (n == 0) return PBRT_HIP_OK;
@@ -344,7 +344,7 @@ int pbrt_hip_sphere_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, u
     if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "sphere_light_probe_batch: build_accel first");
     const LightRec& l = s->lights[light];
     if (l.type != PH_L_AREA || l.prim >= s->tri_mesh.size() || !(s->meshes[s->tri_mesh[l.prim]].flags & PH_MESH_QUADRIC))
-        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "sphere_light_probe_batch: the light is not a spherical area light (pbrt_hip_add_sphere_light); pbrt_hip_light_probe_batch probes the others");
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "sphere_light_probe_batch: the light's shape is not a quadric (a spherical, disk or cylinder area light: pbrt_hip_add_sphere_light, pbrt_hip_add_quadric_light); pbrt_hip_light_probe_batch probes the others");
     if (n == 0) return PBRT_HIP_OK;
     PH_CHECK(s, hipSetDevice(s->device));
     int rc;

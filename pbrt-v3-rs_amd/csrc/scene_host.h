@@ -51,6 +51,7 @@ struct SceneHostState {
     bool general_materials = false;  // some material is not matte: the renderer uses the general BSDF kernel
     bool simple_textures = false;    // every texture program is made of constants, image maps (uv mapping), scale and mix: the texture pass runs its lean instantiation (set at upload)
     std::vector<LightRec> lights;
+    uint32_t quadric_lights = 0;     // lights whose shape is a disk or a cylinder (add_quadric_light): both drivers sample them, the path integrator with no switch (the reference answers at every reference point)
     uint32_t sphere_lights = 0;      // lights whose shape is a sphere (add_sphere_light): the Whitted driver samples them; the path integrator does on a handle with path_sphere_lights set and refuses the scene on any other
     // DiffuseAreaLights of shapes inside an object definition ("Area lights not supported with object instancing", api/src/lib.rs:877-881): the primitives keep their emission,
     // Scene::lights never sees them.  MeshRec::first_light = -2 - index on the host; uploaded behind the scene's lights (DeviceScene::n_lights does not count them).

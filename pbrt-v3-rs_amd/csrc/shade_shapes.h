@@ -28,7 +28,7 @@ struct ShadeRowSky {
     static constexpr bool phi_skip = true, lean_lds = true;
     static constexpr bool sphere_lights = false;
 };
-// The full row where an area light's shape may be a sphere (pbrt_hip_add_sphere_light with pbrt_hip_set_path_sphere_lights on): sample_li, pdf_li and the MIS resolve ask the light's
+// The full row where an area light's shape may be a sphere (pbrt_hip_add_sphere_light with pbrt_hip_set_path_sphere_lights on), a disk or a cylinder (pbrt_hip_add_quadric_light): sample_li, pdf_li and the MIS resolve ask the light's
 // primitive whether it is a quadric (sphere_light.h).  NOT a row of ShadeRows and in no variant of ShadeVariants: wavefront.hip names the one kernel compiled on it next to its
 // launchers and the driver picks it before the table's picker, for such a scene alone, so every other scene launches what pick_shade_variant gives it.
 struct ShadeRowSphereLights : ShadeRowFull {

@@ -53,7 +53,7 @@ PH_DEV uint32_t spatial_voxel_of(const SpatialRec& sr, f3 p) {
 #define PH_SPATIAL_CHUNK 2048
 
 // One block per new voxel (grid-stride over the slots claimed since the last pass).
-// SPHERE: some light's shape may be a sphere (pbrt_hip_add_sphere_light under the path integrator): Light::sample_li is wh_light_sample_li (sphere_light.h), which asks the light's primitive
+// SPHERE: some light's shape may be a sphere (pbrt_hip_add_sphere_light under the path integrator), a disk or a cylinder (pbrt_hip_add_quadric_light): Light::sample_li is wh_light_sample_li (sphere_light.h), which asks the light's primitive
 template <bool SPHERE = false>
 __global__ __launch_bounds__(PH_SPATIAL_BLOCK) void spatial_compute_kernel(DeviceScene sc, SpatialRec sr) {
     __shared__ float buf[PH_SPATIAL_CHUNK];

@@ -1023,7 +1023,7 @@ template <class... V> static void dispatch_shade_variant(ph::ShadeVariantTable<V
     launchers[variant](s, blocks, wp, it);
 }
 // The sphere-light forms (shade_shapes.h: ShadeRowSphereLights; spatial.h: spatial_compute_kernel<true>), outside the tables: one kernel each, named here, launched in place of the
-// table's pick / the triangle-light form for a scene that holds a sphere light (PathPlan::sphere_lights) and for no other.
+// table's pick / the triangle-light form for a scene that holds a sphere, disk or cylinder light (PathPlan::sphere_lights) and for no other.
 static void launch_shade_sphere_lights(PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {
     hipLaunchKernelGGL((ph::shade_kernel<true, true, true, ph::ShadeRowSphereLights>), dim3(blocks), dim3(256), 0, s->stream, s->ds, wp, it);
 }
@@ -1046,7 +1046,7 @@ struct PathPlan {
     bool spatial;        // the spatial light distribution is live: strategy 2 with more than one light (one light -> uniform, light_distrib/mod.rs:59-64)
     bool mat_queues;     // shade-side work queues (matsort.h): scenes with anything but constant matte — the general-BSDF kernel's branches and the texture pass's programs depend on the material
     bool has_quadrics;   // the QUADRIC instantiations of the texture, light-distribution and shade passes
-    bool sphere_lights;  // some light's shape is a sphere and the handle's switch is on (pbrt_hip_set_path_sphere_lights): the sphere-light forms of the shade and light-distribution passes
+    bool sphere_lights;  // some light's shape is a sphere and the handle's switch is on (pbrt_hip_set_path_sphere_lights), or some light's shape is a disk or a cylinder (pbrt_hip_add_quadric_light): the sphere-light forms of the shade and light-distribution passes
     int shade_variant;   // of ph::ShadeVariants: the lights' kinds as upload_scene found them, the sampler and the strategy as they are now; PBRT_HIP_SHADE_ROW=full: the full row for every scene
     int tex_variant[2];  // of ph::TexVariants: [1] the camera round's, [0] the later rounds'
     // Material "none" surfaces are passed through without counting a bounce, so a path may need more rounds than n_iter = max_depth + 1: those are
@@ -1083,7 +1083,7 @@ static int plan_path_frame(PbrtHipScene* s, int max_depth, int light_strategy, c
     p.n_iter = max_depth + 1;
     p.n_iter_cap = s->has_none_material ? p.n_iter + PathPlan::kMaxNullSkips : p.n_iter;
     p.has_quadrics = !s->quadrics.empty();
-    p.sphere_lights = s->sphere_lights != 0 && s->path_sphere_lights;
+    p.sphere_lights = (s->sphere_lights != 0 && s->path_sphere_lights) || s->quadric_lights != 0;
     const char* e = std::getenv("PBRT_HIP_SHADE_ROW");
     p.shade_variant = ph::pick_shade_variant(ph::ShadeTraits{s->general_materials, s->textured_materials, p.has_quadrics},
                                              ph::ShadeFeatures{s->lights_infinite, s->lights_area, s->lights_delta, s->sampler.kind != 0, p.spatial}, e && std::strcmp(e, "full") == 0);

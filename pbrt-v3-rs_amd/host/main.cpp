@@ -19,13 +19,15 @@ static void usage() {
                  "  --quadrics             read Shape \"sphere\", \"cylinder\", \"cone\", \"paraboloid\", \"disk\" and \"hyperboloid\" (without it they are refused as out of scope); a sphere under\n"
                  "                         AreaLightSource \"diffuse\" is an area light, rendered by Integrator \"whitted\"\n"
                  "  --path-sphere-lights   render such a sphere light under Integrator \"path\" too (without it the scene is refused there)\n"
+                 "  --quadric-lights       with --quadrics: a disk or a cylinder under AreaLightSource \"diffuse\" is an area light too, rendered by either integrator (the reference's\n"
+                 "                         cone, paraboloid and hyperboloid have no Shape::sample and stay refused)\n"
                  "  --check                parse and validate only: no GPU is touched and nothing is rendered\n"
                  "  --convert-image IN OUT       decode an image file (PFM, TGA, PNG, EXR) the way ImageTexture would see it and write it as .pfm / .exr / .png / .tga\n"
                  "  --quiet                no warnings / statistics\n");
 }
 
 int main(int argc, char** argv) {
-    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false, quadrics = false, path_sphere_lights = false; float crop[4] = {0, 1, 0, 1};
+    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false, quadrics = false, quadric_lights = false, path_sphere_lights = false; float crop[4] = {0, 1, 0, 1};
     std::vector<std::string> files;
     std::vector<int> devices; bool multi = false;
     for (int i = 1; i < argc; i++) {
@@ -47,6 +49,7 @@ int main(int argc, char** argv) {
         else if (a == "--check") check = true;
         else if (a == "--quadrics") quadrics = true;
         else if (a == "--path-sphere-lights") path_sphere_lights = true;
+        else if (a == "--quadric-lights") quadric_lights = true;
         else if (a == "--convert-image") {
             need(2);
             std::vector<float> rgb; int w = 0, h = 0; std::string err;
@@ -63,7 +66,7 @@ int main(int argc, char** argv) {
         std::unique_ptr<pbrt_host::Api> api_owner((multi && !check) ? new pbrt_host::Api(devices) : new pbrt_host::Api(check ? -1 : device));
         pbrt_host::Api& api = *api_owner;
         if (!api.error.empty()) { std::fprintf(stderr, "Error: %s\n", api.error.c_str()); return 3; }
-        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet; api.quadrics = quadrics; api.path_sphere_lights = path_sphere_lights;
+        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet; api.quadrics = quadrics; api.quadric_lights = quadric_lights; api.path_sphere_lights = path_sphere_lights;
         api.has_crop_override = has_crop; std::memcpy(api.crop_override, crop, sizeof crop);
         pbrt_host::RenderReport rep;
         if (!pbrt_host::parse_file(fn, api, &rep)) { std::fprintf(stderr, "Error: %s: %s\n", fn.c_str(), api.error.c_str()); return 1; }

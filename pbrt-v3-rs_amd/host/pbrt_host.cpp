@@ -687,7 +687,12 @@ void Api::quadric_shape(const std::string& name, const ParamSet& p) {
     const bool light = !gs_.area_light.empty();
     if (light) {
         if (gs_.area_light != "diffuse" && gs_.area_light != "area") { error = "AreaLightSource \"" + gs_.area_light + "\" unknown"; return; }
-        if (name != "sphere") { error = "AreaLightSource \"" + gs_.area_light + "\" on Shape \"" + name + "\": of the quadric shapes only the sphere can be an area light"; return; }
+        const bool sampled = name == "disk" || name == "cylinder";   // the reference's other three quadrics have no Shape::sample
+        if (quadric_lights && name != "sphere" && !sampled) {
+            error = "AreaLightSource \"" + gs_.area_light + "\" on Shape \"" + name + "\": the reference's Shape::sample for this shape is missing (todo!()); only the sphere, the disk and the cylinder can be area lights";
+            return;
+        }
+        if (name != "sphere" && !(quadric_lights && sampled)) { error = "AreaLightSource \"" + gs_.area_light + "\" on Shape \"" + name + "\": of the quadric shapes only the sphere can be an area light"; return; }
         for (auto& u : gs_.area_light_params.unsupported) { error = "AreaLightSource: parameter '" + u + "' has a spectral type this host cannot evaluate"; return; }
     }
     for (const char* an : {"alpha", "shadowalpha"})   // only the triangle mesh reads them (triangle.rs:278-312)
@@ -715,7 +720,12 @@ void Api::quadric_shape(const std::string& name, const ParamSet& p) {
         else if (name == "cone") { kind = 1; a = p.find_one_float("height", 1.0f); b = 0.0f; }                                // cone.rs:321-343
         else if (name == "paraboloid") { kind = 2; a = p.find_one_float("zmin", 0.0f); b = p.find_one_float("zmax", 1.0f); }  // paraboloid.rs:337-361
         else { kind = 3; a = p.find_one_float("height", 0.0f); b = p.find_one_float("innerradius", 0.0f); }                   // disk.rs:237-261
-        if (!check(ABI(pbrt_hip_add_quadric(scene_, kind, ctm_.m, ctm_.mi, radius, a, b, phi_max, mat, flags)), "add_quadric")) return;
+        if (light) {  // as for the sphere above: one DiffuseAreaLight around the shape, numbered where the Shape directive stands
+            const ParamSet& ap = gs_.area_light_params;
+            auto L = mul3(ap.find_one_rgb("L", {1.0f, 1.0f, 1.0f}), ap.find_one_rgb("scale", {1.0f, 1.0f, 1.0f}));
+            if (!check(ABI(pbrt_hip_add_quadric_light(scene_, kind, ctm_.m, ctm_.mi, radius, a, b, phi_max, mat, flags, L.data(), ap.find_one_bool("twosided", false) ? 1 : 0)), "add_quadric_light")) return;
+            n_lights_++;
+        } else if (!check(ABI(pbrt_hip_add_quadric(scene_, kind, ctm_.m, ctm_.mi, radius, a, b, phi_max, mat, flags)), "add_quadric")) return;
     }
     n_quadrics_++;
 }

@@ -111,6 +111,7 @@ class Api {
     int tile_size = 16;
     unsigned long long sample_record_budget = 0;   // --sample-record-budget BYTES (pbrt_hip_set_sample_record_budget); 0 = automatic
     bool path_sphere_lights = false;   // --path-sphere-lights: a sphere light (Shape "sphere" under AreaLightSource "diffuse", read with `quadrics`) is rendered by Integrator "path" too
+    bool quadric_lights = false;   // --quadric-lights (with `quadrics`): Shape "disk" / "cylinder" under AreaLightSource "diffuse" is an area light (pbrt_hip_add_quadric_light), under either integrator
     bool quadrics = false;   // --quadrics: Shape "sphere" / "cylinder" / "cone" / "paraboloid" / "disk" / "hyperboloid" are read; without it they are refused as out of scope
     bool quiet = false;
     std::vector<std::string> warnings;

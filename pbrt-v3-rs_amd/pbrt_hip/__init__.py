@@ -122,6 +122,7 @@ class Binding:
             "add_instance": (C.c_int, [vp, C.c_uint32, fp, fp]),
             "add_sphere": (C.c_int, [vp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
             "add_sphere_light": (C.c_int, [vp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, fp, C.c_int]),
+            "add_quadric_light": (C.c_int, [vp, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, fp, C.c_int]),
             "add_hyperboloid": (C.c_int, [vp, fp, fp, fp, fp, C.c_float, C.c_uint32, C.c_uint32]),
             "add_quadric": (C.c_int, [vp, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
             "add_mipmap": (C.c_int, [vp, C.c_int, C.c_int, fp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, u32p]),
@@ -458,6 +459,13 @@ class Scene:
         self._chk(self.b.fn("add_quadric")(self.h, k, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(a),
                                            C.c_float(b), C.c_float(phi_max), material, 1 if reverse_orientation else 0))
 
+    def add_quadric_light(self, kind, object_to_world, world_to_object, radius, a, b, phi_max=360.0, material=0, reverse_orientation=False, L=(1, 1, 1), two_sided=False):
+        """add_quadric for a "cylinder" or a "disk" plus the DiffuseAreaLight whose shape it is (pbrt_hip_add_quadric_light): the light joins the scene's lights in call order.
+        Rendered by render_path (no switch) and render_whitted.  "cone" and "paraboloid" are refused: the reference's Shape::sample for them is todo!()."""
+        k = self.QUADRIC_KINDS[kind] if isinstance(kind, str) else int(kind)
+        self._chk(self.b.fn("add_quadric_light")(self.h, k, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(a),
+                                                 C.c_float(b), C.c_float(phi_max), material, 1 if reverse_orientation else 0, _ptr(_f32(L), C.c_float), 1 if two_sided else 0))
+
     def object_begin(self) -> int:
         """ObjectBegin (api/src/lib.rs:911-925): meshes added until object_end() belong to the returned object."""
         oid = C.c_uint32()
@@ -738,7 +746,7 @@ class Scene:
         return out
 
     def sphere_light_probe_batch(self, light, op, ref, u=None, wi=None):
-        """A spherical area light as the path integrator's sphere-light shade pass calls it (pbrt_hip_sphere_light_probe_batch): op 0 -> sample_li, op 1 -> pdf_li.  Inputs and the
+        """A spherical, disk or cylinder area light as the path integrator's sphere-light shade pass calls it (pbrt_hip_sphere_light_probe_batch): op 0 -> sample_li, op 1 -> pdf_li.  Inputs and the
         (n,28) output are light_probe_batch's."""
         ref = _f32(ref, (-1, 10)); n = len(ref)
         u = _f32(u, (-1, 2)) if u is not None else np.full((n, 2), 0.5, np.float32)
