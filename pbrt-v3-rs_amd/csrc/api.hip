@@ -122,22 +122,9 @@ int upload_scene(PbrtHipScene* s) {
         for (MeshRec& m : meshes) if (m.first_light <= -2) m.first_light = (int32_t)(s->lights.size() + (size_t)(-2 - m.first_light));
         if ((rc = upload_vec(s, meshes, &d.meshes))) return rc;
     }
-    {   // per material: what the texture pass has to hand to the shade pass (texture.h: eval_lobe_colours / build_hit_lobes use the same slot rules)
-        for (MaterialRec& m : s->materials) {
-            uint32_t cols = m.amount_tex1 ? 1u : 0u; bool hdr = m.bump_tex1 != 0u || m.sigma_tex1 != 0u;
-            for (uint32_t k = 0; k < m.n_lobes; k++) {
-                s->lobes[m.lobe_base + k].slot0 = cols;   // where this lobe's colours start in TexOut (bsdf_general.h: patch_lobe reads them from there)
-                const LobeRec& l = s->lobes[m.lobe_base + k];
-                if (l.has_pre == PH_PRE_RT) { cols += 1u; hdr = true; }   // one product colour per lobe, its black bit and the material's null-BSDF bit in the header
-                else cols += (l.r_tex1 || (l.has_pre == PH_PRE_OPACITY && l.kind != PH_LK_SPEC_T) ? 1u : 0u) + (l.t_tex1 || (l.has_pre == PH_PRE_OPACITY && l.kind == PH_LK_SPEC_T) || l.has_pre == PH_PRE_PASSTHROUGH ? 1u : 0u) +
-                        (l.eta_tex1 ? 1u : 0u) + (l.k_tex1 ? 1u : 0u);
-                if (l.sigma_tex1 || l.ax_tex1 || l.ay_tex1 || l.alt || l.has_pre == PH_PRE_RAW_TEST) hdr = true;
-            }
-            if (m.sigma_tex1 || hdr) cols = std::max(cols, 2u);   // the per-hit scalars travel in the fourth component of the first two colour slots
-            if (m.index_tex1) cols = std::max(cols, 3u);          // ... the per-hit index of refraction in the third one's
-            if (m.rt_mode) hdr = true;
-            m.tex_cols = std::min<uint32_t>(cols, PH_HIT_COLS); m.tex_hdr = hdr ? 1u : 0u;
-        }
+    std::vector<MaterialRec> materials; std::vector<LobeRec> lobes;   // the materials' lists one after the other, with what the texture pass has to hand to the shade pass
+    layout_lobe_pool(s->mats, materials, lobes);
+    {
         s->alpha_lean = s->alpha_textures;
         for (const MeshRec& m : s->meshes)
             for (uint32_t t1 : {m.alpha_tex1, m.shadow_alpha_tex1})
@@ -146,17 +133,17 @@ int upload_scene(PbrtHipScene* s) {
         for (const PbrtHipScene::TextureHost& t : s->textures)
             if (!tex_prog_is_simple(t.prog)) s->simple_textures = false;
     }
-    if ((rc = upload_vec(s, s->materials, &d.materials))) return rc;
-    if ((rc = upload_vec(s, s->lobes, &d.lobes))) return rc;
+    if ((rc = upload_vec(s, materials, &d.materials))) return rc;
+    if ((rc = upload_vec(s, lobes, &d.lobes))) return rc;
     {   // keys of the shade-side work queues (matsort.h): materials the texture pass has work for first, then the others, then "emission only" and "no new vertex"
         const uint32_t kMaxTex = 500u, kMaxPlain = 500u;
-        std::vector<uint16_t> key(std::max<size_t>(s->materials.size(), 1), 0);
+        std::vector<uint16_t> key(std::max<size_t>(materials.size(), 1), 0);
         uint32_t n_tex = 0, n_plain = 0;
-        for (const MaterialRec& m : s->materials) if (!m.none && (m.textured || m.bump_tex1)) n_tex++;
+        for (const MaterialRec& m : materials) if (!m.none && (m.textured || m.bump_tex1)) n_tex++;
         const uint32_t T = std::min(n_tex, kMaxTex);
         uint32_t jt = 0, jp = 0;
-        for (size_t i = 0; i < s->materials.size(); i++) {
-            const MaterialRec& m = s->materials[i];
+        for (size_t i = 0; i < materials.size(); i++) {
+            const MaterialRec& m = materials[i];
             if (!m.none && (m.textured || m.bump_tex1)) key[i] = (uint16_t)std::min(jt++, kMaxTex - 1u);
             else { key[i] = (uint16_t)(T + std::min(jp++, kMaxPlain - 1u)); n_plain++; }
         }
@@ -451,413 +438,86 @@ const char* pbrt_hip_last_error(const PbrtHipScene* s) {
     return g_last_error.c_str();
 }
 
-// ---- materials: the BxDF list compute_scattering_functions builds for constant textures (materials/src/*.rs) ------------------
-namespace {
-float roughness_to_alpha(float roughness) {  // TrowbridgeReitzDistribution::roughness_to_alpha (microfacet/trowbridge_reitz.rs:31-40); host libm logf as for the reference
-    roughness = roughness > 1e-3f ? roughness : 1e-3f;
-    const float x = std::log(roughness);
-    return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
+// ---- materials: each call describes one (material_host.h: MaterialSpec); which lobes it has is derive's business -------------------------------
+using phost::MaterialKind;
+static int add_material(PbrtHipScene* s, const phost::MaterialSpec& spec, uint32_t* out_id) {
+    std::string why;
+    return material_changed(s, phost::add_material(s->mats, spec, out_id, why), why);
 }
-bool clamp3(const float in[3], float out[3]) {  // clamp_default(); returns !is_black()
-    for (int c = 0; c < 3; c++) out[c] = hm::clampf(in[c], 0.0f, hm::kInf);
-    return !(out[0] == 0.0f && out[1] == 0.0f && out[2] == 0.0f);
-}
-LobeRec lobe(uint32_t kind, uint32_t type) { LobeRec l{}; l.kind = kind; l.type = type; l.eta_a = l.eta_b = 1.0f; return l; }
-void set_tr(LobeRec& l, float ax, float ay) { l.ax = 0.001f > ax ? 0.001f : ax; l.ay = 0.001f > ay ? 0.001f : ay; }  // TrowbridgeReitzDistribution::new: max(0.001, alpha)
-enum : uint32_t { T_REFL = 1, T_TRANS = 2, T_DIFF = 4, T_GLOSSY = 8, T_SPEC = 16 };
-int push_material(PbrtHipScene* s, MaterialRec& m, const std::vector<LobeRec>& lobes, bool general, uint32_t* out_id) {
-    m.lobe_base = (uint32_t)s->lobes.size(); m.n_lobes = (uint32_t)lobes.size();
-    s->lobes.insert(s->lobes.end(), lobes.begin(), lobes.end());
-    s->materials.push_back(m);
-    s->material_params.resize(s->materials.size());
-    if (general) s->general_materials = true;
-    if (out_id) *out_id = (uint32_t)s->materials.size() - 1;
-    s->uploaded = false;
-    return PBRT_HIP_OK;
-}
-}  // namespace
 
 int pbrt_hip_add_material_matte(PbrtHipScene* s, const float kd[3], float sigma_deg, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_matte", [&]() -> int {
     if (!s || !kd) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_matte: null argument");
-    MaterialRec m{};
-    for (int c = 0; c < 3; c++) m.kd[c] = hm::clampf(kd[c], 0.0f, hm::kInf);  // clamp_default (matte.rs:63)
-    m.sigma = hm::clampf(sigma_deg, 0.0f, 90.0f);                              // matte.rs:64
-    m.has_bxdf = !(m.kd[0] == 0.0f && m.kd[1] == 0.0f && m.kd[2] == 0.0f);
-    m.bsdf_eta = 1.0f;
-    if (m.sigma != 0.0f) {  // OrenNayar::new (oren_nayar.rs:28-39)
-        float sg = hm::to_radians(m.sigma), s2 = sg * sg;
-        m.a = 1.0f - (s2 / (2.0f * (s2 + 0.33f)));
-        m.b = 0.45f * s2 / (s2 + 0.09f);
-    }
-    std::vector<LobeRec> lobes;
-    if (m.has_bxdf) {
-        LobeRec l = lobe(m.sigma != 0.0f ? PH_LK_OREN : PH_LK_LAMBERT, T_REFL | T_DIFF);
-        std::memcpy(l.r, m.kd, 12); l.a = m.a; l.b = m.b;
-        lobes.push_back(l);
-    }
-    const int rc = push_material(s, m, lobes, false, out_id);
-    if (rc == PBRT_HIP_OK) s->material_params.back().made_as = 6;
-    if (rc == PBRT_HIP_OK && m.has_bxdf) s->material_params.back().lobe[0] = 0;
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Matte); m.set(PBRT_HIP_PARAM_KD, kd); m.sigma = sigma_deg;
+    return add_material(s, m, out_id);
     });
 }
-int pbrt_hip_add_material_none(PbrtHipScene* s, uint32_t* out_id) {  // Material "none" / "" (graphics_state.rs make_material -> None)
+int pbrt_hip_add_material_none(PbrtHipScene* s, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_none", [&]() -> int {
     if (!s) return PBRT_HIP_ERR_INVALID_ARG;
-    MaterialRec m{}; m.bsdf_eta = 1.0f; m.none = 1u;
-    s->has_none_material = true;
-    return push_material(s, m, {}, false, out_id);
+    return add_material(s, phost::MaterialSpec(MaterialKind::None), out_id);
     });
 }
-int pbrt_hip_add_material_mirror(PbrtHipScene* s, const float kr[3], uint32_t* out_id) {  // mirror.rs:40-62
+int pbrt_hip_add_material_mirror(PbrtHipScene* s, const float kr[3], uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_mirror", [&]() -> int {
     if (!s || !kr) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_mirror: null argument");
-    MaterialRec m{}; m.bsdf_eta = 1.0f;
-    std::vector<LobeRec> lobes;
-    float r[3];
-    if (clamp3(kr, r)) { LobeRec l = lobe(PH_LK_SPEC_R, T_REFL | T_SPEC); l.fresnel = PH_FR_NOOP; std::memcpy(l.r, r, 12); lobes.push_back(l); }
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK && !lobes.empty()) s->material_params.back().lobe[2] = 0;
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Mirror); m.set(PBRT_HIP_PARAM_KR, kr);
+    return add_material(s, m, out_id);
     });
 }
-int pbrt_hip_add_material_plastic(PbrtHipScene* s, const float kd[3], const float ks[3], float roughness, int remap_roughness, uint32_t* out_id) {  // plastic.rs:50-82
+int pbrt_hip_add_material_plastic(PbrtHipScene* s, const float kd[3], const float ks[3], float roughness, int remap_roughness, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_plastic", [&]() -> int {
     if (!s || !kd || !ks) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_plastic: null argument");
-    MaterialRec m{}; m.bsdf_eta = 1.0f;
-    std::vector<LobeRec> lobes;
-    float d[3], sp[3];
-    if (clamp3(kd, d)) { LobeRec l = lobe(PH_LK_LAMBERT, T_REFL | T_DIFF); std::memcpy(l.r, d, 12); lobes.push_back(l); }
-    if (clamp3(ks, sp)) {
-        LobeRec l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.5f; l.eta_b = 1.0f; std::memcpy(l.r, sp, 12);
-        const float rough = remap_roughness ? roughness_to_alpha(roughness) : roughness;
-        set_tr(l, rough, rough);
-        lobes.push_back(l);
-    }
-    const int kd_lobe = (!lobes.empty() && lobes[0].kind == PH_LK_LAMBERT) ? 0 : -1, ks_lobe = (!lobes.empty() && lobes.back().kind == PH_LK_MICRO_R) ? (int)lobes.size() - 1 : -1;
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK) { PbrtHipScene::MaterialParams& mp = s->material_params.back(); mp.lobe[0] = kd_lobe; mp.lobe[1] = ks_lobe; mp.rough_lobe = ks_lobe; mp.rough_remap = remap_roughness != 0; }
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Plastic, roughness, roughness, remap_roughness != 0); m.set(PBRT_HIP_PARAM_KD, kd); m.set(PBRT_HIP_PARAM_KS, ks);
+    return add_material(s, m, out_id);
     });
 }
-int pbrt_hip_add_material_glass(PbrtHipScene* s, const float kr[3], const float kt[3], float urough, float vrough, float eta, int remap_roughness,
-                                uint32_t* out_id) {  // glass.rs:62-118 with allow_multiple_lobes = true (path.rs:143)
+int pbrt_hip_add_material_glass(PbrtHipScene* s, const float kr[3], const float kt[3], float urough, float vrough, float eta, int remap_roughness, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_glass", [&]() -> int {
     if (!s || !kr || !kt) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_glass: null argument");
-    MaterialRec m{}; m.bsdf_eta = 1.0f;  // BSDF::new(.., None) (glass.rs:82)
-    const float glass_raw_ur = urough, glass_raw_vr = vrough;   // before remapping: what a later roughness texture's `== 0` test is combined with
-    std::vector<LobeRec> lobes;
-    float r[3], t[3];
-    const bool rb = clamp3(kr, r), tb = clamp3(kt, t);
-    if (rb || tb) {
-        if (urough == 0.0f && vrough == 0.0f) {
-            LobeRec l = lobe(PH_LK_FRESNEL_SPEC, T_REFL | T_TRANS | T_SPEC); std::memcpy(l.r, r, 12); std::memcpy(l.t, t, 12); l.eta_a = 1.0f; l.eta_b = eta;
-            lobes.push_back(l);
-        } else {
-            if (remap_roughness) { urough = roughness_to_alpha(urough); vrough = roughness_to_alpha(vrough); }
-            if (rb) { LobeRec l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = eta; std::memcpy(l.r, r, 12); set_tr(l, urough, vrough); lobes.push_back(l); }
-            if (tb) { LobeRec l = lobe(PH_LK_MICRO_T, T_TRANS | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = eta; std::memcpy(l.t, t, 12); set_tr(l, urough, vrough); lobes.push_back(l); }
-        }
-    }
-    const float raw_ur = urough, raw_vr = vrough;
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK) {  // Kr -> the reflection colour, Kt -> the transmission colour (one FresnelSpecular lobe, or the two microfacet lobes)
-        PbrtHipScene::MaterialParams& mp = s->material_params.back();
-        mp.made_as = 2; std::memcpy(mp.raw_k[2], kr, 12); std::memcpy(mp.raw_k[3], kt, 12); mp.raw_eta = eta; mp.raw_ur = glass_raw_ur; mp.raw_vr = glass_raw_vr; mp.raw_remap = remap_roughness != 0;
-        (void)raw_ur; (void)raw_vr;
-        for (size_t i = 0; i < lobes.size(); i++) {
-            if (lobes[i].kind == PH_LK_FRESNEL_SPEC) { mp.lobe[2] = (int)i; mp.field[2] = 0; mp.lobe[3] = (int)i; mp.field[3] = 1; }
-            else if (lobes[i].kind == PH_LK_MICRO_R) { mp.lobe[2] = (int)i; mp.field[2] = 0; }
-            else if (lobes[i].kind == PH_LK_MICRO_T) { mp.lobe[3] = (int)i; mp.field[3] = 1; }
-        }
-    }
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Glass, urough, vrough, remap_roughness != 0); m.set(PBRT_HIP_PARAM_KR, kr); m.set(PBRT_HIP_PARAM_KT, kt); m.index = eta;
+    return add_material(s, m, out_id);
     });
 }
-int pbrt_hip_add_material_metal(PbrtHipScene* s, const float eta[3], const float k[3], float urough, float vrough, int remap_roughness, uint32_t* out_id) {  // metal.rs:62-98
+int pbrt_hip_add_material_metal(PbrtHipScene* s, const float eta[3], const float k[3], float urough, float vrough, int remap_roughness, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_metal", [&]() -> int {
     if (!s || !eta || !k) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_metal: null argument");
-    MaterialRec m{}; m.bsdf_eta = 1.0f;
-    if (remap_roughness) { urough = roughness_to_alpha(urough); vrough = roughness_to_alpha(vrough); }
-    LobeRec l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_COND;
-    l.r[0] = l.r[1] = l.r[2] = 1.0f; std::memcpy(l.c_eta_t, eta, 12); std::memcpy(l.c_k, k, 12);
-    set_tr(l, urough, vrough);
-    const int rc = push_material(s, m, {l}, true, out_id);
-    if (rc == PBRT_HIP_OK) { s->material_params.back().rough_lobe = 0; s->material_params.back().rough_remap = remap_roughness != 0; s->material_params.back().made_as = 3; }
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Metal, urough, vrough, remap_roughness != 0); m.set(PBRT_HIP_PARAM_ETA, eta); m.set(PBRT_HIP_PARAM_K, k);
+    return add_material(s, m, out_id);
     });
 }
 int pbrt_hip_add_material_uber(PbrtHipScene* s, const float kd[3], const float ks[3], const float kr[3], const float kt[3], const float opacity[3], float urough,
-                               float vrough, float eta, int remap_roughness, uint32_t* out_id) {  // uber.rs:116-186
+                               float vrough, float eta, int remap_roughness, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_uber", [&]() -> int {
     if (!s || !kd || !ks || !kr || !kt || !opacity) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_uber: null argument");
-    MaterialRec m{};
-    const float uber_raw_ur = urough, uber_raw_vr = vrough;
-    std::vector<LobeRec> lobes;
-    float op[3], t[3], tmp[3];
-    clamp3(opacity, op);
-    for (int c = 0; c < 3; c++) tmp[c] = op[c] * -1.0f + 1.0f;  // (-op + Spectrum::ONE)
-    if (clamp3(tmp, t)) {
-        m.bsdf_eta = 1.0f;
-        LobeRec l = lobe(PH_LK_SPEC_T, T_TRANS | T_SPEC); l.fresnel = PH_FR_DIEL; std::memcpy(l.t, t, 12); l.eta_a = 1.0f; l.eta_b = 1.0f; lobes.push_back(l);
-    } else m.bsdf_eta = eta;
-    auto scaled = [&](const float in[3], float out[3]) {  // op * k.clamp_default()
-        float c[3]; clamp3(in, c);
-        for (int i = 0; i < 3; i++) out[i] = op[i] * c[i];
-        return !(out[0] == 0.0f && out[1] == 0.0f && out[2] == 0.0f);
-    };
-    float v[3];
-    if (scaled(kd, v)) { LobeRec l = lobe(PH_LK_LAMBERT, T_REFL | T_DIFF); std::memcpy(l.r, v, 12); lobes.push_back(l); }
-    if (scaled(ks, v)) {
-        LobeRec l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = eta; std::memcpy(l.r, v, 12);
-        if (remap_roughness) { urough = roughness_to_alpha(urough); vrough = roughness_to_alpha(vrough); }
-        set_tr(l, urough, vrough);
-        lobes.push_back(l);
-    }
-    if (scaled(kr, v)) { LobeRec l = lobe(PH_LK_SPEC_R, T_REFL | T_SPEC); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = eta; std::memcpy(l.r, v, 12); lobes.push_back(l); }
-    int kt_lobe = -1;
-    if (scaled(kt, v)) { LobeRec l = lobe(PH_LK_SPEC_T, T_TRANS | T_SPEC); l.fresnel = PH_FR_DIEL; std::memcpy(l.t, v, 12); l.eta_a = 1.0f; l.eta_b = eta; kt_lobe = (int)lobes.size(); lobes.push_back(l); }
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK) {  // texturable: Kd, Ks, Kr, Kt, each multiplied by the (constant) opacity as in `op * k.evaluate().clamp_default()`
-        PbrtHipScene::MaterialParams& mp = s->material_params.back();
-        mp.has_pre = true; std::memcpy(mp.pre, op, 12);
-        mp.made_as = 1; std::memcpy(mp.raw_k[0], kd, 12); std::memcpy(mp.raw_k[1], ks, 12); std::memcpy(mp.raw_k[2], kr, 12); std::memcpy(mp.raw_k[3], kt, 12);
-        mp.raw_eta = eta; mp.raw_ur = uber_raw_ur; mp.raw_vr = uber_raw_vr; mp.raw_remap = remap_roughness != 0;
-        for (size_t i = 0; i < lobes.size(); i++) {
-            if (lobes[i].kind == PH_LK_LAMBERT) mp.lobe[0] = (int)i;
-            else if (lobes[i].kind == PH_LK_MICRO_R) { mp.lobe[1] = (int)i; mp.rough_lobe = (int)i; mp.rough_remap = remap_roughness != 0; }
-            else if (lobes[i].kind == PH_LK_SPEC_R) mp.lobe[2] = (int)i;
-        }
-        if (kt_lobe >= 0) { mp.lobe[3] = kt_lobe; mp.field[3] = 1; }
-    }
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Uber, urough, vrough, remap_roughness != 0); m.index = eta;
+    m.set(PBRT_HIP_PARAM_KD, kd); m.set(PBRT_HIP_PARAM_KS, ks); m.set(PBRT_HIP_PARAM_KR, kr); m.set(PBRT_HIP_PARAM_KT, kt); m.set(PBRT_HIP_PARAM_OPACITY, opacity);
+    return add_material(s, m, out_id);
     });
 }
-
-int pbrt_hip_add_material_substrate(PbrtHipScene* s, const float kd[3], const float ks[3], float urough, float vrough, int remap_roughness, uint32_t* out_id) {  // substrate.rs:55-84
+int pbrt_hip_add_material_substrate(PbrtHipScene* s, const float kd[3], const float ks[3], float urough, float vrough, int remap_roughness, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_substrate", [&]() -> int {
     if (!s || !kd || !ks) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_substrate: null argument");
-    MaterialRec m{}; m.bsdf_eta = 1.0f;
-    std::vector<LobeRec> lobes;
-    float d[3], sp[3];
-    const bool db = clamp3(kd, d), sb = clamp3(ks, sp);
-    if (db || sb) {
-        if (remap_roughness) { urough = roughness_to_alpha(urough); vrough = roughness_to_alpha(vrough); }
-        LobeRec l = lobe(PH_LK_FRESNEL_BLEND, T_REFL | T_GLOSSY); std::memcpy(l.r, d, 12); std::memcpy(l.t, sp, 12); set_tr(l, urough, vrough);
-        lobes.push_back(l);
-    }
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK && !lobes.empty()) { PbrtHipScene::MaterialParams& mp = s->material_params.back(); mp.lobe[0] = 0; mp.field[0] = 0; mp.lobe[1] = 0; mp.field[1] = 1; mp.rough_lobe = 0; mp.rough_remap = remap_roughness != 0; }
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Substrate, urough, vrough, remap_roughness != 0); m.set(PBRT_HIP_PARAM_KD, kd); m.set(PBRT_HIP_PARAM_KS, ks);
+    return add_material(s, m, out_id);
     });
 }
 int pbrt_hip_add_material_translucent(PbrtHipScene* s, const float kd[3], const float ks[3], const float reflect[3], const float transmit[3], float roughness,
-                                      int remap_roughness, uint32_t* out_id) {  // translucent.rs:57-112
+                                      int remap_roughness, uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_translucent", [&]() -> int {
     if (!s || !kd || !ks || !reflect || !transmit) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_translucent: null argument");
-    MaterialRec m{}; m.bsdf_eta = 1.5f;
-    std::vector<LobeRec> lobes;
-    float r[3], t[3], d[3], sp[3], v[3];
-    const bool rb = clamp3(reflect, r), tb = clamp3(transmit, t);
-    if (!rb && !tb) { m.none = 1u; s->has_none_material = true; }   // `return` before a BSDF is made (translucent.rs:72-74): every hit is passed through, as with Material "none" — until a texture takes reflect's / transmit's place
-    auto prod = [&](const float a[3], const float b[3]) { for (int c = 0; c < 3; c++) v[c] = a[c] * b[c]; };
-    // each lobe keeps the reflect / transmit factor of its product (pre, PH_PRE_RAW_TEST) so that a Kd / Ks texture can replace the other factor per hit
-    PbrtHipScene::MaterialParams mp;
-    auto feed = [&](int param, int field) { if (mp.lobe[param] < 0) { mp.lobe[param] = (int)lobes.size(); mp.field[param] = field; } else { mp.lobe2[param] = (int)lobes.size(); mp.field2[param] = field; } };
-    auto raw = [&](LobeRec& l, const float f[3]) { std::memcpy(l.pre, f, 12); l.has_pre = PH_PRE_RAW_TEST; };
-    if (clamp3(kd, d)) {
-        if (rb) { LobeRec l = lobe(PH_LK_LAMBERT, T_REFL | T_DIFF); prod(r, d); std::memcpy(l.r, v, 12); raw(l, r); feed(0, 0); lobes.push_back(l); }
-        if (tb) { LobeRec l = lobe(PH_LK_LAMBERT_T, T_TRANS | T_DIFF); prod(t, d); std::memcpy(l.t, v, 12); raw(l, t); feed(0, 1); lobes.push_back(l); }
-    }
-    if (clamp3(ks, sp)) {
-        const float rough = remap_roughness ? roughness_to_alpha(roughness) : roughness;
-        mp.rough_remap = remap_roughness != 0;
-        if (rb) { LobeRec l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = 1.5f; prod(r, sp); std::memcpy(l.r, v, 12); set_tr(l, rough, rough); raw(l, r);
-                  feed(1, 0); mp.rough_lobe = (int)lobes.size(); lobes.push_back(l); }
-        if (tb) { LobeRec l = lobe(PH_LK_MICRO_T, T_TRANS | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = 1.5f; prod(t, sp); std::memcpy(l.t, v, 12); set_tr(l, rough, rough); raw(l, t);
-                  feed(1, 1); (mp.rough_lobe < 0 ? mp.rough_lobe : mp.rough_lobe2) = (int)lobes.size(); lobes.push_back(l); }
-    }
-    mp.made_as = 5; clamp3(kd, mp.raw_k[0]); clamp3(ks, mp.raw_k[1]); std::memcpy(mp.raw_k[2], r, 12); std::memcpy(mp.raw_k[3], t, 12); mp.raw_ur = roughness; mp.raw_remap = remap_roughness != 0;
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK) s->material_params.back() = mp;
-    return rc;
+    phost::MaterialSpec m(MaterialKind::Translucent, roughness, roughness, remap_roughness != 0);
+    m.set(PBRT_HIP_PARAM_KD, kd); m.set(PBRT_HIP_PARAM_KS, ks); m.set(PBRT_HIP_PARAM_REFLECT, reflect); m.set(PBRT_HIP_PARAM_TRANSMIT, transmit);
+    return add_material(s, m, out_id);
     });
 }
-int pbrt_hip_add_material_mix(PbrtHipScene* s, uint32_t material1, uint32_t material2, const float amount[3], uint32_t* out_id) {  // mix.rs:51-88
+int pbrt_hip_add_material_mix(PbrtHipScene* s, uint32_t material1, uint32_t material2, const float amount[3], uint32_t* out_id) {
     return ph_guard(s, "pbrt_hip_add_material_mix", [&]() -> int {
     if (!s || !amount) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_mix: null argument");
-    if (material1 >= s->materials.size() || material2 >= s->materials.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_mix: unknown material id");
-    MaterialRec m{}; m.bsdf_eta = 1.0f;
-    float s1[3], s2[3], tmp[3];
-    clamp3(amount, s1);
-    for (int c = 0; c < 3; c++) tmp[c] = 1.0f - s1[c];
-    clamp3(tmp, s2);
-    const MaterialRec a = s->materials[material1], b = s->materials[material2];
-    // mix.rs:63-76: m1 bumps `si` itself, m2 a clone of it, and the mixture's BSDF is made on `si`: the first material's bump map shapes the frame of every
-    // lobe, the second one's changes nothing that is used
-    m.bump_tex1 = a.bump_tex1;
-    if (a.amount_tex1 || b.amount_tex1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_material_mix: a sub-material is a mix whose amount is a texture; not supported");
-    if (a.rt_mode || b.rt_mode) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_material_mix: a translucent sub-material with a reflect / transmit texture (a per-hit null BSDF) is not supported");
-    if (a.index_tex1 || b.index_tex1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_material_mix: a sub-material with a textured index of refraction is not supported");
-    if (a.opacity_tex1 && b.opacity_tex1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_material_mix: both sub-materials are uber materials with opacity textures; not supported");
-    m.opacity_tex1 = a.opacity_tex1 ? a.opacity_tex1 : b.opacity_tex1;
-    if (a.n_lobes + b.n_lobes > 8) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_mix: more than MAX_BXDFS = 8 lobes (BSDF::add asserts, bsdf.rs:119-125)");
-    std::vector<LobeRec> lobes;
-    auto take = [&](const MaterialRec& src, const float sc[3]) {
-        for (uint32_t k = 0; k < src.n_lobes; k++) {
-            LobeRec l = s->lobes[src.lobe_base + k];
-            if (l.n_scale >= 2) return false;
-            std::memcpy(l.n_scale == 0 ? l.scale0 : l.scale1, sc, 12); l.n_scale++;
-            lobes.push_back(l);
-        }
-        return true;
-    };
-    if (!take(a, s1) || !take(b, s2)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_material_mix: mix nested deeper than two levels");
-    if (a.textured || b.textured) {
-        // the sub-materials' textures are evaluated per hit and each lobe is kept or dropped as its own material would (mix.rs:63-87); the per-hit list has
-        // PH_HIT_LOBES lobe slots, PH_HIT_COLS colour slots and ONE pair of per-hit scalars (roughness or sigma)
-        uint32_t cols = 0, scal = 0; const LobeRec* first = nullptr;
-        for (const LobeRec& l : lobes) {
-            cols += (l.r_tex1 || (l.has_pre == PH_PRE_OPACITY && l.kind != PH_LK_SPEC_T) ? 1u : 0u) + (l.t_tex1 || (l.has_pre == PH_PRE_OPACITY && l.kind == PH_LK_SPEC_T) || l.has_pre == PH_PRE_PASSTHROUGH ? 1u : 0u) +
-                    (l.eta_tex1 ? 1u : 0u) + (l.k_tex1 ? 1u : 0u);
-            if (l.ax_tex1 || l.ay_tex1 || l.sigma_tex1) {
-                if (!first) { first = &l; scal = 1; }
-                else if (l.ax_tex1 != first->ax_tex1 || l.ay_tex1 != first->ay_tex1 || l.remap != first->remap || l.sigma_tex1 != first->sigma_tex1 || l.ax != first->ax || l.ay != first->ay) scal++;
-            }
-        }
-        if (lobes.size() > PH_HIT_LOBES || cols > PH_HIT_COLS || scal > 1u)
-            return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "add_material_mix: a textured mix may have at most 8 lobes, 6 textured colours and one textured roughness / sigma");
-        m.textured = 1u;
-    }
-    const int rc = push_material(s, m, lobes, true, out_id);
-    if (rc == PBRT_HIP_OK) { s->material_params.back().made_as = 4; s->material_params.back().mix_n1 = (int)a.n_lobes; if (m.bump_tex1) { s->textured_materials = true; s->bump_materials = true; } }
-    return rc;
+    if (material1 >= s->mats.size() || material2 >= s->mats.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_material_mix: unknown material id");
+    return add_material(s, phost::mix_spec(s->mats, material1, material2, amount), out_id);
     });
 }
-
-}  // extern "C"
-
-namespace phost {
-// TranslucentMaterial with a reflect / transmit texture: the lobe list becomes every lobe the material CAN have (translucent.rs:76-98); a lobe's colour is the product of the hit's
-// reflect or transmit with the hit's Kd or Ks, kept where neither factor is black (PH_PRE_RT); where reflect and transmit are both black the hit has no BSDF at all.
-int translucent_rebuild_rt(PbrtHipScene* s, uint32_t material) {
-    PbrtHipScene::MaterialParams& mp = s->material_params[material];
-    MaterialRec& m = s->materials[material];
-    if (m.rt_mode) return PBRT_HIP_OK;
-    std::vector<LobeRec> old(s->lobes.begin() + m.lobe_base, s->lobes.begin() + m.lobe_base + m.n_lobes), lobes;
-    uint32_t btex1[2] = {0u, 0u}, axt = 0u, ayt = 0u;   // Kd / Ks and roughness textures set so far
-    for (int k = 0; k < 2; k++) if (mp.lobe[k] >= 0) { const LobeRec& l = old[(size_t)mp.lobe[k]]; btex1[k] = mp.field[k] == 0 ? l.r_tex1 : l.t_tex1; }
-    if (mp.rough_lobe >= 0) { axt = old[(size_t)mp.rough_lobe].ax_tex1; ayt = old[(size_t)mp.rough_lobe].ay_tex1; }
-    for (int k = 0; k < 4; k++) { mp.lobe[k] = mp.lobe2[k] = -1; mp.field[k] = mp.field2[k] = 0; }
-    mp.rough_lobe = mp.rough_lobe2 = -1;
-    for (int k = 0; k < 2; k++) {
-        const bool black = mp.raw_k[k][0] == 0.0f && mp.raw_k[k][1] == 0.0f && mp.raw_k[k][2] == 0.0f;
-        if (black && !btex1[k]) continue;   // Kd / Ks black at every hit
-        for (int side = 0; side < 2; side++) {
-            LobeRec l;
-            if (k == 0) l = side ? lobe(PH_LK_LAMBERT_T, T_TRANS | T_DIFF) : lobe(PH_LK_LAMBERT, T_REFL | T_DIFF);
-            else {
-                l = side ? lobe(PH_LK_MICRO_T, T_TRANS | T_GLOSSY) : lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY);
-                l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = 1.5f;
-                const float rough = mp.raw_remap ? roughness_to_alpha(mp.raw_ur) : mp.raw_ur;
-                set_tr(l, rough, rough);
-                l.ax_tex1 = axt; l.ay_tex1 = ayt; l.remap = mp.raw_remap ? 1u : 0u;
-                (side ? mp.rough_lobe2 : mp.rough_lobe) = (int)lobes.size();
-            }
-            l.has_pre = PH_PRE_RT; std::memcpy(l.pre, mp.raw_k[k], 12);
-            (side ? l.t_tex1 : l.r_tex1) = btex1[k];
-            (side ? mp.lobe2[k] : mp.lobe[k]) = (int)lobes.size(); (side ? mp.field2[k] : mp.field[k]) = side;
-            lobes.push_back(l);
-        }
-    }
-    mp.rough_remap = mp.raw_remap; mp.has_pre = false;
-    m.lobe_base = (uint32_t)s->lobes.size(); m.n_lobes = (uint32_t)lobes.size();
-    s->lobes.insert(s->lobes.end(), lobes.begin(), lobes.end());
-    m.rt_mode = 1u; m.none = 0u; m.textured = 1u;
-    std::memcpy(m.refl_c, mp.raw_k[2], 12); std::memcpy(m.trans_c, mp.raw_k[3], 12);
-    s->has_none_material = true;   // some hits of this material may have no BSDF: paths can need more rounds than max_depth + 1
-    s->textured_materials = true; s->general_materials = true;
-    s->uploaded = false;
-    return PBRT_HIP_OK;
-}
-// UberMaterial with an opacity texture: the lobe list becomes every lobe the material CAN have (uber.rs:126-160); colours, presence and BSDF::eta are decided per hit.
-// The new list is appended to the lobe pool (the old one stays behind, unused).
-int uber_rebuild_for_opacity(PbrtHipScene* s, uint32_t material) {
-    PbrtHipScene::MaterialParams& mp = s->material_params[material];
-    MaterialRec& m = s->materials[material];
-    if (mp.rebuilt) return PBRT_HIP_OK;
-    std::vector<LobeRec> old(s->lobes.begin() + m.lobe_base, s->lobes.begin() + m.lobe_base + m.n_lobes), lobes;
-    int oldp[4]; for (int k = 0; k < 4; k++) oldp[k] = mp.lobe[k];
-    const int old_rough = mp.rough_lobe;
-    for (int k = 0; k < 4; k++) { mp.lobe[k] = -1; mp.field[k] = 0; }
-    mp.rough_lobe = -1;
-    { LobeRec l = lobe(PH_LK_SPEC_T, T_TRANS | T_SPEC); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = 1.0f; l.has_pre = PH_PRE_PASSTHROUGH; lobes.push_back(l); }
-    const float e = mp.raw_eta;
-    for (int k = 0; k < 4; k++) {
-        float base[3];
-        const bool nonblack = clamp3(mp.raw_k[k], base);
-        const LobeRec* ol = oldp[k] >= 0 ? &old[(size_t)oldp[k]] : nullptr;
-        const uint32_t tex1 = ol ? (k == 3 ? ol->t_tex1 : ol->r_tex1) : 0u;
-        if (!nonblack && !tex1) continue;   // op * 0 is black at every hit: the lobe is never added
-        LobeRec l;
-        if (k == 0) { l = lobe(PH_LK_LAMBERT, T_REFL | T_DIFF); l.r_tex1 = tex1; }
-        else if (k == 1) {
-            l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = e; l.r_tex1 = tex1;
-            float ur = mp.raw_ur, vr = mp.raw_vr;
-            if (mp.raw_remap) { ur = roughness_to_alpha(ur); vr = roughness_to_alpha(vr); }
-            set_tr(l, ur, vr);
-            if (old_rough >= 0) { const LobeRec& r = old[(size_t)old_rough]; l.ax_tex1 = r.ax_tex1; l.ay_tex1 = r.ay_tex1; l.remap = r.remap; }
-            mp.rough_lobe = (int)lobes.size(); mp.rough_remap = mp.raw_remap;
-        }
-        else if (k == 2) { l = lobe(PH_LK_SPEC_R, T_REFL | T_SPEC); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = e; l.r_tex1 = tex1; }
-        else { l = lobe(PH_LK_SPEC_T, T_TRANS | T_SPEC); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = e; l.t_tex1 = tex1; mp.field[3] = 1; }
-        l.has_pre = PH_PRE_OPACITY; std::memcpy(l.pre, base, 12);
-        mp.lobe[k] = (int)lobes.size();
-        lobes.push_back(l);
-    }
-    mp.has_pre = false;   // the per-hit opacity takes the constant's place (set_material_texture must not overwrite has_pre = PH_PRE_OPACITY)
-    m.lobe_base = (uint32_t)s->lobes.size(); m.n_lobes = (uint32_t)lobes.size();
-    s->lobes.insert(s->lobes.end(), lobes.begin(), lobes.end());
-    m.bsdf_eta = 1.0f; m.bsdf_eta_alt = e; m.uber_eta = 1u;
-    mp.rebuilt = true;
-    return PBRT_HIP_OK;
-}
-// GlassMaterial with a roughness texture: which lobes a hit gets depends on `urough == 0 && vrough == 0` there (glass.rs:110-141): the list holds the smooth
-// alternative (FresnelSpecular; allow_multiple_lobes is true on this path) and the rough one (the microfacet pair)
-int glass_rebuild_for_roughness(PbrtHipScene* s, uint32_t material) {
-    PbrtHipScene::MaterialParams& mp = s->material_params[material];
-    MaterialRec& m = s->materials[material];
-    if (mp.rebuilt) return PBRT_HIP_OK;
-    uint32_t rtex1 = 0, ttex1 = 0;
-    for (uint32_t k = 0; k < m.n_lobes; k++) { const LobeRec& l = s->lobes[m.lobe_base + k]; if (l.r_tex1) rtex1 = l.r_tex1; if (l.t_tex1) ttex1 = l.t_tex1; }
-    float r[3], t[3];
-    const bool rb = clamp3(mp.raw_k[2], r), tb = clamp3(mp.raw_k[3], t);
-    std::vector<LobeRec> lobes;
-    for (int k = 0; k < 4; k++) { mp.lobe[k] = mp.lobe2[k] = -1; mp.field[k] = mp.field2[k] = 0; }
-    mp.rough_lobe = mp.rough_lobe2 = -1;
-    const bool has_r = rb || rtex1, has_t = tb || ttex1;
-    if (has_r || has_t) {
-        float ur = mp.raw_ur, vr = mp.raw_vr;
-        if (mp.raw_remap) { ur = roughness_to_alpha(ur); vr = roughness_to_alpha(vr); }
-        auto tag = [&](LobeRec& l, uint32_t alt) { l.alt = alt; l.ur_raw = mp.raw_ur; l.vr_raw = mp.raw_vr; set_tr(l, ur, vr); };
-        LobeRec f = lobe(PH_LK_FRESNEL_SPEC, T_REFL | T_TRANS | T_SPEC); std::memcpy(f.r, r, 12); std::memcpy(f.t, t, 12); f.r_tex1 = rtex1; f.t_tex1 = ttex1; f.eta_a = 1.0f; f.eta_b = mp.raw_eta;
-        tag(f, 1u);
-        mp.lobe[2] = 0; mp.field[2] = 0; mp.lobe[3] = 0; mp.field[3] = 1;
-        lobes.push_back(f);
-        if (has_r) { LobeRec l = lobe(PH_LK_MICRO_R, T_REFL | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = mp.raw_eta; std::memcpy(l.r, r, 12); l.r_tex1 = rtex1; tag(l, 2u);
-                     mp.lobe2[2] = (int)lobes.size(); mp.field2[2] = 0; lobes.push_back(l); }
-        if (has_t) { LobeRec l = lobe(PH_LK_MICRO_T, T_TRANS | T_GLOSSY); l.fresnel = PH_FR_DIEL; l.eta_a = 1.0f; l.eta_b = mp.raw_eta; std::memcpy(l.t, t, 12); l.t_tex1 = ttex1; tag(l, 2u);
-                     mp.lobe2[3] = (int)lobes.size(); mp.field2[3] = 1; lobes.push_back(l); }
-    }
-    m.lobe_base = (uint32_t)s->lobes.size(); m.n_lobes = (uint32_t)lobes.size();
-    s->lobes.insert(s->lobes.end(), lobes.begin(), lobes.end());
-    mp.rebuilt = true;
-    return PBRT_HIP_OK;
-}
-}  // namespace phost
-
-extern "C" {
 
 // "the intersection is bogus" (triangle.rs:548-574): depends only on the triangle, so it is decided once here.
 static bool triangle_is_bogus(hm::V3 p0, hm::V3 p1, hm::V3 p2, const float* uv0, const float* uv1, const float* uv2) {
@@ -885,7 +545,7 @@ int pbrt_hip_add_mesh(PbrtHipScene* s, const float* P, uint32_t n_verts, const u
                       float shadow_alpha) {
     return ph_guard(s, "pbrt_hip_add_mesh", [&]() -> int {
     if (!s || !P || !indices) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_mesh: null argument");
-    if (material_id >= s->materials.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_mesh: unknown material id");
+    if (material_id >= s->mats.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_mesh: unknown material id");
     for (uint32_t i = 0; i < 3 * n_tris; i++)
         if (indices[i] >= n_verts) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_mesh: vertex index out of bounds (triangle.rs:252-261)");
     if (first_area_light_id >= 0) {
@@ -955,7 +615,7 @@ static void quadric_world_bound(const float o2w_m[16], const float obj_lo[3], co
 }
 static int add_quadric_common(PbrtHipScene* s, const char* what, QuadricRec& q, const float o2w_m[16], const float o2w_minv[16], const float obj_lo[3], const float obj_hi[3],
                               uint32_t material_id, uint32_t flags) {
-    if (material_id >= s->materials.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": unknown material id");
+    if (material_id >= s->mats.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": unknown material id");
     if (s->open_object >= 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, std::string(what) + ": quadric shapes inside an object definition are not supported");
     if (!s->lights.empty() && s->lights.back().type == PH_L_AREA && s->lights.back().prim == 0xFFFFFFFFu)
         return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, std::string(what) + ": a quadric cannot be the shape of a diffuse area light (the unclaimed area lights created last would be its); attach them to a mesh");
@@ -1417,9 +1077,10 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
     // material classes (shade-side sorting key): materials with the same sequence of lobe kinds share a class; at most 7 classes
     {
         std::vector<uint64_t> sigs;
-        for (MaterialRec& m : s->materials) {
+        for (phost::MaterialHost::Item& it : s->mats.items) {
+            MaterialRec& m = it.rec;
             uint64_t sig = 1;
-            for (uint32_t k = 0; k < m.n_lobes; k++) sig = sig * 8 + (s->lobes[m.lobe_base + k].kind + 1);
+            for (const LobeRec& l : it.lobes) sig = sig * 8 + (l.kind + 1);
             size_t c = 0;
             while (c < sigs.size() && sigs[c] != sig) c++;
             if (c == sigs.size()) sigs.push_back(sig);
@@ -1431,7 +1092,7 @@ int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_nod
     std::vector<uint32_t> build_flags(s->tri_flags);
     for (size_t t = 0; t < build_flags.size(); t++) {   // shade-side sorting keys travel in the TriRec: the material's class and its id (scene_types.h)
         const uint32_t mat = s->meshes[s->tri_mesh[t]].material;
-        build_flags[t] |= (s->materials[mat].sort_class << PH_TRI_CLASS_SHIFT) | (std::min<uint32_t>(mat, 0xFFFu) << PH_TRI_MAT_SHIFT);
+        build_flags[t] |= (s->mats.items[mat].rec.sort_class << PH_TRI_CLASS_SHIFT) | (std::min<uint32_t>(mat, 0xFFFu) << PH_TRI_MAT_SHIFT);
     }
     phost::BuildInput in;
     in.P = s->P.data(); in.idx = s->idx.data(); in.n_tris = s->idx.size() / 3; in.tri_flags = build_flags.data(); in.tri_mesh = s->tri_mesh.data();

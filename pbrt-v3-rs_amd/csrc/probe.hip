@@ -214,13 +214,13 @@ int pbrt_hip_bsdf_probe_batch(PbrtHipScene* s, uint32_t material, int op, int pa
                               float* out) {
     return ph_guard(s, "pbrt_hip_bsdf_probe_batch", [&]() -> int {
     if (!s || (n && (!wo || !wi || !u || !flags || !out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "bsdf_probe_batch: null argument");
-    if (material >= s->materials.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "bsdf_probe_batch: unknown material");
+    if (material >= s->mats.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "bsdf_probe_batch: unknown material");
     if (op < 0 || op > 2 || path < 0 || path > 1) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "bsdf_probe_batch: op must be 0, 1 or 2 and path 0 or 1");
     if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "bsdf_probe_batch: too many probes");
-    const MaterialRec& m = s->materials[material];
+    const MaterialRec& m = s->mats.items[material].rec;
     if (material_reads_a_texture(m)) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "bsdf_probe_batch: the material takes a parameter from a texture (its BSDF differs from hit to hit)");
     if (path == 1) {
-        if (s->material_params[material].made_as != 6) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "bsdf_probe_batch: path 1 is the one-lobe BSDF of MatteMaterial; this material is not matte");
+        if (s->mats.items[material].spec.kind != phost::MaterialKind::Matte) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "bsdf_probe_batch: path 1 is the one-lobe BSDF of MatteMaterial; this material is not matte");
         for (uint64_t i = 0; i < n; i++)
             if ((flags[i] & 5u) != 5u) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "bsdf_probe_batch: path 1 has no flags; every flags[i] must hold REFLECTION | DIFFUSE");
     }

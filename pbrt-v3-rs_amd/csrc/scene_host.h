@@ -4,6 +4,7 @@
 #include "band_plan.h"
 #include "bvh_build.h"
 #include "guard.h"
+#include "material_host.h"
 #include "raysort_plan.h"
 #include "scene_types.h"
 #include "shade_shapes.h"
@@ -30,22 +31,15 @@ struct SceneHostState {
     std::vector<QuadricRec> quadrics;
     std::vector<float> quadric_bounds;
     std::vector<uint32_t> prim_quadric;
-    std::vector<MaterialRec> materials;
-    std::vector<LobeRec> lobes;
+    phost::MaterialHost mats;        // every material's description, record and lobe list (material_host.h); the device arrays are laid out at upload
     // textures: every texture id owns a flattened postfix program (its children's programs followed by its own op)
     struct TextureHost { std::vector<TexOp> prog; int stack_need = 1; };
     std::vector<TextureHost> textures;
     std::vector<MipRec> mipmaps;
     std::vector<Texel> texels;
-    // which lobe and which of its two colours each texturable parameter of a material feeds (set_material_texture); -1 = that lobe was not made
-    struct MaterialParams { int lobe[4] = {-1, -1, -1, -1}; int field[4] = {0, 0, 0, 0}; int lobe2[4] = {-1, -1, -1, -1}; int field2[4] = {0, 0, 0, 0}; bool has_pre = false; float pre[3] = {1, 1, 1}; int rough_lobe = -1, rough_lobe2 = -1; bool rough_remap = false;
-                            // what the material was made from, for the setters that rebuild the lobe list (uber opacity / glass roughness textures), and the mix's split
-                            int made_as = 0;  /* 0 other, 1 uber, 2 glass, 3 metal, 4 mix, 5 translucent, 6 matte */ float raw_k[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}; float raw_eta = 1.5f, raw_ur = 0, raw_vr = 0;
-                            bool raw_remap = false, rebuilt = false; int mix_n1 = 0; };  // [Kd, Ks, Kr, Kt]; field 0 = r, 1 = t; pre: uber's opacity; lobe2 / field2 / rough_lobe2: a second lobe fed by the same parameter (translucent's reflection + transmission pair); rough_lobe: owner of the Trowbridge-Reitz distribution
-    std::vector<MaterialParams> material_params;
     bool alpha_textures = false;      // some mesh has an alpha / shadowalpha texture: traversal uses the ALPHA kernel variants
     bool alpha_lean = false;          // ... and all of them are constants / uv-mapped image maps / scale / mix: the inlined test (set at upload)
-    bool bump_materials = false;      // some material has a bump map
+    bool bump_materials = false;      // some material has a bump map (these four: material_changed, after every change to a material; other scene content sets some of them too)
     bool textured_materials = false;  // some material evaluates a texture per hit
     bool has_none_material = false;  // some material is "none": paths may need more wavefront iterations than max_depth + 1
     bool general_materials = false;  // some material is not matte: the renderer uses the general BSDF kernel
@@ -124,6 +118,14 @@ int set_err(PbrtHipScene* s, int code, const std::string& msg);
 int hip_fail(PbrtHipScene* s, hipError_t e, const char* what);
 int ensure_buf(PbrtHipScene* s, DevBuf& b, size_t bytes);
 int upload_scene(PbrtHipScene* s);
+// after a call that changes s->mats (material_host.h): a refusal's message (nothing has changed then); else the scene flags take the materials' and the device copy is stale
+inline int material_changed(PbrtHipScene* s, int rc, const std::string& why) {
+    if (rc) return set_err(s, rc, why);
+    const MaterialFlags f = s->mats.flags();
+    s->general_materials |= f.general; s->textured_materials |= f.textured; s->bump_materials |= f.bump; s->has_none_material |= f.has_none;
+    s->uploaded = false;
+    return PBRT_HIP_OK;
+}
 // a texture program of constants, uv-mapped image maps, scale and mix only: what the lean alpha test (alpha_prog_r), the texture pass's SIMPLE evaluator and the texture probes' variants 2 to 4 admit
 inline bool tex_prog_is_simple(const std::vector<TexOp>& prog) {
     for (const TexOp& op : prog)
@@ -151,9 +153,6 @@ int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t 
 int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, void** keep_nodes = nullptr, void** keep_tris = nullptr,
                      const ForestSpec* forest = nullptr, std::vector<ForestTreeOut>* trees_out = nullptr);
 void free_tree_dev(PbrtHipScene* s);
-int uber_rebuild_for_opacity(PbrtHipScene* s, uint32_t material);    // api.hip: lobe lists remade when a structural parameter becomes a texture
-int glass_rebuild_for_roughness(PbrtHipScene* s, uint32_t material);
-int translucent_rebuild_rt(PbrtHipScene* s, uint32_t material);      // api.hip: TranslucentMaterial -> its per-hit form (a reflect / transmit texture)
 // wavefront.hip: the renderer's building blocks, shared with the multi-device driver (multi.hip)
 #define PH_MAX_TILE_PARTS 64
 int check_render_args(PbrtHipScene* s, int max_depth, int light_strategy, const int* pixel_bounds, int tile_size, int part, int parts);

@@ -307,124 +307,38 @@ int pbrt_hip_set_texture_mapping(PbrtHipScene* s, uint32_t texture, int kind, co
 }
 // Replaces a material's constant colour parameter by a texture evaluated at every hit.  The material must have been created with a non-black
 // constant for that parameter (so that its lobe exists); which lobes a hit finally gets follows the reference's `is_black` tests on the
-// texture's value at that hit.
+// texture's value at that hit.  Which materials take which parameter, and what a texture changes about the lobe list: material_host.cpp.
 int pbrt_hip_set_material_texture(PbrtHipScene* s, uint32_t material, int param, uint32_t texture) {
     return ph_guard(s, "pbrt_hip_set_material_texture", [&]() -> int {
-    if (!s || material >= s->materials.size() || texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_texture: unknown material or texture");
-    if (param < 0 || param > 9) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_texture: param must be PBRT_HIP_PARAM_KD / KS / KR / KT / OPACITY / AMOUNT / ETA / K / REFLECT / TRANSMIT");
-    if (param >= PBRT_HIP_PARAM_OPACITY) {   // parameters that are not one lobe's colour
-        PbrtHipScene::MaterialParams& mq = s->material_params[material];
-        if (param == PBRT_HIP_PARAM_REFLECT || param == PBRT_HIP_PARAM_TRANSMIT) {   // translucent.rs:70-71
-            if (mq.made_as != 5) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_texture: reflect / transmit belong to TranslucentMaterial");
-            const int rc = translucent_rebuild_rt(s, material);
-            if (rc) return rc;
-            MaterialRec& mt = s->materials[material];
-            (param == PBRT_HIP_PARAM_REFLECT ? mt.refl_tex1 : mt.trans_tex1) = texture + 1u;
-            s->uploaded = false;
-            return PBRT_HIP_OK;
-        }
-        MaterialRec& mm = s->materials[material];
-        if (param == PBRT_HIP_PARAM_OPACITY) {      // uber.rs:126-160
-            if (mq.made_as != 1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_texture: opacity belongs to UberMaterial");
-            const int rc = uber_rebuild_for_opacity(s, material);
-            if (rc) return rc;
-            mm.opacity_tex1 = texture + 1u;
-        } else if (param == PBRT_HIP_PARAM_AMOUNT) {  // mix.rs:59-60
-            if (mq.made_as != 4) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_texture: amount belongs to MixMaterial");
-            uint32_t cols = 1;
-            for (uint32_t i = 0; i < mm.n_lobes; i++) {
-                LobeRec& l = s->lobes[mm.lobe_base + i];
-                l.amt = ((int)i < mq.mix_n1 ? 1u : 2u) | ((l.n_scale - 1u) << 8);
-                cols += (l.r_tex1 || (l.has_pre == PH_PRE_OPACITY && l.kind != PH_LK_SPEC_T) ? 1u : 0u) + (l.t_tex1 || (l.has_pre == PH_PRE_OPACITY && l.kind == PH_LK_SPEC_T) || l.has_pre == PH_PRE_PASSTHROUGH ? 1u : 0u) +
-                        (l.eta_tex1 ? 1u : 0u) + (l.k_tex1 ? 1u : 0u);
-            }
-            if (cols > PH_HIT_COLS || mm.n_lobes > PH_HIT_LOBES) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_texture: a mix with a textured amount may have at most 5 more per-hit colours");
-            mm.amount_tex1 = texture + 1u;
-        } else {                                     // metal.rs:121-125
-            if (mq.made_as != 3) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_texture: eta / k belong to MetalMaterial");
-            LobeRec& l = s->lobes[mm.lobe_base];
-            (param == PBRT_HIP_PARAM_ETA ? l.eta_tex1 : l.k_tex1) = texture + 1u;
-        }
-        mm.textured = 1u;
-        s->textured_materials = true;
-        s->uploaded = false;
-        return PBRT_HIP_OK;
-    }
-    const PbrtHipScene::MaterialParams& mp = s->material_params[material];
-    if (mp.lobe[param] < 0)
-        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_texture: this material has no lobe fed by that parameter (matte Kd, plastic Kd / Ks, mirror Kr, substrate Kd / Ks, "
-                                                   "glass Kr / Kt, uber Kd / Ks / Kr / Kt and translucent Kd / Ks take textures; create the material with a non-black placeholder for the parameter)");
-    MaterialRec& m = s->materials[material];
-    const int fed[2] = {mp.lobe[param], mp.lobe2[param]}, fields[2] = {mp.field[param], mp.field2[param]};
-    for (int k = 0; k < 2; k++) if (fed[k] >= 0) {
-        LobeRec& l = s->lobes[m.lobe_base + (uint32_t)fed[k]];
-        if (fields[k] == 0) l.r_tex1 = texture + 1u; else l.t_tex1 = texture + 1u;
-        if (mp.has_pre && l.has_pre < PH_PRE_OPACITY) { l.has_pre = 1u; std::memcpy(l.pre, mp.pre, 12); }
-        if ((l.kind == PH_LK_LAMBERT || l.kind == PH_LK_OREN) && m.n_lobes == 1u && l.has_pre == 0u) m.kd_tex1 = texture + 1u;  // MatteMaterial: the one-lobe kernel reads kd_tex1
-    }
-    m.textured = 1u;
-    s->textured_materials = true;
-    s->uploaded = false;
-    return PBRT_HIP_OK;
+    if (!s || material >= s->mats.size() || texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_texture: unknown material or texture");
+    std::string why;
+    return material_changed(s, set_colour_texture(s->mats, material, param, texture, why), why);
     });
 }
-// Replaces a scalar parameter by a float texture evaluated at every hit: MatteMaterial's sigma (matte.rs:64-70) or the Trowbridge-Reitz roughness of plastic / uber /
-// substrate / metal (remapped per hit when the material was created with remap_roughness).  fparam: 0 sigma, 1 uroughness, 2 vroughness (plastic's single `roughness`: set both).
+// Replaces a scalar parameter by a float texture evaluated at every hit: MatteMaterial's sigma (matte.rs:64-70), the Trowbridge-Reitz roughness of plastic / uber / substrate /
+// metal / translucent / glass (remapped per hit when the material was created with remap_roughness) or the index of refraction of glass / uber.
+// fparam: 0 sigma, 1 uroughness, 2 vroughness (plastic's single `roughness`: set both), 3 index.
 int pbrt_hip_set_material_float_texture(PbrtHipScene* s, uint32_t material, int fparam, uint32_t texture) {
     return ph_guard(s, "pbrt_hip_set_material_float_texture", [&]() -> int {
-    if (!s || material >= s->materials.size() || texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_float_texture: unknown material or texture");
-    if (fparam < 0 || fparam > 3) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_float_texture: fparam must be 0 sigma, 1 uroughness, 2 vroughness or 3 index");
-    if (fparam == 3) {   // `let eta = self.index.evaluate(..)` (glass.rs:102) / `let e = self.index.evaluate(..)` (uber.rs:128): every dielectric lobe of the hit takes it
-        const int made_as = s->material_params[material].made_as;
-        if (made_as != 1 && made_as != 2) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_float_texture: index belongs to GlassMaterial and UberMaterial");
-        if (made_as == 1 && !s->materials[material].opacity_tex1) {
-            // UberMaterial decides BSDF::eta and the pass-through lobe per hit once anything about them is per hit: the constant opacity becomes a constant texture (same values at every hit)
-            const PbrtHipScene::MaterialParams mq = s->material_params[material];
-            const float one[3] = {1.0f, 1.0f, 1.0f};
-            uint32_t op_tex = 0;
-            int rc = pbrt_hip_add_texture_constant(s, mq.has_pre ? mq.pre : one, &op_tex);
-            if (rc == PBRT_HIP_OK) rc = pbrt_hip_set_material_texture(s, material, PBRT_HIP_PARAM_OPACITY, op_tex);
-            if (rc) return rc;
-        }
-        MaterialRec& mi = s->materials[material];
-        if (mi.n_lobes == 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_float_texture: this material has no lobe (black Kr and Kt)");
-        mi.index_tex1 = texture + 1u; mi.textured = 1u;
-        s->textured_materials = true; s->general_materials = true;
-        s->uploaded = false;
-        return PBRT_HIP_OK;
-    }
-    MaterialRec& m = s->materials[material];
-    const PbrtHipScene::MaterialParams& mp = s->material_params[material];
-    if (fparam == 0) {
-        if (m.none || m.n_lobes != 1u || !(s->lobes[m.lobe_base].kind == PH_LK_LAMBERT || s->lobes[m.lobe_base].kind == PH_LK_OREN))
-            return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_float_texture: sigma belongs to MatteMaterial (created with a non-black Kd)");
-        s->lobes[m.lobe_base].sigma_tex1 = texture + 1u; m.sigma_tex1 = texture + 1u;
-    } else if (mp.made_as == 2) {   // glass: both alternatives carry the textures (the smooth one for its `== 0` test), glass.rs:110-141
-        const int rc = glass_rebuild_for_roughness(s, material);
+    if (!s || material >= s->mats.size() || texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_float_texture: unknown material or texture");
+    float opacity[3];
+    if (fparam == phost::PH_FPARAM_INDEX && uber_index_needs_opacity(s->mats, material, opacity)) {
+        // UberMaterial decides BSDF::eta and the pass-through lobe per hit once anything about them is per hit: the constant opacity becomes a constant texture (same values at every hit)
+        uint32_t op_tex = 0;
+        int rc = pbrt_hip_add_texture_constant(s, opacity, &op_tex);
+        if (rc == PBRT_HIP_OK) rc = pbrt_hip_set_material_texture(s, material, PBRT_HIP_PARAM_OPACITY, op_tex);
         if (rc) return rc;
-        MaterialRec& mg = s->materials[material];
-        if (mg.n_lobes == 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_float_texture: this glass has neither reflection nor transmission");
-        for (uint32_t i = 0; i < mg.n_lobes; i++) { LobeRec& l = s->lobes[mg.lobe_base + i]; (fparam == 1 ? l.ax_tex1 : l.ay_tex1) = texture + 1u; l.remap = s->material_params[material].raw_remap ? 1u : 0u; }
-    } else {
-        if (mp.rough_lobe < 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "set_material_float_texture: this material has no microfacet lobe whose roughness could be textured (plastic, uber, substrate, translucent and metal have; glass switches lobes on roughness == 0 and is not wired)");
-        const int rl[2] = {mp.rough_lobe, mp.rough_lobe2};
-        for (int k = 0; k < 2; k++) if (rl[k] >= 0) { LobeRec& l = s->lobes[m.lobe_base + (uint32_t)rl[k]]; (fparam == 1 ? l.ax_tex1 : l.ay_tex1) = texture + 1u; l.remap = mp.rough_remap ? 1u : 0u; }
     }
-    m.textured = 1u;
-    s->textured_materials = true;
-    s->uploaded = false;
-    return PBRT_HIP_OK;
+    std::string why;
+    return material_changed(s, set_float_texture(s->mats, material, fparam, texture, why), why);
     });
 }
 // Material::bump's displacement texture (core/src/material.rs:62-101; the `bumpmap` parameter every material takes)
 int pbrt_hip_set_material_bump(PbrtHipScene* s, uint32_t material, uint32_t texture) {
     return ph_guard(s, "pbrt_hip_set_material_bump", [&]() -> int {
-    if (!s || material >= s->materials.size() || texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_bump: unknown material or texture");
-    if (s->materials[material].none) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_bump: Material \"none\" has no BSDF to bump");
-    s->materials[material].bump_tex1 = texture + 1u;
-    s->textured_materials = true; s->bump_materials = true;
-    s->uploaded = false;
-    return PBRT_HIP_OK;
+    if (!s || material >= s->mats.size() || texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "set_material_bump: unknown material or texture");
+    std::string why;
+    return material_changed(s, set_bump_texture(s->mats, material, texture, why), why);
     });
 }
 int pbrt_hip_add_material_matte_tex(PbrtHipScene* s, uint32_t kd_tex, float sigma_deg, uint32_t* out_id) {  // matte.rs:47-76, Kd a texture

@@ -1119,7 +1119,7 @@ static int bind_path_frame(PbrtHipScene* s, const PathPlan& p, int max_depth, fl
     wp.cam = s->cam; wp.sp = s->sampler;
     wp.textured = s->textured_materials ? 1u : 0u; wp.cam_dev = nullptr; wp.tex_out = nullptr;
     wp.any_rt = 0u;
-    for (const MaterialRec& mr : s->materials) if (mr.rt_mode) wp.any_rt = 1u;
+    for (const phost::MaterialHost::Item& it : s->mats.items) if (it.rec.rt_mode) wp.any_rt = 1u;
     if (s->textured_materials) {
         if ((rc = ensure_buf(s, w.d_cam, sizeof(CameraRec)))) return rc;
         PH_CHECK(s, hipMemcpyAsync(w.d_cam.p, &s->cam, sizeof(CameraRec), hipMemcpyHostToDevice, s->stream));

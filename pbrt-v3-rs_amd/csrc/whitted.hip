@@ -51,7 +51,7 @@ size_t whitted_chunk_bytes_per_sample(uint32_t n_frames) { WhittedWorkspace w; r
 // a single vertex with neither.
 static long long whitted_dimension_bound(const PbrtHipScene* s, int max_depth) {
     bool refl = false, trans = false;
-    for (const LobeRec& l : s->lobes) if (l.type & ph::BX_SPEC) { refl = refl || (l.type & ph::BX_REFL); trans = trans || (l.type & ph::BX_TRANS); }
+    for (const phost::MaterialHost::Item& it : s->mats.items) for (const LobeRec& l : it.lobes) if (l.type & ph::BX_SPEC) { refl = refl || (l.type & ph::BX_REFL); trans = trans || (l.type & ph::BX_TRANS); }
     const int d = std::max(max_depth, 1);
     long long vertices = 1, inner = d > 1 ? 1 : 0;
     if (refl && trans) { vertices = (1ll << d) - 1; inner = (1ll << (d - 1)) - 1; }

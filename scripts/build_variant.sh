@@ -8,7 +8,7 @@ B=$R/gpurun_out/build_$NAME; mkdir -p $B
 FLAGS="-std=c++17 -O3 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-result -pthread $EXTRA"
 cd $R/pbrt-v3-rs_amd/csrc
 for f in api textures_api wavefront multi bvh_device bvh_sah_device; do /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o $B/$f.o & done
-for f in bvh_build host_setup; do /opt/rocm/bin/hipcc $FLAGS -x hip -c $f.cpp -o $B/$f.o & done
+for f in bvh_build host_setup material_host; do /opt/rocm/bin/hipcc $FLAGS -x hip -c $f.cpp -o $B/$f.o & done
 wait
 /opt/rocm/bin/hipcc $FLAGS -shared -o $R/pbrt-v3-rs_amd/libpbrt_hip_$NAME.so $B/*.o -ldl
 echo built $R/pbrt-v3-rs_amd/libpbrt_hip_$NAME.so

@@ -204,6 +204,31 @@ def test_device_textured_parameter_films_bit_exact(host, name, mat, instance):
     assert _same(g, o), f"{name}: {(g[0].view(np.uint32) != o[0].view(np.uint32)).any(axis=2).sum()} pixels differ, counters {g[2]} vs {o[2]}"
 
 
+def glass_black_kr(kr_first):
+    """A smooth glass whose Kr is black but for an image texture, with constant-texture roughness 0.2 / 0.1: the rough alternative's reflection lobe exists because of the
+    texture alone (glass.rs:110-141 evaluates Kr at the hit), whichever of the setters is called first."""
+    def make(sc):
+        m = sc.add_material_glass((0.0, 0.0, 0.0), (0.8, 0.85, 0.9), 0.0, 0.0, 1.5, True)
+        def kr(): sc.set_material_texture(m, "Kr", image(16)(sc))
+        def rough():
+            sc.set_material_float_texture(m, "uroughness", const(0.2)(sc))
+            sc.set_material_float_texture(m, "vroughness", const(0.1)(sc))
+        for call in ((rough,) if kr_first is None else (kr, rough) if kr_first else (rough, kr)): call()
+        return m
+    return make
+
+
+@pytest.mark.gpu
+def test_device_glass_film_does_not_depend_on_the_order_of_its_texture_setters(host):
+    first = _film(pbrt_hip.Scene, host, glass_black_kr(True))
+    last = _film(pbrt_hip.Scene, host, glass_black_kr(False))
+    assert float(first[0].max()) > 0
+    assert _same(first, last), f"{(first[0].view(np.uint32) != last[0].view(np.uint32)).any(axis=2).sum()} pixels differ, counters {first[2]} vs {last[2]}"
+    o = _film(OracleScene, host, glass_black_kr(True))      # (the oracle takes the reference's order: the Kr texture is there when the roughness textures split the list)
+    assert _same(first, o), f"{(first[0].view(np.uint32) != o[0].view(np.uint32)).any(axis=2).sum()} pixels differ from the oracle's, counters {first[2]} vs {o[2]}"
+    assert not _same(o, _film(OracleScene, host, glass_black_kr(None)))      # ... and the film shows that lobe: without the Kr texture it is another
+
+
 def test_oracle_checkerboard_index_is_one_of_the_two_constants_per_pixel(host):
     """A glass floor whose index of refraction is a checkerboard of 1.2 and 1.9, seen at depth 1 with one sample per pixel: a pixel whose sample lands on a square of one
     kind shows exactly the film of the glass made with that constant (the Fresnel term, and with it the lobe choice and the reflected radiance, depend on the index)."""
