@@ -551,6 +551,21 @@ int pbrt_hip_bump_probe_batch(PbrtHipScene*, uint32_t texture, int variant, uint
  * pbrt_hip_intersect_batch.  Nothing is launched on a refusal and the handle stays usable. */
 int pbrt_hip_traverse_probe(PbrtHipScene*, int mode, const PbrtHipRay* rays_cl, uint32_t n_cl, const PbrtHipRay* rays_sh, uint32_t n_sh, const uint32_t* order /* NULL or n_cl + n_sh */,
                             uint32_t n_heads, uint32_t head_chunk, uint32_t blocks, PbrtHipHit* hits_out /* n_cl */, uint8_t* occluded_out /* n_sh */);
+/* pbrt_hip_film_probe: the film side of a render (FilmTile::add_sample per tile, Film::merge_film_tile) on explicit camera samples instead of an integrator's.  Needs
+ * pbrt_hip_set_film and a sampler (for its samples per pixel); no accelerator.  The tiles t with t % tile_parts == tile_part, their pixel list, the bands under
+ * pbrt_hip_set_sample_record_budget, the record buffers, the film pass and the merge are the render's own.
+ * pbrt_hip_film_probe_layout: out[0] = n_px, the length of this part's pixel list (tile by tile in increasing index, row-major inside a tile), out[1] = its tiles,
+ * out[2], out[3] = width and height of a tile's slot in the tile buffer (4 floats per slot pixel: contribution rgb, weight sum; a tile's pixel (x, y) at row y - pb[1], column
+ * x - pb[0] of its slot, the rest of the slot zero); out_px_xy (NULL or 2 n_px) = the list's pixels; out_tile_pb (NULL or 4 per tile) = every tile's FilmTile pixel bounds.
+ * pbrt_hip_film_probe: L[spp][n_px][3] radiance and p_film[spp][n_px][2] film positions in that order; a NaN p_film x means "no sample taken" (a pixel outside an integrator's
+ * pixel bounds).  d_tile_buffer: a DEVICE buffer of pbrt_hip_tile_buffer_floats floats for this part's tiles, or NULL for the handle's own.  out_xyz / out_weight (both or
+ * neither; only with d_tile_buffer NULL): the film of this part's tiles alone, as pbrt_hip_render_path gives it.  out_tiles: NULL or a host copy of the tile buffer.
+ * PBRT_HIP_ERR_INVALID_ARG, before anything is launched and leaving the handle usable: a null argument; a bad partition; n_px other than the list's length; a position outside
+ * [x, x + 1] x [y, y + 1] of its pixel (the upper ends are positions that float32 rounded up onto the next pixel: the film pass rests on this bound); a non-finite radiance
+ * (the integrators zero those before they record a sample).  PBRT_HIP_ERR_STATE: no film or no sampler. */
+int pbrt_hip_film_probe_layout(PbrtHipScene*, int tile_size, int tile_part, int tile_parts, uint64_t out[4], int32_t* out_px_xy, int32_t* out_tile_pb);
+int pbrt_hip_film_probe(PbrtHipScene*, int tile_size, int tile_part, int tile_parts, uint64_t n_px, const float* L, const float* p_film, void* d_tile_buffer, float* out_xyz,
+                        float* out_weight, float* out_tiles);
 
 #ifdef __cplusplus
 }

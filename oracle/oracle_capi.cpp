@@ -970,6 +970,50 @@ int oracle_render_path_ex(OracleScene* s, int max_depth, float rr_threshold, int
     if (out_nv_nt) { out_nv_nt[0] = r.total_stats.nv_regular; out_nv_nt[1] = r.total_stats.nt_regular; out_nv_nt[2] = r.total_stats.nv_shadow; out_nv_nt[3] = r.total_stats.nt_shadow; }
     return 0;
 }
+// The film side alone on explicit camera samples (Renderer::film_probe): what pbrt_hip_film_probe runs on the device.  Needs set_film and a sampler (for spp) only.
+// oracle_film_probe_layout: out[0] = pixels of the part's list, out[1] = its tiles, out[2] = floats of all its tiles packed (4 per tile pixel: contribution rgb, weight sum;
+// row-major inside a tile's pixel bounds, tiles in increasing index), out[3] = 0; out_px_xy (NULL or 2 per pixel), out_tile_pb (NULL or 4 per tile).
+static bool film_probe_args(OracleScene* s, int tile_size, int tile_part, int tile_parts) {
+    if (tile_size <= 0 || tile_parts <= 0 || tile_part < 0 || tile_part >= tile_parts) { s->err = "film_probe: bad tile partition"; return false; }
+    return true;
+}
+int oracle_film_probe_layout(OracleScene* s, int tile_size, int tile_part, int tile_parts, uint64_t out[4], int32_t* out_px_xy, int32_t* out_tile_pb) {
+    if (!s || !out) return -1;
+    if (!film_probe_args(s, tile_size, tile_part, tile_parts)) return -1;
+    if (!s->have_film) { s->err = "film_probe_layout: set_film first"; return -2; }
+    const Renderer& r = s->r;
+    int sb[4]; r.sample_bounds(sb);
+    const int ntx = pmax((sb[2] - sb[0] + tile_size - 1) / tile_size, 0), nty = pmax((sb[3] - sb[1] + tile_size - 1) / tile_size, 0);
+    uint64_t n_px = 0, n_tiles = 0, floats = 0;
+    for (int t = tile_part; t < ntx * nty; t += tile_parts) {
+        int tb[4]; r.tile_bounds(t, ntx, sb, tile_size, tb);
+        const Renderer::FilmTile ft = r.get_film_tile(tb);
+        if (out_tile_pb) for (int i = 0; i < 4; i++) out_tile_pb[4 * n_tiles + i] = ft.b[i];
+        Bounds2i::raw(tb[0], tb[1], tb[2], tb[3]).for_each([&](int x, int y) { if (out_px_xy) { out_px_xy[2 * n_px] = x; out_px_xy[2 * n_px + 1] = y; } n_px++; });
+        n_tiles++; floats += 4 * (uint64_t)ft.wsum.size();
+    }
+    out[0] = n_px; out[1] = n_tiles; out[2] = floats; out[3] = 0;
+    return 0;
+}
+int oracle_film_probe(OracleScene* s, int tile_size, int tile_part, int tile_parts, uint64_t n_px, const float* L, const float* p_film, void* d_tile_buffer /* the product's: NULL here */,
+                      float* out_xyz, float* out_weight, float* out_tiles) {
+    if (!s || (n_px && (!L || !p_film)) || (!out_xyz != !out_weight) || d_tile_buffer) return -1;
+    if (!film_probe_args(s, tile_size, tile_part, tile_parts)) return -1;
+    if (!s->have_film || !s->have_sampler || s->r.scfg.spp == 0) { s->err = "film_probe: set_film and set_sampler first"; return -2; }
+    uint64_t lay[4];
+    if (int rc = oracle_film_probe_layout(s, tile_size, tile_part, tile_parts, lay, nullptr, nullptr)) return rc;
+    if (lay[0] != n_px) { s->err = "film_probe: n_px is not the length of this part's pixel list"; return -1; }
+    std::vector<Renderer::FilmTile> tiles;
+    s->r.film_probe(tile_size, tile_part, tile_parts, s->r.scfg.spp, (size_t)n_px, L, p_film, out_xyz, out_weight, &tiles);
+    if (out_tiles) {
+        size_t o = 0;
+        for (size_t t = (size_t)tile_part; t < tiles.size(); t += (size_t)tile_parts)
+            for (size_t i = 0; i < tiles[t].wsum.size(); i++, o += 4) {
+                out_tiles[o] = tiles[t].contrib[3 * i]; out_tiles[o + 1] = tiles[t].contrib[3 * i + 1]; out_tiles[o + 2] = tiles[t].contrib[3 * i + 2]; out_tiles[o + 3] = tiles[t].wsum[i];
+            }
+    }
+    return 0;
+}
 int oracle_add_material_substrate(OracleScene* s, const float kd[3], const float ks[3], float urough, float vrough, int remap, uint32_t* out_id) {  // substrate.rs:55-84
     if (!s || !kd || !ks) return -1;
     Material m; m.general = true;

@@ -1748,6 +1748,52 @@ struct Renderer {
         tb[0] = b.x0; tb[1] = b.y0; tb[2] = b.x1; tb[3] = b.y1;
     }
 
+    // Film::merge_film_tile (film/mod.rs:220-279) over the part's tiles in increasing tile index; tiles = one entry per tile of the frame
+    void merge_tiles(const std::vector<FilmTile>& tiles, int tile_part, int tile_parts, Float* out_xyz, Float* out_weight) const {
+        int cw = film.crop[2] - film.crop[0], ch = film.crop[3] - film.crop[1];
+        size_t npx = (size_t)pmax(cw, 0) * pmax(ch, 0);
+        for (size_t i = 0; i < 3 * npx; i++) out_xyz[i] = 0.0f;
+        for (size_t i = 0; i < npx; i++) out_weight[i] = 0.0f;
+        for (int t = 0; t < (int)tiles.size(); t++) {
+            if (t % tile_parts != tile_part) continue;
+            const FilmTile& ft = tiles[t];
+            int w = ft.b[2] - ft.b[0];
+            for (int y = ft.b[1]; y < ft.b[3]; y++)
+                for (int x = ft.b[0]; x < ft.b[2]; x++) {
+                    size_t to = (size_t)(x - ft.b[0]) + (size_t)(y - ft.b[1]) * w;
+                    size_t fo = (size_t)(x - film.crop[0]) + (size_t)(y - film.crop[1]) * cw;
+                    Float xyz[3]; rgb_to_xyz(&ft.contrib[3 * to], xyz);
+                    out_xyz[3 * fo] += xyz[0]; out_xyz[3 * fo + 1] += xyz[1]; out_xyz[3 * fo + 2] += xyz[2];
+                    out_weight[fo] += ft.wsum[to];
+                }
+        }
+    }
+
+    // The film side alone, on explicit camera samples: over the part's tiles in increasing index get_film_tile, then add_sample over the tile's pixels row-major and per pixel by
+    // sample index (the order render_tile_with takes them in), then the merge.  L[spp][n_px][3], p_film[spp][n_px][2] in the order of the part's pixel list (tile by tile); a NaN
+    // p_film.x: no sample taken.  tiles_out: one entry per tile of the frame.
+    void film_probe(int tile_size, int tile_part, int tile_parts, uint32_t spp, size_t n_px, const Float* L, const Float* p_film, Float* out_xyz, Float* out_weight,
+                    std::vector<FilmTile>* tiles_out) const {
+        int sb[4]; sample_bounds(sb);
+        const int ntx = pmax((sb[2] - sb[0] + tile_size - 1) / tile_size, 0), nty = pmax((sb[3] - sb[1] + tile_size - 1) / tile_size, 0);
+        std::vector<FilmTile> tiles((size_t)ntx * nty);
+        size_t px = 0;
+        for (int t = tile_part; t < ntx * nty; t += tile_parts) {
+            int tb[4]; tile_bounds(t, ntx, sb, tile_size, tb);
+            tiles[t] = get_film_tile(tb);
+            Bounds2i::raw(tb[0], tb[1], tb[2], tb[3]).for_each([&](int, int) {
+                for (uint32_t k = 0; k < spp && px < n_px; k++) {
+                    const size_t o = (size_t)k * n_px + px;
+                    if (p_film[2 * o] != p_film[2 * o]) continue;
+                    add_sample(tiles[t], V2(p_film[2 * o], p_film[2 * o + 1]), Spec(L[3 * o], L[3 * o + 1], L[3 * o + 2]), 1.0f);
+                }
+                px++;
+            });
+        }
+        if (out_xyz && out_weight) merge_tiles(tiles, tile_part, tile_parts, out_xyz, out_weight);
+        if (tiles_out) *tiles_out = std::move(tiles);
+    }
+
     // SamplerIntegrator::render (sampler_integrator.rs:243-304).  Tiles are merged in increasing tile index
     // (= the reference with --nthreads 1; with more threads the reference's merge order is completion order).
     void render(int tile_size, int tile_part, int tile_parts, int n_threads, Float* out_xyz, Float* out_weight, std::vector<FilmTile>* keep_tiles = nullptr) {
@@ -1782,24 +1828,7 @@ struct Renderer {
         for (int i = 1; i < n_threads; i++) th.emplace_back(worker);
         worker();
         for (auto& t : th) t.join();
-        // Film::merge_film_tile (film/mod.rs:220-279)
-        int cw = film.crop[2] - film.crop[0], ch = film.crop[3] - film.crop[1];
-        size_t npx = (size_t)pmax(cw, 0) * pmax(ch, 0);
-        for (size_t i = 0; i < 3 * npx; i++) out_xyz[i] = 0.0f;
-        for (size_t i = 0; i < npx; i++) out_weight[i] = 0.0f;
-        for (int t = 0; t < tile_count; t++) {
-            if (t % tile_parts != tile_part) continue;
-            const FilmTile& ft = tiles[t];
-            int w = ft.b[2] - ft.b[0];
-            for (int y = ft.b[1]; y < ft.b[3]; y++)
-                for (int x = ft.b[0]; x < ft.b[2]; x++) {
-                    size_t to = (size_t)(x - ft.b[0]) + (size_t)(y - ft.b[1]) * w;
-                    size_t fo = (size_t)(x - film.crop[0]) + (size_t)(y - film.crop[1]) * cw;
-                    Float xyz[3]; rgb_to_xyz(&ft.contrib[3 * to], xyz);
-                    out_xyz[3 * fo] += xyz[0]; out_xyz[3 * fo + 1] += xyz[1]; out_xyz[3 * fo + 2] += xyz[2];
-                    out_weight[fo] += ft.wsum[to];
-                }
-        }
+        merge_tiles(tiles, tile_part, tile_parts, out_xyz, out_weight);
         if (keep_tiles) *keep_tiles = std::move(tiles);
     }
     // Film::get_pixel_rgb (film/mod.rs:392-417), splat = 0

@@ -8,6 +8,7 @@
 #include "wf_device.h"
 #include "texture.h"
 #include "sphere_light.h"
+#include "film_plan.h"
 #include <cstring>
 #include <vector>
 
@@ -161,6 +162,22 @@ __global__ __launch_bounds__(PH_TEX_LDS_THREADS) void bump_probe_kernel(DeviceSc
     bump_shading<(VARIANT & 2) != 0, (VARIANT & 1) != 0>(sc.self, tex, c, c.p, ld3(q + 15), ld3(q + 18), ld3(q + 21), ld3(q + 24), ld3(q + 27), ld3(q + 30), &b);
     float* o = out + 6 * (size_t)i;
     o[0] = b.ns.x; o[1] = b.ns.y; o[2] = b.ns.z; o[3] = b.dpdu_s.x; o[4] = b.dpdu_s.y; o[5] = b.dpdu_s.z;
+}
+
+// The film probe's stand-in for an integrator: the records of one band, [sample][pixel of the band], from the caller's arrays [sample][pixel of the rank]; a NaN p_film.x stays
+// the "no sample taken" mark.  The rounded-up mark is raygen's own (film_plan.h).
+__global__ __launch_bounds__(256) void film_probe_fill_kernel(uint32_t band_px, uint32_t px0, uint32_t rank_px, uint32_t spp, const int2* px_xy, const float* L, const float* p_film,
+                                                              float4* rec_L, float* rec_py, uint8_t* px_rounded) {
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (uint64_t)band_px * spp) return;
+    const uint32_t s = (uint32_t)(gid / band_px), pix = (uint32_t)(gid % band_px);
+    const size_t src = (size_t)s * rank_px + px0 + pix, dst = (size_t)s * band_px + pix;
+    const float px = p_film[2 * src], py = p_film[2 * src + 1];
+    if (px != px) { rec_L[dst] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0x7fc00000u)); rec_py[dst] = 0.0f; return; }
+    rec_L[dst] = make_float4(L[3 * src], L[3 * src + 1], L[3 * src + 2], px);
+    rec_py[dst] = py;
+    const int2 xy = px_xy[pix];
+    phfilm::mark_rounded_up(px_rounded, pix, xy.x, xy.y, px, py);
 }
 
 }  // namespace ph
@@ -476,6 +493,95 @@ int pbrt_hip_traverse_probe(PbrtHipScene* s, int mode, const PbrtHipRay* rays_cl
     if (n_sh) PH_CHECK(s, hipMemcpyAsync(occluded_out, d + o_occ, (size_t)n_sh, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));   // (`counts` and the caller's arrays are pageable: the copies above have left them by now)
     return traversal_overflow_check(s);
+    });
+}
+
+// The film side of a render on explicit samples: the rank's tile and pixel lists, the bands, the record buffers and the film pass are the render's own (samples_begin ..
+// samples_to_tiles, merge_own_tiles); film_probe_fill_kernel stands where an integrator would fill the records.
+namespace {
+int film_probe_args(PbrtHipScene* s, const char* who, int tile_size, int tile_part, int tile_parts) {
+    const std::string w(who);
+    if (tile_size <= 0 || tile_parts <= 0 || tile_parts > PH_MAX_TILE_PARTS || tile_part < 0 || tile_part >= tile_parts) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, w + ": bad tile partition");
+    if (!s->have_film) return set_err(s, PBRT_HIP_ERR_STATE, w + ": set_film first");
+    return PBRT_HIP_OK;
+}
+}  // namespace
+
+int pbrt_hip_film_probe_layout(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, uint64_t out[4], int32_t* out_px_xy, int32_t* out_tile_pb) {
+    return ph_guard(s, "pbrt_hip_film_probe_layout", [&]() -> int {
+    if (!s || !out) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "film_probe_layout: null argument");
+    int rc;
+    if ((rc = film_probe_args(s, "film_probe_layout", tile_size, tile_part, tile_parts))) return rc;
+    PH_CHECK(s, hipSetDevice(s->device));
+    SampleRecords rec;
+    if ((rc = samples_begin(s, tile_size, tile_part, tile_parts, &rec))) return rc;
+    const int2* px; size_t n_px; std::vector<int32_t> pb; uint32_t sw, sh;
+    film_layout(s, &px, &n_px, &pb, &sw, &sh);
+    out[0] = n_px; out[1] = pb.size() / 4; out[2] = sw; out[3] = sh;
+    if (out_px_xy) for (size_t i = 0; i < n_px; i++) { out_px_xy[2 * i] = px[i].x; out_px_xy[2 * i + 1] = px[i].y; }
+    if (out_tile_pb && !pb.empty()) std::memcpy(out_tile_pb, pb.data(), pb.size() * 4);
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_film_probe(PbrtHipScene* s, int tile_size, int tile_part, int tile_parts, uint64_t n_px, const float* L, const float* p_film, void* d_tile_buffer, float* out_xyz,
+                        float* out_weight, float* out_tiles) {
+    return ph_guard(s, "pbrt_hip_film_probe", [&]() -> int {
+    if (!s || (n_px && (!L || !p_film)) || (!out_xyz != !out_weight)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "film_probe: null argument");
+    if (d_tile_buffer && out_xyz) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "film_probe: the film comes from the handle's own tile buffer; merge a caller's buffers with pbrt_hip_merge_tiles_device");
+    int rc;
+    if ((rc = film_probe_args(s, "film_probe", tile_size, tile_part, tile_parts))) return rc;
+    if (!s->have_sampler || s->sampler.spp == 0) return set_err(s, PBRT_HIP_ERR_STATE, "film_probe: set_sampler first (its samples per pixel size the records)");
+    PH_CHECK(s, hipSetDevice(s->device));
+    SampleRecords rec;
+    if ((rc = samples_begin(s, tile_size, tile_part, tile_parts, &rec))) return rc;
+    if (n_px != rec.n_px) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "film_probe: n_px is not the length of this part's pixel list (pbrt_hip_film_probe_layout)");
+    const uint32_t spp = s->sampler.spp;
+    {   // what the film pass rests on: a sample of pixel (x, y) lies in [x, x + 1] x [y, y + 1], the upper ends being positions rounded up; the integrators zero a non-finite radiance
+        const int2* px; size_t n; std::vector<int32_t> pb; uint32_t sw, sh;
+        film_layout(s, &px, &n, &pb, &sw, &sh);
+        for (uint32_t k = 0; k < spp; k++)
+            for (size_t i = 0; i < n; i++) {
+                const size_t o = (size_t)k * n + i;
+                const float x = p_film[2 * o], y = p_film[2 * o + 1];
+                if (x != x) continue;   // no sample taken
+                if (!(x >= (float)px[i].x && x <= (float)(px[i].x + 1) && y >= (float)px[i].y && y <= (float)(px[i].y + 1)))
+                    return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "film_probe: a film position lies outside its pixel");
+                if (!std::isfinite(L[3 * o]) || !std::isfinite(L[3 * o + 1]) || !std::isfinite(L[3 * o + 2])) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "film_probe: a radiance is not finite");
+            }
+    }
+    const size_t tile_floats = tile_buffer_floats_for(s, tile_size, tile_part, tile_parts);
+    void* tiles = d_tile_buffer;
+    if (!tiles) {
+        DevBuf& own = tile_buffer_of(s);
+        if ((rc = ensure_buf(s, own, tile_floats * 4))) return rc;
+        tiles = own.p;
+    }
+    if (rec.n_px == 0) PH_CHECK(s, hipMemsetAsync(tiles, 0, tile_floats * 4, s->stream));
+    else {
+        if ((rc = samples_plan_bands(s, &rec, 0, 0))) return rc;
+        if ((rc = samples_alloc(s, &rec))) return rc;
+        const size_t n_rec = (size_t)spp * rec.n_px, o_L = 0, o_p = up256(n_rec * 12), total = o_p + up256(n_rec * 8);
+        Scratch sx;
+        PH_CHECK(s, hipMalloc(&sx.p, total));
+        char* d = static_cast<char*>(sx.p);
+        PH_CHECK(s, hipMemcpyAsync(d + o_L, L, n_rec * 12, hipMemcpyHostToDevice, s->stream));
+        PH_CHECK(s, hipMemcpyAsync(d + o_p, p_film, n_rec * 8, hipMemcpyHostToDevice, s->stream));
+        for (size_t b = 0; b < rec.bands.size(); b++) {
+            SampleRecords br;
+            if ((rc = samples_band(s, rec, b, &br))) return rc;
+            const uint64_t threads = (uint64_t)br.n_px * spp;
+            hipLaunchKernelGGL(ph::film_probe_fill_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s->stream, br.n_px, br.band.px0, rec.n_px, spp, br.px_xy,
+                               (const float*)(d + o_L), (const float*)(d + o_p), br.rec_L, br.rec_py, br.px_rounded);
+            PH_CHECK(s, hipGetLastError());
+            if ((rc = samples_to_tiles(s, br, tiles))) return rc;
+        }
+        PH_CHECK(s, hipStreamSynchronize(s->stream));   // (the caller's arrays are pageable: the copies above have left them by now; the scratch goes with this scope)
+    }
+    if (out_tiles) PH_CHECK(s, hipMemcpyAsync(out_tiles, tiles, tile_floats * 4, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    if (out_xyz) return merge_own_tiles(s, tile_size, tile_part, tile_parts, out_xyz, out_weight);
+    return PBRT_HIP_OK;
     });
 }
 

@@ -174,6 +174,8 @@ int samples_plan_bands(PbrtHipScene* s, SampleRecords* out, size_t chunk_held, s
 int samples_alloc(PbrtHipScene* s, SampleRecords* out);                                        // the records of the largest band
 int samples_band(PbrtHipScene* s, const SampleRecords& r, size_t band, SampleRecords* out);   // one band of them, px_rounded cleared
 int samples_to_tiles(PbrtHipScene* s, const SampleRecords& r, void* d_tile_buffer);            // the film pass over a band, into its tiles' slots
+// what samples_begin left for the rank: its pixel list on the host, its tiles' FilmTile pixel bounds (4 per tile, list order), the tile-buffer slot (the film probe, probe.hip)
+void film_layout(PbrtHipScene* s, const int2** px_xy, size_t* n_px, std::vector<int32_t>* tile_pb, uint32_t* slot_w, uint32_t* slot_h);
 size_t path_chunk_bytes_per_path(bool general_materials, bool textured_materials);   // what the path driver's chunk table (chunk_plan.h) sums to, for scripts/chunk_plan_check.cpp
 // whitted.hip
 void free_whitted(PbrtHipScene* s);

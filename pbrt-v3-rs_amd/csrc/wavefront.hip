@@ -27,6 +27,7 @@
 #include "matsort.h"
 #include "wf_device.h"
 #include "chunk_plan.h"
+#include "film_plan.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void raygen_kernel(DeviceScene sc, WfParams w)
             generate_camera_ray(w.cam, p_film, time, lens, ray);
             w.rec_L[gsi] = make_float4(0.0f, 0.0f, 0.0f, p_film.x);
             w.rec_py[gsi] = p_film.y;
-            if (p_film.x == (float)(xy.x + 1) || p_film.y == (float)(xy.y + 1)) w.px_rounded[pix] = 1u;   // (every writer writes the same byte)
+            phfilm::mark_rounded_up(w.px_rounded, pix, xy.x, xy.y, p_film.x, p_film.y);
             lens_keep = lens;
         } else {
             w.rec_L[gsi] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0x7fc00000u));  // NaN p_film.x marks "no sample"
@@ -716,35 +717,26 @@ __global__ __launch_bounds__(256) void film_tiles_kernel(FilmParams p) {
     if (kx < pw && ky < phh) {
         const int x = t.pb[0] + kx, y = t.pb[1] + ky;
         const float rx = p.film.radius[0], ry = p.film.radius[1];
-        // a sample at film position p reaches pixel x iff ceil(p-.5-r) <= x <= floor(p-.5+r), i.e. p in [x+.5-r, x+.5+r]; samples of
-        // pixel sx have p in [sx, sx+1), so only sx in [floor(x+.5-r), floor(x+.5+r)] can contribute (evaluated in f64: exact) ...
-        const int sx0n = (int)floor((double)x + 0.5 - (double)rx), sy0n = (int)floor((double)y + 0.5 - (double)ry);
-        // ... except that `pixel + offset` is an f32 sum: an offset within half an ulp of 1 puts the sample ON the next pixel's coordinate, p = sx + 1 (beyond x = 512
-        // every offset above 1 - 2^-15 does; at 512 spp the Halton points reach 1 - 2^-17).  Where x + .5 - r is a whole number such a sample of pixel sx0n - 1 still
-        // reaches x: that column / row is scanned too, for the samples whose position is exactly sx + 1 (round 3: found by the configs[4] crop at 512 spp)
-        const int sx0e = (int)ceil((double)x - 0.5 - (double)rx) < sx0n ? sx0n - 1 : sx0n, sy0e = (int)ceil((double)y - 0.5 - (double)ry) < sy0n ? sy0n - 1 : sy0n;
-        const int sx0 = pmaxi(sx0e, t.tb[0]), sx1 = pmini((int)floor((double)x + 0.5 + (double)rx), t.tb[2] - 1);
-        const int sy0 = pmaxi(sy0e, t.tb[1]), sy1 = pmini((int)floor((double)y + 0.5 + (double)ry), t.tb[3] - 1);
+        // which sample columns and rows of the tile can add to (x, y), in add_sample's own float32 arithmetic (film_plan.h); below .full only the samples ON the next
+        // column's / row's coordinate do (round 3: found by the configs[4] crop at 512 spp), and raygen marked the pixels that have any (a few per cent of them at 512 spp)
+        const phfilm::Reach cx = phfilm::reach_columns(x, rx, t.tb[0], t.tb[2]), cy = phfilm::reach_columns(y, ry, t.tb[1], t.tb[3]);
         const int tw = t.tb[2] - t.tb[0];
-        for (int sy = sy0; sy <= sy1; sy++)
-            for (int sx = sx0; sx <= sx1; sx++) {
+        for (int sy = cy.lo; sy <= cy.hi; sy++)
+            for (int sx = cx.lo; sx <= cx.hi; sx++) {
                 const size_t pix = (size_t)(t.px_off - p.px_base) + (size_t)(sy - t.tb[1]) * tw + (size_t)(sx - t.tb[0]);
-                const bool up_x = sx < sx0n, up_y = sy < sy0n;   // only samples rounded up onto the next column / row matter from here ...
-                if ((up_x || up_y) && !p.px_rounded[pix]) continue;   // ... and raygen noted which pixels have any (a few per cent of them at 512 spp)
+                if ((sx < cx.full || sy < cy.full) && !p.px_rounded[pix]) continue;
                 for (uint32_t s = 0; s < p.spp; s++) {
                     const float4 r = p.rec_L[(size_t)s * p.n_px + pix];   // (both loads issued before either is tested: one latency per sample, not two)
                     const float pfy = p.rec_py[(size_t)s * p.n_px + pix];
                     if (r.w != r.w) continue;  // pixel outside pixel_bounds: no sample was taken
-                    if ((up_y && pfy != (float)(sy + 1)) || (up_x && r.w != (float)(sx + 1))) continue;
                     const float pfx = r.w;
+                    // the one test that decides a contribution, before any work on the radiance (both axes evaluated, one branch)
+                    const bool in_x = phfilm::sample_reaches(pfx, rx, x, t.pb[0], t.pb[2]), in_y = phfilm::sample_reaches(pfy, ry, y, t.pb[1], t.pb[3]);
+                    if (!in_x || !in_y) continue;
                     spec l = mks(r.x, r.y, r.z);
                     const float ly = lum_y(l);
                     if (ly > p.film.max_lum) l = l * p.film.max_lum / ly;
                     const float pdx = pfx - 0.5f, pdy = pfy - 0.5f;
-                    int p0x = f2i_sat(ceilf(pdx - rx)), p0y = f2i_sat(ceilf(pdy - ry));
-                    int p1x = f2i_sat(floorf(pdx + rx)) + 1, p1y = f2i_sat(floorf(pdy + ry)) + 1;
-                    p0x = pmaxi(p0x, t.pb[0]); p0y = pmaxi(p0y, t.pb[1]); p1x = pmini(p1x, t.pb[2]); p1y = pmini(p1y, t.pb[3]);
-                    if (x < p0x || x >= p1x || y < p0y || y >= p1y) continue;
                     const float fx = pabs(((float)x - pdx) * p.film.inv_radius[0] * 16.0f);
                     const float fy = pabs(((float)y - pdy) * p.film.inv_radius[1] * 16.0f);
                     const uint32_t ix = f2u_sat(pminf(floorf(fx), 15.0f)), iy = f2u_sat(pminf(floorf(fy), 15.0f));
@@ -765,27 +757,22 @@ struct MergeParams {
     const float4* bufs[PH_MAX_TILE_PARTS];
     float* out_xyz; float* out_w;
 };
-PH_DEV void tile_pixel_bounds(const FilmRec& f, const int tb[4], int pb[4]) {  // Film::get_film_tile (film/mod.rs:182-198)
-    const int p0x = f2i_sat(ceilf((float)tb[0] - 0.5f - f.radius[0])), p0y = f2i_sat(ceilf((float)tb[1] - 0.5f - f.radius[1]));
-    const int p1x = f2i_sat(floorf((float)tb[2] - 0.5f + f.radius[0])) + 1, p1y = f2i_sat(floorf((float)tb[3] - 0.5f + f.radius[1])) + 1;
-    pb[0] = pmaxi(p0x, f.crop[0]); pb[1] = pmaxi(p0y, f.crop[1]); pb[2] = pmini(p1x, f.crop[2]); pb[3] = pmini(p1y, f.crop[3]);
-}
 __global__ __launch_bounds__(256) void merge_kernel(MergeParams p) {
     const int cw = p.film.crop[2] - p.film.crop[0], ch = p.film.crop[3] - p.film.crop[1];
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (cw <= 0 || ch <= 0 || gid >= (uint64_t)cw * ch) return;
     const int x = p.film.crop[0] + (int)(gid % cw), y = p.film.crop[1] + (int)(gid / cw);
-    const int ext_x = (int)ceilf(p.film.radius[0] + 0.5f) + 1, ext_y = (int)ceilf(p.film.radius[1] + 0.5f) + 1;
-    const int tx_lo = pmaxi((x - ext_x - p.sb[0]) / p.tile_size - 1, 0), tx_hi = pmini((x + ext_x - p.sb[0]) / p.tile_size + 1, p.ntx - 1);
-    const int ty_lo = pmaxi((y - ext_y - p.sb[1]) / p.tile_size - 1, 0), ty_hi = pmini((y + ext_y - p.sb[1]) / p.tile_size + 1, p.nty - 1);
+    int tx_lo, tx_hi, ty_lo, ty_hi;
+    phfilm::tiles_holding(x, p.film.radius[0], p.sb[0], p.tile_size, p.ntx, &tx_lo, &tx_hi);
+    phfilm::tiles_holding(y, p.film.radius[1], p.sb[1], p.tile_size, p.nty, &ty_lo, &ty_hi);
     float X = 0.0f, Y = 0.0f, Z = 0.0f, W = 0.0f;
     const uint32_t slot_px = p.slot_w * p.slot_h;
     for (int ty = ty_lo; ty <= ty_hi; ty++)
         for (int tx = tx_lo; tx <= tx_hi; tx++) {
             int tb[4], pb[4];
-            tb[0] = p.sb[0] + tx * p.tile_size; tb[2] = pmini(tb[0] + p.tile_size, p.sb[2]);
-            tb[1] = p.sb[1] + ty * p.tile_size; tb[3] = pmini(tb[1] + p.tile_size, p.sb[3]);
-            tile_pixel_bounds(p.film, tb, pb);
+            phfilm::tile_samples(p.sb[0], p.sb[2], p.tile_size, tx, &tb[0], &tb[2]); phfilm::tile_samples(p.sb[1], p.sb[3], p.tile_size, ty, &tb[1], &tb[3]);
+            phfilm::tile_pixels(tb[0], tb[2], p.film.radius[0], p.film.crop[0], p.film.crop[2], &pb[0], &pb[2]);   // Film::get_film_tile
+            phfilm::tile_pixels(tb[1], tb[3], p.film.radius[1], p.film.crop[1], p.film.crop[3], &pb[1], &pb[3]);
             if (x < pb[0] || x >= pb[2] || y < pb[1] || y >= pb[3]) continue;
             const uint32_t t = (uint32_t)(ty * p.ntx + tx);
             const float4 c = p.bufs[t % p.parts][(size_t)(t / p.parts) * slot_px + (size_t)(y - pb[1]) * p.slot_w + (size_t)(x - pb[0])];
@@ -880,19 +867,16 @@ void launch_raysort(PbrtHipScene* s, const uint32_t* keys_cl, const uint32_t* ke
 }
 
 size_t path_chunk_bytes_per_path(bool general, bool textured) { Wavefront w; return chunk_bytes_per_path(w.chunk_table(textured, general || textured)); }
-static int sat_i(float v) { if (v != v) return 0; if (v >= 2147483648.0f) return 2147483647; if (v <= -2147483648.0f) return (int)0x80000000; return (int)v; }
 
 // Frame-wide tile grid: Film::get_sample_bounds (film/mod.rs:150-159), the tile counts of SamplerIntegrator::render (sampler_integrator.rs:252-259)
-// and the tile-buffer slot big enough for any tile's FilmTile pixel bounds.  Independent of which part of the tiles a rank renders.
+// and the tile-buffer slot big enough for any tile's FilmTile pixel bounds, all from film_plan.h.  Independent of which part of the tiles a rank renders.
 struct TileGrid { int sb[4]; int ntx, nty; uint32_t slot_w, slot_h; };
 static TileGrid tile_grid(const FilmRec& f, int tile_size) {
     TileGrid g;
-    g.sb[0] = sat_i(std::floor((float)f.crop[0] + 0.5f - f.radius[0])); g.sb[1] = sat_i(std::floor((float)f.crop[1] + 0.5f - f.radius[1]));
-    g.sb[2] = sat_i(std::ceil((float)f.crop[2] - 0.5f + f.radius[0])); g.sb[3] = sat_i(std::ceil((float)f.crop[3] - 0.5f + f.radius[1]));
-    g.ntx = std::max((g.sb[2] - g.sb[0] + tile_size - 1) / tile_size, 0); g.nty = std::max((g.sb[3] - g.sb[1] + tile_size - 1) / tile_size, 0);
-    const int e_lo_x = sat_i(std::floor(0.5f + f.radius[0])), e_hi_x = sat_i(std::floor(f.radius[0] - 0.5f)) + 1;
-    const int e_lo_y = sat_i(std::floor(0.5f + f.radius[1])), e_hi_y = sat_i(std::floor(f.radius[1] - 0.5f)) + 1;
-    g.slot_w = (uint32_t)std::max(tile_size + e_lo_x + e_hi_x, 1); g.slot_h = (uint32_t)std::max(tile_size + e_lo_y + e_hi_y, 1);
+    g.sb[0] = phfilm::sample_begin(f.crop[0], f.radius[0]); g.sb[1] = phfilm::sample_begin(f.crop[1], f.radius[1]);
+    g.sb[2] = phfilm::sample_end(f.crop[2], f.radius[0]); g.sb[3] = phfilm::sample_end(f.crop[3], f.radius[1]);
+    g.ntx = phfilm::tile_count(g.sb[0], g.sb[2], tile_size); g.nty = phfilm::tile_count(g.sb[1], g.sb[3], tile_size);
+    g.slot_w = (uint32_t)phfilm::slot_extent(f.crop[0], f.crop[2], f.radius[0], tile_size); g.slot_h = (uint32_t)phfilm::slot_extent(f.crop[1], f.crop[3], f.radius[1], tile_size);
     return g;
 }
 
@@ -915,11 +899,9 @@ static int setup_tiles(PbrtHipScene* s, int tile_size, int part, int parts) {
     for (int t = part; t < ntx * nty; t += parts) {
         ph::TileInfo ti{};
         const int tx = t % ntx, ty = t / ntx;
-        ti.tb[0] = sb[0] + tx * tile_size; ti.tb[2] = std::min(ti.tb[0] + tile_size, sb[2]);
-        ti.tb[1] = sb[1] + ty * tile_size; ti.tb[3] = std::min(ti.tb[1] + tile_size, sb[3]);
-        const int p0x = sat_i(std::ceil((float)ti.tb[0] - 0.5f - f.radius[0])), p0y = sat_i(std::ceil((float)ti.tb[1] - 0.5f - f.radius[1]));
-        const int p1x = sat_i(std::floor((float)ti.tb[2] - 0.5f + f.radius[0])) + 1, p1y = sat_i(std::floor((float)ti.tb[3] - 0.5f + f.radius[1])) + 1;
-        ti.pb[0] = std::max(p0x, f.crop[0]); ti.pb[1] = std::max(p0y, f.crop[1]); ti.pb[2] = std::min(p1x, f.crop[2]); ti.pb[3] = std::min(p1y, f.crop[3]);
+        phfilm::tile_samples(sb[0], sb[2], tile_size, tx, &ti.tb[0], &ti.tb[2]); phfilm::tile_samples(sb[1], sb[3], tile_size, ty, &ti.tb[1], &ti.tb[3]);
+        phfilm::tile_pixels(ti.tb[0], ti.tb[2], f.radius[0], f.crop[0], f.crop[2], &ti.pb[0], &ti.pb[2]);
+        phfilm::tile_pixels(ti.tb[1], ti.tb[3], f.radius[1], f.crop[1], f.crop[3], &ti.pb[1], &ti.pb[3]);
         ti.px_off = (uint32_t)w.px_xy.size(); ti.tile_index = (uint32_t)t;
         for (int y = ti.tb[1]; y < ti.tb[3]; y++)
             for (int x = ti.tb[0]; x < ti.tb[2]; x++) w.px_xy.push_back(make_int2(x, y));  // Bounds2i iteration order (bounds2.rs:347-359)
@@ -932,6 +914,14 @@ static int setup_tiles(PbrtHipScene* s, int tile_size, int part, int parts) {
     if (!w.px_xy.empty()) PH_CHECK(s, hipMemcpy(w.d_px.p, w.px_xy.data(), w.px_xy.size() * sizeof(int2), hipMemcpyHostToDevice));
     std::memcpy(w.tiles_key, key, sizeof key); w.tiles_valid = true;
     return PBRT_HIP_OK;
+}
+
+// What setup_tiles left for the rank (after samples_begin): its pixel list on the host, its tiles' FilmTile pixel bounds in list order, the tile-buffer slot
+void film_layout(PbrtHipScene* s, const int2** px_xy, size_t* n_px, std::vector<int32_t>* tile_pb, uint32_t* slot_w, uint32_t* slot_h) {
+    const Wavefront& w = *s->wf;
+    *px_xy = w.px_xy.data(); *n_px = w.px_xy.size(); *slot_w = w.slot_w; *slot_h = w.slot_h;
+    tile_pb->clear();
+    for (const ph::TileInfo& t : w.tiles) tile_pb->insert(tile_pb->end(), t.pb, t.pb + 4);
 }
 
 size_t tile_buffer_floats_for(const PbrtHipScene* s, int tile_size, int part, int parts) {

@@ -10,6 +10,7 @@
 #include "texture.h"
 #include "wf_device.h"
 #include "sphere_light.h"
+#include "film_plan.h"
 
 namespace ph {
 
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256) void whitted_raygen_kernel(DeviceScene sc, WhP
             generate_camera_ray(w.cam, p_film, time, lens, ray);
             w.rec_L[gsi] = make_float4(0.0f, 0.0f, 0.0f, p_film.x);
             w.rec_py[gsi] = p_film.y;
-            if (p_film.x == (float)(xy.x + 1) || p_film.y == (float)(xy.y + 1)) w.px_rounded[pix] = 1u;
+            phfilm::mark_rounded_up(w.px_rounded, pix, xy.x, xy.y, p_film.x, p_film.y);
             fr = w.frames + (size_t)pid * w.n_frames;
             fr->ray = ray; fr->has_diff = w.diffs;
             if (w.diffs) {

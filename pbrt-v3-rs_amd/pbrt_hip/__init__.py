@@ -170,6 +170,8 @@ class Binding:
             "set_path_sphere_lights": (C.c_int, [vp, C.c_int]),
             "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
             "traverse_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+            "film_probe_layout": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), ip, ip]),
+            "film_probe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, fp, fp, vp, fp, fp, fp]),
         }
         for name, (res, args) in self._optional.items():
             if hasattr(self.lib, prefix + name):
@@ -785,6 +787,35 @@ class Scene:
         self._chk(self.b.fn("traverse_probe")(self.h, mode, ptr(rays_cl), len(rays_cl), ptr(rays_sh), len(rays_sh), order.ctypes.data if order is not None else None,
                                               n_heads, head_chunk, blocks, ptr(hits), ptr(occ)))
         return hits, occ
+
+    def film_probe_layout(self, tile_size=16, tile_part=0, tile_parts=1):
+        """What film_probe's arrays are laid out by (pbrt_hip_film_probe_layout): (pixels (n_px, 2) int32 of this part's pixel list, tile pixel bounds (n_tiles, 4) int32,
+        (slot_w, slot_h) of a tile's slot in the tile buffer)."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.b.fn("film_probe_layout")(self.h, tile_size, tile_part, tile_parts, out, None, None))
+        px = np.zeros((int(out[0]), 2), np.int32); pb = np.zeros((int(out[1]), 4), np.int32)
+        self._chk(self.b.fn("film_probe_layout")(self.h, tile_size, tile_part, tile_parts, out, _ptr(px, C.c_int) if len(px) else None, _ptr(pb, C.c_int) if len(pb) else None))
+        return px, pb, (int(out[2]), int(out[3]))
+
+    def _film_probe_tile_floats(self, tile_size, tile_part, tile_parts):
+        return self.tile_buffer_floats(tile_size, tile_part, tile_parts)
+
+    def film_probe(self, L, p_film, tile_size=16, tile_part=0, tile_parts=1, d_tile_buffer_ptr=None, film=True, tiles=False):
+        """The film pass and the merge on explicit camera samples (pbrt_hip_film_probe): L (spp, n_px, 3) and p_film (spp, n_px, 2) in the order of film_probe_layout's pixel
+        list, a NaN p_film x meaning no sample.  Returns (xyz, weight, tile buffer): the film of this part's tiles alone (None, None with film=False or a caller's device
+        buffer) and a host copy of the part's tile buffer (None without tiles=True)."""
+        L = _f32(L); pf = _f32(p_film)
+        assert L.ndim == 3 and pf.ndim == 3 and L.shape[:2] == pf.shape[:2] and L.shape[2] == 3 and pf.shape[2] == 2
+        xyz = wt = buf = None
+        if film and d_tile_buffer_ptr is None:
+            h, w = self._film_hw()
+            xyz = np.zeros((h, w, 3), np.float32); wt = np.zeros((h, w), np.float32)
+        if tiles:
+            buf = np.zeros(self._film_probe_tile_floats(tile_size, tile_part, tile_parts), np.float32)
+        n = L.shape[1]
+        self._chk(self.b.fn("film_probe")(self.h, tile_size, tile_part, tile_parts, n, _ptr(L, C.c_float) if L.size else None, _ptr(pf, C.c_float) if pf.size else None,
+                                          d_tile_buffer_ptr, _ptr(xyz, C.c_float), _ptr(wt, C.c_float), _ptr(buf, C.c_float) if buf is not None and buf.size else None))
+        return xyz, wt, buf
 
     def mipmap_pyramid(self, mipmap):
         """The pyramid the host built: list of (h, w, 3) float32 arrays, finest first (row 0 = t 0 = the image's bottom row)."""

@@ -115,6 +115,23 @@ class OracleScene(pbrt_hip.Scene):
                                                   C.byref(st), threads, 1 if count_traversal else 0, nvnt))
         return xyz, wt, st, list(nvnt)
 
+    def _film_probe_tile_floats(self, tile_size, tile_part, tile_parts):
+        out = (C.c_uint64 * 4)()
+        self._chk(self.b.fn("film_probe_layout")(self.h, tile_size, tile_part, tile_parts, out, None, None))
+        return int(out[2])
+
+    def film_probe_tiles(self, L, p_film, tile_size=16, tile_part=0, tile_parts=1):
+        """oracle_film_probe: (xyz, weight, tiles) with tiles = this part's FilmTiles in increasing index, each (pixel bounds (4,), sums (h, w, 4): contribution rgb, weight sum).
+        film_probe / film_probe_layout themselves are the inherited methods; the layout's third entry is (floats of all tiles packed, 0) here."""
+        xyz, wt, buf = self.film_probe(L, p_film, tile_size, tile_part, tile_parts, tiles=True)
+        _, pbs, _ = self.film_probe_layout(tile_size, tile_part, tile_parts)
+        tiles, o = [], 0
+        for pb in pbs:
+            w, h = max(int(pb[2] - pb[0]), 0), max(int(pb[3] - pb[1]), 0)
+            tiles.append((pb.copy(), buf[o:o + 4 * w * h].reshape(h, w, 4))); o += 4 * w * h
+        assert o == len(buf)
+        return xyz, wt, tiles
+
     def bsdf_probe(self, material, op, wo=(0, 0, 1), wi=(0, 0, 1), u=(0.5, 0.5), flags=31):
         """BSDF of `material` in the canonical frame: op 0 -> (f rgb, pdf), op 1 -> sample_f (f rgb, pdf, wi xyz, type), op 2 -> counts."""
         out = np.zeros(8, np.float32)
