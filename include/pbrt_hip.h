@@ -436,7 +436,30 @@ int pbrt_hip_render_whitted(PbrtHipScene*, int max_depth, const int pixel_bounds
 int pbrt_hip_render_whitted_devices(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                                     float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
 
-/* Memory for the sample records.  A render keeps one 20-byte record {L.rgb, p_film} per camera sample until the film pass has replayed FilmTile::add_sample over it
+/* Integrator::render for DirectLightingIntegrator (core/src/integrator/sampler_integrator.rs:243-415 + integrators/src/direct_lighting.rs:110-166), on the Whitted driver:
+ * film, sampler, camera, tiles, pixel_bounds, the recursion (specular_reflect then specular_transmit, sampler_integrator.rs:79-238, while depth + 1 < max_depth), the BSDF
+ * (allow_multiple_lobes = false), the miss and the Material "none" cases are pbrt_hip_render_whitted's.  What differs is the light phase of a vertex, after `L += isect.le(wo)`:
+ * strategy 0 ("all"): uniform_sample_all_lights AS IT RUNS in the reference (core/src/integrator/common.rs:22-78).  preprocess (direct_lighting.rs:72-90) requests sample arrays on
+ *   the integrator's own sampler, but render_tile works on clone_sampler copies that hold none (samplers/src/halton.rs:177-183, sobol.rs:110-112), get_2d_array returns an empty
+ *   vector (core/src/sampler/common.rs:108-122) and the branch `nl == 0 || sl == 0` (common.rs:42-57) is always taken: per light, in Scene::lights order, u_light = get_2d,
+ *   u_scattering = get_2d, l += estimate_direct; `l` joins L once.  n_light_samples never matters and no array dimension is skipped.
+ * strategy 1 ("one"): uniform_sample_one_light with no distribution (common.rs:89-133): get_1d, light = min(u * n, n - 1), then u_light, u_scattering, estimate_direct / (1 / n).
+ * estimate_direct (common.rs:146-299, specular = false, handle_media = false) is the path integrator's: the light half behind an occlusion ray, weighted by the power heuristic
+ * for a non-delta light; for such a light also the BSDF half, a closest-hit ray that counts where it meets this very light (or, on a miss, its le).  Those rays count as regular_rays.
+ * INVALID_ARG: strategy other than 0 / 1, max_depth outside [0, 16].  UNSUPPORTED, before any work: a recursion that COULD draw more sampler dimensions than the tables hold —
+ * 5 + V * D + I * 4 with V and I as for pbrt_hip_render_whitted and D = 4 * n_lights (all) or 5 (one; 0 without lights) must stay below 1000 (Halton) / 1024 (Sobol) and within the
+ * n32 / 52 dimensions given to pbrt_hip_set_sobol_tables; a scene with a light made by pbrt_hip_add_sphere_light on a handle without pbrt_hip_set_path_sphere_lights (the MIS weight
+ * needs Sphere::pdf_solid_angle, whose inside branch is that switch's documented departure; disk and cylinder lights need no switch); a handle made by pbrt_hip_scene_create_multi
+ * (several devices render with pbrt_hip_render_direct_devices).  The outputs are untouched and the handle stays usable.
+ * out_stats: camera_rays, regular_rays, shadow_rays and render_seconds are filled, the rest is zero. */
+int pbrt_hip_render_direct(PbrtHipScene*, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                           float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
+/* pbrt_hip_render_direct for a handle over any number of devices, as pbrt_hip_render_whitted_devices is for pbrt_hip_render_whitted (sampler_integrator.rs:254-296; the merge:
+ * core/src/film/mod.rs:220-279): the same tile deal, gather, merge order, stats and refusals, and a film that equals the one-device film bit for bit. */
+int pbrt_hip_render_direct_devices(PbrtHipScene*, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                                   float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
+
+/* Memory for the sample records. A render keeps one 20-byte record {L.rgb, p_film} per camera sample until the film pass has replayed FilmTile::add_sample over it
  * (core/src/film/film_tile.rs:62-108).  The reference holds O(pixels): every worker thread adds its samples to its FilmTile as they are made and Film::merge_film_tile
  * (core/src/film/mod.rs:220-279) folds the tile into the film.  Here the records of a frame are resident in BANDS: consecutive runs of this rank's 16x16 (tile_size) tiles,
  * in increasing tile index, each band with all of its samples.  A FilmTile takes samples of its own tile only (film_tile.rs:62-108; Film::get_film_tile, film/mod.rs:182-198),
@@ -465,6 +488,10 @@ int pbrt_hip_render_path_tiles_device(PbrtHipScene*, int max_depth, float rr_thr
  * (Film::merge_film_tile, core/src/film/mod.rs:220-279).  One process per GPU renders a Whitted frame with it as with the path form. */
 int pbrt_hip_render_whitted_tiles_device(PbrtHipScene*, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                                          void* d_tile_buffer, PbrtHipStats* out_stats);
+/* ... and for the direct-lighting integrator (direct_lighting.rs:110-166): pbrt_hip_render_direct's arguments and refusals (then INVALID_ARG for a null buffer), this rank's
+ * FilmTiles (sampler_integrator.rs:254-296) into the caller's device buffer, ready for pbrt_hip_merge_tiles_device. */
+int pbrt_hip_render_direct_tiles_device(PbrtHipScene*, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
+                                        void* d_tile_buffer, PbrtHipStats* out_stats);
 /* Film::merge_film_tile (core/src/film/mod.rs:220-279) in increasing tile order over tile_parts device buffers. */
 int pbrt_hip_merge_tiles_device(PbrtHipScene*, int tile_size, int tile_parts, const void* const* d_tile_buffers,
                                 float* out_xyz, float* out_weight);

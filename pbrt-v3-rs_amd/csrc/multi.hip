@@ -269,12 +269,14 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
 }
 
 // The Whitted integrator's frame on the same driver (pbrt_hip_render_whitted_devices): every device runs render_whitted_tiles with its own workspace, chunk plan and bands.
-int render_whitted_multi(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
-                         PbrtHipStats* out_stats) {
+// strategy < 0: Whitted; 0 / 1: the direct-lighting mode (pbrt_hip_render_direct_devices, render_direct_tiles)
+static int render_recursion_multi(PbrtHipScene* s, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz,
+                                  float* out_weight, PbrtHipStats* out_stats) {
     std::vector<PbrtHipScene*> devs;
     std::vector<PbrtHipStats> stats;
     int rc = render_on_devices(s, tile_size, tile_part, tile_parts, out_xyz, out_weight,
                                [&](PbrtHipScene* d, int part, int parts, void* d_tile_buffer, PbrtHipStats* st) {
+                                   if (strategy >= 0) return render_direct_tiles(d, strategy, max_depth, pixel_bounds, tile_size, part, parts, d_tile_buffer, st);
                                    return render_whitted_tiles(d, max_depth, pixel_bounds, tile_size, part, parts, d_tile_buffer, st);
                                }, devs, stats);
     if (rc) return rc;
@@ -287,6 +289,14 @@ int render_whitted_multi(PbrtHipScene* s, int max_depth, const int pixel_bounds[
         }
     }
     return PBRT_HIP_OK;
+}
+int render_whitted_multi(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                         PbrtHipStats* out_stats) {
+    return render_recursion_multi(s, -1, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
+}
+int render_direct_multi(PbrtHipScene* s, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                        PbrtHipStats* out_stats) {
+    return render_recursion_multi(s, strategy, max_depth, pixel_bounds, tile_size, tile_part, tile_parts, out_xyz, out_weight, out_stats);
 }
 
 }  // namespace phost

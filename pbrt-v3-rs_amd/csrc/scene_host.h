@@ -182,6 +182,9 @@ void free_whitted(PbrtHipScene* s);
 size_t whitted_chunk_bytes_per_sample(uint32_t n_frames);   // ... and the Whitted driver's
 // the Whitted driver itself: this context's tiles of the part into d_tile_buffer, as render_tiles does for the path integrator (arguments checked by the caller)
 int render_whitted_tiles(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats);
+// ... and its direct-lighting mode (strategy 0 all, 1 one); what the chunk table sums to in that mode
+int render_direct_tiles(PbrtHipScene* s, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int part, int parts, void* d_tile_buffer, PbrtHipStats* out_stats);
+size_t direct_chunk_bytes_per_sample(uint32_t n_frames);
 // ORs the voxels whose light distribution the context's last spatial render filled into `touched` (one byte per voxel, sized on first use); *count = voxels set so far
 int spatial_voxels_touched(PbrtHipScene* s, std::vector<uint8_t>& touched, uint64_t* count);
 // multi.hip
@@ -189,6 +192,8 @@ int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int li
                       float* out_xyz, float* out_weight, PbrtHipStats* out_stats);
 int render_whitted_multi(PbrtHipScene* s, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
                          PbrtHipStats* out_stats);
+int render_direct_multi(PbrtHipScene* s, int strategy, int max_depth, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts, float* out_xyz, float* out_weight,
+                        PbrtHipStats* out_stats);
 void free_multi(PbrtHipScene* s);
 }  // namespace phost
 

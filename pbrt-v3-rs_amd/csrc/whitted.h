@@ -43,6 +43,15 @@ struct alignas(16) WhSample {
     uint32_t light_next, n_pend, sh_base, pad_;  // the light loop's next light; occlusion rays sent last round: rays_sh[sh_base .. sh_base + n_pend)
     float pend[PH_WH_SLICE][4];                  // their f * Li * |wi.ns| / pdf, added to the frame's L in the lights' order where the ray arrives
 };
+// DirectLightingIntegrator::li on the same driver (PH_WH_DIRECT): what a sample keeps of its vertex's light phase between rounds, in a buffer the Whitted mode never allocates
+struct alignas(16) WhDirect {
+    float acc[3]; uint32_t flags;   // uniform_sample_all_lights' local `l` / uniform_sample_one_light's estimate so far; WD_* of the non-delta light whose estimate_direct is in flight
+    float f[3], weight;             // its BSDF half: f * |wi.ns| and power_heuristic(scattering_pdf, light_pdf)
+    float spdf; uint32_t light, pad_[2];   // scattering_pdf, the light's index
+};
+enum : uint32_t { WD_SH = 1u,     // the last of this round's occlusion rays belongs to the non-delta light (the light half of its estimate_direct)
+                  WD_MIS = 2u };  // the sample's closest-hit slot holds its BSDF-sampled ray
+enum : int { PH_WH_WHITTED = 0, PH_WH_DIRECT = 1 };   // the state kernel's MODE
 struct WhCounters { uint32_t n_cl, n_sh, n_live, head; };
 struct WhDevStats { unsigned long long camera_rays; };
 
@@ -60,6 +69,11 @@ struct WhParams {
     WhCounters* ctr;             // [2], per round parity
     WhDevStats* stats;
     WhSample* samples; WhFrame* frames;   // frames[pid * n_frames + depth]
+};
+// what the direct-lighting mode's state kernel takes besides
+struct WhDirectArgs {
+    WhDirect* direct;            // [sample of the chunk]
+    uint32_t strategy;           // 0 uniform_sample_all_lights, 1 uniform_sample_one_light
 };
 
 PH_DEV f3 ld3f(const float* p) { return mk3(p[0], p[1], p[2]); }
@@ -276,12 +290,90 @@ PH_DEV void wh_sample_specular(const WhBsdf& b, f3 wo_w, f2 u, bool transmit, sp
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// estimate_direct (core/src/integrator/common.rs:146-299, specular = false, handle_media = false) for the direct-lighting mode, in the two pieces a round boundary cuts it into.
+// Every expression is the path shade kernel's (wavefront.hip, "estimate_direct" and "K6").
+PH_DEV bool wd_is_delta(const LightRec& l) { return l.type == PH_L_DISTANT || l.type == PH_L_POINT || l.type == PH_L_SPOT || l.type == PH_L_PROJECTION || l.type == PH_L_GONIO; }
+// The sending half.  Returns through `sh` / `mis` the occlusion ray of the light sample and the BSDF-sampled ray, where estimate_direct traces them.
+template <bool QUADRIC>
+PH_DEV void wd_estimate_send(const DeviceScene& sc, const LightRec& light, uint32_t light_num, const SurfHit& si, const WhBsdf& bsdf, f2 u_light, f2 u_scatter,
+                             bool& want_sh, RayIn& sh, float* pend, bool& want_mis, RayIn& mis, WhDirect* dl) {
+    const bool is_delta = wd_is_delta(light);
+    want_sh = false; want_mis = false;
+    const LiSample ls = wh_light_sample_li<QUADRIC>(sc, light, si, u_light);
+    if (ls.valid && ls.pdf > 0.0f && !is_black(ls.value)) {
+        const spec f = bsdf_f(bsdf.g, si.wo, ls.wi, BX_ALL & ~BX_SPEC) * abs_dot(ls.wi, si.ns);
+        const float scattering_pdf = bsdf_pdf(bsdf.g, si.wo, ls.wi, BX_ALL & ~BX_SPEC);
+        if (!is_black(f)) {
+            sh = spawn_ray_to_hit(si, ls.vp, ls.vperr, ls.vn);   // VisibilityTester::unoccluded
+            want_sh = true;
+            spec A;
+            if (is_delta) A = f * ls.value / ls.pdf;
+            else A = f * ls.value * power_heuristic1(ls.pdf, scattering_pdf) / ls.pdf;
+            pend[0] = A.r; pend[1] = A.g; pend[2] = A.b;
+        }
+    }
+    if (!is_delta) {
+        spec f1; float spdf; f3 wi2; uint32_t st;
+        bsdf_sample_f(bsdf.g, si.wo, u_scatter, BX_ALL & ~BX_SPEC, f1, spdf, wi2, st);   // never specular with these flags: sampled_specular = false
+        const spec f = f1 * abs_dot(wi2, si.ns);
+        if (!is_black(f) && spdf > 0.0f) {
+            float lp;
+            if constexpr (QUADRIC) lp = sl_light_pdf_li(sc, light, si, wi2);
+            else lp = light_pdf_li<true>(sc, light, si, wi2);
+            if (lp != 0.0f) {   // lp == 0: `return ld` with the light half only
+                mis = spawn_ray(si, wi2);
+                want_mis = true;
+                sts3(dl->f, f); dl->weight = power_heuristic1(spdf, lp); dl->spdf = spdf; dl->light = light_num;
+            }
+        }
+    }
+}
+// The receiving half, a round later: the delta lights' samples of the slice in the lights' order, then the non-delta light's two halves, each light's `ld` added to `acc`.
+// The BSDF-sampled ray's hit is read where the traversal left it; WhFrame::hit stays the vertex's own.
+template <bool QUADRIC>
+PH_DEV void wd_estimate_receive(const DeviceScene& sc, const WhParams& w, int par, const WhSample* sm, WhDirect* dl) {
+    spec acc = lds3(dl->acc);
+    const uint32_t flags = dl->flags;
+    const uint32_t n_delta = sm->n_pend - ((flags & WD_SH) ? 1u : 0u);
+    for (uint32_t k = 0; k < n_delta; k++) if (!w.occ[sm->sh_base + k]) acc = acc + mks(sm->pend[k][0], sm->pend[k][1], sm->pend[k][2]);
+    if (flags & (WD_SH | WD_MIS)) {
+        spec ld = mks1(0.0f);
+        if ((flags & WD_SH) && !w.occ[sm->sh_base + n_delta]) ld = ld + mks(sm->pend[n_delta][0], sm->pend[n_delta][1], sm->pend[n_delta][2]);
+        if (flags & WD_MIS) {
+            const RayIn mr = load_ray(w.rays_cl[par] + sm->slot);
+            const float4* hp = reinterpret_cast<const float4*>(w.hits_cl + sm->slot);
+            const float4 h0 = hp[0];
+            const uint32_t hprim = __float_as_uint(h0.y);
+            const f3 wi = mk3(mr.dx, mr.dy, mr.dz);
+            const LightRec& lt = sc.lights[dl->light];
+            spec li2 = mks1(0.0f);
+            if (hprim != 0xFFFFFFFFu) {
+                if (lt.type == PH_L_AREA && lt.prim == hprim) {   // the hit primitive's area light IS the sampled light
+                    const float4 h1 = hp[1];
+                    MeshRec m;
+                    QSurf lqs; lqs.hit = 0u;
+                    const SurfHit lh = make_surface_hit_q<QUADRIC>(sc, mk3(mr.ox, mr.oy, mr.oz), wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &lqs);
+                    li2 = area_L(lt, lh.n, -wi);   // SurfaceInteraction::le (surface_interaction.rs:283-289)
+                }
+            } else li2 = light_le<true>(sc, lt, wi);
+            if (!is_black(li2)) ld = ld + lds3(dl->f) * li2 * mks1(1.0f) * dl->weight / dl->spdf;   // f * li * tr * weight / scattering_pdf
+        }
+        acc = acc + ld;
+    }
+    sts3(dl->acc, acc);
+    dl->flags = 0u;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Light::sample_li as the light loop calls it: wh_light_sample_li (sphere_light.h).
 // The state kernel: one thread per running sample and round.  It adds last round's unoccluded light samples to their frame, then advances the sample's recursion until it
 // has a closest-hit ray to send, has sent PH_WH_SLICE occlusion rays, or frame 0 has returned.  A vertex is rebuilt from the frame (ray, hit, vertex record) whenever the
 // sample comes back to it: its light loop's next slice, the refracted ray once the reflected subtree has returned.
-template <bool QUADRIC>
-__global__ __launch_bounds__(256) void whitted_state_kernel(DeviceScene sc, WhParams w, int par) {
+// MODE PH_WH_DIRECT: DirectLightingIntegrator::li (integrators/src/direct_lighting.rs:110-166) — the same recursion with estimate_direct in the light phase: per round a slice of
+// delta lights and at most one non-delta light, whose BSDF-sampled ray takes the sample's closest-hit slot (no frame ray is in flight during a light phase).
+// `x` is read by that mode only; the Whitted instantiations keep the code they had without it.
+template <bool QUADRIC, int MODE>
+__global__ __launch_bounds__(256) void whitted_state_kernel(DeviceScene sc, WhParams w, int par, WhDirectArgs x) {
     const uint32_t n_live = w.ctr[par].n_live;
     WhCounters* next = w.ctr + (par ^ 1);
     for (uint32_t base = blockIdx.x * blockDim.x; base < n_live; base += gridDim.x * blockDim.x) {
@@ -301,6 +393,9 @@ __global__ __launch_bounds__(256) void whitted_state_kernel(DeviceScene sc, WhPa
             const int2 xy = w.px_xy[ppix];
             SamplerCursor cur = cursor_for(sc, w.sp, xy.x, xy.y, w.s0 + (pid - ppix * w.chunk_spp), dim);
             // last round's light samples: `L += f * Li * |wi.ns| / pdf` where the occlusion ray arrived (whitted.rs:88-104), in the lights' order
+            if constexpr (MODE == PH_WH_DIRECT) {
+                if (sm->n_pend || x.direct[pid].flags) wd_estimate_receive<QUADRIC>(sc, w, par, sm, x.direct + pid);
+            } else
             if (sm->n_pend) {
                 WhFrame* fr = frames + depth;
                 spec L = lds3(fr->L);
@@ -357,7 +452,36 @@ __global__ __launch_bounds__(256) void whitted_state_kernel(DeviceScene sc, WhPa
                     if (m.first_light >= 0) L = L + area_L(sc.lights[(uint32_t)m.first_light + (hprim - m.tri_base)], si.n, wo);
                     sts3(fr->L, L);
                     phase = WH_LIGHTS; light_next = 0u;
+                    if constexpr (MODE == PH_WH_DIRECT) { WhDirect* dl = x.direct + pid; sts3(dl->acc, mks1(0.0f)); dl->flags = 0u; }
                 }
+                if constexpr (MODE == PH_WH_DIRECT) {
+                if (phase == WH_LIGHTS) {   // uniform_sample_all_lights as it runs (common.rs:42-57: one get_2d pair and one estimate_direct per light) / uniform_sample_one_light (common.rs:111-132)
+                    WhDirect* dl = x.direct + pid;
+                    bool in_flight = false;   // a non-delta light's estimate_direct is: the slice ends with it
+                    while (light_next < sc.n_lights && n_sh < PH_WH_SLICE && !in_flight) {
+                        uint32_t k = light_next++;
+                        if (x.strategy == 1u) {
+                            const float nl = (float)sc.n_lights;
+                            k = (uint32_t)pminf(get_1d(sc, w.sp, cur) * nl, nl - 1.0f);
+                            light_next = sc.n_lights;
+                        }
+                        const f2 u_light = get_2d(sc, w.sp, cur);
+                        const f2 u_scatter = get_2d(sc, w.sp, cur);
+                        bool sh = false, mis = false;
+                        wd_estimate_send<QUADRIC>(sc, sc.lights[k], k, si, bsdf, u_light, u_scatter, sh, ray_sh[n_sh], sm->pend[n_sh], mis, ray_cl, dl);
+                        if (sh) n_sh++;
+                        if (!wd_is_delta(sc.lights[k]) && (sh || mis)) {
+                            dl->flags = (sh ? WD_SH : 0u) | (mis ? WD_MIS : 0u);
+                            want_cl = mis; in_flight = true;
+                        }
+                    }
+                    if (light_next < sc.n_lights || n_sh || in_flight) break;   // more lights, or samples in flight: they join `acc` next round, before L sees it
+                    spec ld = lds3(dl->acc);
+                    if (x.strategy == 1u && sc.n_lights) ld = ld / ph_div(1.0f, (float)sc.n_lights);   // `estimate / light_pdf` (common.rs:113, :132)
+                    sts3(fr->L, lds3(fr->L) + ld);   // `l += light_sample` (direct_lighting.rs:143)
+                    phase = WH_REFL;
+                }
+                } else
                 if (phase == WH_LIGHTS) {   // one sample of every light, in the lights' order (whitted.rs:88-104)
                     while (light_next < sc.n_lights && n_sh < PH_WH_SLICE) {
                         const f2 u = get_2d(sc, w.sp, cur);

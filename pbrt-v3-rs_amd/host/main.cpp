@@ -17,7 +17,7 @@ static void usage() {
                  "  --sample-record-budget BYTES   device memory for the per-sample records: the frame renders in bands of whole tiles, the image is the same (default 0: automatic)\n"
                  "  --sobol-tables FILE    raw Sobol generator matrices (needed for Sampler \"sobol\")\n"
                  "  --quadrics             read Shape \"sphere\", \"cylinder\", \"cone\", \"paraboloid\", \"disk\" and \"hyperboloid\" (without it they are refused as out of scope); a sphere under\n"
-                 "                         AreaLightSource \"diffuse\" is an area light, rendered by Integrator \"whitted\"\n"
+                 "                         AreaLightSource \"diffuse\" is an area light, rendered by Integrator \"whitted\" (\"path\" and \"directlighting\" with --path-sphere-lights)\n"
                  "  --path-sphere-lights   render such a sphere light under Integrator \"path\" too (without it the scene is refused there)\n"
                  "  --quadric-lights       with --quadrics: a disk or a cylinder under AreaLightSource \"diffuse\" is an area light too, rendered by either integrator (the reference's\n"
                  "                         cone, paraboloid and hyperboloid have no Shape::sample and stay refused)\n"
@@ -72,9 +72,10 @@ int main(int argc, char** argv) {
         if (!pbrt_host::parse_file(fn, api, &rep)) { std::fprintf(stderr, "Error: %s: %s\n", fn.c_str(), api.error.c_str()); return 1; }
         if (check) {
             std::printf("{\"file\": \"%s\", \"triangles\": %llu, \"lights\": %llu, \"instances\": %llu, \"xres\": %d, \"yres\": %d, \"crop\": [%d, %d, %d, %d], \"spp\": %d, \"integrator\": \"%s\", \"max_depth\": %d, "
-                        "\"light_strategy\": %d, \"pixel_bounds\": [%d, %d, %d, %d], \"out_file\": \"%s\", \"warnings\": %zu, \"quadrics\": %llu}\n",
+                        "\"light_strategy\": %d, \"pixel_bounds\": [%d, %d, %d, %d], \"out_file\": \"%s\", \"warnings\": %zu, \"quadrics\": %llu%s}\n",
                         fn.c_str(), (unsigned long long)rep.n_triangles, (unsigned long long)rep.n_lights, (unsigned long long)rep.n_instances, rep.xres, rep.yres, rep.crop[0], rep.crop[1], rep.crop[2], rep.crop[3],
-                        rep.spp, rep.integrator.c_str(), rep.max_depth, rep.light_strategy, rep.pixel_bounds[0], rep.pixel_bounds[1], rep.pixel_bounds[2], rep.pixel_bounds[3], rep.out_file.c_str(), rep.warnings.size(), (unsigned long long)rep.n_quadrics);
+                        rep.spp, rep.integrator.c_str(), rep.max_depth, rep.light_strategy, rep.pixel_bounds[0], rep.pixel_bounds[1], rep.pixel_bounds[2], rep.pixel_bounds[3], rep.out_file.c_str(), rep.warnings.size(), (unsigned long long)rep.n_quadrics,
+                        rep.integrator == "directlighting" ? (", \"strategy\": \"" + rep.direct_strategy + "\"").c_str() : "");   // a key of this integrator only
             continue;
         }
         if (!quiet && !rep.out_file.empty()) {

@@ -834,6 +834,11 @@ int Api::pbrt_world_end(RenderReport& rep) {
         error = "Shape \"sphere\" under AreaLightSource \"diffuse\" (a sphere light) is rendered by Integrator \"whitted\" only, not by \"path\" (unless run with --path-sphere-lights)";
         return PBRT_HIP_ERR_UNSUPPORTED;
     }
+    // estimate_direct's MIS weight is the same pdf: the direct-lighting integrator follows the path integrator's rule (pbrt_hip_render_direct)
+    if (sphere_light_ && integrator_name_ == "directlighting" && !path_sphere_lights) {
+        error = "Shape \"sphere\" under AreaLightSource \"diffuse\" (a sphere light) is rendered by Integrator \"directlighting\" only when run with --path-sphere-lights";
+        return PBRT_HIP_ERR_UNSUPPORTED;
+    }
 
     // ---- filter + film (make_filter / make_film, graphics_state.rs:600-690; film/mod.rs:420-487)
     int fkind = -1; float rad[2] = {0.5f, 0.5f}, fparams[2] = {0.0f, 0.0f};
@@ -942,9 +947,16 @@ int Api::pbrt_world_end(RenderReport& rep) {
     if (!check(brc, "build_accel")) return PBRT_HIP_ERR_DEVICE;
     rep.build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 
-    // ---- integrator (path.rs:287-327, whitted.rs:121-150: "maxdepth" 5 and "pixelbounds", read the same way)
-    const bool whitted = integrator_name_ == "whitted";
-    if (integrator_name_ != "path" && !whitted) { error = "Integrator \"" + integrator_name_ + "\" is outside the hot-path scope (supported: path, whitted)"; return PBRT_HIP_ERR_UNSUPPORTED; }
+    // ---- integrator (path.rs:287-327, whitted.rs:121-150, direct_lighting.rs:169-213: "maxdepth" 5 and "pixelbounds", read the same way)
+    const bool whitted = integrator_name_ == "whitted", direct = integrator_name_ == "directlighting";
+    if (integrator_name_ != "path" && !whitted && !direct) { error = "Integrator \"" + integrator_name_ + "\" is outside the hot-path scope (supported: path, whitted), directlighting"; return PBRT_HIP_ERR_UNSUPPORTED; }
+    int direct_strategy = 0;   // direct_lighting.rs:178-186
+    if (direct) {
+        const std::string st = integrator_p_.find_one_string("strategy", "all");
+        if (st == "one") direct_strategy = 1;
+        else if (st != "all") warn("Strategy '" + st + "' for direct lighting unknown. Using 'all'.");
+        rep.direct_strategy = direct_strategy ? "one" : "all";
+    }
     const int max_depth = integrator_p_.find_one_int("maxdepth", 5);
     int pb[4] = {sb[0], sb[1], sb[2], sb[3]};
     if (const std::vector<int>* v = integrator_p_.find_ints("pixelbounds")) {
@@ -971,8 +983,9 @@ int Api::pbrt_world_end(RenderReport& rep) {
     if (!check(pbrt_hip_set_sample_record_budget(scene_, sample_record_budget), "set_sample_record_budget")) return PBRT_HIP_ERR_INVALID_ARG;
     if (!check(pbrt_hip_set_path_sphere_lights(scene_, path_sphere_lights ? 1 : 0), "set_path_sphere_lights")) return PBRT_HIP_ERR_INVALID_ARG;
     int rc = whitted ? pbrt_hip_render_whitted_devices(scene_, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
-                     : pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
-    if (!check(rc, whitted ? "render_whitted_devices" : "render_path")) return rc;
+             : direct ? pbrt_hip_render_direct_devices(scene_, direct_strategy, max_depth, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats)
+                      : pbrt_hip_render_path(scene_, max_depth, rr, strategy, pb, tile_size, 0, 1, xyz.data(), wt.data(), &rep.stats);
+    if (!check(rc, whitted ? "render_whitted_devices" : direct ? "render_direct_devices" : "render_path")) return rc;
     if (!check(pbrt_hip_film_to_rgb(scene_, xyz.data(), wt.data(), rgb.data()), "film_to_rgb")) return PBRT_HIP_ERR_DEVICE;
     std::string err;
     if (!write_image(filename, rgb.data(), cb[2] - cb[0], cb[3] - cb[1], err)) { error = err; return PBRT_HIP_ERR_INVALID_ARG; }

@@ -54,7 +54,8 @@ struct RenderReport {
     double build_seconds = 0, load_seconds = 0;
     uint64_t n_triangles = 0, n_lights = 0, n_instances = 0;  // n_triangles counts instanced triangles once per instance
     uint64_t n_quadrics = 0;  // sphere, cylinder, cone, paraboloid, disk, hyperboloid (read with Api::quadrics)
-    std::string integrator;  // "path" or "whitted"
+    std::string integrator;  // "path", "whitted" or "directlighting"
+    std::string direct_strategy;   // "all" or "one": Integrator "directlighting" only
     int spp = 0, max_depth = 0, light_strategy = 0, pixel_bounds[4] = {0, 0, 0, 0};
     std::vector<std::string> warnings;
 };

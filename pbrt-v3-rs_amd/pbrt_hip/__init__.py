@@ -106,6 +106,9 @@ class Binding:
             "render_whitted": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
             "render_whitted_devices": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
             "render_whitted_tiles_device": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Stats)]),
+            "render_direct": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
+            "render_direct_devices": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(Stats)]),
+            "render_direct_tiles_device": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Stats)]),
             "render_path_tiles_device": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Stats)]),
             "merge_tiles_device": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), fp, fp]),
             "add_material_none": (C.c_int, [vp, u32p]),
@@ -902,6 +905,31 @@ class Scene:
         self._chk(self.b.fn("render_whitted_devices")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
         return xyz, wt, st
 
+    @staticmethod
+    def _direct_strategy(strategy):
+        """"all" / "one" (or the C ABI's 0 / 1) -> the C ABI's int; anything else goes through for the library to refuse."""
+        return {"all": 0, "one": 1}.get(strategy, strategy)
+
+    def render_direct(self, strategy="all", max_depth=5, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1):
+        """DirectLightingIntegrator (pbrt_hip_render_direct), strategy "all" or "one": the same film, tiles and return value as render_whitted."""
+        h, w = self._film_hw()
+        xyz = np.zeros((h, w, 3), np.float32); wt = np.zeros((h, w), np.float32)
+        pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
+        st = Stats()
+        self._chk(self.b.fn("render_direct")(self.h, self._direct_strategy(strategy), max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts,
+                                             _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
+        return xyz, wt, st
+
+    def render_direct_devices(self, strategy="all", max_depth=5, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1):
+        """render_direct on a handle over any number of devices (pbrt_hip_render_direct_devices), as render_whitted_devices is for render_whitted."""
+        h, w = self._film_hw()
+        xyz = np.zeros((h, w, 3), np.float32); wt = np.zeros((h, w), np.float32)
+        pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
+        st = Stats()
+        self._chk(self.b.fn("render_direct_devices")(self.h, self._direct_strategy(strategy), max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts,
+                                                     _ptr(xyz, C.c_float), _ptr(wt, C.c_float), C.byref(st)))
+        return xyz, wt, st
+
     def set_sample_record_budget(self, nbytes=0):
         """Bound on the bytes of sample records resident at once (pbrt_hip_set_sample_record_budget): the frame renders in bands of whole tiles, bit for bit the
         one-band film.  0 = automatic.  Holds until changed."""
@@ -947,6 +975,14 @@ class Scene:
         pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
         st = Stats()
         self._chk(self.b.fn("render_whitted_tiles_device")(self.h, max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts, d_tile_buffer_ptr, C.byref(st)))
+        return st
+
+    def render_direct_tiles_device(self, d_tile_buffer_ptr, strategy="all", max_depth=5, pixel_bounds=None, tile_size=16, tile_part=0, tile_parts=1):
+        """The direct-lighting integrator's rank form (pbrt_hip_render_direct_tiles_device): this part's FilmTiles into a device buffer of tile_buffer_floats floats."""
+        pb = np.ascontiguousarray(pixel_bounds if pixel_bounds is not None else self.sample_bounds, dtype=np.int32)
+        st = Stats()
+        self._chk(self.b.fn("render_direct_tiles_device")(self.h, self._direct_strategy(strategy), max_depth, _ptr(pb, C.c_int), tile_size, tile_part, tile_parts,
+                                                          d_tile_buffer_ptr, C.byref(st)))
         return st
 
     def merge_tiles_device(self, d_ptrs, tile_size=16, out=None):
