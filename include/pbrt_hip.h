@@ -53,6 +53,7 @@ typedef struct PbrtHipRay {
  * leaves them in `r.t_max` (transformed_primitive.rs:56).  pad[1] = 0 otherwise.
  * A quadric shape (pbrt_hip_add_sphere / _add_quadric / _add_hyperboloid) takes ONE slot of that primitive list, in call order with the meshes' triangles: a hit on it
  * reports t and prim, b0 = b1 = b2 = 0 and pad[1] = 0.
+ * A curve segment (pbrt_hip_add_curve makes 2^split_depth of them, one slot each) reports t and prim, b0 = u, b1 = v of Curve::intersect's SurfaceInteraction, b2 = 0 and pad[1] = 0.
  * pad[0] carries the library's leaf-order index of the hit triangle and pad[2] its material class | material id << 3 (internal shortcuts for the shade stage and its work queues); ignore them. */
 typedef struct PbrtHipHit {
     float t;
@@ -181,6 +182,20 @@ int pbrt_hip_add_hyperboloid(PbrtHipScene*, const float o2w_m[16], const float o
                              uint32_t material_id, uint32_t flags);
 int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const float o2w_minv[16], float radius, float a, float b, float phi_max_deg,
                          uint32_t material_id, uint32_t flags);
+
+/* Curve::create_segments (shapes/src/curve.rs:105-140): ONE cubic Bezier curve — the CurveData of CurveData::new (:743-762), stored once — cut into 2^split_depth Curve
+ * segments over equal u ranges, which take that many consecutive slots of the primitive list, in order.  cp = the four control points in object space (what Curve::from_props,
+ * :149-316, arrives at after degree elevation and b-spline blossoming); width = the widths at u = 0 and u = 1; type 0 flat, 1 cylinder, 2 ribbon; n = a ribbon's two end normals
+ * (6 floats; read for type 2 only, may be NULL otherwise).  object_to_world as for the quadrics; flags bit 0 = reverse orientation.  Each segment enters the accelerator with its own
+ * Shape::world_bound (Curve::object_bound, :660-674, through Transform::transform_bounds) and is intersected as the reference RUNS Curve::intersect / intersect_p (:339-645), which
+ * differ from each other and depend on the t_max the ray carries when the segment is tested: DESIGN §4.4 lists the quirks that are reproduced and the one departure (where the
+ * reference would panic — assert!(dpdu != 0), a degenerate LookAt — the segment is missed).  A segment is a quadric in every other respect: scenes with instances and with
+ * alpha-masked meshes, all three integrators, every driver, both device builders.
+ * PBRT_HIP_ERR_INVALID_ARG: a null handle, matrix, cp or width; a type outside 0 .. 2; a ribbon without n; split_depth outside [0, 16]; an unknown material.
+ * PBRT_HIP_ERR_UNSUPPORTED, with nothing changed: between object_begin and object_end; while pbrt_hip_add_light_diffuse_area lights that no mesh has claimed are pending (the
+ * curve would be their shape, and Curve::sample is todo!(), :709-711); pbrt_hip_set_last_mesh_alpha_textures when the shape added last is a curve segment. */
+int pbrt_hip_add_curve(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], int type, const float cp[12], const float width[2], const float* n /* 6 or NULL */,
+                       int split_depth, uint32_t material_id, uint32_t flags);
 
 /* A sphere that is the shape of a DiffuseAreaLight (Shape "sphere" under AreaLightSource "diffuse": api/src/lib.rs:783-812 makes the shape, then the light of lights/src/diffuse.rs:46-82
  * around it): pbrt_hip_add_sphere with the same arguments, plus one light that joins the scene's lights in call order.  The light's area is Sphere::area — phi_max * radius *
@@ -546,6 +561,13 @@ int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int varian
  * output layout are pbrt_hip_light_probe_batch's; the handle's pbrt_hip_set_path_sphere_lights switch is not consulted.  PBRT_HIP_ERR_UNSUPPORTED: the light's shape is not
  * a quadric.  PBRT_HIP_ERR_INVALID_ARG: unknown light or op; a null handle; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built. */
 int pbrt_hip_sphere_light_probe_batch(PbrtHipScene*, uint32_t light, int op, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/, float* out /*28n*/);
+/* pbrt_hip_curve_probe_batch: the two device functions behind a curve segment, on explicit rays (a test aid like the probes above).  prim = the segment's slot in the primitive list.
+ * Each ray is tested with its OWN t_max by curve_test — Curve::intersect(r, is_shadow_ray) up to the accept decision (curve.rs:543-645 with recursive_intersect, :339-501) —; on a hit
+ * in closest-hit mode (shadow == 0) curve_surface rebuilds the SurfaceInteraction from (ray, t, u, v) as the shade pass does (:463-471, :496-534).  out, 20 floats per ray: hit flag
+ * (1.0 / 0.0), t, u, v, then in world space p, p_error, dpdu, dpdv, n (3 each), one pad word; everything after the flag is zero on a miss and with shadow != 0 (Curve::intersect_p).
+ * PBRT_HIP_ERR_INVALID_ARG: a null handle; a null array with n > 0; n > 2^32 - 1; prim is not a curve segment.  PBRT_HIP_ERR_STATE: no accelerator built. */
+#define PBRT_HIP_CURVE_PROBE_STRIDE 20
+int pbrt_hip_curve_probe_batch(PbrtHipScene*, uint32_t prim, int shadow, uint64_t n, const PbrtHipRay* rays, float* out /*20n*/);
 /* pbrt_hip_raysort_probe: the ray binning between wavefront rounds (csrc/raysort.h) on explicit keys, through the launch the path integrator's rounds use.  keys_cl / keys_sh = the
  * bin keys (< 4096) of n_cl closest-hit and n_sh any-hit rays; the keys and the two counts are uploaded and read from device memory, as in a render.  order_out[0 .. n_cl + n_sh) =
  * the queue positions (closest-hit rays 0 .. n_cl, any-hit rays behind them) grouped by bin, closest-hit rays first; the order inside a bin is unspecified.  sort_blocks = the grid

@@ -3,6 +3,7 @@
 // gfx950 device pbrt_hip_scene_create returns NULL and every compute entry point fails with PBRT_HIP_ERR_NO_DEVICE.
 #include "host_math.h"
 #include "scene_host.h"
+#include "curve_host.h"
 #include "traverse.h"
 #include "texture.h"
 #include <algorithm>
@@ -184,7 +185,14 @@ int upload_scene(PbrtHipScene* s) {
     if ((rc = upload_vec(s, s->infinite_lights, &d.infinite_lights))) return rc;
     d.n_infinite = (uint32_t)s->infinite_lights.size();
     if ((rc = upload_vec(s, s->inst_recs, &d.instances))) return rc;
-    if ((rc = upload_vec(s, s->quadrics, &d.quadrics))) return rc;
+    if (s->curves.empty()) { if ((rc = upload_vec(s, s->quadrics, &d.quadrics))) return rc; }
+    else {   // the CurveRecs travel behind the last QuadricRec (scene_types.h: ph_curve_rec), in whole QuadricRec slots
+        std::vector<QuadricRec> all(s->quadrics);
+        for (QuadricRec& q : all) q.curves_at = (uint32_t)s->quadrics.size();
+        all.resize(s->quadrics.size() + (s->curves.size() * sizeof(CurveRec) + sizeof(QuadricRec) - 1) / sizeof(QuadricRec));
+        std::memcpy(static_cast<void*>(all.data() + s->quadrics.size()), s->curves.data(), s->curves.size() * sizeof(CurveRec));
+        if ((rc = upload_vec(s, all, &d.quadrics))) return rc;
+    }
     d.n_instances = (uint32_t)s->inst_recs.size();
     // a forest whose trees are all single leaves has no interior node at all (d.nodes == nullptr): the records still need their bounds / root / transform
     if (!s->inst_recs.empty() && !s->top_items.empty() && d.tris) {   // instance leaf records + hints (patch_inst_records_kernel)
@@ -757,6 +765,32 @@ int pbrt_hip_add_quadric_light(PbrtHipScene* s, int kind, const float o2w_m[16],
     s->meshes.back().first_light = (int32_t)s->lights.size();
     s->lights.push_back(l);
     s->quadric_lights++;
+    return PBRT_HIP_OK;
+    });
+}
+
+// Curve::create_segments (shapes/src/curve.rs:105-140): one CurveData, 2^split_depth Curve segments over equal u ranges, each a primitive of its own with its own
+// Shape::world_bound (object_bound, :660-674, through transform_bounds).  A segment is a QuadricRec of kind PH_Q_CURVE: it shares the quadrics' leaf record, builders and kernel rows
+int pbrt_hip_add_curve(PbrtHipScene* s, const float o2w_m[16], const float o2w_minv[16], int type, const float cp[12], const float width[2], const float* n, int split_depth,
+                       uint32_t material_id, uint32_t flags) {
+    return ph_guard(s, "pbrt_hip_add_curve", [&]() -> int {
+    if (!s || !o2w_m || !o2w_minv || !cp || !width) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_curve: null argument");
+    if (type != PH_CURVE_FLAT && type != PH_CURVE_CYLINDER && type != PH_CURVE_RIBBON) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_curve: type must be 0 flat, 1 cylinder or 2 ribbon");
+    if (type == PH_CURVE_RIBBON && !n) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_curve: a ribbon curve needs its two end normals");
+    if (split_depth < 0 || split_depth > 16) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_curve: split_depth must lie in [0, 16]");
+    CurveRec c;
+    pcurve::curve_data(type, cp, width, type == PH_CURVE_RIBBON ? n : nullptr, c);   // (from_props drops the normals of any other type, curve.rs:211-214)
+    const uint32_t curve = (uint32_t)s->curves.size();
+    const int n_segments = 1 << split_depth;
+    for (int i = 0; i < n_segments; i++) {
+        QuadricRec q{}; float lo[3], hi[3];
+        q.kind = PH_Q_CURVE; q.curve = curve;
+        pcurve::segment_range(i, split_depth, q.z_min, q.z_max);
+        pcurve::segment_object_bound(c, q.z_min, q.z_max, lo, hi);
+        const int rc = add_quadric_common(s, "add_curve", q, o2w_m, o2w_minv, lo, hi, material_id, flags);   // its refusals depend on the scene alone: the first segment meets them, before anything changed
+        if (rc) return rc;
+    }
+    s->curves.push_back(c);
     return PBRT_HIP_OK;
     });
 }

@@ -128,6 +128,26 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void sphere_light_probe_kernel(Devi
     }
 }
 
+// curve_test, then — closest-hit mode, on a hit — curve_surface (curve.h) for quadric slot `qi` (a curve segment), each ray with its own t_max: the two calls the traversal kernel's leaf
+// step and make_surface_hit_q make, with the hit's t, u, v carried from one to the other as HitOut carries them
+__global__ __launch_bounds__(PH_PROBE_BLOCK) void curve_probe_kernel(DeviceScene sc, uint32_t qi, uint32_t shadow, uint32_t n, const RayIn* rays, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RayIn ray = load_ray(rays + i);
+    float* o = out + PBRT_HIP_CURVE_PROBE_STRIDE * (size_t)i;
+    for (int k = 0; k < PBRT_HIP_CURVE_PROBE_STRIDE; k++) o[k] = 0.0f;
+    const QTest qt = curve_test(sc.self, qi, ray.ox, ray.oy, ray.oz, ray.t_max, ray.dx, ray.dy, ray.dz, shadow);
+    if (!qt.hit) return;
+    o[0] = 1.0f;
+    if (shadow) return;
+    o[1] = qt.t; o[2] = qt.u; o[3] = qt.v;
+    float rtuv[9] = {ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, qt.t, qt.u, qt.v};
+    QSurf qs;
+    curve_surface(sc.self, qi, rtuv, &qs);
+    o[4] = qs.p.x; o[5] = qs.p.y; o[6] = qs.p.z; o[7] = qs.p_error.x; o[8] = qs.p_error.y; o[9] = qs.p_error.z;
+    o[10] = qs.dpdu.x; o[11] = qs.dpdu.y; o[12] = qs.dpdu.z; o[13] = qs.dpdv.x; o[14] = qs.dpdv.y; o[15] = qs.dpdv.z; o[16] = qs.n.x; o[17] = qs.n.y; o[18] = qs.n.z;
+}
+
 // the 15 floats of pbrt_hip_texture_eval_batch.  NODIFF: the context of every ray but a camera ray, as tex_ctx_from and alpha_accept make it — the nine derivative fields are zero
 // (the NODIFF evaluator skips only the image maps' filtered look-up; the procedural classes and bump_shading read the fields)
 template <bool NODIFF>
@@ -376,6 +396,32 @@ int pbrt_hip_sphere_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, u
     PH_CHECK(s, hipMemcpyAsync(d + o_wi, wi, n * 12, hipMemcpyHostToDevice, s->stream));
     hipLaunchKernelGGL(ph::sphere_light_probe_kernel, dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, light, op, (uint32_t)n,
                        (const float*)(d + o_ref), (const float*)(d + o_u), (const float*)(d + o_wi), (float*)(d + o_out));
+    PH_CHECK(s, hipGetLastError());
+    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_curve_probe_batch(PbrtHipScene* s, uint32_t prim, int shadow, uint64_t n, const PbrtHipRay* rays, float* out) {
+    return ph_guard(s, "pbrt_hip_curve_probe_batch", [&]() -> int {
+    if (!s || (n && (!rays || !out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "curve_probe_batch: null argument");
+    if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "curve_probe_batch: too many rays");
+    if (prim >= s->prim_quadric.size() || s->prim_quadric[prim] == 0u || s->quadrics[s->prim_quadric[prim] - 1u].kind != PH_Q_CURVE)
+        return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "curve_probe_batch: the primitive is not a curve segment (pbrt_hip_add_curve)");
+    if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "curve_probe_batch: build_accel first");
+    if (n == 0) return PBRT_HIP_OK;
+    PH_CHECK(s, hipSetDevice(s->device));
+    int rc;
+    if ((rc = upload_scene(s))) return rc;
+    const size_t stride = PBRT_HIP_CURVE_PROBE_STRIDE * sizeof(float);
+    const size_t o_rays = 0, o_out = o_rays + up256(n * sizeof(PbrtHipRay)), total = o_out + up256(n * stride);
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    PH_CHECK(s, hipMemcpyAsync(d + o_rays, rays, n * sizeof(PbrtHipRay), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(ph::curve_probe_kernel, dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, s->prim_quadric[prim] - 1u,
+                       shadow ? 1u : 0u, (uint32_t)n, (const ph::RayIn*)(d + o_rays), (float*)(d + o_out));
     PH_CHECK(s, hipGetLastError());
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));

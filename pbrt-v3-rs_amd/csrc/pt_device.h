@@ -479,14 +479,15 @@ PH_DEV SurfHit make_surface_hit_any(const DeviceScene& sc, f3 rd_world, float ti
 }
 // The same for a scene that may hold quadric shapes (QUADRIC instantiations of the shade / texture kernels only): a hit whose leaf record is a quadric repeats the shape's test on the
 // same ray out of line and takes the world-space SurfaceInteraction from it (quadric.h: quadric_surface); shading frame = geometric frame.  `qs` keeps what the texture pass needs beyond SurfHit.
-template <bool QUADRIC> PH_DEV SurfHit make_surface_hit_q(const DeviceScene& sc, f3 ro, f3 rd_world, float time, uint32_t tri_index, uint32_t inst, float b0, float b1, float b2, MeshRec& m_out, QSurf* qs) {
+// A curve segment's test is NOT repeated — its answer depends on the t_max the traversal held at that moment —: the hit's t and the u, v it retired with (b0, b1) go to curve_surface.
+template <bool QUADRIC> PH_DEV SurfHit make_surface_hit_q(const DeviceScene& sc, f3 ro, f3 rd_world, float time, uint32_t tri_index, uint32_t inst, float b0, float b1, float b2, MeshRec& m_out, QSurf* qs, float t_hit) {
     if (QUADRIC) {
         const float4* tp = reinterpret_cast<const float4*>(sc.tris + tri_index);
         const float4 a = tp[0];
         const uint32_t rflags = __float_as_uint(tp[1].w);
         if (rflags & PH_TRI_QUADRIC) {
             m_out = sc.meshes[__float_as_uint(tp[2].w)];
-            float rod[6] = {ro.x, ro.y, ro.z, rd_world.x, rd_world.y, rd_world.z};
+            float rod[9] = {ro.x, ro.y, ro.z, rd_world.x, rd_world.y, rd_world.z, t_hit, b0, b1};   // t, u, v: read for a curve segment only (curve.h: curve_surface)
             quadric_surface(sc.self, __float_as_uint(a.x), rod, qs);
             SurfHit si;
             si.p = qs->p; si.p_error = qs->p_error; si.wo = qs->wo; si.n = qs->n;

@@ -5,9 +5,11 @@
 //   quadric_surface  — the same test on the same ray, then the tail of ::intersect: the SurfaceInteraction carried to world space (transform.rs:566-590), for the shade and texture passes.
 // Repeating the test in the shade pass gives the bits the traversal saw: the roots do not depend on ray.t_max, and every ray.t_max comparison the traversal's (shorter) t_max passed
 // is passed by the ray's own.  Expression order is the reference's, f32 without contraction; phi is atan2 evaluated in f64 and rounded once.
+// Both entry points hand a record of kind PH_Q_CURVE — one segment of a Curve — on to curve.h, for which none of the above holds: its test depends on ray.t_max.
 #pragma once
 #include "dmath.h"
 #include "scene_types.h"
+#include "curve.h"
 
 namespace ph {
 
@@ -150,20 +152,24 @@ PH_DEV bool quadric_core(const QuadricRec& q, f3 ro, f3 rd, float ray_t_max, QHi
     return true;
 }
 
-// the traversal kernel's leaf test: the hit's t (> 0), or -1 for a miss.  Arguments in registers, the record through DeviceScene::self
-static __device__ __noinline__ float quadric_test(const DeviceScene* dsc, uint32_t qi, float ox, float oy, float oz, float t_max, float dx, float dy, float dz) {
-    QHit h;
-    return quadric_core(dsc->quadrics[qi], mk3(ox, oy, oz), mk3(dx, dy, dz), t_max, h) ? h.t : -1.0f;
+// the traversal kernel's leaf test: hit or miss, the hit's t and (a curve's) u, v.  Arguments in registers, the record through DeviceScene::self.  A record that names a curve
+// segment goes on to curve_test (curve.h), the one test that reads `shadow`: Curve::intersect_p is not Curve::intersect cut short
+static __device__ __noinline__ QTest quadric_test(const DeviceScene* dsc, uint32_t qi, float ox, float oy, float oz, float t_max, float dx, float dy, float dz, uint32_t shadow) {
+    if (dsc->quadrics[qi].kind == PH_Q_CURVE) return curve_test(dsc, qi, ox, oy, oz, t_max, dx, dy, dz, shadow);
+    QHit h; QTest r;
+    r.hit = quadric_core(dsc->quadrics[qi], mk3(ox, oy, oz), mk3(dx, dy, dz), t_max, h) ? 1u : 0u;
+    r.t = r.hit ? h.t : -1.0f; r.u = 0.0f; r.v = 0.0f;
+    return r;
 }
 
-// What the shade and texture passes read of a quadric hit, in world space
-struct QSurf { f3 p, p_error, wo, n, dpdu, dpdv, dndu, dndv; float u, v; uint32_t hit; };
+// (QSurf, what the shade and texture passes read of the hit in world space: curve.h)
 PH_DEV f3 q_xf_vec(const float* m, f3 v) { return mk3(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z); }   // transform_vector
 PH_DEV f3 q_xf_normal(const float* mi, f3 n) { return mk3(mi[0] * n.x + mi[4] * n.y + mi[8] * n.z, mi[1] * n.x + mi[5] * n.y + mi[9] * n.z, mi[2] * n.x + mi[6] * n.y + mi[10] * n.z); }   // transform_normal
 // tails of the six ::intersect (sphere.rs:173-241, cylinder.rs:146-196, cone.rs:132-190, paraboloid.rs:132-200, disk.rs:106-140, hyperboloid.rs:192-262): parametric form, dn/du and
 // dn/dv from the fundamental forms, SurfaceInteraction::new (surface_interaction.rs:69-98), then object_to_world.transform_surface_interaction (transform.rs:566-590)
-static __device__ __noinline__ void quadric_surface(const DeviceScene* dsc, uint32_t qi, const float* ray_o_d /* o xyz, d xyz */, QSurf* out) {
+static __device__ __noinline__ void quadric_surface(const DeviceScene* dsc, uint32_t qi, const float* ray_o_d /* o xyz, d xyz; for a curve segment then the hit's t, u, v */, QSurf* out) {
     const QuadricRec& q = dsc->quadrics[qi];
+    if (q.kind == PH_Q_CURVE) { curve_surface(dsc, qi, ray_o_d, out); return; }
     const f3 ro = mk3(ray_o_d[0], ray_o_d[1], ray_o_d[2]), rd = mk3(ray_o_d[3], ray_o_d[4], ray_o_d[5]);
     QHit h;
     QSurf s;

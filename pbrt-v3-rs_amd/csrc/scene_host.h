@@ -29,6 +29,7 @@ struct SceneHostState {
     // quadric shapes (add_sphere / add_quadric / add_hyperboloid): each owns one MeshRec and ONE slot of the primitive list (idx holds three zeros for it, tri_flags 0: the builder sets PH_TRI_QUADRIC in the leaf record from prim_quadric);
     // quadric_bounds = its Shape::world_bound {lo xyz, hi xyz}; prim_quadric[prim] = 0, or 1 + the quadric in that slot (sized with the primitive list once a quadric exists)
     std::vector<QuadricRec> quadrics;
+    std::vector<CurveRec> curves;   // one CurveData per add_curve, named by its segments' QuadricRec::curve (a segment is a quadric slot of kind PH_Q_CURVE)
     std::vector<float> quadric_bounds;
     std::vector<uint32_t> prim_quadric;
     phost::MaterialHost mats;        // every material's description, record and lobe list (material_host.h); the device arrays are laid out at upload

@@ -59,7 +59,8 @@ struct InstRec {
 
 // One quadric of the reference's shapes crate (shapes/src/{sphere,cylinder,disk,cone,paraboloid,hyperboloid}.rs), as its constructor leaves it: parameters clamped and derived on the
 // host (api.hip: add_quadric_common).  It takes ONE slot of the primitive list and owns one MeshRec (PH_MESH_QUADRIC; vert_base = its index here).
-enum { PH_Q_CYLINDER = 0, PH_Q_CONE = 1, PH_Q_PARABOLOID = 2, PH_Q_DISK = 3, PH_Q_SPHERE = 4, PH_Q_HYPERBOLOID = 5 };
+enum { PH_Q_CYLINDER = 0, PH_Q_CONE = 1, PH_Q_PARABOLOID = 2, PH_Q_DISK = 3, PH_Q_SPHERE = 4, PH_Q_HYPERBOLOID = 5,
+       PH_Q_CURVE = 6 /* one segment of a Curve (shapes/src/curve.rs): z_min / z_max = its u_min / u_max, `curve` = its CurveRec; the transforms and flip as for a quadric */ };
 struct alignas(16) QuadricRec {
     float w2o[16], o2w[16];   // row-major 4x4: the Transform's inverse and matrix as the caller handed them over (never inverted here)
     uint32_t kind, flip;      // flip = reverse_orientation ^ transform_swaps_handedness
@@ -68,7 +69,18 @@ struct alignas(16) QuadricRec {
     float height, inner_radius;     // cone, disk
     float ah, ch;                   // hyperboloid (hyperboloid.rs:70-88)
     float p1[3], p2[3];             // hyperboloid, after the constructor's swap
-    uint32_t pad_[2];
+    uint32_t curve;                 // curve segment: its CurveRec ...
+    uint32_t curves_at;             // ... in the array that starts behind QuadricRec number `curves_at` of DeviceScene::quadrics (the number of QuadricRecs; set at upload)
+};
+// CurveData (curve.rs:716-763), stored once per pbrt_hip_add_curve and shared by its 2^split_depth segments: the cubic Bezier control points in object space, the end widths,
+// the ribbon's normalised end normals with the angle between them and 1 / sin of it (acos and sin in f64, rounded once: DESIGN §2)
+enum { PH_CURVE_FLAT = 0, PH_CURVE_CYLINDER = 1, PH_CURVE_RIBBON = 2 };
+struct alignas(16) CurveRec {
+    float cp[12];
+    float width[2];
+    float normal_angle, inv_sin_normal_angle;
+    float n[6];
+    uint32_t type, pad_;
 };
 
 // ---- shading-side geometry (indexed by prim, add_mesh order) ---------------------------------------------------------
@@ -277,5 +289,7 @@ struct DeviceScene {
     const uint32_t* sobol32;
     const uint64_t* vdc;
     const uint64_t* vdc_inv;
-    const QuadricRec* quadrics;   // null unless the scene holds a quadric shape
+    const QuadricRec* quadrics;   // null unless the scene holds a quadric shape or a curve; the scene's CurveRecs lie behind its last QuadricRec (curve.h: ph_curve_rec)
 };
+// The CurveRecs have no pointer of their own: DeviceScene is an argument of every kernel and keeps the parent's layout (and the kernels of scenes without curves their
+// instructions).  The array is uploaded in the quadrics' buffer, behind the last QuadricRec, and a segment's record says where that is (curve.h: ph_curve_rec)

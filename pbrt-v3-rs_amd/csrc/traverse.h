@@ -332,7 +332,7 @@ static __device__ __forceinline__ bool alpha_accept_lean(const DeviceScene& sc, 
 // QUADRIC = true adds the reference's six quadric shapes (quadric.h): a leaf record with PH_TRI_QUADRIC names a QuadricRec, and the lane runs the analytic test out of line instead of the
 //   triangle test — one "primitive test" of the reference either way, same place in the leaf's order, same `r.t_max = t`.  RayState keeps no direction, so the lane reads its ray's
 //   from the queue again (the instancing kernel's lesson — that line has left the caches by then — is accepted here: no speed target for quadric scenes yet).  An accepted
-//   quadric is remembered like a triangle, by its record; the ray retires with zero barycentrics.  Instantiated only for scenes that hold a quadric (pick_shape): with
+//   quadric is remembered like a triangle, by its record; the ray retires with zero barycentrics — a curve segment (a quadric record whose QuadricRec is of kind PH_Q_CURVE, curve.h) with the u, v of its accepted test in b0, b1.  Instantiated only for scenes that hold a quadric (pick_shape): with
 //   QUADRIC = false every line below compiles to what it was.
 //   QUADRIC with ALPHA != 0 (quadrics beside alpha-masked meshes): a quadric record carries no PH_TRI_ALPHATEX (set_last_mesh_alpha_textures refuses a quadric), so a lane at one never sets
 //   alpha_wait and a waiting lane always stands at a triangle.  The leaf step has ONE test site for both (a second copy of the test gave wrong hits on this toolchain); a lane
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                     if (hit_tri != 0xFFFFFFFFu) {
                         const float4* tp = reinterpret_cast<const float4*>(sc.tris + hit_tri);
                         const float4 a = tp[0], b = tp[1], c = tp[2];
-                        if (QUADRIC && (__float_as_uint(b.w) & PH_TRI_QUADRIC)) hb0 = hb1 = hb2 = 0.0f;
+                        if (QUADRIC && (__float_as_uint(b.w) & PH_TRI_QUADRIC)) { (void)hb0; (void)hb1; hb2 = 0.0f; }   // hb0, hb1 stay what the accepted test reported (a curve's u, v; zero for a quadric).  (Named in this order: the closure's captures keep theirs, and the instantiations without quadrics their instructions)
                         else
                         tri_bary(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), hb0, hb1, hb2);
                         hit_prim = __float_as_uint(a.w); hit_cls = (__float_as_uint(b.w) >> PH_TRI_CLASS_SHIFT) & PH_TRI_KEY_MASK;
@@ -689,9 +689,10 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                             float qdx, qdy, qdz;
                             if constexpr (INST && QUADRIC) { qdx = wdx; qdy = wdy; qdz = wdz; }   // (a discarded statement otherwise: the other instantiations capture what they did)
                             else { const float4 rdq = reinterpret_cast<const float4*>((MIXED && ah) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index)[1]; qdx = rdq.x; qdy = rdq.y; qdz = rdq.z; }
-                            t = quadric_test(sc.self, __float_as_uint(a.x), r.ox, r.oy, r.oz, r.t_max, qdx, qdy, qdz);
-                            b0 = b1 = b2 = 0.0f;
-                            return t > 0.0f;
+                            QTest qt;   // (t, then the record, then the barycentric slots: the closure's captures keep the order they had, and the instantiations without quadrics their instructions)
+                            t = (qt = quadric_test(sc.self, __float_as_uint(a.x), r.ox, r.oy, r.oz, r.t_max, qdx, qdy, qdz, ah ? 1u : 0u)).t;
+                            b0 = qt.u; b1 = qt.v; b2 = 0.0f;
+                            return qt.hit != 0u;
                         };
                         if ((QUADRIC && (flags & PH_TRI_QUADRIC)) ? quadric_leaf() : tri_test(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), t, b0, b1, b2)) {
                             // post-t rejections: degenerate triangle (triangle.rs:567-570 / 862-866), alpha == 0 (:603 / :886-893)
@@ -710,6 +711,7 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                                 else {
                                     r.t_max = t; hit_tri = ti;
                                     if (!LEAN) { hit_prim = __float_as_uint(a.w); hb0 = b0; hb1 = b1; hb2 = b2; hit_cls = (flags >> PH_TRI_CLASS_SHIFT) & PH_TRI_KEY_MASK; }
+                                    else if (QUADRIC && (flags & PH_TRI_QUADRIC)) { hb0 = b0; hb1 = b1; }   // a curve's u, v cannot be recomputed when the ray retires: the test depended on the t_max of this moment (curve.h)
                                     if (INST) { hit_inst = in_inst & 0x3FFFFFFFu; inst_hit = true; }   // (a scene-level hit, triangle or quadric: in_inst == 0, so hit_inst = 0; inst_hit is set too, harmlessly — it is reset on entering an instance and read only on leaving one)
                                 }
                             }

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void spatial_mark_kernel(DeviceScene sc, WfPar
         f3 p = h0.z * mk3(a.x, a.y, a.z) + h0.w * mk3(b.x, b.y, b.z) + h1.x * mk3(c.x, c.y, c.z);  // = SurfHit::p (make_surface_hit_tv)
         if (QUADRIC && (__float_as_uint(b.w) & PH_TRI_QUADRIC)) {
             const RayIn ray = load_ray(w.rays_cl[it & 1] + idx4.x);
-            float rod[6] = {ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz};
+            float rod[9] = {ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, h0.x, h0.z, h0.w};   // (t, u, v: a curve segment's, make_surface_hit_q)
             QSurf qs; quadric_surface(sc.self, __float_as_uint(a.x), rod, &qs);
             p = qs.p;
         }
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per
         const f3 rd = mk3(ray.dx, ray.dy, ray.dz);
         MeshRec m;
         QSurf qs; qs.hit = 0u;
-        const SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs)
+        const SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs, h0.x)
                                    : make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
         const bool on_quadric = QUADRIC && (m.flags & PH_MESH_QUADRIC) != 0u;
         const MaterialRec& mr = sc.materials[m.material];
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                                 SurfHit lh;
                                 if constexpr (Row::sphere_lights) {   // the sampled light may be a sphere: its interaction comes from the shape's own test on the MIS ray
                                     QSurf lqs;
-                                    lh = make_surface_hit_q<true>(sc, mk3(mr.ox, mr.oy, mr.oz), wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &lqs);
+                                    lh = make_surface_hit_q<true>(sc, mk3(mr.ox, mr.oy, mr.oz), wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &lqs, h0.x);
                                 } else
                                 lh = make_surface_hit_any(sc, wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
                                 li2 = area_L(lt, lh.n, -wi);  // SurfaceInteraction::le (surface_interaction.rs:283-289)
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                     MeshRec m;
                     PHC_BEGIN(1);
                     QSurf qs;
-                    SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs)
+                    SurfHit si = QUADRIC ? make_surface_hit_q<QUADRIC>(sc, mk3(ray.ox, ray.oy, ray.oz), rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs, h0.x)
                                          : make_surface_hit_any(sc, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m);
                     if (emit) {
                         if (Row::area && m.first_light >= 0) L = L + beta * area_L(sc.lights[(uint32_t)m.first_light + (hprim - m.tri_base)], si.n, -rd);

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(PH_TEX_LDS_THREADS) __attribute__((amdgpu_waves_per
         const f3 ro = mk3(ray.ox, ray.oy, ray.oz), rd = mk3(ray.dx, ray.dy, ray.dz);
         MeshRec m;
         QSurf qs; qs.hit = 0u;
-        const SurfHit si = make_surface_hit_q<QUADRIC>(sc, ro, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs);
+        const SurfHit si = make_surface_hit_q<QUADRIC>(sc, ro, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs, h0.x);
         const bool on_quadric = QUADRIC && (m.flags & PH_MESH_QUADRIC) != 0u;
         const MaterialRec& mr = sc.materials[m.material];
         if (mr.none) continue;
@@ -352,7 +352,7 @@ PH_DEV void wd_estimate_receive(const DeviceScene& sc, const WhParams& w, int pa
                     const float4 h1 = hp[1];
                     MeshRec m;
                     QSurf lqs; lqs.hit = 0u;
-                    const SurfHit lh = make_surface_hit_q<QUADRIC>(sc, mk3(mr.ox, mr.oy, mr.oz), wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &lqs);
+                    const SurfHit lh = make_surface_hit_q<QUADRIC>(sc, mk3(mr.ox, mr.oy, mr.oz), wi, mr.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &lqs, h0.x);
                     li2 = area_L(lt, lh.n, -wi);   // SurfaceInteraction::le (surface_interaction.rs:283-289)
                 }
             } else li2 = light_le<true>(sc, lt, wi);
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void whitted_state_kernel(DeviceScene sc, WhPa
                 const uint32_t hprim = __float_as_uint(h0.y);
                 MeshRec m;
                 QSurf qs; qs.hit = 0u;
-                SurfHit si = make_surface_hit_q<QUADRIC>(sc, ro, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs);
+                SurfHit si = make_surface_hit_q<QUADRIC>(sc, ro, rd, ray.time, __float_as_uint(h1.y), __float_as_uint(h1.z), h0.z, h0.w, h1.x, m, &qs, h0.x);
                 const MaterialRec& mr = sc.materials[m.material];
                 if (mr.none) {   // bsdf.is_none(): `return self.li(&isect.spawn_ray(&ray.d), ..)` at the same depth (whitted.rs:63-66); the new ray has no differentials
                     ray_cl = spawn_ray(si, rd);

@@ -18,6 +18,7 @@ static void usage() {
                  "  --sobol-tables FILE    raw Sobol generator matrices (needed for Sampler \"sobol\")\n"
                  "  --quadrics             read Shape \"sphere\", \"cylinder\", \"cone\", \"paraboloid\", \"disk\" and \"hyperboloid\" (without it they are refused as out of scope); a sphere under\n"
                  "                         AreaLightSource \"diffuse\" is an area light, rendered by Integrator \"whitted\" (\"path\" and \"directlighting\" with --path-sphere-lights)\n"
+                 "  --curves               read Shape \"curve\" (flat, cylinder and ribbon curves; bezier and bspline bases of degree 2 and 3; without it the directive is refused as out of scope)\n"
                  "  --path-sphere-lights   render such a sphere light under Integrator \"path\" too (without it the scene is refused there)\n"
                  "  --quadric-lights       with --quadrics: a disk or a cylinder under AreaLightSource \"diffuse\" is an area light too, rendered by either integrator (the reference's\n"
                  "                         cone, paraboloid and hyperboloid have no Shape::sample and stay refused)\n"
@@ -27,7 +28,7 @@ static void usage() {
 }
 
 int main(int argc, char** argv) {
-    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false, quadrics = false, quadric_lights = false, path_sphere_lights = false; float crop[4] = {0, 1, 0, 1};
+    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false, quadrics = false, curves = false, quadric_lights = false, path_sphere_lights = false; float crop[4] = {0, 1, 0, 1};
     std::vector<std::string> files;
     std::vector<int> devices; bool multi = false;
     for (int i = 1; i < argc; i++) {
@@ -48,6 +49,7 @@ int main(int argc, char** argv) {
         else if (a == "--quiet") quiet = true;
         else if (a == "--check") check = true;
         else if (a == "--quadrics") quadrics = true;
+        else if (a == "--curves") curves = true;
         else if (a == "--path-sphere-lights") path_sphere_lights = true;
         else if (a == "--quadric-lights") quadric_lights = true;
         else if (a == "--convert-image") {
@@ -66,22 +68,23 @@ int main(int argc, char** argv) {
         std::unique_ptr<pbrt_host::Api> api_owner((multi && !check) ? new pbrt_host::Api(devices) : new pbrt_host::Api(check ? -1 : device));
         pbrt_host::Api& api = *api_owner;
         if (!api.error.empty()) { std::fprintf(stderr, "Error: %s\n", api.error.c_str()); return 3; }
-        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet; api.quadrics = quadrics; api.quadric_lights = quadric_lights; api.path_sphere_lights = path_sphere_lights;
+        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet; api.quadrics = quadrics; api.curves = curves; api.quadric_lights = quadric_lights; api.path_sphere_lights = path_sphere_lights;
         api.has_crop_override = has_crop; std::memcpy(api.crop_override, crop, sizeof crop);
         pbrt_host::RenderReport rep;
         if (!pbrt_host::parse_file(fn, api, &rep)) { std::fprintf(stderr, "Error: %s: %s\n", fn.c_str(), api.error.c_str()); return 1; }
         if (check) {
             std::printf("{\"file\": \"%s\", \"triangles\": %llu, \"lights\": %llu, \"instances\": %llu, \"xres\": %d, \"yres\": %d, \"crop\": [%d, %d, %d, %d], \"spp\": %d, \"integrator\": \"%s\", \"max_depth\": %d, "
-                        "\"light_strategy\": %d, \"pixel_bounds\": [%d, %d, %d, %d], \"out_file\": \"%s\", \"warnings\": %zu, \"quadrics\": %llu%s}\n",
+                        "\"light_strategy\": %d, \"pixel_bounds\": [%d, %d, %d, %d], \"out_file\": \"%s\", \"warnings\": %zu, \"quadrics\": %llu, \"curves\": %llu%s}\n",
                         fn.c_str(), (unsigned long long)rep.n_triangles, (unsigned long long)rep.n_lights, (unsigned long long)rep.n_instances, rep.xres, rep.yres, rep.crop[0], rep.crop[1], rep.crop[2], rep.crop[3],
-                        rep.spp, rep.integrator.c_str(), rep.max_depth, rep.light_strategy, rep.pixel_bounds[0], rep.pixel_bounds[1], rep.pixel_bounds[2], rep.pixel_bounds[3], rep.out_file.c_str(), rep.warnings.size(), (unsigned long long)rep.n_quadrics,
+                        rep.spp, rep.integrator.c_str(), rep.max_depth, rep.light_strategy, rep.pixel_bounds[0], rep.pixel_bounds[1], rep.pixel_bounds[2], rep.pixel_bounds[3], rep.out_file.c_str(), rep.warnings.size(), (unsigned long long)rep.n_quadrics, (unsigned long long)rep.n_curves,
                         rep.integrator == "directlighting" ? (", \"strategy\": \"" + rep.direct_strategy + "\"").c_str() : "");   // a key of this integrator only
             continue;
         }
         if (!quiet && !rep.out_file.empty()) {
             const PbrtHipStats& s = rep.stats;
             const double rays = (double)(s.regular_rays + s.shadow_rays);
-            const std::string shapes = rep.n_quadrics ? ", " + std::to_string(rep.n_quadrics) + " quadric shapes" : std::string();
+            const std::string shapes = (rep.n_quadrics ? ", " + std::to_string(rep.n_quadrics) + " quadric shapes" : std::string()) +
+                                       (rep.n_curves ? ", " + std::to_string(rep.n_curves) + " curve segments" : std::string());
             std::printf("%s: %llu triangles%s, %llu lights, BVH %.3f s, render %.3f s, %.1f Mrays/s (%llu regular + %llu shadow rays), zero-radiance paths %.2f%% -> %s\n",
                         fn.c_str(), (unsigned long long)rep.n_triangles, shapes.c_str(), (unsigned long long)rep.n_lights, rep.build_seconds, s.render_seconds,
                         s.render_seconds > 0 ? rays / s.render_seconds * 1e-6 : 0.0, (unsigned long long)s.regular_rays, (unsigned long long)s.shadow_rays,

@@ -1,5 +1,6 @@
 // Host-side scene API over the C ABI.  See pbrt_host.hpp for scope; reference: api/src/lib.rs, api/src/graphics_state.rs.
 #include "pbrt_host.hpp"
+#include "../csrc/curve_host.h"
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -730,9 +731,58 @@ void Api::quadric_shape(const std::string& name, const ParamSet& p) {
     n_quadrics_++;
 }
 
+// Shape "curve" (Api::curves): Curve::from_props (shapes/src/curve.rs:149-316).  The parameters, defaults and warnings are the reference's; where it panics — a bad degree or
+// basis, a wrong number of control points or normals, a ribbon without N — the parse stops with one sentence.  The conversion to cubic Bezier segments (degree elevation,
+// b-spline blossoming, per-segment widths) is csrc/curve_host.h; each Bezier segment becomes one pbrt_hip_add_curve, i.e. 2^splitdepth Curve segments.
+void Api::curve_shape(const ParamSet& p) {
+    // what the library refuses is refused here as well: check mode calls nothing in it
+    if (!current_object_.empty()) { error = "Shape \"curve\" between ObjectBegin and ObjectEnd: curves inside object definitions are not supported"; return; }
+    if (!gs_.area_light.empty()) { error = "AreaLightSource \"" + gs_.area_light + "\" on Shape \"curve\": a curve cannot be an area light (the reference's Curve::sample is todo!())"; return; }
+    for (const char* an : {"alpha", "shadowalpha"})   // only the triangle mesh reads them (triangle.rs:278-312)
+        if (p.floats.count(an) || p.textures.count(an)) warn(std::string("Shape \"curve\": the reference's curves read no '") + an + "'; ignoring it");
+    const float width = p.find_one_float("width", 1.0f);
+    const float width0 = p.find_one_float("width0", width), width1 = p.find_one_float("width1", width);
+    const int degree = p.find_one_int("degree", 3);
+    const std::string basis = p.find_one_string("basis", "bezier");
+    if (degree != 2 && degree != 3) { error = "Shape \"curve\": Invalid degree " + std::to_string(degree) + ": only degree 2 and 3 curves are supported."; return; }
+    if (basis != "bezier" && basis != "bspline") { error = "Shape \"curve\": Invalid basis '" + basis + "': only 'bezier' and 'bspline' are supported."; return; }
+    static const std::vector<float> none;
+    const std::vector<float>* pp = p.find_floats("P");
+    const std::vector<float>& P = pp ? *pp : none;
+    std::vector<pcurve::PropSegment> segs;
+    const std::string bad = pcurve::from_props_segments(degree, basis == "bspline", P.data(), P.size() / 3, width0, width1, segs);
+    if (!bad.empty()) { error = "Shape \"curve\": " + bad; return; }
+    const std::string type_name = p.find_one_string("type", "flat");
+    int type = PH_CURVE_CYLINDER;
+    if (type_name == "flat") type = PH_CURVE_FLAT;
+    else if (type_name == "ribbon") type = PH_CURVE_RIBBON;
+    else if (type_name != "cylinder") warn("Unknown curve type '" + type_name + "'.  Using 'cylinder'.");
+    const std::vector<float>* np_ = p.find_floats("N");
+    std::vector<float> N = np_ ? *np_ : none;
+    if (!N.empty()) {
+        if (type != PH_CURVE_RIBBON) { warn("Curve normals are only used with 'ribbon' type curves."); N.clear(); }
+        else if (N.size() / 3 != segs.size() + 1) {
+            error = "Shape \"curve\": Invalid number of normals " + std::to_string(N.size() / 3) + ": must provide " + std::to_string(segs.size() + 1) + " normals for ribbon curves with " +
+                    std::to_string(segs.size()) + " segments.";
+            return;
+        }
+    } else if (type == PH_CURVE_RIBBON) { error = "Shape \"curve\": Must provide normals 'N' at curve endpoints with ribbon curves."; return; }
+    // `splitdepth` read as a float (truncated), then as an int with that as its default (:228-229)
+    const int sd = p.find_one_int("splitdepth", (int)p.find_one_float("splitdepth", 3.0f));
+    if (sd < 0 || sd > 16) { error = "Shape \"curve\": splitdepth " + std::to_string(sd) + " is outside [0, 16]"; return; }
+    const uint32_t mat = material_id_for(material_for_shape(p));
+    if (!error.empty()) return;
+    const uint32_t flags = gs_.reverse_orientation ? 1u : 0u;
+    for (size_t k = 0; k < segs.size(); k++) {
+        if (!check(ABI(pbrt_hip_add_curve(scene_, ctm_.m, ctm_.mi, type, segs[k].cp, segs[k].width, N.empty() ? nullptr : N.data() + 3 * k, sd, mat, flags)), "add_curve")) return;
+        n_curves_ += 1ull << sd;
+    }
+}
+
 void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::string& scene_dir) {
     if (!verify_world("Shape") || !error.empty() || (!scene_ && !check_only_)) return;
     if (quadrics && is_quadric_shape(name)) { quadric_shape(name, p); return; }
+    if (curves && name == "curve") { curve_shape(p); return; }
     std::vector<float> P, N, S, UV;
     std::vector<uint32_t> idx;
     if (name == "trianglemesh") {  // shapes/src/triangle.rs:184-330
@@ -768,7 +818,7 @@ void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::stri
         if (mesh.P.empty() || mesh.indices.empty()) { warn("PLY file '" + fn + "' is invalid! No face/vertex elements found!"); return; }
         P.swap(mesh.P); N.swap(mesh.N); UV.swap(mesh.UV); idx.swap(mesh.indices);
     } else {
-        error = "Shape \"" + name + "\" is outside the hot-path scope (supported: trianglemesh, plymesh" + (is_quadric_shape(name) ? "; the six quadric shapes are read with --quadrics)" : ")");
+        error = "Shape \"" + name + "\" is outside the hot-path scope (supported: trianglemesh, plymesh" + (is_quadric_shape(name) ? "; the six quadric shapes are read with --quadrics)" : name == "curve" ? "; curves are read with --curves)" : ")");
         return;
     }
     // alpha / shadowalpha (triangle.rs:278-312): a float texture by name (constant ones fold to the constant, the others are evaluated per candidate hit) or a float
@@ -942,7 +992,7 @@ int Api::pbrt_world_end(RenderReport& rep) {
     // "sah" and "hlbvh" trees are made on the GPU, scenes with object instances included (same trees: csrc/bvh_sah_device.hip, bvh_device.hip); everything else by the library's host builder
     int brc = PBRT_HIP_ERR_UNSUPPORTED;
     if ((split == 0 || split == 1) && !check_only_)   // pbrt_hip_build_accel_device refuses the SAH tree of a scene with quadric shapes; the _shapes entry builds either
-        brc = n_quadrics_ ? pbrt_hip_build_accel_device_shapes(scene_, split, max_prims) : pbrt_hip_build_accel_device(scene_, split, max_prims);
+        brc = (n_quadrics_ || n_curves_) ? pbrt_hip_build_accel_device_shapes(scene_, split, max_prims) : pbrt_hip_build_accel_device(scene_, split, max_prims);
     if (brc == PBRT_HIP_ERR_UNSUPPORTED) brc = ABI(pbrt_hip_build_accel(scene_, split, max_prims));
     if (!check(brc, "build_accel")) return PBRT_HIP_ERR_DEVICE;
     rep.build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
@@ -974,7 +1024,7 @@ int Api::pbrt_world_end(RenderReport& rep) {
     else { warn("Light sample distribution type \"" + lss + "\" unknown. Using \"spatial\"."); strategy = 2; }
 
     rep.xres = xres; rep.yres = yres; std::memcpy(rep.crop, cb, sizeof cb);
-    rep.n_triangles = n_tris_; rep.n_lights = n_lights_; rep.n_instances = n_instances_; rep.n_quadrics = n_quadrics_; rep.warnings = warnings;
+    rep.n_triangles = n_tris_; rep.n_lights = n_lights_; rep.n_instances = n_instances_; rep.n_quadrics = n_quadrics_; rep.n_curves = n_curves_; rep.warnings = warnings;
     rep.integrator = integrator_name_;
     rep.spp = spp; rep.max_depth = max_depth; rep.light_strategy = strategy; std::memcpy(rep.pixel_bounds, pb, sizeof pb);
     if (check_only_) { rep.out_file = filename; return PBRT_HIP_OK; }

@@ -54,6 +54,7 @@ struct RenderReport {
     double build_seconds = 0, load_seconds = 0;
     uint64_t n_triangles = 0, n_lights = 0, n_instances = 0;  // n_triangles counts instanced triangles once per instance
     uint64_t n_quadrics = 0;  // sphere, cylinder, cone, paraboloid, disk, hyperboloid (read with Api::quadrics)
+    uint64_t n_curves = 0;    // Curve segments made from Shape "curve" (read with Api::curves): 2^splitdepth per cubic Bezier segment
     std::string integrator;  // "path", "whitted" or "directlighting"
     std::string direct_strategy;   // "all" or "one": Integrator "directlighting" only
     int spp = 0, max_depth = 0, light_strategy = 0, pixel_bounds[4] = {0, 0, 0, 0};
@@ -113,6 +114,7 @@ class Api {
     unsigned long long sample_record_budget = 0;   // --sample-record-budget BYTES (pbrt_hip_set_sample_record_budget); 0 = automatic
     bool path_sphere_lights = false;   // --path-sphere-lights: a sphere light (Shape "sphere" under AreaLightSource "diffuse", read with `quadrics`) is rendered by Integrator "path" too
     bool quadric_lights = false;   // --quadric-lights (with `quadrics`): Shape "disk" / "cylinder" under AreaLightSource "diffuse" is an area light (pbrt_hip_add_quadric_light), under either integrator
+    bool curves = false;     // --curves: Shape "curve" is read (Curve::from_props, shapes/src/curve.rs:149-316); without it the directive is refused as out of scope
     bool quadrics = false;   // --quadrics: Shape "sphere" / "cylinder" / "cone" / "paraboloid" / "disk" / "hyperboloid" are read; without it they are refused as out of scope
     bool quiet = false;
     std::vector<std::string> warnings;
@@ -140,6 +142,7 @@ class Api {
     std::string current_object_;                // "" outside ObjectBegin/ObjectEnd
     uint64_t n_instances_ = 0;
     uint64_t n_quadrics_ = 0;
+    uint64_t n_curves_ = 0;
     bool sphere_light_ = false;   // a Shape "sphere" stood under AreaLightSource "diffuse": the Whitted integrator renders it, the path integrator with path_sphere_lights
     int n_devices_ = 1;   // GPUs behind scene_ (--devices)
     bool verify_options(const char* func);
@@ -148,6 +151,7 @@ class Api {
     uint32_t material_id_for(const MaterialDesc& m);
     MaterialDesc material_for_shape(const ParamSet& shape_params) const;
     void quadric_shape(const std::string& name, const ParamSet& p);
+    void curve_shape(const ParamSet& p);
     bool check(int rc, const char* what);
 };
 

@@ -172,6 +172,8 @@ class Binding:
             "bump_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
             "set_path_sphere_lights": (C.c_int, [vp, C.c_int]),
             "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
+            "add_curve": (C.c_int, [vp, fp, fp, C.c_int, fp, fp, fp, C.c_int, C.c_uint32, C.c_uint32]),
+            "curve_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, vp, fp]),
             "traverse_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
             "film_probe_layout": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), ip, ip]),
             "film_probe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, fp, fp, vp, fp, fp, fp]),
@@ -470,6 +472,27 @@ class Scene:
         k = self.QUADRIC_KINDS[kind] if isinstance(kind, str) else int(kind)
         self._chk(self.b.fn("add_quadric_light")(self.h, k, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), C.c_float(radius), C.c_float(a),
                                                  C.c_float(b), C.c_float(phi_max), material, 1 if reverse_orientation else 0, _ptr(_f32(L), C.c_float), 1 if two_sided else 0))
+
+    CURVE_TYPES = {"flat": 0, "cylinder": 1, "ribbon": 2}
+
+    def add_curve(self, object_to_world, world_to_object, curve_type, cp, width, n=None, split_depth=3, material=0, reverse_orientation=False):
+        """Curve::create_segments (shapes/src/curve.rs:105-140, pbrt_hip_add_curve): one cubic Bezier curve, control points cp (4,3) in object space, end widths
+        width (2,), type "flat" | "cylinder" | "ribbon" (or its number), a ribbon's end normals n (2,3).  Takes 2^split_depth consecutive slots of the primitive list; a hit
+        on a segment reports b0 = u, b1 = v."""
+        k = self.CURVE_TYPES[curve_type] if isinstance(curve_type, str) else int(curve_type)
+        nn = None if n is None else _f32(n, (6,))
+        self._chk(self.b.fn("add_curve")(self.h, _ptr(_f32(object_to_world), C.c_float), _ptr(_f32(world_to_object), C.c_float), k, _ptr(_f32(cp, (12,)), C.c_float),
+                                         _ptr(_f32(width, (2,)), C.c_float), _ptr(nn, C.c_float), int(split_depth), material, 1 if reverse_orientation else 0))
+
+    CURVE_PROBE_STRIDE = 20
+
+    def curve_probe(self, prim, rays, shadow=False):
+        """curve_test, then curve_surface, of the curve segment in primitive slot `prim` on explicit rays, each with its own t_max (pbrt_hip_curve_probe_batch), a probe for the
+        parity tests.  Returns (n,20): hit flag, t, u, v, then world-space p, p_error, dpdu, dpdv, n (one pad word).  shadow=True: Curve::intersect_p's decision in column 0 alone."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        out = np.zeros((len(rays), self.CURVE_PROBE_STRIDE), np.float32)
+        self._chk(self.b.fn("curve_probe_batch")(self.h, prim, 1 if shadow else 0, len(rays), rays.ctypes.data, _ptr(out, C.c_float)))
+        return out
 
     def object_begin(self) -> int:
         """ObjectBegin (api/src/lib.rs:911-925): meshes added until object_end() belong to the returned object."""
