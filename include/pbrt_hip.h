@@ -489,6 +489,12 @@ int pbrt_hip_set_sample_record_budget(PbrtHipScene*, uint64_t bytes);
  * chunk, out[5] bytes of the chunk-scaled buffers for them, out[6] = out[7] = 0.  All zero before the first render; out[0] = 0 after a render without pixels.
  * A multi-device handle reports, entry by entry, the largest value any of its devices came to. */
 int pbrt_hip_get_render_footprint(PbrtHipScene*, uint64_t out[8]);
+/* pbrt_hip_get_mis_escape: *out = 1 if the handle's last pbrt_hip_render_path* call traced estimate_direct's BSDF-sampled ray as an escape query, else 0 (also before any render).
+ * In a scene without area lights of any shape, whose traversal row has neither alpha-mask textures nor quadrics, and with traversal counting off, the shade pass reads one bit of
+ * that ray's result — did it hit anything —, so the traversal kernel stops it at the first primitive the reference's intersect would accept instead of refining a closest hit
+ * nobody reads.  The ray remains a closest-hit ray in every respect a caller can see: the film, PbrtHipStats (regular_rays, shadow_rays, paths) and the footprint
+ * (pbrt_hip_get_render_footprint: bytes per path, paths per chunk) are bit for bit what they are without the query.  PBRT_HIP_ERR_INVALID_ARG: a null argument. */
+int pbrt_hip_get_mis_escape(PbrtHipScene*, int* out);
 
 /* Multi-GPU form: writes this rank's FilmTiles (contrib rgb + weight, 4 floats per tile pixel, tiles in
  * increasing index order, each tile's pixel bounds as Film::get_film_tile computes them) into a DEVICE buffer
@@ -572,7 +578,10 @@ int pbrt_hip_curve_probe_batch(PbrtHipScene*, uint32_t prim, int shadow, uint64_
  * bin keys (< 4096) of n_cl closest-hit and n_sh any-hit rays; the keys and the two counts are uploaded and read from device memory, as in a render.  order_out[0 .. n_cl + n_sh) =
  * the queue positions (closest-hit rays 0 .. n_cl, any-hit rays behind them) grouped by bin, closest-hit rays first; the order inside a bin is unspecified.  sort_blocks = the grid
  * of the two passes over the keys (a render uses 1024).  Needs a handle only: no geometry, no accelerator.
- * PBRT_HIP_ERR_INVALID_ARG: a null handle; sort_blocks 0 or above 65536; a null array with a non-zero count; a key >= 4096; n_cl + n_sh >= 0x7FFF0000.  Nothing is launched on a refusal. */
+ * A closest-hit key may carry the escape-query mark, 4096, on top of its bin (pbrt_hip_get_mis_escape): that ray's entry of order_out then has bit 31 set, and the ray is grouped
+ * with the unmarked closest-hit rays of its bin; an unmarked key gives the entry it always gave.
+ * PBRT_HIP_ERR_INVALID_ARG: a null handle; sort_blocks 0 or above 65536; a null array with a non-zero count; a closest-hit key >= 8192 or an any-hit key >= 4096;
+ * n_cl + n_sh >= 0x7FFF0000.  Nothing is launched on a refusal. */
 int pbrt_hip_raysort_probe(PbrtHipScene*, uint32_t n_cl, uint32_t n_sh, const uint32_t* keys_cl, const uint32_t* keys_sh, uint32_t sort_blocks, uint32_t* order_out /* n_cl + n_sh */);
 /* pbrt_hip_texture_probe_batch (a-SI, f3): texture number `texture` at n explicit contexts (the 15 floats per point of pbrt_hip_texture_eval_batch), through each piece of code the
  * renderer evaluates textures with; 3 floats out per probe.
@@ -594,9 +603,12 @@ int pbrt_hip_bump_probe_batch(PbrtHipScene*, uint32_t texture, int variant, uint
  * is used and head_chunk is ignored.  blocks = the grid: 1 .. the resident grid the handle launches its renders with (6 blocks of 256 lanes per CU).  The kernel row is the scene's,
  * the counting rows with pbrt_hip_set_traversal_counting on.  hits_out[n_cl] / occluded_out[n_sh] = what pbrt_hip_intersect_batch / pbrt_hip_occluded_batch give for the same rays:
  * the result of a ray depends on nothing but the ray.  A result the kernel did not write comes back as 0xFF bytes.
+ * An entry of `order` with bit 31 set (mode 2, a closest-hit position, a scene whose kernel row has neither alpha-mask textures nor quadrics, counting off) passes through to the
+ * kernel as the ray binning would hand it over: that ray is an escape query (pbrt_hip_get_mis_escape).  Its hit record comes back as t = the ray's t_max when it stopped,
+ * prim = 0 if it hit anything and 0xFFFFFFFF if not — the same verdict as the unmarked ray's prim != 0xFFFFFFFF —, b0 = b1 = 0, and the other 16 bytes as they were (0xFF).
  * PBRT_HIP_ERR_INVALID_ARG: a null handle; a null array with a non-zero count; an unknown mode; mode 0 with n_sh > 0 or mode 1 with n_cl > 0; n_cl + n_sh >= 0x7FFF0000; n_heads 0 or
  * above 8; n_heads > 1 with head_chunk 0 or no multiple of 64 (the kernel's precondition: a batch of 64 rays lies in one chunk); blocks 0 or above the resident grid; an order that
- * is no permutation of 0 .. n_cl + n_sh (checked on the host).  PBRT_HIP_ERR_STATE: no accelerator built.  PBRT_HIP_ERR_DEVICE: a ray's traversal stack ran over, as in
+ * is no permutation of 0 .. n_cl + n_sh, bit 31 aside (checked on the host); bit 31 on an entry where the line above does not allow it.  PBRT_HIP_ERR_STATE: no accelerator built.  PBRT_HIP_ERR_DEVICE: a ray's traversal stack ran over, as in
  * pbrt_hip_intersect_batch.  Nothing is launched on a refusal and the handle stays usable. */
 int pbrt_hip_traverse_probe(PbrtHipScene*, int mode, const PbrtHipRay* rays_cl, uint32_t n_cl, const PbrtHipRay* rays_sh, uint32_t n_sh, const uint32_t* order /* NULL or n_cl + n_sh */,
                             uint32_t n_heads, uint32_t head_chunk, uint32_t blocks, PbrtHipHit* hits_out /* n_cl */, uint8_t* occluded_out /* n_sh */);

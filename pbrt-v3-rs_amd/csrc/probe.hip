@@ -460,7 +460,8 @@ int pbrt_hip_raysort_probe(PbrtHipScene* s, uint32_t n_cl, uint32_t n_sh, const 
     if (sort_blocks == 0 || sort_blocks > 65536u) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: sort_blocks must be 1 .. 65536");
     const uint64_t n = (uint64_t)n_cl + n_sh;
     if (n >= 0x7FFF0000ull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: more rays than a round's queues hold");
-    for (uint32_t i = 0; i < n_cl; i++) if (keys_cl[i] >= PH_SORT_BINS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a key is not below 4096");
+    // (a closest-hit key may carry the escape-query mark, PH_SORT_BINS, on top of its bin: mis_escape.h)
+    for (uint32_t i = 0; i < n_cl; i++) if (keys_cl[i] >= PH_SORT_KEYS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a closest-hit key is not below 4096, marked or not");
     for (uint32_t i = 0; i < n_sh; i++) if (keys_sh[i] >= PH_SORT_BINS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a key is not below 4096");
     PH_CHECK(s, hipSetDevice(s->device));
     const size_t o_cl = 0, o_sh = o_cl + up256((size_t)n_cl * 4), o_n = o_sh + up256((size_t)n_sh * 4), o_order = o_n + 256, o_ws = o_order + up256(n * 4),
@@ -497,10 +498,16 @@ int pbrt_hip_traverse_probe(PbrtHipScene* s, int mode, const PbrtHipRay* rays_cl
     if (n_heads > 1 && (head_chunk == 0 || head_chunk % PH_BATCH != 0)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: with several heads head_chunk must be a non-zero multiple of 64");
     if (blocks == 0) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: blocks must be at least 1");
     if (order) {   // a permutation of 0 .. n: any other list would leave a ray untraced or trace one twice
+        // An entry may carry the escape-query mark (PH_ORDER_ESCAPE, mis_escape.h) as the ray binning writes it for a marked key: only on a closest-hit position, only in mode 2
+        // and only where the scene's kernel row reads it — any other kernel would take the marked entry for a queue position.  It passes through to the kernel as it is.
+        const bool marks_ok = mode == 2 && ph::mis_escape_row(!s->alpha_textures ? 0 : s->alpha_lean ? 1 : 2, !s->quadrics.empty(), s->count_traversal);
         std::vector<bool> seen(n, false);
         for (uint64_t i = 0; i < n; i++) {
-            if (order[i] >= n || seen[order[i]]) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: order is not a permutation of the queue positions");
-            seen[order[i]] = true;
+            const uint32_t pos = order[i] & ~PH_ORDER_ESCAPE;
+            if (pos >= n || seen[pos]) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: order is not a permutation of the queue positions");
+            if ((order[i] & PH_ORDER_ESCAPE) && (!marks_ok || pos >= n_cl))
+                return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: an escape-query mark on an any-hit position, outside mode 2, or in a scene whose kernel row serves none");
+            seen[pos] = true;
         }
     }
     if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "traverse_probe: call pbrt_hip_build_accel first");

@@ -6,7 +6,8 @@
 // These kernels produce `order`, a permutation of the round's queue positions grouped by the cell of the ray origin (Morton order
 // of a 16^3 grid over the scene bound), closest-hit rays first, any-hit rays behind them —
 // the traversal kernel walks the queue through it.  Rays are not moved: the kernel that writes a ray (shade) also writes its 4-byte bin key, the two
-// passes here read the keys and write 4 B of `order` per ray.
+// passes here read the keys and write 4 B of `order` per ray.  A closest-hit key may carry the escape-query mark (mis_escape.h: PH_SORT_BINS on top of the bin, written by the path
+// integrator's shade pass alone): the ray is binned by its cell as every other, and bit 31 of its entry of `order` hands the mark on to the traversal kernel.
 //
 // A counting sort without global atomics per ray, in two passes over the keys.  Every block owns a contiguous slice of the queue (raysort_plan.h: the same slice in
 // both passes).  The first pass histograms the slice in LDS and adds the non-empty bins to the global tallies, one atomic per block and bin; what the atomic
@@ -20,6 +21,7 @@
 // ballot loop — a wave of the path-ordered queue holds many distinct keys, the loop cost more than the plain atomics: binning 28 -> 70 ms per configs[2] frame.)
 #pragma once
 #include "raysort_plan.h"
+#include "mis_escape.h"
 #include "traverse.h"
 
 namespace ph {
@@ -56,9 +58,12 @@ PH_DEV uint32_t ray_sort_key(const RaySortGrid& g, float ox, float oy, float oz)
 // The keys of one run of a slice (raysort_plan.h), each handed on by exactly one thread of the block with its joint key (key + key_add) and its joint queue position (position
 // in the run's array + pos_add): scalar head, 16-byte body, scalar tail.  The body goes PH_SORT_DEPTH vectors per lane at a time while that many are left, all loads issued
 // before `fv` sees them (fv(v, i0): v[d] holds the keys of positions i0 + 4 * d * PH_SORT_BLOCK + 0 .. 3), and one vector at a time through `f1(key, position)` after that.
-template <class FV, class F1>
+// CL: the run is the closest-hit keys', of which the shade pass may have marked some as escape queries (mis_escape.h): the joint key then carries the mark in bit 31, above
+// every bin — raysort_bin drops it, the scatter pass hands it on into `order`.  A key below PH_SORT_BINS (every key of a frame without the query) is its own joint key.
+template <bool CL, class FV, class F1>
 PH_DEV void raysort_walk_run(const uint32_t* keys, const RaySortRun& r, uint32_t key_add, uint32_t pos_add, FV&& fv, F1&& f1) {
-    if (r.head + threadIdx.x < r.body) f1(keys[r.head + threadIdx.x] + key_add, r.head + threadIdx.x + pos_add);
+    auto joint = [&](uint32_t k) -> uint32_t { return CL ? mis_escape_joint_key(k) : k + key_add; };
+    if (r.head + threadIdx.x < r.body) f1(joint(keys[r.head + threadIdx.x]), r.head + threadIdx.x + pos_add);
     const uint4* body = reinterpret_cast<const uint4*>(keys + r.body);
     const uint32_t n_vec = (r.tail - r.body) >> 2;
     uint32_t j = threadIdx.x;
@@ -68,27 +73,28 @@ PH_DEV void raysort_walk_run(const uint32_t* keys, const RaySortRun& r, uint32_t
         for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) v[d] = body[j + d * PH_SORT_BLOCK];
         __builtin_amdgcn_sched_barrier(0);   // (left alone, the scheduler sinks each load to just above its first use: one in flight again)
 #pragma unroll
-        for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) { v[d].x += key_add; v[d].y += key_add; v[d].z += key_add; v[d].w += key_add; }
+        for (uint32_t d = 0; d < PH_SORT_DEPTH; d++) { v[d].x = joint(v[d].x); v[d].y = joint(v[d].y); v[d].z = joint(v[d].z); v[d].w = joint(v[d].w); }
         fv(v, r.body + 4u * j + pos_add);
     }
     for (; j < n_vec; j += PH_SORT_BLOCK) {
         const uint4 v = body[j];
         const uint32_t i = r.body + 4u * j + pos_add;
-        f1(v.x + key_add, i); f1(v.y + key_add, i + 1u); f1(v.z + key_add, i + 2u); f1(v.w + key_add, i + 3u);
+        f1(joint(v.x), i); f1(joint(v.y), i + 1u); f1(joint(v.z), i + 2u); f1(joint(v.w), i + 3u);
     }
-    if (r.tail + threadIdx.x < r.end) f1(keys[r.tail + threadIdx.x] + key_add, r.tail + threadIdx.x + pos_add);
+    if (r.tail + threadIdx.x < r.end) f1(joint(keys[r.tail + threadIdx.x]), r.tail + threadIdx.x + pos_add);
 }
 // every ray of the slice; an any-hit ray's key lies PH_SORT_BINS up, its position n_cl up
 template <class FV, class F1>
 PH_DEV void raysort_walk_slice(const RaySortParams& p, const RaySortSlice& s, uint32_t n_cl, FV&& fv, F1&& f1) {
-    raysort_walk_run(p.keys_cl, s.cl, 0u, 0u, fv, f1);
-    raysort_walk_run(p.keys_sh, s.sh, PH_SORT_BINS, n_cl, fv, f1);
+    raysort_walk_run<true>(p.keys_cl, s.cl, 0u, 0u, fv, f1);
+    raysort_walk_run<false>(p.keys_sh, s.sh, PH_SORT_BINS, n_cl, fv, f1);
 }
 PH_DEV RaySortSlice raysort_slice(const RaySortParams& p, uint32_t n_cl, uint32_t n_sh) {
     return raysort_plan(n_cl, n_sh, gridDim.x, PH_SORT_BLOCK, PH_SORT_FLOOR, blockIdx.x, (uint32_t)((uintptr_t)p.keys_cl >> 2) & 3u, (uint32_t)((uintptr_t)p.keys_sh >> 2) & 3u);
 }
-// a key outside the table (the shade pass writes none) must not reach past the LDS array
+// a key outside the table (the shade pass writes none) must not reach past the LDS array; the mark of an escape query (bit 31 of a joint key) is no part of the bin
 PH_DEV uint32_t raysort_bin(uint32_t key) { return key & (PH_SORT_KEYS - 1u); }
+PH_DEV uint32_t raysort_mark(uint32_t key) { return key & PH_ORDER_ESCAPE; }
 
 __global__ __launch_bounds__(PH_SORT_BLOCK) void raysort_hist_kernel(RaySortParams p) {
     __shared__ uint32_t h[PH_SORT_KEYS];
@@ -163,10 +169,10 @@ __global__ __launch_bounds__(PH_SORT_BLOCK) void raysort_scatter_kernel(RaySortP
                 const uint32_t rz = zx ? rx + 1u + yx : zy ? ry + 1u : at[d].z;
                 const uint32_t rw = wx ? rx + 1u + yx + zx : wy ? ry + 1u + zy : wz ? rz + 1u : at[d].w;
                 const uint32_t i = i0 + 4u * d * PH_SORT_BLOCK;
-                p.order[rx] = i; p.order[ry] = i + 1u; p.order[rz] = i + 2u; p.order[rw] = i + 3u;
+                p.order[rx] = i | raysort_mark(v[d].x); p.order[ry] = (i + 1u) | raysort_mark(v[d].y); p.order[rz] = (i + 2u) | raysort_mark(v[d].z); p.order[rw] = (i + 3u) | raysort_mark(v[d].w);
             }
         },
-        [&](uint32_t key, uint32_t i) { p.order[atomicAdd(&base[raysort_bin(key)], 1u)] = i; });
+        [&](uint32_t key, uint32_t i) { p.order[atomicAdd(&base[raysort_bin(key)], 1u)] = i | raysort_mark(key); });
 }
 
 }  // namespace ph

@@ -112,6 +112,7 @@ struct PbrtHipScene : SceneHostState {
     uint64_t record_budget = 0;
     bool path_sphere_lights = false;   // pbrt_hip_set_path_sphere_lights: the path integrator samples sphere lights (SceneHostState::sphere_lights) instead of refusing the scene
     uint64_t footprint[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool last_mis_escape = false;      // what the last path render's plan said (PathPlan::mis_escape; pbrt_hip_get_mis_escape)
 };
 
 namespace phost {

@@ -23,6 +23,7 @@
 #include "dmath.h"
 #include "scene_types.h"
 #include "quadric.h"
+#include "mis_escape.h"
 
 constexpr int PH_TRAV_BLOCK = 256;  // threads per traversal block (texture.h checks it against the texture evaluator's LDS stack)
 constexpr int PH_MAX_STACK = 64;    // the reference's nodes_to_visit[64] (bvh/mod.rs:185)
@@ -417,6 +418,9 @@ constexpr int trav_stack_cap(bool inst) { return inst ? 2 * PH_MAX_STACK : PH_MA
 template <class Shape, int MODE>
 __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(Shape::wpe ? Shape::wpe : 1, Shape::wpe ? Shape::wpe : 8))) void traverse_kernel(DeviceScene sc, TravParams p) {
     constexpr bool ANYHIT = MODE == TRAV_ANY, MIXED = MODE == TRAV_MIXED, COUNT = Shape::count, INST = Shape::inst, QUADRIC = Shape::quadric;
+    // The mixed kernels of the rows without alpha masks, quadrics and counters serve escape queries (mis_escape.h): closest-hit rays whose entry of `order` carries PH_ORDER_ESCAPE
+    // are walked as any-hit lanes (`ah`) under the closest-hit acceptance rule and retire with one 16-byte store.  Every other instantiation compiles to what it was.
+    constexpr bool ESCAPE = MIXED && mis_escape_row(Shape::alpha, QUADRIC, COUNT);
     constexpr int LEAF_MIN = Shape::leaf_min, REFILL_MIN = Shape::refill_min, LDS_DEPTH = Shape::lds_depth, NODE_STEPS = Shape::node_steps, ALPHA = Shape::alpha, ALPHA_MIN = Shape::alpha_min;
     static_assert(MODE == TRAV_CLOSEST || MODE == TRAV_ANY || MODE == TRAV_MIXED, "no such mode");
     static_assert(LDS_DEPTH >= TravShapes::spill_lds_depth(INST), "the spill region starts at the shallowest LDS stack of the table's rows: a shape outside the table would write past it");
@@ -503,6 +507,15 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
     // lane idles exactly as an empty one does: every test of the loop below excludes cur == PH_INVALID_REF.
     auto retire = [&]() {
             PHC_BEGIN(6);
+            if constexpr (ESCAPE) {   // (a discarded statement otherwise: the other instantiations keep their captures and their instructions)
+                if (ah && ray_index < n_first) {   // an escape query: the one bit its reader looks at (hprim != 0xFFFFFFFF) — no tri_bary, no second fetch of the TriRec, 16 bytes
+                    float4* hp = reinterpret_cast<float4*>(reinterpret_cast<HitOut*>(p.out) + ray_index);
+                    ph_stream_store(make_float4(r.t_max, __uint_as_float(occluded ? 0u : 0xFFFFFFFFu), 0.0f, 0.0f), hp);
+                    has_ray = false;
+                    PHC_END(6);
+                    return;
+                }
+            }
             if (MIXED && ah) p.out2[ray_index - n_first] = occluded ? 1 : 0;
             else if (!MIXED && ANYHIT) reinterpret_cast<uint8_t*>(p.out)[ray_index] = occluded ? 1 : 0;
             else {
@@ -561,7 +574,10 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                     if (!has_ray && rank < avail) {
                         ray_index = p.order ? ph_stream_load(p.order + batch_next + rank) : batch_next + rank;
                         if (MIXED) ah = ray_index >= n_first;
-                        const float4* rp = reinterpret_cast<const float4*>((MIXED && ah) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index);
+                        // bit 31 of the entry (PH_ORDER_ESCAPE): a closest-hit ray that only asks whether it hits anything.  The marked entry lies above every queue position, so
+                        // `ah` is already set: the lane walks as an any-hit lane, and its queue position — below n_first — tells it from one.
+                        if constexpr (ESCAPE) ray_index &= ~PH_ORDER_ESCAPE;
+                        const float4* rp = reinterpret_cast<const float4*>((MIXED && (ESCAPE ? ray_index >= n_first : ah)) ? p.rays2 + (ray_index - n_first) : p.rays + ray_index);
                         const float4 a = ph_stream_load(rp), b = ph_stream_load(rp + 1);
                         RayIn in; in.ox = a.x; in.oy = a.y; in.oz = a.z; in.t_max = a.w; in.dx = b.x; in.dy = b.y; in.dz = b.z; in.time = b.w;
                         ray_setup(r, in);
@@ -696,7 +712,8 @@ __global__ __launch_bounds__(PH_TRAV_BLOCK) __attribute__((amdgpu_waves_per_eu(S
                         };
                         if ((QUADRIC && (flags & PH_TRI_QUADRIC)) ? quadric_leaf() : tri_test(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), t, b0, b1, b2)) {
                             // post-t rejections: degenerate triangle (triangle.rs:567-570 / 862-866), alpha == 0 (:603 / :886-893)
-                            const uint32_t reject = ah ? (PH_TRI_BOGUS | PH_TRI_ALPHA0 | PH_TRI_SALPHA0) : (PH_TRI_BOGUS | PH_TRI_ALPHA0);
+                            // (an escape query is the reference's intersect, not intersect_p: a mesh with constant shadowalpha 0 stops it)
+                            const uint32_t reject = (ESCAPE ? ray_index >= n_first : ah) ? (PH_TRI_BOGUS | PH_TRI_ALPHA0 | PH_TRI_SALPHA0) : (PH_TRI_BOGUS | PH_TRI_ALPHA0);
                             bool accept = !(flags & reject);
                             if (ALPHA && accept && (flags & PH_TRI_ALPHATEX)) {
                                 if (ALPHA_MIN > 0 && !second_meeting) { alpha_wait = true; accept = false; }   // first meeting: the lane stays at this record and waits for companions

@@ -81,6 +81,7 @@ struct WfParams {
     // shade-side work queues (matsort.h): this round's list positions grouped by material key, and the bins' starts; null = the texture / light-distribution / shade passes walk the list in queue order
     const uint32_t* m_order; const uint32_t* m_bins;
     unsigned long long* phase;   // PH_PHASE_CLOCK builds: the shade kernel's phase tallies (phase_clock.h)
+    uint32_t mis_escape;         // PathPlan::mis_escape: the BSDF-sampled MIS ray's bin key carries the escape-query mark (mis_escape.h)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -650,7 +651,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                 float4* d = reinterpret_cast<float4*>(rays_out + mis_slot);
                 float4 ro, rdv; LDS::get(stage, s_u, 1, tid, kInf, ray_time, ro, rdv);
                 d[0] = ro; d[1] = rdv;
-                w.keys_cl[mis_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z);
+                w.keys_cl[mis_slot] = ray_sort_key(w.sort_grid, ro.x, ro.y, ro.z) | (w.mis_escape ? PH_SORT_BINS : 0u);   // the resolve of the next round reads only whether this ray hit anything: an escape query
             }
             if (want_sh) {
                 float4* d = reinterpret_cast<float4*>(w.rays_sh + sh_slot);
@@ -1047,6 +1048,7 @@ struct PathPlan {
     size_t B;
     uint32_t shade_blocks;
     bool identity;       // does pixel_bounds cover every pixel of this rank's tiles?
+    bool mis_escape;     // estimate_direct's BSDF-sampled ray is traced as an escape query (mis_escape.h): no area light, a traversal row without alpha masks and quadrics, counting off
     // ray binning between rounds and per-XCD queue heads (raysort.h, traverse.h): 8 heads, served in chunks of 49 152 rays (a multiple of every batch size); 1 024 blocks per sort pass
     // (the three raysort kernels per configs[2] frame: 512 blocks 9.40 ms, 1 024: 9.18, 2 048: 9.19)
     static constexpr uint32_t n_heads = 8, head_chunk = 49152, sort_blocks = 1024;
@@ -1073,6 +1075,8 @@ static int plan_path_frame(PbrtHipScene* s, int max_depth, int light_strategy, c
     p.n_iter = max_depth + 1;
     p.n_iter_cap = s->has_none_material ? p.n_iter + PathPlan::kMaxNullSkips : p.n_iter;
     p.has_quadrics = !s->quadrics.empty();
+    p.mis_escape = ph::mis_escape_eligible(s->lights_area, !s->alpha_textures ? 0 : s->alpha_lean ? 1 : 2, p.has_quadrics, s->count_traversal);   // (the row launch_traverse_kernel picks)
+    s->last_mis_escape = p.mis_escape;
     p.sphere_lights = (s->sphere_lights != 0 && s->path_sphere_lights) || s->quadric_lights != 0;
     const char* e = std::getenv("PBRT_HIP_SHADE_ROW");
     p.shade_variant = ph::pick_shade_variant(ph::ShadeTraits{s->general_materials, s->textured_materials, p.has_quadrics},
@@ -1117,6 +1121,7 @@ static int bind_path_frame(PbrtHipScene* s, const PathPlan& p, int max_depth, fl
     }
     for (int i = 0; i < 4; i++) wp.pixel_bounds[i] = pixel_bounds[i];
     wp.max_depth = max_depth; wp.rr_threshold = rr_threshold; wp.identity_slots = p.identity ? 1u : 0u;
+    wp.mis_escape = p.mis_escape ? 1u : 0u;
     wp.rays_cl[0] = (ph::RayIn*)w.d_rays_cl[0].p; wp.rays_cl[1] = (ph::RayIn*)w.d_rays_cl[1].p;
     wp.hits_cl = (ph::HitOut*)w.d_hits.p; wp.rays_sh = (ph::RayIn*)w.d_rays_sh.p; wp.occ = (uint8_t*)w.d_occ.p;
     wp.live[0] = (uint32_t*)w.d_live[0].p; wp.live[1] = (uint32_t*)w.d_live[1].p;
@@ -1531,6 +1536,14 @@ int pbrt_hip_get_render_footprint(PbrtHipScene* s, uint64_t out[8]) {
     return ph_guard(s, "pbrt_hip_get_render_footprint", [&]() -> int {
     if (!s || !out) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "get_render_footprint: null argument");
     std::memcpy(out, s->footprint, sizeof s->footprint);
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_get_mis_escape(PbrtHipScene* s, int* out) {
+    return ph_guard(s, "pbrt_hip_get_mis_escape", [&]() -> int {
+    if (!s || !out) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "get_mis_escape: null argument");
+    *out = s->last_mis_escape ? 1 : 0;
     return PBRT_HIP_OK;
     });
 }

@@ -164,6 +164,7 @@ class Binding:
             "selftest_rccl_gather": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint64)]),
             "set_sample_record_budget": (C.c_int, [vp, C.c_uint64]),
             "get_render_footprint": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+            "get_mis_escape": (C.c_int, [vp, C.POINTER(C.c_int)]),
             "bsdf_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, u32p, fp, fp]),
             "sampler_value_batch": (C.c_int, [vp, C.c_uint64, ip, u32p, u32p, C.c_int, fp]),
             "light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, fp, fp, fp, fp]),
@@ -802,7 +803,8 @@ class Scene:
         return out
 
     def traverse_probe(self, mode, rays_cl=None, rays_sh=None, order=None, n_heads=1, head_chunk=49152, blocks=1):
-        """The traversal kernel on an explicit queue (pbrt_hip_traverse_probe).  mode 0: rays_cl, 1: rays_sh, 2: both in one launch.  Returns (hits, occluded)."""
+        """The traversal kernel on an explicit queue (pbrt_hip_traverse_probe).  mode 0: rays_cl, 1: rays_sh, 2: both in one launch.  Returns (hits, occluded).  An entry of
+        `order` with bit 31 set marks that closest-hit ray as an escape query (mode 2, eligible scenes): its record says only whether it hit anything."""
         rays_cl = np.ascontiguousarray(rays_cl if rays_cl is not None else [], dtype=RAY_DTYPE)
         rays_sh = np.ascontiguousarray(rays_sh if rays_sh is not None else [], dtype=RAY_DTYPE)
         hits = np.zeros(len(rays_cl), HIT_DTYPE); occ = np.zeros(len(rays_sh), np.uint8)
@@ -968,6 +970,12 @@ class Scene:
         c = (C.c_uint64 * 8)()
         self._chk(self.b.fn("get_render_footprint")(self.h, c))
         return {"bands": int(c[0]), "band_tiles": int(c[1]), "record_bytes": int(c[2]), "record_budget": int(c[3]), "chunk_paths": int(c[4]), "chunk_bytes": int(c[5])}
+
+    def mis_escape(self):
+        """Did the last render_path trace the BSDF-sampled MIS ray as an escape query (pbrt_hip_get_mis_escape)?"""
+        v = C.c_int(0)
+        self._chk(self.b.fn("get_mis_escape")(self.h, C.byref(v)))
+        return bool(v.value)
 
     def film_to_rgb(self, xyz, weight):
         rgb = np.zeros_like(xyz)
