@@ -197,6 +197,27 @@ int pbrt_hip_add_quadric(PbrtHipScene*, int kind, const float o2w_m[16], const f
 int pbrt_hip_add_curve(PbrtHipScene*, const float o2w_m[16], const float o2w_minv[16], int type, const float cp[12], const float width[2], const float* n /* 6 or NULL */,
                        int split_depth, uint32_t material_id, uint32_t flags);
 
+/* LoopSubDiv::subdivide (shapes/src/loopsubdiv.rs:321-659, with from_props :668-689 and beta, loop_gamma, weight_one_ring, weight_boundary :695-768): the control mesh
+ * (P, n_verts positions in object space; indices, of which those beyond the last multiple of 3 are ignored) refined n_levels times by the Loop rules, every vertex pushed to the
+ * limit surface, a normal s x t per vertex from the ring of limit positions (not normalised), and the move to world space of TriangleMesh::new (shapes/src/triangle.rs:75-113):
+ * P through the matrix, N through the transpose of the inverse.  F control faces give F 4^n_levels triangles; V' = V + E, E' = 2E + 3F, F' = 4F per level.  The control
+ * mesh's pointers and flags are made on the host (csrc/loopsubdiv_host.h), the levels, limit positions, normals and world pass run as kernels on the handle's first device and
+ * stream (csrc/loopsubdiv.hip) in the reference's f32 expression order — the mesh equals the reference's word for word; cos / sin come from a host table (cosf / sinf).
+ *   pbrt_hip_loopsubdiv_mesh  writes the counts, then the mesh: out_P and out_N 3 * *out_n_verts floats, out_indices 3 * *out_n_tris (face.v[0..3] in face order, :636-643).
+ *                             With the three out arrays NULL it only validates and writes the counts — no device work, and the handle may be NULL (what a caller uses to size
+ *                             the arrays and the area lights).  o2w_m NULL: the mesh stays in object space (o2w_minv is not read).
+ *   pbrt_hip_add_loopsubdiv   the call above followed by exactly what pbrt_hip_add_mesh does with that P, N and indices (S and UV absent): area lights (one per output triangle,
+ *                             pbrt_hip_add_light_diffuse_area with n_tris = F 4^n_levels), object definitions, pbrt_hip_set_last_mesh_alpha_textures afterwards, every builder,
+ *                             integrator and driver serve it as they serve a mesh.  flags, first_area_light_id, alpha, shadow_alpha as for pbrt_hip_add_mesh.
+ * PBRT_HIP_ERR_INVALID_ARG, with nothing changed and one sentence in pbrt_hip_last_error — where the reference panics, or its ring walks would not end: no indices, or no P
+ * (:674-679); an index >= n_verts; a face that names a vertex twice; a vertex no face uses (:377-382); an edge in more than two faces; an edge its two faces run through in the
+ * same direction; n_levels < 0; a count of vertices or faces, at any level, above 0x7FFFFFFF / 3 = 715 827 882 (the library forms 3 * index in 32 signed bits); also null count pointers, some but not all of the out arrays, a matrix without its inverse, and whatever
+ * pbrt_hip_add_mesh refuses.  Accepted as the reference accepts it: a vertex whose faces form several fans (its ring is the fan of its start_face, the last face naming it). */
+int pbrt_hip_loopsubdiv_mesh(PbrtHipScene*, const float* o2w_m /* 16 or NULL */, const float* o2w_minv, const float* P, uint32_t n_verts, const uint32_t* indices, uint32_t n_indices,
+                             int n_levels, uint32_t* out_n_verts, uint32_t* out_n_tris, float* out_P, float* out_N, uint32_t* out_indices);
+int pbrt_hip_add_loopsubdiv(PbrtHipScene*, const float* o2w_m /* 16 or NULL */, const float* o2w_minv, const float* P, uint32_t n_verts, const uint32_t* indices, uint32_t n_indices,
+                            int n_levels, uint32_t material_id, int32_t first_area_light_id, uint32_t flags, float alpha, float shadow_alpha);
+
 /* A sphere that is the shape of a DiffuseAreaLight (Shape "sphere" under AreaLightSource "diffuse": api/src/lib.rs:783-812 makes the shape, then the light of lights/src/diffuse.rs:46-82
  * around it): pbrt_hip_add_sphere with the same arguments, plus one light that joins the scene's lights in call order.  The light's area is Sphere::area — phi_max * radius *
  * (z_max - z_min) of the constructor's clamped values — so a partial sphere emits and is sampled as the reference does it: Sphere::sample_solid_angle (shapes/src/sphere.rs:344-410)

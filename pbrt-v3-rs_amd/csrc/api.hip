@@ -4,6 +4,7 @@
 #include "host_math.h"
 #include "scene_host.h"
 #include "curve_host.h"
+#include "loopsubdiv_device.h"
 #include "traverse.h"
 #include "texture.h"
 #include <algorithm>
@@ -792,6 +793,60 @@ int pbrt_hip_add_curve(PbrtHipScene* s, const float o2w_m[16], const float o2w_m
     }
     s->curves.push_back(c);
     return PBRT_HIP_OK;
+    });
+}
+
+// LoopSubDiv::subdivide (shapes/src/loopsubdiv.rs:321-659): the control mesh on the host (loopsubdiv_host.h), the refinement on the device (loopsubdiv.hip).
+// The first half: argument checks and the control mesh, built once per call; needs no device and no handle
+static int loopsubdiv_control(PbrtHipScene* s, const char* what, const float* o2w_m, const float* o2w_minv, const float* P, uint32_t n_verts, const uint32_t* indices,
+                              uint32_t n_indices, int n_levels, ploop::Control& c) {
+    if (o2w_m && !o2w_minv) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": a matrix without its inverse");
+    const std::string bad = ploop::build_control(P, n_verts, indices, n_indices, n_levels, c);
+    if (!bad.empty()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": " + bad);
+    return PBRT_HIP_OK;
+}
+// The second half: the mesh of `c` into arrays of 3 * c.out_verts, 3 * c.out_verts and 3 * c.out_faces, on the handle's first device and its stream
+static int loopsubdiv_refine(PbrtHipScene* s, const char* what, const ploop::Control& c, const float* o2w_m, const float* o2w_minv, const float* P, int n_levels, float* out_P,
+                             float* out_N, uint32_t* out_indices) {
+    PH_CHECK(s, hipSetDevice(s->device));
+    std::string e;
+    if (phost::loopsubdiv_device(c, P, n_levels, o2w_m, o2w_minv, s->stream, out_P, out_N, out_indices, e) != 0) return set_err(s, PBRT_HIP_ERR_DEVICE, std::string(what) + ": " + e);
+    return PBRT_HIP_OK;
+}
+
+int pbrt_hip_loopsubdiv_mesh(PbrtHipScene* s, const float* o2w_m, const float* o2w_minv, const float* P, uint32_t n_verts, const uint32_t* indices, uint32_t n_indices, int n_levels,
+                             uint32_t* out_n_verts, uint32_t* out_n_tris, float* out_P, float* out_N, uint32_t* out_indices) {
+    return ph_guard(s, "pbrt_hip_loopsubdiv_mesh", [&]() -> int {
+    const char* what = "loopsubdiv_mesh";
+    if (!out_n_verts || !out_n_tris) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": null count pointer");
+    const bool counts_only = !out_P && !out_N && !out_indices;
+    if (!counts_only && (!out_P || !out_N || !out_indices)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": out_P, out_N and out_indices go together");
+    if (!counts_only && !s) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, std::string(what) + ": null handle (only the counts need none)");
+    ploop::Control c;
+    const int rc = loopsubdiv_control(s, what, o2w_m, o2w_minv, P, n_verts, indices, n_indices, n_levels, c);
+    if (rc) return rc;
+    *out_n_verts = (uint32_t)c.out_verts; *out_n_tris = (uint32_t)c.out_faces;
+    if (counts_only) return PBRT_HIP_OK;
+    return loopsubdiv_refine(s, what, c, o2w_m, o2w_minv, P, n_levels, out_P, out_N, out_indices);
+    });
+}
+// The mesh of the call above, then pbrt_hip_add_mesh with its P, N and indices: TriangleMesh::create without S, UV or alpha textures (loopsubdiv.rs:645-658)
+int pbrt_hip_add_loopsubdiv(PbrtHipScene* s, const float* o2w_m, const float* o2w_minv, const float* P, uint32_t n_verts, const uint32_t* indices, uint32_t n_indices, int n_levels,
+                            uint32_t material_id, int32_t first_area_light_id, uint32_t flags, float alpha, float shadow_alpha) {
+    return ph_guard(s, "pbrt_hip_add_loopsubdiv", [&]() -> int {
+    const char* what = "add_loopsubdiv";
+    if (!s) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_loopsubdiv: null handle");
+    if (material_id >= s->mats.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_loopsubdiv: unknown material id");   // (before any device work; add_mesh checks the rest)
+    ploop::Control c;
+    int rc = loopsubdiv_control(s, what, o2w_m, o2w_minv, P, n_verts, indices, n_indices, n_levels, c);
+    if (rc) return rc;
+    const uint32_t nv = (uint32_t)c.out_verts, nt = (uint32_t)c.out_faces;
+    if (first_area_light_id >= 0 && (size_t)first_area_light_id + nt > s->lights.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "add_loopsubdiv: area light ids out of range (one light per output triangle)");
+    std::vector<float> mp(3 * (size_t)nv), mn(3 * (size_t)nv);
+    std::vector<uint32_t> mi(3 * (size_t)nt);
+    rc = loopsubdiv_refine(s, what, c, o2w_m, o2w_minv, P, n_levels, mp.data(), mn.data(), mi.data());
+    if (rc) return rc;
+    return pbrt_hip_add_mesh(s, mp.data(), nv, mi.data(), nt, mn.data(), nullptr, nullptr, material_id, first_area_light_id, flags, alpha, shadow_alpha);
     });
 }
 

@@ -19,6 +19,8 @@ static void usage() {
                  "  --quadrics             read Shape \"sphere\", \"cylinder\", \"cone\", \"paraboloid\", \"disk\" and \"hyperboloid\" (without it they are refused as out of scope); a sphere under\n"
                  "                         AreaLightSource \"diffuse\" is an area light, rendered by Integrator \"whitted\" (\"path\" and \"directlighting\" with --path-sphere-lights)\n"
                  "  --curves               read Shape \"curve\" (flat, cylinder and ribbon curves; bezier and bspline bases of degree 2 and 3; without it the directive is refused as out of scope)\n"
+                 "  --loopsubdiv           read Shape \"loopsubdiv\" (Loop subdivision surfaces: \"nlevels\", \"indices\", \"P\"; refined on the device into F * 4^nlevels triangles; without it the\n"
+                 "                         directive is refused as out of scope)\n"
                  "  --path-sphere-lights   render such a sphere light under Integrator \"path\" too (without it the scene is refused there)\n"
                  "  --quadric-lights       with --quadrics: a disk or a cylinder under AreaLightSource \"diffuse\" is an area light too, rendered by either integrator (the reference's\n"
                  "                         cone, paraboloid and hyperboloid have no Shape::sample and stay refused)\n"
@@ -28,7 +30,7 @@ static void usage() {
 }
 
 int main(int argc, char** argv) {
-    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false, quadrics = false, curves = false, quadric_lights = false, path_sphere_lights = false; float crop[4] = {0, 1, 0, 1};
+    std::string outfile, sobol; int device = 0, tile = 16; unsigned long long record_budget = 0; bool quiet = false, has_crop = false, check = false, quadrics = false, curves = false, loopsubdiv = false, quadric_lights = false, path_sphere_lights = false; float crop[4] = {0, 1, 0, 1};
     std::vector<std::string> files;
     std::vector<int> devices; bool multi = false;
     for (int i = 1; i < argc; i++) {
@@ -50,6 +52,7 @@ int main(int argc, char** argv) {
         else if (a == "--check") check = true;
         else if (a == "--quadrics") quadrics = true;
         else if (a == "--curves") curves = true;
+        else if (a == "--loopsubdiv") loopsubdiv = true;
         else if (a == "--path-sphere-lights") path_sphere_lights = true;
         else if (a == "--quadric-lights") quadric_lights = true;
         else if (a == "--convert-image") {
@@ -68,7 +71,7 @@ int main(int argc, char** argv) {
         std::unique_ptr<pbrt_host::Api> api_owner((multi && !check) ? new pbrt_host::Api(devices) : new pbrt_host::Api(check ? -1 : device));
         pbrt_host::Api& api = *api_owner;
         if (!api.error.empty()) { std::fprintf(stderr, "Error: %s\n", api.error.c_str()); return 3; }
-        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet; api.quadrics = quadrics; api.curves = curves; api.quadric_lights = quadric_lights; api.path_sphere_lights = path_sphere_lights;
+        api.override_outfile = outfile; api.sobol_tables_file = sobol; api.tile_size = tile; api.sample_record_budget = record_budget; api.quiet = quiet; api.quadrics = quadrics; api.curves = curves; api.loopsubdiv = loopsubdiv; api.quadric_lights = quadric_lights; api.path_sphere_lights = path_sphere_lights;
         api.has_crop_override = has_crop; std::memcpy(api.crop_override, crop, sizeof crop);
         pbrt_host::RenderReport rep;
         if (!pbrt_host::parse_file(fn, api, &rep)) { std::fprintf(stderr, "Error: %s: %s\n", fn.c_str(), api.error.c_str()); return 1; }

@@ -1,6 +1,7 @@
 // Host-side scene API over the C ABI.  See pbrt_host.hpp for scope; reference: api/src/lib.rs, api/src/graphics_state.rs.
 #include "pbrt_host.hpp"
 #include "../csrc/curve_host.h"
+#include "../csrc/loopsubdiv_host.h"
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -779,10 +780,53 @@ void Api::curve_shape(const ParamSet& p) {
     }
 }
 
+// Shape "loopsubdiv" (Api::loopsubdiv): LoopSubDiv::from_props (shapes/src/loopsubdiv.rs:668-689) — "nlevels" (default 3), "indices", "P".  Its two panics, and every mesh the
+// library refuses (csrc/loopsubdiv_host.h: check mode calls nothing in the library, so the same header runs here), stop the parse with one sentence.  The surface becomes
+// F 4^nlevels triangles through pbrt_hip_add_loopsubdiv: to everything after this function it is a trianglemesh — area lights one per output triangle, object definitions,
+// reverse orientation, material parameters on the shape.  TriangleMesh::create is called without alpha textures (:645-658): "alpha" / "shadowalpha" are not read.
+void Api::loopsubdiv_shape(const ParamSet& p) {
+    const std::string me = "Shape \"loopsubdiv\": ";
+    for (const char* an : {"alpha", "shadowalpha"})
+        if (p.floats.count(an) || p.textures.count(an)) warn(me + "the reference's loopsubdiv reads no '" + an + "'; ignoring it");
+    const int n_levels = p.find_one_int("nlevels", 3);
+    const std::vector<int>* vi = p.find_ints("indices");
+    const std::vector<float>* pp = p.find_floats("P");
+    if (!vi || vi->empty()) { error = me + "Vertex indices 'indices' not provided for LoopSubDiv shape."; return; }
+    if (!pp || pp->size() < 3) { error = me + "Vertex positions 'P' not provided for LoopSubDiv shape."; return; }
+    const size_t nv = pp->size() / 3;
+    for (int v : *vi)
+        if (v < 0) { error = me + "Vertex index " + std::to_string(v) + " is out of bounds (" + std::to_string(nv) + " vertices)."; return; }
+    if (vi->size() % 3) warn(me + std::to_string(vi->size()) + " indices are no multiple of 3; the last " + std::to_string(vi->size() % 3) + " are dropped");
+    const std::vector<uint32_t> idx(vi->begin(), vi->end());
+    ploop::Control c;
+    const std::string bad = ploop::build_control(pp->data(), nv, idx.data(), idx.size(), n_levels, c);
+    if (!bad.empty()) { error = me + bad; return; }
+    const uint32_t mat = material_id_for(material_for_shape(p));
+    if (!error.empty()) return;
+    const uint32_t n_tris = (uint32_t)c.out_faces;
+    const uint32_t flags = (gs_.reverse_orientation ? 1u : 0u) | (pbrt_hip_host_swaps_handedness(ctm_.m) ? 2u : 0u);
+    int32_t first_light = -1;
+    const bool in_object = !current_object_.empty();
+    if (!gs_.area_light.empty()) {  // one DiffuseAreaLight per OUTPUT triangle, numbered where the Shape directive stands (lib.rs:783-812)
+        if (gs_.area_light != "diffuse" && gs_.area_light != "area") { error = "AreaLightSource \"" + gs_.area_light + "\" unknown"; return; }
+        const ParamSet& ap = gs_.area_light_params;
+        for (auto& u : ap.unsupported) { error = "AreaLightSource: parameter '" + u + "' has a spectral type this host cannot evaluate"; return; }
+        auto L = mul3(ap.find_one_rgb("L", {1.0f, 1.0f, 1.0f}), ap.find_one_rgb("scale", {1.0f, 1.0f, 1.0f}));
+        uint32_t id = 0;
+        if (!check(ABI(pbrt_hip_add_light_diffuse_area(scene_, L.data(), ap.find_one_bool("twosided", false) ? 1 : 0, n_tris, &id)), "add_light_diffuse_area")) return;
+        first_light = (int32_t)id;
+        if (in_object) warn("Area lights not supported with object instancing.");
+        else n_lights_ += n_tris;
+    }
+    if (!check(ABI(pbrt_hip_add_loopsubdiv(scene_, ctm_.m, ctm_.mi, pp->data(), (uint32_t)nv, idx.data(), (uint32_t)idx.size(), n_levels, mat, first_light, flags, 1.0f, 1.0f)), "add_loopsubdiv")) return;
+    if (!in_object) n_tris_ += n_tris; else object_tris_[current_object_] += n_tris;
+}
+
 void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::string& scene_dir) {
     if (!verify_world("Shape") || !error.empty() || (!scene_ && !check_only_)) return;
     if (quadrics && is_quadric_shape(name)) { quadric_shape(name, p); return; }
     if (curves && name == "curve") { curve_shape(p); return; }
+    if (loopsubdiv && name == "loopsubdiv") { loopsubdiv_shape(p); return; }
     std::vector<float> P, N, S, UV;
     std::vector<uint32_t> idx;
     if (name == "trianglemesh") {  // shapes/src/triangle.rs:184-330
@@ -818,7 +862,7 @@ void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::stri
         if (mesh.P.empty() || mesh.indices.empty()) { warn("PLY file '" + fn + "' is invalid! No face/vertex elements found!"); return; }
         P.swap(mesh.P); N.swap(mesh.N); UV.swap(mesh.UV); idx.swap(mesh.indices);
     } else {
-        error = "Shape \"" + name + "\" is outside the hot-path scope (supported: trianglemesh, plymesh" + (is_quadric_shape(name) ? "; the six quadric shapes are read with --quadrics)" : name == "curve" ? "; curves are read with --curves)" : ")");
+        error = "Shape \"" + name + "\" is outside the hot-path scope (supported: trianglemesh, plymesh" + (is_quadric_shape(name) ? "; the six quadric shapes are read with --quadrics)" : name == "curve" ? "; curves are read with --curves)" : name == "loopsubdiv" ? "; subdivision surfaces are read with --loopsubdiv)" : ")");
         return;
     }
     // alpha / shadowalpha (triangle.rs:278-312): a float texture by name (constant ones fold to the constant, the others are evaluated per candidate hit) or a float

@@ -115,6 +115,7 @@ class Api {
     bool path_sphere_lights = false;   // --path-sphere-lights: a sphere light (Shape "sphere" under AreaLightSource "diffuse", read with `quadrics`) is rendered by Integrator "path" too
     bool quadric_lights = false;   // --quadric-lights (with `quadrics`): Shape "disk" / "cylinder" under AreaLightSource "diffuse" is an area light (pbrt_hip_add_quadric_light), under either integrator
     bool curves = false;     // --curves: Shape "curve" is read (Curve::from_props, shapes/src/curve.rs:149-316); without it the directive is refused as out of scope
+    bool loopsubdiv = false; // --loopsubdiv: Shape "loopsubdiv" is read (LoopSubDiv::from_props, shapes/src/loopsubdiv.rs:668-689) and refined on the device; without it the directive is refused as out of scope
     bool quadrics = false;   // --quadrics: Shape "sphere" / "cylinder" / "cone" / "paraboloid" / "disk" / "hyperboloid" are read; without it they are refused as out of scope
     bool quiet = false;
     std::vector<std::string> warnings;
@@ -152,6 +153,7 @@ class Api {
     MaterialDesc material_for_shape(const ParamSet& shape_params) const;
     void quadric_shape(const std::string& name, const ParamSet& p);
     void curve_shape(const ParamSet& p);
+    void loopsubdiv_shape(const ParamSet& p);
     bool check(int rc, const char* what);
 };
 

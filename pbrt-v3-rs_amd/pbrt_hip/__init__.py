@@ -175,6 +175,8 @@ class Binding:
             "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
             "add_curve": (C.c_int, [vp, fp, fp, C.c_int, fp, fp, fp, C.c_int, C.c_uint32, C.c_uint32]),
             "curve_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, vp, fp]),
+            "loopsubdiv_mesh": (C.c_int, [vp, fp, fp, fp, C.c_uint32, u32p, C.c_uint32, C.c_int, u32p, u32p, fp, fp, u32p]),
+            "add_loopsubdiv": (C.c_int, [vp, fp, fp, fp, C.c_uint32, u32p, C.c_uint32, C.c_int, C.c_uint32, C.c_int32, C.c_uint32, C.c_float, C.c_float]),
             "traverse_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
             "film_probe_layout": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), ip, ip]),
             "film_probe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, fp, fp, vp, fp, fp, fp]),
@@ -494,6 +496,35 @@ class Scene:
         out = np.zeros((len(rays), self.CURVE_PROBE_STRIDE), np.float32)
         self._chk(self.b.fn("curve_probe_batch")(self.h, prim, 1 if shadow else 0, len(rays), rays.ctypes.data, _ptr(out, C.c_float)))
         return out
+
+    def loopsubdiv_mesh(self, P, indices, n_levels=3, object_to_world=None, world_to_object=None, counts_only=False):
+        """LoopSubDiv::subdivide (shapes/src/loopsubdiv.rs:321-659, pbrt_hip_loopsubdiv_mesh): the control mesh P (n,3), indices refined n_levels times on the device, pushed to
+        the limit surface, with the normals s x t, moved to world space by object_to_world and its inverse (None: object space).  Returns (P (V,3), N (V,3), indices (3 F 4^L,));
+        counts_only=True validates only and returns (V, F 4^L), no device work."""
+        P = _f32(P, (-1, 3)); idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        m = None if object_to_world is None else _f32(object_to_world, (16,))
+        mi = None if world_to_object is None else _f32(world_to_object, (16,))
+        nv, nt = C.c_uint32(0), C.c_uint32(0)
+        call = self.b.fn("loopsubdiv_mesh")
+        head = (self.h, _ptr(m, C.c_float), _ptr(mi, C.c_float), _ptr(P, C.c_float) if len(P) else None, len(P), _ptr(idx, C.c_uint32) if len(idx) else None, len(idx), int(n_levels),
+                C.byref(nv), C.byref(nt))
+        self._chk(call(*head, None, None, None))
+        if counts_only:
+            return nv.value, nt.value
+        oP, oN, oI = np.empty((nv.value, 3), np.float32), np.empty((nv.value, 3), np.float32), np.empty(3 * nt.value, np.uint32)
+        self._chk(call(*head, _ptr(oP, C.c_float), _ptr(oN, C.c_float), _ptr(oI, C.c_uint32)))
+        return oP, oN, oI
+
+    def add_loopsubdiv(self, P, indices, n_levels=3, material=0, object_to_world=None, world_to_object=None, first_area_light=-1, reverse_orientation=False,
+                       swaps_handedness=False, alpha=1.0, shadow_alpha=1.0):
+        """pbrt_hip_add_loopsubdiv: loopsubdiv_mesh followed by exactly what add_mesh does with its P, N and indices; an area light needs one light per OUTPUT triangle
+        (add_light_diffuse_area(L, n_tris=F 4^L), the count loopsubdiv_mesh(.., counts_only=True) gives)."""
+        P = _f32(P, (-1, 3)); idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        m = None if object_to_world is None else _f32(object_to_world, (16,))
+        mi = None if world_to_object is None else _f32(world_to_object, (16,))
+        flags = (1 if reverse_orientation else 0) | (2 if swaps_handedness else 0)
+        self._chk(self.b.fn("add_loopsubdiv")(self.h, _ptr(m, C.c_float), _ptr(mi, C.c_float), _ptr(P, C.c_float) if len(P) else None, len(P), _ptr(idx, C.c_uint32) if len(idx) else None,
+                                              len(idx), int(n_levels), material, first_area_light, flags, C.c_float(alpha), C.c_float(shadow_alpha)))
 
     def object_begin(self) -> int:
         """ObjectBegin (api/src/lib.rs:911-925): meshes added until object_end() belong to the returned object."""
