@@ -595,6 +595,35 @@ int pbrt_hip_sphere_light_probe_batch(PbrtHipScene*, uint32_t light, int op, uin
  * PBRT_HIP_ERR_INVALID_ARG: a null handle; a null array with n > 0; n > 2^32 - 1; prim is not a curve segment.  PBRT_HIP_ERR_STATE: no accelerator built. */
 #define PBRT_HIP_CURVE_PROBE_STRIDE 20
 int pbrt_hip_curve_probe_batch(PbrtHipScene*, uint32_t prim, int shadow, uint64_t n, const PbrtHipRay* rays, float* out /*20n*/);
+/* pbrt_hip_surface_probe_batch: the code between "the traversal reported (prim, b0, b1, b2, instance)" and "BSDF, textures, lights and the next ray read a surface interaction", on
+ * explicit hits (a test aid like the probes above).  Needs a built accelerator — the leaf records and a hit's pad[0] exist only then.  Per probe: the world-space ray; a PbrtHipHit as
+ * pbrt_hip_intersect_batch writes it, whose t, b0, b1, b2 the caller may then set freely (a quadric's interaction is rebuilt from the ray, a curve segment's from the ray and t, b0, b1);
+ * and PBRT_HIP_SURFACE_PROBE_AUX = 48 floats:
+ *   [0..1] p_film  [2..3] lens sample  [4..6] wi  [7..9] hp  [10..12] hp_error  [13..15] hn (the target of spawn_ray_to_hit)
+ *   op 4 only: [16..18] / [19..21] the parent ray's rx_direction / ry_direction (its offset origins are not read by the reference's formulas), [22..25] du/dx dv/dx du/dy dv/dy,
+ *   [26..28] dp/dx, [29..31] dp/dy, [32..34] dn/du, [35..37] dn/dv, [38] the BSDF's eta, [39] != 0: the refracted ray, else the reflected one.  [40..47] spare.
+ * variant = how the interaction is made: 0 make_surface_hit, indexed by prim (what Light::pdf_li's Triangle::intersect uses; PBRT_HIP_ERR_UNSUPPORTED for a hit with pad[1] != 0 — there
+ * is no such path for instances — and for a quadric's or curve segment's slot); 1 make_surface_hit_any, from the leaf record, through an instance if pad[1] != 0 (UNSUPPORTED for a
+ * quadric's or curve segment's slot); 2 make_surface_hit_q<true>, the form of scenes that hold quadric shapes (UNSUPPORTED for a scene without one: its kernels have no such instantiation).
+ * op = what is computed from that interaction, by the functions the render kernels call.  Output: PBRT_HIP_SURFACE_PROBE_STRIDE = 40 words per probe, zeroed first, then
+ *   op 0  the interaction: [0..2] p, [3..5] p_error, [6..8] wo, [9..11] n, [12..14] shading n, [15..17] shading dp/du, [18] time, [19] prim (as an integer's bits)
+ *   op 1  the texture side without displacement: [0..1] uv, [2..4] / [5..7] the geometric dp/du, dp/dv in world space, [8..11] du/dx dv/dx du/dy dv/dy and [12..14] / [15..17]
+ *         dp/dx, dp/dy of the context the texture pass evaluates (hit_tex_ctx; for a quadric or curve hit tex_ctx_from on the shape's own u, v, dp/du, dp/dv) — zero unless camera_ray —,
+ *         [18..29] rx_origin, ry_origin, rx_direction, ry_direction of the camera ray's scaled differentials (camera_ray_differentials on p_film, lens and the ray; zero unless camera_ray),
+ *         [30..32] / [33..35] the shading dn/du, dn/dv (tri_shading_dn; the shape's own for a quadric)
+ *   op 2  Material::bump with `texture` as the displacement on op 1's context (hit_bump; bump_shading on the shape's frame for a quadric): [0..2] the new shading n, [3..5] shading dp/du
+ *   op 3  [0..7] Interaction::spawn_ray(wi) and [8..15] spawn_ray_to_hit(hp, hp_error, hn), each as a PbrtHipRay: origin, t_max, direction, time
+ *   op 4  the differentials of the specularly reflected / refracted ray (sampler_integrator.rs:96-119, :171-230) with the interaction's p, wo and shading n, the direction wi and
+ *         aux[16..39]: [0..2] rx_origin, [3..5] ry_origin, [6..8] rx_direction, [9..11] ry_direction
+ *   [39] is left zero (the test oracle's counterpart reports the branches a probe took there).
+ * camera_ray != 0 (ops 1 and 2): the ray is a camera ray of the handle's camera, made at p_film with the lens sample `lens`; the sampler supplies its samples per pixel.
+ * Refusals, before anything is launched; the handle stays usable.  PBRT_HIP_ERR_INVALID_ARG: a null handle; a null array with n > 0; n > 2^32 - 1; an unknown op or variant; a hit
+ * whose prim is 0xFFFFFFFF or no primitive, whose pad[0] is no leaf record of that primitive or whose pad[1] names no instance that holds it; an unknown texture under op 2.
+ * PBRT_HIP_ERR_STATE: no accelerator; camera_ray under op 1 or 2 without a camera, a film and a sampler.  PBRT_HIP_ERR_UNSUPPORTED: as listed with the variants; op 2 on a curve segment. */
+#define PBRT_HIP_SURFACE_PROBE_AUX 48
+#define PBRT_HIP_SURFACE_PROBE_STRIDE 40
+int pbrt_hip_surface_probe_batch(PbrtHipScene*, int op, int variant, uint32_t texture, int camera_ray, uint64_t n, const PbrtHipRay* rays, const PbrtHipHit* hits,
+                                 const float* aux /*48n*/, float* out /*40n*/);
 /* pbrt_hip_raysort_probe: the ray binning between wavefront rounds (csrc/raysort.h) on explicit keys, through the launch the path integrator's rounds use.  keys_cl / keys_sh = the
  * bin keys (< 4096) of n_cl closest-hit and n_sh any-hit rays; the keys and the two counts are uploaded and read from device memory, as in a render.  order_out[0 .. n_cl + n_sh) =
  * the queue positions (closest-hit rays 0 .. n_cl, any-hit rays behind them) grouped by bin, closest-hit rays first; the order inside a bin is unspecified.  sort_blocks = the grid

@@ -1292,6 +1292,228 @@ int oracle_light_probe_batch(OracleScene* s, uint32_t light, int op, int variant
     return 0;
 }
 
+// Surface probe, with the contract and the layouts of pbrt_hip_surface_probe_batch (include/pbrt_hip.h): Renderer::make_surface_hit on an explicit hit, then per op what the
+// integrators do with the interaction — compute_differentials with the camera's scaled ray differentials, bump with a named texture, spawn_ray / spawn_ray_to_hit, the
+// differential block of specular_reflect / specular_transmit.  `variant` names the product's code paths and is ignored here; pad[0] of a hit is the product's and is not read.
+// Word 39 of a record, which the product leaves zero, is the probe's BRANCH MASK: one ORC_SB_* bit per branch of the reference's code the probe took (tests/surface_probe_cases.py
+// lists them).  The mask is worked out beside the calls, from the same quantities, so that the functions under test stay as the renders use them.
+enum : uint32_t {
+    ORC_SB_UV_DEGENERATE = 1u << 0,    // |uv determinant| < 1e-8 (triangle.rs:558)
+    ORC_SB_DPDU_CROSS_ZERO = 1u << 1,  // determinant fine, dpdu x dpdv == 0 (:565)
+    ORC_SB_N_ZERO = 1u << 2,           // interpolated N of zero length: ns = n (:640)
+    ORC_SB_S_ZERO = 1u << 3,           // interpolated S of zero length: ss = normalize(dpdu) (:656)
+    ORC_SB_TS_ZERO = 1u << 4,          // S parallel to N: coordinate_system(ns) (:668)
+    ORC_SB_FLIP_N = 1u << 5,           // reverse_orientation != swaps_handedness: n negated (:627)
+    ORC_SB_REV_TS = 1u << 6,           // reverse_orientation: ts negated (:716)
+    ORC_SB_FACE_FORWARD = 1u << 7,     // set_shading_geometry's face_forward turned n (surface_interaction.rs:164)
+    ORC_SB_INST_IDENTITY = 1u << 8,    // an instance whose transform is the identity: no transform_surface_interaction (transformed_primitive.rs:58)
+    ORC_SB_INST_TRANSFORM = 1u << 9,   // ... any other instance
+    ORC_SB_INST_NS_FLIP = 1u << 10,    // face_forward(ns, n) after the instance transform turned ns (transform.rs:583)
+    ORC_SB_WO_ZERO = 1u << 11,         // length_squared(wo) == 0: wo stays as given (interaction/mod.rs:146)
+    ORC_SB_TX_EARLY_OUT = 1u << 12,    // tx or ty infinite or NaN: all differentials zero (surface_interaction.rs:222 / :232)
+    ORC_SB_DIFF_DET_SMALL = 1u << 13,  // |det| < 1e-10 in solve_linear_system_2x2 (matrix4x4.rs:308)
+    ORC_SB_AXIS_X = 1u << 14, ORC_SB_AXIS_Y = 1u << 15, ORC_SB_AXIS_Z = 1u << 16,   // the dominant axis of n that compute_differentials drops
+    ORC_SB_OFFSET_ZERO = 1u << 17,     // a zero component of offset_origin's offset: that coordinate stays (ray.rs:118-126)
+    ORC_SB_OFFSET_NEG = 1u << 18,      // dot(w, n) < 0: the offset is negated (ray.rs:113)
+    ORC_SB_DN_UV_DEGENERATE = 1u << 19,  // dn/du, dn/dv from coordinate_system(dn) (triangle.rs:692-706)
+    ORC_SB_DN_ZERO = 1u << 20,         // ... with dn == 0: both stay zero
+    ORC_SB_BUMP_DU_DEFAULT = 1u << 21, // Material::bump's du or dv == 0 -> 0.0005 (material.rs:72 / :86)
+    ORC_SB_SPEC_FLIP = 1u << 22,       // specular_transmit with dot(wo, ns) < 0: eta inverted, the normal and its derivatives negated (sampler_integrator.rs:203)
+    ORC_SB_SPEC_TRANSMIT = 1u << 23, ORC_SB_SPEC_REFLECT = 1u << 24,
+    ORC_SB_QUADRIC = 1u << 25,         // the hit lies on a quadric shape: the interaction is rebuilt from the ray
+    ORC_SB_CAMERA_LENS = 1u << 26,     // the camera's differentials come through a lens sample (lens_radius > 0)
+    ORC_SB_DIFF_SOLVED = 1u << 27,     // compute_differentials ran to its end and both 2x2 systems were solved
+};
+static uint32_t offset_origin_bits(V3 p_error, V3 n, V3 w) {
+    const Float d = dot(vabs(n), p_error);
+    V3 offset = d * n;
+    uint32_t b = 0;
+    if (dot(w, n) < 0.0f) { offset = -offset; b |= ORC_SB_OFFSET_NEG; }
+    for (int a = 0; a < 3; a++) if (offset[a] == 0.0f) b |= ORC_SB_OFFSET_ZERO;
+    return b;
+}
+// the branches of Triangle::intersect's tail for primitive `prim` at (b0, b1, b2), read off the mesh the way make_surface_hit_local reads it
+static uint32_t triangle_tail_bits(const Scene& s, uint32_t prim, Float b0, Float b1, Float b2) {
+    const Mesh& m = s.mesh_of(prim);
+    uint32_t bits = 0;
+    const uint32_t i0 = s.idx[3 * prim], i1 = s.idx[3 * prim + 1], i2 = s.idx[3 * prim + 2];
+    const V3 p0 = s.P[i0], p1 = s.P[i1], p2 = s.P[i2];
+    V2 uv[3]; s.tri_uvs(prim, uv);
+    const V2 duv02(uv[0].x - uv[2].x, uv[0].y - uv[2].y), duv12(uv[1].x - uv[2].x, uv[1].y - uv[2].y);
+    const Float determinant = duv02.x * duv12.y - duv02.y * duv12.x;
+    const bool degenerate_uv = std::fabs(determinant) < 1e-8f;
+    if (degenerate_uv) bits |= ORC_SB_UV_DEGENERATE;
+    else {
+        const Float invdet = 1.0f / determinant;
+        const V3 dp02 = p0 - p2, dp12 = p1 - p2;
+        const V3 du = (duv12.y * dp02 - duv02.y * dp12) * invdet, dv = (-duv12.x * dp02 + duv02.x * dp12) * invdet;
+        if (length_squared(cross(du, dv)) == 0.0f) bits |= ORC_SB_DPDU_CROSS_ZERO;
+    }
+    V3 dpdu, dpdv; s.tri_dpdu_dpdv(prim, dpdu, dpdv);
+    V3 n = normalize(cross(p0 - p2, p1 - p2));
+    if (m.reverse_orientation ^ m.swaps_handedness) { n = -n; bits |= ORC_SB_FLIP_N; }
+    if (m.has_n || m.has_s) {
+        V3 ns = n;
+        if (m.has_n) {
+            const V3 ns2 = b0 * s.N[i0] + b1 * s.N[i1] + b2 * s.N[i2];
+            if (length_squared(ns2) > 0.0f) ns = normalize(ns2); else bits |= ORC_SB_N_ZERO;
+        }
+        V3 ss = normalize(dpdu);
+        if (m.has_s) {
+            const V3 ss2 = b0 * s.S[i0] + b1 * s.S[i1] + b2 * s.S[i2];
+            if (length_squared(ss2) > 0.0f) ss = normalize(ss2); else bits |= ORC_SB_S_ZERO;
+        }
+        V3 ts = cross(ss, ns);
+        if (length_squared(ts) > 0.0f) { ts = normalize(ts); ss = cross(ts, ns); }
+        else { coordinate_system(ns, ss, ts); bits |= ORC_SB_TS_ZERO; }
+        if (m.has_n) {
+            if (degenerate_uv) {
+                bits |= ORC_SB_DN_UV_DEGENERATE;
+                if (length_squared(cross(s.N[i2] - s.N[i0], s.N[i1] - s.N[i0])) == 0.0f) bits |= ORC_SB_DN_ZERO;
+            }
+        }
+        if (m.reverse_orientation) { ts = -ts; bits |= ORC_SB_REV_TS; }
+        const V3 nsh = normalize(cross(ss, ts));
+        if (dot(n, nsh) < 0.0f) bits |= ORC_SB_FACE_FORWARD;
+    }
+    return bits;
+}
+int oracle_surface_probe_batch(OracleScene* s, int op, int /*variant*/, uint32_t texture, int camera_ray, uint64_t n, const OracleRay* rays, const OracleHit* hits, const float* aux,
+                               float* out) {
+    if (!s) return -1;
+    if (n && (!rays || !hits || !aux || !out)) { s->err = "surface_probe_batch: null argument"; return -1; }
+    if (n > 0xFFFFFFFFull) { s->err = "surface_probe_batch: too many probes"; return -1; }
+    if (op < 0 || op > 4) { s->err = "surface_probe_batch: unknown op"; return -1; }
+    if (op == 2 && texture >= s->sc.textures.size()) { s->err = "surface_probe_batch: unknown texture"; return -1; }
+    if (!s->built) { s->err = "surface_probe_batch: build_accel first"; return -2; }
+    const bool cam_ray = camera_ray != 0 && (op == 1 || op == 2);
+    if (cam_ray && !(s->have_camera && s->have_film && s->have_sampler && s->r.scfg.spp > 0)) { s->err = "surface_probe_batch: a camera ray needs a camera, a film and a sampler"; return -2; }
+    const Scene& sc = s->sc;
+    for (uint64_t i = 0; i < n; i++) {
+        if (hits[i].prim == 0xffffffffu || hits[i].prim >= sc.n_tris()) { s->err = "surface_probe_batch: a hit names no primitive"; return -1; }
+        if (hits[i].pad[1] > sc.instances.size()) { s->err = "surface_probe_batch: a hit's pad[1] names no instance"; return -1; }
+        if (hits[i].pad[1]) { const Object& ob = sc.objects[sc.instances[hits[i].pad[1] - 1].object]; if (hits[i].prim < ob.tri0 || hits[i].prim >= ob.tri1) { s->err = "surface_probe_batch: a hit's pad[1] names an instance of another object"; return -1; } }
+    }
+    const int stride = 40, n_aux = 48;
+    auto put3 = [](float* o, V3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+    auto put_ray = [](float* o, const Ray& r) { o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.t_max; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.time; };
+    for (uint64_t i = 0; i < n; i++) {
+        const float* a = aux + (size_t)n_aux * i;
+        float* o = out + (size_t)stride * i;
+        for (int k = 0; k < stride; k++) o[k] = 0.0f;
+        uint32_t bits = 0;
+        Ray ray(V3(rays[i].o[0], rays[i].o[1], rays[i].o[2]), V3(rays[i].d[0], rays[i].d[1], rays[i].d[2]), rays[i].t_max, rays[i].time);
+        const uint32_t prim = hits[i].prim;
+        TriHit h; h.t = hits[i].t; h.b0 = hits[i].b0; h.b1 = hits[i].b1; h.b2 = hits[i].b2; h.inst = hits[i].pad[1];
+        const Mesh& m = sc.mesh_of(prim);
+        const bool on_quadric = m.sphere >= 0 || m.hyper >= 0 || m.quadric >= 0;
+        if (on_quadric) {   // the interaction of a quadric is rebuilt from the ray: the shape's own test on it, with the ray's whole extent
+            bits |= ORC_SB_QUADRIC;
+            const Ray whole(ray.o, ray.d, INF, ray.time);
+            if (m.sphere >= 0) (void)sc.sphere_intersect(whole, sc.spheres[(size_t)m.sphere], h);
+            else if (m.hyper >= 0) (void)sc.hyperboloid_intersect(whole, sc.hyperboloids[(size_t)m.hyper], h);
+            else (void)sc.quadric_intersect(whole, sc.quadrics[(size_t)m.quadric], h);
+            h.inst = 0;
+        } else {
+            bits |= triangle_tail_bits(sc, prim, h.b0, h.b1, h.b2);
+            Ray local = ray;
+            if (h.inst) {
+                const Transform& t = sc.instances[h.inst - 1].i2w;
+                bits |= t.is_identity() ? ORC_SB_INST_IDENTITY : ORC_SB_INST_TRANSFORM;
+                local = transform_ray(t.inv(), ray);
+            }
+            if (length_squared(local.d) == 0.0f) bits |= ORC_SB_WO_ZERO;
+        }
+        SurfaceHit si = s->r.make_surface_hit(ray, prim, h);
+        if (!on_quadric && h.inst && !sc.instances[h.inst - 1].i2w.is_identity()) {
+            const Transform& t = sc.instances[h.inst - 1].i2w;
+            SurfaceHit li = s->r.make_surface_hit_local(transform_ray(t.inv(), ray), prim, h);
+            if (dot(normalize(t.normal(li.ns)), si.n) < 0.0f) bits |= ORC_SB_INST_NS_FLIP;
+        }
+        const V3 wi(a[4], a[5], a[6]);
+        if (op == 0) {
+            put3(o, si.p); put3(o + 3, si.p_error); put3(o + 6, si.wo); put3(o + 9, si.n); put3(o + 12, si.ns); put3(o + 15, si.dpdu_s);
+            o[18] = si.time; std::memcpy(o + 19, &si.prim, 4);
+        } else if (op == 1 || op == 2) {
+            if (cam_ray) {   // the camera's differentials at (p_film, lens), about the probe's own ray, scaled by 1 / sqrt(spp) (sampler_integrator.rs:352-358)
+                const V2 p_film(a[0], a[1]), lens(a[2], a[3]);
+                Ray cr;
+                if (s->r.cam.kind == 2) {   // Camera::generate_ray_differential's default (camera.rs:29-78) with the probe's ray as the main ray
+                    const Float eps = 0.05f;
+                    const Ray rx = s->r.generate_ray_environment_main(V2(p_film.x + eps, p_film.y), 0.0f), ry = s->r.generate_ray_environment_main(V2(p_film.x, p_film.y + eps), 0.0f);
+                    cr.rx_o = ray.o + (rx.o - ray.o) / eps; cr.rx_d = ray.d + (rx.d - ray.d) / eps;
+                    cr.ry_o = ray.o + (ry.o - ray.o) / eps; cr.ry_d = ray.d + (ry.d - ray.d) / eps;
+                } else cr = s->r.generate_ray(p_film, 0.0f, lens);
+                if (s->r.cam.kind != 2 && s->r.cam.lens_radius > 0.0f) bits |= ORC_SB_CAMERA_LENS;
+                ray.has_diff = true; ray.rx_o = cr.rx_o; ray.ry_o = cr.ry_o; ray.rx_d = cr.rx_d; ray.ry_d = cr.ry_d;
+                Renderer::scale_differentials(ray, 1.0f / std::sqrt((Float)s->r.scfg.spp));
+                put3(o + 18, ray.rx_o); put3(o + 21, ray.ry_o); put3(o + 24, ray.rx_d); put3(o + 27, ray.ry_d);
+                // which way compute_differentials goes
+                const Float d = dot(si.n, si.p);
+                const Float tx = -(dot(si.n, ray.rx_o) - d) / dot(si.n, ray.rx_d), ty = -(dot(si.n, ray.ry_o) - d) / dot(si.n, ray.ry_d);
+                if (std::isinf(tx) || tx != tx || std::isinf(ty) || ty != ty) bits |= ORC_SB_TX_EARLY_OUT;
+                else {
+                    const V3 an = vabs(si.n);
+                    int d0, d1;
+                    if (an.x > an.y && an.x > an.z) { bits |= ORC_SB_AXIS_X; d0 = 1; d1 = 2; } else if (an.y > an.z) { bits |= ORC_SB_AXIS_Y; d0 = 0; d1 = 2; } else { bits |= ORC_SB_AXIS_Z; d0 = 0; d1 = 1; }
+                    const Float det = si.dpdu[d0] * si.dpdv[d1] - si.dpdv[d0] * si.dpdu[d1];
+                    if (std::fabs(det) < 1e-10f) bits |= ORC_SB_DIFF_DET_SMALL;
+                }
+            }
+            Renderer::compute_differentials(si, ray);
+            if (cam_ray && !(bits & (ORC_SB_TX_EARLY_OUT | ORC_SB_DIFF_DET_SMALL)) && (si.dudx != 0.0f || si.dvdx != 0.0f) && (si.dudy != 0.0f || si.dvdy != 0.0f)) bits |= ORC_SB_DIFF_SOLVED;
+            if (op == 1) {
+                o[0] = si.uv.x; o[1] = si.uv.y; put3(o + 2, si.dpdu); put3(o + 5, si.dpdv);
+                o[8] = si.dudx; o[9] = si.dvdx; o[10] = si.dudy; o[11] = si.dvdy; put3(o + 12, si.dpdx); put3(o + 15, si.dpdy);
+                put3(o + 30, si.dndu_s); put3(o + 33, si.dndv_s);
+            } else {
+                for (int k = 18; k < 30; k++) o[k] = 0.0f;
+                if (0.5f * (std::fabs(si.dudx) + std::fabs(si.dudy)) == 0.0f || 0.5f * (std::fabs(si.dvdx) + std::fabs(si.dvdy)) == 0.0f) bits |= ORC_SB_BUMP_DU_DEFAULT;
+                TexCtx c; c.uv = si.uv; c.dudx = si.dudx; c.dvdx = si.dvdx; c.dudy = si.dudy; c.dvdy = si.dvdy; c.p = si.p; c.dpdx = si.dpdx; c.dpdy = si.dpdy;
+                Renderer::BumpFrame f{si.n, si.ns, si.dpdu_s, si.dpdv_s, si.dndu_s, si.dndv_s};
+                Renderer::bump_frame(sc.textures, sc.mipmaps, (int)texture, c, f);
+                put3(o, f.ns); put3(o + 3, f.dpdu_s);
+            }
+        } else if (op == 3) {
+            const V3 hp(a[7], a[8], a[9]), hperr(a[10], a[11], a[12]), hn(a[13], a[14], a[15]);
+            put_ray(o, spawn_ray(si.p, si.p_error, si.n, si.time, wi));
+            put_ray(o + 8, spawn_ray_to_hit(si.p, si.p_error, si.n, si.time, hp, hperr, hn));
+            bits |= offset_origin_bits(si.p_error, si.n, wi) | offset_origin_bits(si.p_error, si.n, hp - si.p);
+        } else {   // the differential block of specular_reflect / specular_transmit (sampler_integrator.rs:96-119, :171-230) on explicit values: Renderer::whitted_specular's lines
+            const V3 prx_d(a[16], a[17], a[18]), pry_d(a[19], a[20], a[21]), dpdx(a[26], a[27], a[28]), dpdy(a[29], a[30], a[31]), dndu(a[32], a[33], a[34]), dndv(a[35], a[36], a[37]);
+            const Float dudx = a[22], dvdx = a[23], dudy = a[24], dvdy = a[25], bsdf_eta = a[38];
+            const bool transmit = a[39] != 0.0f;
+            const V3 wo = si.wo;
+            V3 ns = si.ns;
+            Ray rd;
+            rd.rx_o = si.p + dpdx; rd.ry_o = si.p + dpdy;
+            V3 dndx = dndu * dudx + dndv * dvdx;
+            V3 dndy = dndu * dudy + dndv * dvdy;
+            if (!transmit) {
+                bits |= ORC_SB_SPEC_REFLECT;
+                const V3 dwodx = -prx_d - wo, dwody = -pry_d - wo;
+                const Float ddndx = dot(dwodx, ns) + dot(wo, dndx), ddndy = dot(dwody, ns) + dot(wo, dndy);
+                rd.rx_d = wi - dwodx + 2.0f * (dot(wo, ns) * dndx + ddndx * ns);
+                rd.ry_d = wi - dwody + 2.0f * (dot(wo, ns) * dndy + ddndy * ns);
+            } else {
+                bits |= ORC_SB_SPEC_TRANSMIT;
+                Float eta = 1.0f / bsdf_eta;
+                if (dot(wo, ns) < 0.0f) { eta = 1.0f / eta; ns = -ns; dndx = -dndx; dndy = -dndy; bits |= ORC_SB_SPEC_FLIP; }
+                const V3 dwodx = -prx_d - wo, dwody = -pry_d - wo;
+                const Float ddndx = dot(dwodx, ns) + dot(wo, dndx), ddndy = dot(dwody, ns) + dot(wo, dndy);
+                const Float mu = eta * dot(wo, ns) - abs_dot(wi, ns);
+                const Float dmudx = (eta - (eta * eta * dot(wo, ns)) / abs_dot(wi, ns)) * ddndx;
+                const Float dmudy = (eta - (eta * eta * dot(wo, ns)) / abs_dot(wi, ns)) * ddndy;
+                rd.rx_d = wi - eta * dwodx + (mu * dndx + dmudx * ns);
+                rd.ry_d = wi - eta * dwody + (mu * dndy + dmudy * ns);
+            }
+            put3(o, rd.rx_o); put3(o + 3, rd.ry_o); put3(o + 6, rd.rx_d); put3(o + 9, rd.ry_d);
+        }
+        std::memcpy(o + 39, &bits, 4);
+    }
+    return 0;
+}
+
 // geometry probes that replay the reference's proptests (core/src/geometry/*.rs #[cfg(test)])
 // op: 0 dot 1 cross 2 normalize 3 length 4 abs 5 min/max component 6 max_dimension 7 permute(xyz->a[3..6]) 8 ray.at
 //     9 coordinate_system 10 matrix inverse (16 in, 16 out) 11 face_forward 12 distance_squared 13 box test

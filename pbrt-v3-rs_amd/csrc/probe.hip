@@ -1,6 +1,7 @@
 // Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_sphere_light_probe_batch, pbrt_hip_raysort_probe, pbrt_hip_texture_probe_batch,
-// pbrt_hip_bump_probe_batch, pbrt_hip_traverse_probe): the device's BSDF, sampler, light and texture code, the ray binning between wavefront rounds and the traversal kernel's queue on explicit inputs.
-// Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h); no formula lives here.
+// pbrt_hip_bump_probe_batch, pbrt_hip_traverse_probe, pbrt_hip_surface_probe_batch): the device's BSDF, sampler, light, texture and hit-to-interaction code, the ray binning between wavefront rounds and the
+// traversal kernel's queue on explicit inputs.
+// Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h, shading_diff.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
 #include "pt_device.h"
@@ -8,6 +9,7 @@
 #include "wf_device.h"
 #include "texture.h"
 #include "sphere_light.h"
+#include "shading_diff.h"
 #include "film_plan.h"
 #include <cstring>
 #include <vector>
@@ -146,6 +148,88 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void curve_probe_kernel(DeviceScene
     curve_surface(sc.self, qi, rtuv, &qs);
     o[4] = qs.p.x; o[5] = qs.p.y; o[6] = qs.p.z; o[7] = qs.p_error.x; o[8] = qs.p_error.y; o[9] = qs.p_error.z;
     o[10] = qs.dpdu.x; o[11] = qs.dpdu.y; o[12] = qs.dpdu.z; o[13] = qs.dpdv.x; o[14] = qs.dpdv.y; o[15] = qs.dpdv.z; o[16] = qs.n.x; o[17] = qs.n.y; o[18] = qs.n.z;
+}
+
+// The hit-to-interaction stage on explicit hits (include/pbrt_hip.h: pbrt_hip_surface_probe_batch gives the layouts).  VARIANT 0: make_surface_hit (by prim), 1: make_surface_hit_any
+// (leaf record, instances), 2: make_surface_hit_q<true> (scenes with quadric shapes); everything after the interaction is the texture pass's / the Whitted kernels' own sequence of calls:
+// hit_tex_ctx or tex_ctx_from, camera_ray_differentials, tri_shading_dn, hit_bump or bump_shading, spawn_ray, spawn_ray_to_hit, specular_ray_differentials.  The camera travels by value.
+PH_DEV void put3(float* o, f3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+PH_DEV void put_ray(float* o, const RayIn& r) { o[0] = r.ox; o[1] = r.oy; o[2] = r.oz; o[3] = r.t_max; o[4] = r.dx; o[5] = r.dy; o[6] = r.dz; o[7] = r.time; }
+template <int VARIANT>
+__global__ __launch_bounds__(PH_TEX_LDS_THREADS) void surface_probe_kernel(DeviceScene sc, CameraRec cam, uint32_t spp, int op, uint32_t tex, uint32_t camera_ray, uint32_t n, const RayIn* rays,
+                                                                            const PbrtHipHit* hits, const float* aux, float* out) {
+    if (op == 2) noise_lds_fill();   // (the one op that evaluates a texture; uniform over the grid)
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RayIn ray = load_ray(rays + i);
+    const float4* hp = reinterpret_cast<const float4*>(hits + i);
+    const float4 h0 = hp[0], h1 = hp[1];
+    const uint32_t prim = __float_as_uint(h0.y), tri_index = __float_as_uint(h1.y), inst = __float_as_uint(h1.z);
+    const f3 ro = mk3(ray.ox, ray.oy, ray.oz), rd = mk3(ray.dx, ray.dy, ray.dz), bary = mk3(h0.z, h0.w, h1.x);
+    const float* a = aux + PBRT_HIP_SURFACE_PROBE_AUX * (size_t)i;
+    float* o = out + PBRT_HIP_SURFACE_PROBE_STRIDE * (size_t)i;
+    for (int k = 0; k < PBRT_HIP_SURFACE_PROBE_STRIDE; k++) o[k] = 0.0f;
+    MeshRec m;
+    QSurf qs; qs.hit = 0u;
+    SurfHit si;
+    if (VARIANT == 0) { si = make_surface_hit(sc, rd, ray.time, prim, bary.x, bary.y, bary.z); m = sc.meshes[sc.tri_mesh[prim]]; }
+    else if (VARIANT == 1) si = make_surface_hit_any(sc, rd, ray.time, tri_index, inst, bary.x, bary.y, bary.z, m);
+    else si = make_surface_hit_q<true>(sc, ro, rd, ray.time, tri_index, inst, bary.x, bary.y, bary.z, m, &qs, h0.x);
+    const bool on_quadric = VARIANT == 2 && (m.flags & PH_MESH_QUADRIC) != 0u;
+    const f2 p_film = mk2(a[0], a[1]), lens = mk2(a[2], a[3]);
+    const f3 wi = ld3(a + 4);
+    if (op == 0) {
+        put3(o, si.p); put3(o + 3, si.p_error); put3(o + 6, si.wo); put3(o + 9, si.n); put3(o + 12, si.ns); put3(o + 15, si.dpdu_s);
+        o[18] = si.time; o[19] = __uint_as_float(si.prim);
+    } else if (op == 1 || op == 2) {
+        const TexCtx ctx = on_quadric ? tex_ctx_from(&cam, spp, mk2(qs.u, qs.v), qs.dpdu, qs.dpdv, si.p, si.n, ro, rd, p_film, lens, camera_ray)
+                                      : hit_tex_ctx(sc.self, &cam, spp, tri_index, inst, bary, si.p, si.n, ro, rd, p_film, lens, camera_ray);
+        if (op == 1) {
+            f3 dpdu, dpdv, dndu, dndv;
+            if (on_quadric) { dpdu = qs.dpdu; dpdv = qs.dpdv; dndu = qs.dndu; dndv = qs.dndv; }
+            else {   // the geometric dp/du, dp/dv as whitted_vertex_kernel takes them: tri_dpdu on the leaf record, carried to world space for an instance
+                const float4* tp = reinterpret_cast<const float4*>(sc.tris + tri_index);
+                const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+                const uint32_t rprim = __float_as_uint(ta.w);
+                TriVerts t;
+                t.p0 = mk3(ta.x, ta.y, ta.z); t.p1 = mk3(tb.x, tb.y, tb.z); t.p2 = mk3(tc.x, tc.y, tc.z);
+                t.i0 = t.i1 = t.i2 = 0;
+                if (m.flags & PH_MESH_UV) { t.i0 = sc.idx[3 * rprim]; t.i1 = sc.idx[3 * rprim + 1]; t.i2 = sc.idx[3 * rprim + 2]; }
+                tri_dpdu(sc, m, t, dpdu, dpdv);
+                if (inst != 0u) {
+                    const InstRec& I = sc.instances[inst - 1u];
+                    if (!(I.flags & PH_INST_IDENTITY)) { dpdu = xf_vec(I.i2w, dpdu); dpdv = xf_vec(I.i2w, dpdv); }
+                }
+                tri_shading_dn(sc, tri_index, inst, dndu, dndv);
+            }
+            o[0] = ctx.uv.x; o[1] = ctx.uv.y; put3(o + 2, dpdu); put3(o + 5, dpdv);
+            o[8] = ctx.dudx; o[9] = ctx.dvdx; o[10] = ctx.dudy; o[11] = ctx.dvdy; put3(o + 12, ctx.dpdx); put3(o + 15, ctx.dpdy);
+            if (camera_ray) {
+                const RayDiff rdf = camera_ray_differentials(cam, p_film, lens, ro, rd, spp);
+                put3(o + 18, rdf.rx_o); put3(o + 21, rdf.ry_o); put3(o + 24, rdf.rx_d); put3(o + 27, rdf.ry_d);
+            }
+            put3(o + 30, dndu); put3(o + 33, dndv);
+        } else {
+            BumpOut bo;
+            if (on_quadric) {
+                if (camera_ray) bump_shading<false, false>(sc.self, tex, ctx, si.p, si.n, si.ns, si.dpdu_s, qs.dpdv, qs.dndu, qs.dndv, &bo);
+                else bump_shading<false, true>(sc.self, tex, ctx, si.p, si.n, si.ns, si.dpdu_s, qs.dpdv, qs.dndu, qs.dndv, &bo);
+            } else {
+                BumpIn bi; bi.tex = tex; bi.tri_index = tri_index; bi.inst = inst; bi.bary = bary;
+                bi.p = si.p; bi.n = si.n; bi.ns = si.ns; bi.dpdu_s = si.dpdu_s; bi.c = ctx;
+                if (camera_ray) hit_bump<false, false>(sc.self, &bi, &bo);   // the texture pass's instantiation for camera rays ...
+                else hit_bump<false, true>(sc.self, &bi, &bo);               // ... and for every later round
+            }
+            put3(o, bo.ns); put3(o + 3, bo.dpdu_s);
+        }
+    } else if (op == 3) {
+        put_ray(o, spawn_ray(si, wi));
+        put_ray(o + 8, spawn_ray_to_hit(si, ld3(a + 7), ld3(a + 10), ld3(a + 13)));
+    } else {
+        const RayDiff r = specular_ray_differentials(si.p, si.wo, si.ns, wi, ld3(a + 26), ld3(a + 29), ld3(a + 32), ld3(a + 35), a[22], a[23], a[24], a[25], ld3(a + 16), ld3(a + 19), a[38],
+                                                     a[39] != 0.0f);
+        put3(o, r.rx_o); put3(o + 3, r.ry_o); put3(o + 6, r.rx_d); put3(o + 9, r.ry_d);
+    }
 }
 
 // the 15 floats of pbrt_hip_texture_eval_batch.  NODIFF: the context of every ray but a camera ray, as tex_ctx_from and alpha_accept make it — the nine derivative fields are zero
@@ -424,6 +508,71 @@ int pbrt_hip_curve_probe_batch(PbrtHipScene* s, uint32_t prim, int shadow, uint6
                        shadow ? 1u : 0u, (uint32_t)n, (const ph::RayIn*)(d + o_rays), (float*)(d + o_out));
     PH_CHECK(s, hipGetLastError());
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_surface_probe_batch(PbrtHipScene* s, int op, int variant, uint32_t texture, int camera_ray, uint64_t n, const PbrtHipRay* rays, const PbrtHipHit* hits, const float* aux,
+                                 float* out) {
+    return ph_guard(s, "pbrt_hip_surface_probe_batch", [&]() -> int {
+    if (!s || (n && (!rays || !hits || !aux || !out))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: null argument");
+    if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: too many probes");
+    if (op < 0 || op > 4 || variant < 0 || variant > 2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: op must be 0 .. 4 and variant 0, 1 or 2");
+    if (op == 2 && texture >= s->textures.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: unknown texture");
+    if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "surface_probe_batch: build_accel first (the leaf records and a hit's pad[0] come from it)");
+    const bool cam_ray = camera_ray != 0 && (op == 1 || op == 2);
+    if (cam_ray && !(s->have_camera && s->have_film && s->have_sampler && s->sampler.spp > 0))
+        return set_err(s, PBRT_HIP_ERR_STATE, "surface_probe_batch: a camera ray's differentials need set_camera, set_film and set_sampler (its samples per pixel scale them)");
+    if (variant == 2 && s->quadrics.empty())
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "surface_probe_batch: variant 2 is the code of scenes that hold a quadric shape; this scene's kernels have no such instantiation");
+    if (n == 0) return PBRT_HIP_OK;
+    PH_CHECK(s, hipSetDevice(s->device));
+    // the leaf records, to check every hit against: the host's copy, or the device's where the tree was left there
+    std::vector<TriRec> fetched;
+    const TriRec* recs = s->bvh.tris.data(); size_t n_recs = s->bvh.tris.size();
+    if (n_recs == 0 && s->tree_dev_tris) {
+        fetched.resize(s->tree_dev_n_tris);
+        PH_CHECK(s, hipMemcpy(fetched.data(), s->tree_dev_tris, fetched.size() * sizeof(TriRec), hipMemcpyDeviceToHost));
+        recs = fetched.data(); n_recs = fetched.size();
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        const PbrtHipHit& h = hits[i];
+        if (h.prim == 0xFFFFFFFFu || h.prim >= s->tri_mesh.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit names no primitive");
+        if (h.pad[0] >= n_recs) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit's pad[0] is no leaf record");
+        const TriRec& r = recs[h.pad[0]];
+        if ((r.flags & PH_TRI_INSTANCE) || r.prim != h.prim) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit's pad[0] is not the leaf record of its primitive");
+        if (h.pad[1] > s->instances.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit's pad[1] names no instance");
+        if (h.pad[1]) {
+            const SceneHostState::ObjectHost& ob = s->objects[s->instances[h.pad[1] - 1u].object];
+            if (h.prim < ob.tri0 || h.prim >= ob.tri1) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit's pad[1] names an instance of another object");
+            if (variant == 0) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "surface_probe_batch: variant 0 is the interaction made from a primitive number alone; no such path exists for a hit inside an instance");
+        }
+        const uint32_t q1 = h.prim < s->prim_quadric.size() ? s->prim_quadric[h.prim] : 0u;
+        if (((r.flags & PH_TRI_QUADRIC) != 0u) != (q1 != 0u)) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit's pad[0] is not the leaf record of its primitive");
+        if (q1 && variant != 2) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "surface_probe_batch: a quadric shape's or curve segment's interaction is made by variant 2 alone");
+        if (q1 && op == 2 && s->quadrics[q1 - 1u].kind == PH_Q_CURVE) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "surface_probe_batch: op 2 does not take a curve segment");
+    }
+    int rc;
+    if ((rc = upload_scene(s))) return rc;
+    const size_t in_b = PBRT_HIP_SURFACE_PROBE_AUX * sizeof(float), out_b = PBRT_HIP_SURFACE_PROBE_STRIDE * sizeof(float);
+    const size_t o_rays = 0, o_hits = o_rays + up256(n * sizeof(PbrtHipRay)), o_aux = o_hits + up256(n * sizeof(PbrtHipHit)), o_out = o_aux + up256(n * in_b), total = o_out + up256(n * out_b);
+    Scratch sx;
+    PH_CHECK(s, hipMalloc(&sx.p, total));
+    char* d = static_cast<char*>(sx.p);
+    PH_CHECK(s, hipMemcpyAsync(d + o_rays, rays, n * sizeof(PbrtHipRay), hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_hits, hits, n * sizeof(PbrtHipHit), hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d + o_aux, aux, n * in_b, hipMemcpyHostToDevice, s->stream));
+    const dim3 grid((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), block(PH_PROBE_BLOCK);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, s->cam, cam_ray ? s->sampler.spp : 1u, op, texture, cam_ray ? 1u : 0u, (uint32_t)n, (const ph::RayIn*)(d + o_rays),
+                           (const PbrtHipHit*)(d + o_hits), (const float*)(d + o_aux), (float*)(d + o_out));
+    };
+    if (variant == 0) launch(ph::surface_probe_kernel<0>);
+    else if (variant == 1) launch(ph::surface_probe_kernel<1>);
+    else launch(ph::surface_probe_kernel<2>);
+    PH_CHECK(s, hipGetLastError());
+    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * out_b, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
     return PBRT_HIP_OK;
     });

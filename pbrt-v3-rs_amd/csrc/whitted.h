@@ -8,6 +8,7 @@
 #pragma once
 #include "bsdf_general.h"
 #include "texture.h"
+#include "shading_diff.h"
 #include "wf_device.h"
 #include "sphere_light.h"
 #include "film_plan.h"
@@ -127,36 +128,7 @@ __global__ __launch_bounds__(256) void whitted_raygen_kernel(DeviceScene sc, WhP
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// dn/du, dn/dv of a triangle's shading geometry (triangle.rs:681-715; zero without per-vertex normals), in world space for an instanced hit (transform.rs:566-590)
-PH_DEV void tri_shading_dn(const DeviceScene& sc, uint32_t tri_index, uint32_t inst, f3& dndu, f3& dndv) {
-    dndu = mk3(0.0f, 0.0f, 0.0f); dndv = dndu;
-    const float4* tp = reinterpret_cast<const float4*>(sc.tris + tri_index);
-    const uint32_t prim = __float_as_uint(tp[0].w);
-    const MeshRec m = sc.meshes[__float_as_uint(tp[2].w)];
-    if (!(m.flags & PH_MESH_N)) return;
-    const uint32_t i0 = sc.idx[3 * prim], i1 = sc.idx[3 * prim + 1], i2 = sc.idx[3 * prim + 2];
-    const f3 n0 = ld3(sc.N + 3 * (size_t)i0), n1 = ld3(sc.N + 3 * (size_t)i1), n2 = ld3(sc.N + 3 * (size_t)i2);
-    f2 uv0 = mk2(0.0f, 0.0f), uv1 = mk2(1.0f, 0.0f), uv2 = mk2(1.0f, 1.0f);
-    if (m.flags & PH_MESH_UV) {
-        uv0 = mk2(sc.UV[2 * (size_t)i0], sc.UV[2 * (size_t)i0 + 1]); uv1 = mk2(sc.UV[2 * (size_t)i1], sc.UV[2 * (size_t)i1 + 1]);
-        uv2 = mk2(sc.UV[2 * (size_t)i2], sc.UV[2 * (size_t)i2 + 1]);
-    }
-    const f2 duv02 = mk2(uv0.x - uv2.x, uv0.y - uv2.y), duv12 = mk2(uv1.x - uv2.x, uv1.y - uv2.y);
-    const f3 dn1 = n0 - n2, dn2 = n1 - n2;
-    const float determinant = duv02.x * duv12.y - duv02.y * duv12.x;
-    if (fabsf(determinant) < 1e-8f) {
-        const f3 dn = cross(n2 - n0, n1 - n0);
-        if (length_squared(dn) != 0.0f) coordinate_system(dn, dndu, dndv);
-    } else {
-        const float invdet = ph_div(1.0f, determinant);
-        dndu = (duv12.y * dn1 - duv02.y * dn2) * invdet;
-        dndv = (-duv12.x * dn1 + duv02.x * dn2) * invdet;
-    }
-    if (inst != 0u) {
-        const InstRec& I = sc.instances[inst - 1u];
-        if (!(I.flags & PH_INST_IDENTITY)) { dndu = xf_normal(I.w2i, dndu); dndv = xf_normal(I.w2i, dndv); }
-    }
-}
+// (dn/du, dn/dv of a triangle's shading geometry: tri_shading_dn, shading_diff.h)
 
 // The vertex pass: one thread per running sample whose frame met a surface this round.  compute_differentials with the frame's ray differentials (camera rays AND the
 // reflected / refracted rays below them carry some), Material::bump, the textured lobe colours — texture_kernel's work (wavefront.hip) with the differentials taken from
@@ -514,26 +486,9 @@ __global__ __launch_bounds__(256) void whitted_state_kernel(DeviceScene sc, WhPa
                     cf->ray = ray_cl; cf->has_diff = 0u;
                     if (has_diff) {   // sampler_integrator.rs:96-119, :171-230
                         cf->has_diff = 1u;
-                        const f3 dpdx = ld3f(fr->v.dpdx), dpdy = ld3f(fr->v.dpdy), dndu = ld3f(fr->v.dndu), dndv = ld3f(fr->v.dndv);
-                        st3f(cf->rx_o, si.p + dpdx); st3f(cf->ry_o, si.p + dpdy);
-                        f3 dndx = dndu * fr->v.dudx + dndv * fr->v.dvdx;
-                        f3 dndy = dndu * fr->v.dudy + dndv * fr->v.dvdy;
-                        const f3 dwodx = -ld3f(fr->rx_d) - wo, dwody = -ld3f(fr->ry_d) - wo;
-                        if (!transmit) {
-                            const float ddndx = dot(dwodx, ns) + dot(wo, dndx), ddndy = dot(dwody, ns) + dot(wo, dndy);
-                            st3f(cf->rx_d, wi - dwodx + 2.0f * (dot(wo, ns) * dndx + ddndx * ns));
-                            st3f(cf->ry_d, wi - dwody + 2.0f * (dot(wo, ns) * dndy + ddndy * ns));
-                        } else {
-                            float eta = ph_div(1.0f, bsdf.g.eta);
-                            f3 nn = ns;
-                            if (dot(wo, nn) < 0.0f) { eta = ph_div(1.0f, eta); nn = -nn; dndx = -dndx; dndy = -dndy; }
-                            const float ddndx = dot(dwodx, nn) + dot(wo, dndx), ddndy = dot(dwody, nn) + dot(wo, dndy);
-                            const float mu = eta * dot(wo, nn) - abs_dot(wi, nn);
-                            const float dmudx = (eta - ph_div(eta * eta * dot(wo, nn), abs_dot(wi, nn))) * ddndx;
-                            const float dmudy = (eta - ph_div(eta * eta * dot(wo, nn), abs_dot(wi, nn))) * ddndy;
-                            st3f(cf->rx_d, wi - eta * dwodx + (mu * dndx + dmudx * nn));
-                            st3f(cf->ry_d, wi - eta * dwody + (mu * dndy + dmudy * nn));
-                        }
+                        const RayDiff cd = specular_ray_differentials(si.p, wo, ns, wi, ld3f(fr->v.dpdx), ld3f(fr->v.dpdy), ld3f(fr->v.dndu), ld3f(fr->v.dndv), fr->v.dudx, fr->v.dvdx, fr->v.dudy,
+                                                                      fr->v.dvdy, ld3f(fr->rx_d), ld3f(fr->ry_d), bsdf.g.eta, transmit);   // shading_diff.h
+                        st3f(cf->rx_o, cd.rx_o); st3f(cf->ry_o, cd.ry_o); st3f(cf->rx_d, cd.rx_d); st3f(cf->ry_d, cd.ry_d);
                     }
                     sts3(fr->f, f); fr->abs_dot = abs_dot(wi, ns); fr->pdf = pdf;
                     fr->has_diff = (fr->has_diff & 1u) | (transmit ? 256u : 0u);   // bit 8: the child in flight is the refracted one

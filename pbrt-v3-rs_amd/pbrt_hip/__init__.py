@@ -175,6 +175,7 @@ class Binding:
             "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
             "add_curve": (C.c_int, [vp, fp, fp, C.c_int, fp, fp, fp, C.c_int, C.c_uint32, C.c_uint32]),
             "curve_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, vp, fp]),
+            "surface_probe_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint64, vp, vp, fp, fp]),
             "loopsubdiv_mesh": (C.c_int, [vp, fp, fp, fp, C.c_uint32, u32p, C.c_uint32, C.c_int, u32p, u32p, fp, fp, u32p]),
             "add_loopsubdiv": (C.c_int, [vp, fp, fp, fp, C.c_uint32, u32p, C.c_uint32, C.c_int, C.c_uint32, C.c_int32, C.c_uint32, C.c_float, C.c_float]),
             "traverse_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
@@ -814,6 +815,20 @@ class Scene:
         assert len(u) == n and len(wi) == n
         out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
         self._chk(self.b.fn("sphere_light_probe_batch")(self.h, light, op, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
+        return out
+
+    SURFACE_PROBE_AUX, SURFACE_PROBE_STRIDE = 48, 40
+
+    def surface_probe_batch(self, op, rays, hits, aux, variant=1, texture=0, camera_ray=False):
+        """The hit-to-interaction code on explicit hits (pbrt_hip_surface_probe_batch), a probe for the parity tests: rays (n,) RAY_DTYPE in world space; hits (n,) HIT_DTYPE as
+        intersect_batch wrote them, t and b0..b2 then set freely; aux (n,48) = p_film, lens, wi, hp, hp_error, hn and op 4's differentials.  op 0 the interaction, 1 the texture
+        context and shading dn/du, dn/dv, 2 Material::bump with `texture`, 3 spawn_ray / spawn_ray_to_hit, 4 the specular ray differentials.  variant 0 make_surface_hit (by prim),
+        1 make_surface_hit_any (leaf record, instances), 2 make_surface_hit_q (scenes with quadrics).  Returns (n,40) float32; include/pbrt_hip.h gives the slots."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE); hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE); n = len(rays)
+        aux = _f32(aux, (-1, self.SURFACE_PROBE_AUX))
+        assert len(hits) == n and len(aux) == n
+        out = np.zeros((n, self.SURFACE_PROBE_STRIDE), np.float32)
+        self._chk(self.b.fn("surface_probe_batch")(self.h, op, variant, texture, 1 if camera_ray else 0, n, rays.ctypes.data, hits.ctypes.data, _ptr(aux, C.c_float), _ptr(out, C.c_float)))
         return out
 
     def texture_probe_batch(self, texture, contexts, variant=0):
