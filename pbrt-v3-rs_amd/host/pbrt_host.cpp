@@ -53,10 +53,6 @@ static Xform identity_xform() {
     return x;
 }
 
-// device < 0 = check mode: directives are parsed, validated and counted, nothing is sent to the library and nothing is
-// rendered (there is no CPU renderer to fall back to).
-#define ABI(call) (check_only_ ? (int)PBRT_HIP_OK : (call))
-
 Api::Api(int device) : check_only_(device < 0), ctm_(identity_xform()), camera_to_world_(identity_xform()) {
     if (check_only_) return;
     scene_ = pbrt_hip_scene_create(device);
@@ -184,196 +180,7 @@ void Api::pbrt_transform_end() {
     ctm_ = ctm_stack_.back(); ctm_stack_.pop_back();
 }
 
-void Api::pbrt_texture(const std::string& name, const std::string& type, const std::string& tex_class, const ParamSet& p, const std::string& scene_dir) {
-    if (!verify_world("Texture")) return;
-    const bool is_float = type == "float", is_spec = type == "color" || type == "spectrum";
-    if (!is_float && !is_spec) { warn("Texture type '" + type + "' unknown."); return; }
-    // "scale" and "mix" of constant textures are constant: fold them (textures/src/scale.rs:38-40 tex1 * tex2; mix.rs:44-49 (1 - amt) * t1 + amt * t2)
-    if (tex_class == "scale" || tex_class == "mix") {
-        bool ok = true;
-        auto fget = [&](const char* n, float d) {
-            std::string tn = p.find_one_texture(n);
-            if (!tn.empty()) { auto it = gs_.float_textures.find(tn); if (it != gs_.float_textures.end()) return it->second; ok = false; }
-            return p.find_one_float(n, d);
-        };
-        auto sget = [&](const char* n, std::array<float, 3> d) {
-            std::string tn = p.find_one_texture(n);
-            if (!tn.empty()) { auto it = gs_.spectrum_textures.find(tn); if (it != gs_.spectrum_textures.end()) return it->second; ok = false; }
-            return p.find_one_rgb(n, d);
-        };
-        if (is_float) {
-            const float t1 = fget("tex1", tex_class == "scale" ? 1.0f : 0.0f), t2 = fget("tex2", 1.0f);
-            const float v = tex_class == "scale" ? t1 * t2 : ((1.0f - fget("amount", 0.5f)) * t1 + fget("amount", 0.5f) * t2);
-            if (ok) { gs_.unsupported_textures.erase(name); gs_.device_textures.erase(name); gs_.float_textures[name] = v; return; }
-        } else {
-            const std::array<float, 3> t1 = sget("tex1", tex_class == "scale" ? std::array<float, 3>{1, 1, 1} : std::array<float, 3>{0, 0, 0}), t2 = sget("tex2", {1, 1, 1});
-            std::array<float, 3> v;
-            const float amt = fget("amount", 0.5f);
-            for (int c = 0; c < 3; c++) v[c] = tex_class == "scale" ? t1[c] * t2[c] : ((1.0f - amt) * t1[c] + amt * t2[c]);
-            if (ok) { gs_.unsupported_textures.erase(name); gs_.device_textures.erase(name); gs_.spectrum_textures[name] = v; return; }
-        }
-    }
-    // get_texture_mapping (textures/src/lib.rs:44-67): "uv" travels in the texture's own parameters, the other three are attached afterwards
-    auto mapping_ok = [&](const std::string& mp) { return mp == "uv" || mp == "spherical" || mp == "cylindrical" || mp == "planar"; };
-    auto attach_mapping = [&](uint32_t id) -> bool {
-        const std::string mp = p.find_one_string("mapping", "uv");
-        if (mp == "uv" || !mapping_ok(mp)) return true;   // unknown names fall back to uv with a warning (issued by the caller)
-        if (mp == "planar") {
-            float prm[8] = {1, 0, 0, 0, 1, 0, p.find_one_float("udelta", 0.0f), p.find_one_float("vdelta", 0.0f)};
-            if (const std::vector<float>* v = p.find_floats("v1")) if (v->size() >= 3) for (int k = 0; k < 3; k++) prm[k] = (*v)[(size_t)k];
-            if (const std::vector<float>* v = p.find_floats("v2")) if (v->size() >= 3) for (int k = 0; k < 3; k++) prm[3 + k] = (*v)[(size_t)k];
-            return check(ABI(pbrt_hip_set_texture_mapping(scene_, id, 3, prm)), "set_texture_mapping");
-        }
-        return check(ABI(pbrt_hip_set_texture_mapping(scene_, id, mp == "spherical" ? 1 : 2, ctm_.mi)), "set_texture_mapping");  // tex2world.inverse()
-    };
-    auto forget = [&]() { gs_.unsupported_textures.erase(name); gs_.float_textures.erase(name); gs_.spectrum_textures.erase(name); gs_.device_textures.erase(name); };
-    if (tex_class == "imagemap") {  // ImageTexture::from (textures/src/imagemap.rs:117-160)
-        forget();
-        const std::string mapping = p.find_one_string("mapping", "uv");
-        if (!mapping_ok(mapping)) warn("Error 2D texture mapping '" + mapping + "' unknown");
-        std::string file = p.find_one_string("filename", "");
-        if (file.empty()) { if (error.empty()) error = "imagemap path not specified."; return; }
-        if (file[0] != '/' && !scene_dir.empty()) file = scene_dir + "/" + file;
-        const bool trilinear = p.find_one_bool("trilinear", false);
-        const float max_aniso = p.find_one_float("maxanisotropy", 8.0f), scale = p.find_one_float("scale", 1.0f);
-        const std::string wrap_s = p.find_one_string("wrap", "repeat");
-        const int wrap = wrap_s == "black" ? 1 : (wrap_s == "clamp" ? 2 : 0);
-        auto ends = [&](const char* e) { const size_t n = std::strlen(e); return file.size() >= n && file.compare(file.size() - n, n, e) == 0; };
-        const bool gamma = p.find_one_bool("gamma", ends(".tga") || ends(".png"));
-        char key[64];
-        std::snprintf(key, sizeof key, "|%d|%d|%d|%a|%d|%a", is_float ? 1 : 0, trilinear ? 0 : 1, wrap, (double)scale, gamma ? 1 : 0, (double)max_aniso);
-        const std::string ck = file + key;
-        uint32_t mip = 0;
-        auto it = mipmap_cache_.find(ck);
-        if (it != mipmap_cache_.end()) mip = it->second;
-        else {
-            std::vector<float> rgb; int w = 0, h = 0; std::string err;
-            if (!read_image(file, rgb, w, h, err)) { if (error.empty()) error = "Unable to load MIPMap: Error reading texture " + file + ", " + err; return; }
-            if (!check(ABI(pbrt_hip_add_mipmap(scene_, w, h, rgb.data(), is_float ? 1 : 0, scale, gamma ? 1 : 0, trilinear ? 0 : 1, wrap, max_aniso, &mip)), "add_mipmap")) return;
-            mipmap_cache_[ck] = mip;
-        }
-        uint32_t id = 0;
-        if (!check(ABI(pbrt_hip_add_texture_imagemap(scene_, mip, p.find_one_float("uscale", 1.0f), p.find_one_float("vscale", 1.0f), p.find_one_float("udelta", 0.0f),
-                                                     p.find_one_float("vdelta", 0.0f), &id)), "add_texture_imagemap")) return;
-        if (!attach_mapping(id)) return;
-        gs_.device_textures[name] = GraphicsState::DeviceTexture{is_float, id};
-        return;
-    }
-    if (tex_class == "scale" || tex_class == "mix") {  // an operand is evaluated per hit: the whole tree goes to the library
-        bool ok = true;
-        auto operand = [&](const char* pn, bool want_float, std::array<float, 3> dflt) -> uint32_t {
-            const std::string tn = p.find_one_texture(pn);
-            if (!tn.empty()) {
-                auto dt = gs_.device_textures.find(tn);
-                if (dt != gs_.device_textures.end() && dt->second.is_float == want_float) return dt->second.id;
-                std::array<float, 3> v = dflt; bool found = false;
-                if (want_float) { auto f = gs_.float_textures.find(tn); if (f != gs_.float_textures.end()) { v = {f->second, f->second, f->second}; found = true; } }
-                else { auto sp = gs_.spectrum_textures.find(tn); if (sp != gs_.spectrum_textures.end()) { v = sp->second; found = true; } }
-                if (!found) { ok = false; return 0u; }
-                dflt = v;
-            } else if (want_float) { const float f = p.find_one_float(pn, dflt[0]); dflt = {f, f, f}; }
-            else dflt = p.find_one_rgb(pn, dflt);
-            uint32_t id = 0;
-            if (!check(ABI(pbrt_hip_add_texture_constant(scene_, dflt.data(), &id)), "add_texture_constant")) ok = false;
-            return id;
-        };
-        const float d1 = tex_class == "scale" ? 1.0f : 0.0f;
-        const uint32_t t1 = operand("tex1", is_float, {d1, d1, d1}), t2 = operand("tex2", is_float, {1.0f, 1.0f, 1.0f});
-        uint32_t id = 0;
-        if (ok && tex_class == "scale") ok = check(ABI(pbrt_hip_add_texture_scale(scene_, t1, t2, &id)), "add_texture_scale");
-        else if (ok) { const uint32_t amt = operand("amount", true, {0.5f, 0.5f, 0.5f}); if (ok) ok = check(ABI(pbrt_hip_add_texture_mix(scene_, t1, t2, amt, &id)), "add_texture_mix"); }
-        if (ok) { forget(); gs_.device_textures[name] = GraphicsState::DeviceTexture{is_float, id}; return; }
-    }
-    if ((tex_class == "checkerboard" && p.find_one_int("dimension", 2) != 3) || tex_class == "uv" || tex_class == "bilerp" || tex_class == "dots") {  // 2D procedural textures (textures/src/*.rs)
-        const std::string mapping = p.find_one_string("mapping", "uv");
-        if (!mapping_ok(mapping)) warn("Error 2D texture mapping '" + mapping + "' unknown");
-        if (tex_class == "checkerboard" && p.find_one_int("dimension", 2) != 2 && p.find_one_int("dimension", 2) != 3) {
-            if (error.empty()) error = "Texture \"" + name + "\": " + std::to_string(p.find_one_int("dimension", 2)) + " dimensional checkerboard texture not supported";
-            return;
-        }
-        if (tex_class == "uv" && is_float) { warn("Unable to create float texture 'uv'."); return; }   // textures/src/lib.rs: only a spectrum variant exists
-        const float su = p.find_one_float("uscale", 1.0f), sv = p.find_one_float("vscale", 1.0f), du = p.find_one_float("udelta", 0.0f), dv = p.find_one_float("vdelta", 0.0f);
-        bool ok = true;
-        auto operand = [&](const char* pn, float dflt) -> uint32_t {  // a texture reference of this texture's own type, or a constant
-            std::array<float, 3> v = {dflt, dflt, dflt};
-            const std::string tn = p.find_one_texture(pn);
-            if (!tn.empty()) {
-                auto dt = gs_.device_textures.find(tn);
-                if (dt != gs_.device_textures.end() && dt->second.is_float == is_float) return dt->second.id;
-                bool found = false;
-                if (is_float) { auto f = gs_.float_textures.find(tn); if (f != gs_.float_textures.end()) { v = {f->second, f->second, f->second}; found = true; } }
-                else { auto sp = gs_.spectrum_textures.find(tn); if (sp != gs_.spectrum_textures.end()) { v = sp->second; found = true; } }
-                if (!found) { ok = false; if (error.empty()) error = "Texture \"" + name + "\": operand '" + tn + "' is not a texture the library evaluates"; return 0u; }
-            } else if (is_float) { const float f = p.find_one_float(pn, dflt); v = {f, f, f}; }
-            else v = p.find_one_rgb(pn, v);
-            uint32_t id = 0;
-            if (!check(ABI(pbrt_hip_add_texture_constant(scene_, v.data(), &id)), "add_texture_constant")) ok = false;
-            return id;
-        };
-        uint32_t id = 0;
-        if (tex_class == "checkerboard") {
-            const uint32_t t1 = operand("tex1", 1.0f), t2 = operand("tex2", 0.0f);
-            std::string aa = p.find_one_string("aamode", "closedform");
-            if (aa != "none" && aa != "closedform") { warn("Antialiasing mode '" + aa + "' not understood by Checkerboard2DTexture; using 'closedform'"); aa = "closedform"; }
-            if (ok) ok = check(ABI(pbrt_hip_add_texture_checkerboard(scene_, t1, t2, su, sv, du, dv, aa == "none" ? 0 : 1, &id)), "add_texture_checkerboard");
-        } else if (tex_class == "dots") {
-            // Quirk B13 (textures/src/dots.rs:61-66): the reference's constructor from parameters hands (inside, outside) to DotsTexture::new(outside_dot, inside_dot), so
-            // a scene file's "inside" value is what shows OUTSIDE the dots and "outside" fills them — its own render of scenes/shapes/triangles-alpha-mask.pbrt (an opaque
-            // cube with holes where `"float inside" 1 "float outside" 0` asks for the opposite) confirms it.  The C ABI keeps DotsTexture's meaning; the swap lives here.
-            const uint32_t param_inside = operand("inside", 1.0f), param_outside = operand("outside", 0.0f);
-            if (ok) ok = check(ABI(pbrt_hip_add_texture_dots(scene_, /*inside_dot=*/param_outside, /*outside_dot=*/param_inside, su, sv, du, dv, &id)), "add_texture_dots");
-        } else if (tex_class == "uv") ok = check(ABI(pbrt_hip_add_texture_uv(scene_, su, sv, du, dv, &id)), "add_texture_uv");
-        else {
-            auto corner = [&](const char* pn, float d) { std::array<float, 3> v = {d, d, d}; if (is_float) { const float f = p.find_one_float(pn, d); v = {f, f, f}; } else v = p.find_one_rgb(pn, v); return v; };
-            const std::array<float, 3> v00 = corner("v00", 0.0f), v01 = corner("v01", 1.0f), v10 = corner("v10", 0.0f), v11 = corner("v11", 1.0f);
-            ok = check(ABI(pbrt_hip_add_texture_bilerp(scene_, v00.data(), v01.data(), v10.data(), v11.data(), su, sv, du, dv, &id)), "add_texture_bilerp");
-        }
-        if (ok) ok = attach_mapping(id);
-        if (ok) { forget(); gs_.device_textures[name] = GraphicsState::DeviceTexture{is_float, id}; }
-        return;
-    }
-    const bool checker3d = tex_class == "checkerboard" && p.find_one_int("dimension", 2) == 3;
-    if (tex_class == "fbm" || tex_class == "wrinkled" || tex_class == "windy" || tex_class == "marble" || checker3d) {  // 3D procedural textures over IdentityMapping3D
-        // the reference builds IdentityMapping3D from tex2world = the CTM at the Texture directive (textures/src/fbm.rs:63-65) and applies it as is
-        if (tex_class == "marble" && is_float) { warn("Unable to create float texture 'marble'."); return; }
-        const float omega = p.find_one_float("roughness", 0.5f); const int octaves = p.find_one_int("octaves", 8);
-        uint32_t id = 0; bool ok = true;
-        if (tex_class == "fbm") ok = check(ABI(pbrt_hip_add_texture_fbm(scene_, ctm_.m, omega, octaves, &id)), "add_texture_fbm");
-        else if (tex_class == "wrinkled") ok = check(ABI(pbrt_hip_add_texture_wrinkled(scene_, ctm_.m, omega, octaves, &id)), "add_texture_wrinkled");
-        else if (tex_class == "windy") ok = check(ABI(pbrt_hip_add_texture_windy(scene_, ctm_.m, &id)), "add_texture_windy");
-        else if (tex_class == "marble") ok = check(ABI(pbrt_hip_add_texture_marble(scene_, ctm_.m, omega, octaves, p.find_one_float("scale", 1.0f), p.find_one_float("variation", 0.2f), &id)), "add_texture_marble");
-        else {
-            auto operand = [&](const char* pn, float dflt) -> uint32_t {
-                std::array<float, 3> v = {dflt, dflt, dflt};
-                const std::string tn = p.find_one_texture(pn);
-                if (!tn.empty()) {
-                    auto dt = gs_.device_textures.find(tn);
-                    if (dt != gs_.device_textures.end() && dt->second.is_float == is_float) return dt->second.id;
-                    bool found = false;
-                    if (is_float) { auto f = gs_.float_textures.find(tn); if (f != gs_.float_textures.end()) { v = {f->second, f->second, f->second}; found = true; } }
-                    else { auto sp = gs_.spectrum_textures.find(tn); if (sp != gs_.spectrum_textures.end()) { v = sp->second; found = true; } }
-                    if (!found) { ok = false; if (error.empty()) error = "Texture \"" + name + "\": operand '" + tn + "' is not a texture the library evaluates"; return 0u; }
-                } else if (is_float) { const float f = p.find_one_float(pn, dflt); v = {f, f, f}; }
-                else v = p.find_one_rgb(pn, v);
-                uint32_t cid = 0;
-                if (!check(ABI(pbrt_hip_add_texture_constant(scene_, v.data(), &cid)), "add_texture_constant")) ok = false;
-                return cid;
-            };
-            const uint32_t t1 = operand("tex1", 1.0f), t2 = operand("tex2", 0.0f);
-            if (ok) ok = check(ABI(pbrt_hip_add_texture_checkerboard3d(scene_, t1, t2, ctm_.m, &id)), "add_texture_checkerboard3d");
-        }
-        if (ok) { forget(); gs_.device_textures[name] = GraphicsState::DeviceTexture{is_float, id}; }
-        return;
-    }
-    if (tex_class != "constant") {  // ptex: not evaluated by the library
-        forget();
-        gs_.unsupported_textures[name] = tex_class;
-        return;
-    }
-    forget();
-    if (is_float) gs_.float_textures[name] = p.find_one_float("value", 1.0f);
-    else gs_.spectrum_textures[name] = p.find_one_rgb("value", {1.0f, 1.0f, 1.0f});
-}
+// pbrt_texture and the table of texture names: textures.cpp
 void Api::pbrt_material(const std::string& name, const ParamSet& p) { if (!verify_world("Material")) return; gs_.material.type = name; gs_.material.params = p; }
 void Api::pbrt_make_named_material(const std::string& name, const ParamSet& p) {
     if (!verify_world("MakeNamedMaterial")) return;
@@ -478,204 +285,7 @@ void Api::pbrt_light_source(const std::string& name, const ParamSet& p, const st
 }
 void Api::pbrt_area_light_source(const std::string& name, const ParamSet& p) { if (!verify_world("AreaLightSource")) return; gs_.area_light = name; gs_.area_light_params = p; }
 
-// MatteMaterial From<&TextureParams> (materials/src/matte.rs:95-110) with TextureParams's lookup order: shape parameters
-// first, then the material's own (core/src/paramset/texture_params.rs).
-uint32_t Api::material_id_for(const MaterialDesc& m) {
-    std::array<float, 3> kd = {0.5f, 0.5f, 0.5f};
-    float sigma = 0.0f;
-    int64_t ftex_param[4] = {-1, -1, -1, -1};     // [sigma, uroughness, vroughness, index]: the same for float parameters
-    int64_t tex_param[10] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // [Kd, Ks, Kr, Kt, opacity, amount, eta, k, reflect, transmit]: the parameter names a texture the library evaluates per hit
-    auto spectrum_tex = [&](const std::string& pname, std::array<float, 3> d) {
-        std::string tn = m.params.find_one_texture(pname);
-        if (!tn.empty()) {
-            auto dt = gs_.device_textures.find(tn);
-            if (dt != gs_.device_textures.end()) {
-                // a texture the library evaluates per hit: the material is created with a white placeholder and the texture attached afterwards
-                const int param = pname == "Kd" ? 0 : (pname == "Ks" ? 1 : (pname == "Kr" ? 2 : (pname == "Kt" ? 3 : (pname == "opacity" ? 4 : (pname == "amount" ? 5 : (pname == "eta" ? 6 : (pname == "k" ? 7 : (pname == "reflect" ? 8 : (pname == "transmit" ? 9 : -1)))))))));
-                const bool takes = (m.type == "matte" && param == 0) || ((m.type == "plastic" || m.type == "substrate") && (param == 0 || param == 1)) || (m.type == "mirror" && param == 2) ||
-                                   (m.type == "glass" && (param == 2 || param == 3)) || (m.type == "uber" && param >= 0 && param <= 4) || (m.type == "translucent" && (param == 0 || param == 1 || param == 8 || param == 9)) ||
-                                   (m.type == "mix" && param == 5) || (m.type == "metal" && (param == 6 || param == 7));
-                if (!takes || dt->second.is_float) {
-                    if (error.empty()) error = "texture '" + tn + "' on parameter '" + pname + "' of Material \"" + m.type + "\": per-hit spectrum textures are wired to matte Kd, plastic Kd / Ks, mirror Kr, substrate Kd / Ks, glass Kr / Kt, uber Kd / Ks / Kr / Kt / opacity, translucent Kd / Ks / reflect / transmit, mix amount and metal eta / k";
-                    return m.params.find_one_rgb(pname, d);
-                }
-                tex_param[param] = (int64_t)dt->second.id;
-                return std::array<float, 3>{1.0f, 1.0f, 1.0f};
-            }
-            auto it = gs_.spectrum_textures.find(tn);
-            if (it != gs_.spectrum_textures.end()) return it->second;
-            auto un = gs_.unsupported_textures.find(tn);
-            if (un != gs_.unsupported_textures.end() && error.empty())
-                error = "texture '" + tn + "' of class '" + un->second + "' is not evaluated by the library yet (constant, scale, mix and imagemap are)";
-            else if (error.empty()) warn("Couldn't find spectrum texture named '" + tn + "' for parameter '" + pname + "'");
-        }
-        return m.params.find_one_rgb(pname, d);
-    };
-    auto float_tex = [&](const std::string& pname, float d) {
-        std::string tn = m.params.find_one_texture(pname);
-        if (!tn.empty()) {
-            auto dtf = gs_.device_textures.find(tn);
-            if (dtf != gs_.device_textures.end()) {
-                // a float texture the library evaluates per hit: sigma (matte) or the microfacet roughness (plastic, uber, substrate, metal, translucent)
-                const int fp = pname == "sigma" ? 0 : ((pname == "uroughness" || pname == "roughness") ? 1 : (pname == "vroughness" ? 2 : (pname == "index" ? 3 : -1)));
-                const bool takes = dtf->second.is_float && ((m.type == "matte" && fp == 0) || ((m.type == "plastic" || m.type == "uber" || m.type == "substrate" || m.type == "metal" || m.type == "translucent") && (fp == 1 || fp == 2)) ||
-                                                            (m.type == "glass" && (fp == 1 || fp == 2) && pname != "roughness") || ((m.type == "glass" || m.type == "uber") && fp == 3));
-                if (!takes) {
-                    if (error.empty()) error = "texture '" + tn + "' on parameter '" + pname + "' of Material \"" + m.type + "\": per-hit float textures are wired to matte sigma and to the roughness of plastic / uber / substrate / metal / translucent / glass";
-                    return m.params.find_one_float(pname, d);
-                }
-                if (pname == "roughness") { if (ftex_param[1] < 0) ftex_param[1] = (int64_t)dtf->second.id; if (ftex_param[2] < 0) ftex_param[2] = (int64_t)dtf->second.id; }
-                else ftex_param[fp] = (int64_t)dtf->second.id;
-                return d;   // placeholder: the texture replaces it
-            }
-            auto it = gs_.float_textures.find(tn);
-            if (it != gs_.float_textures.end()) return it->second;
-            auto un = gs_.unsupported_textures.find(tn);
-            if (un != gs_.unsupported_textures.end() && error.empty())
-                error = "texture '" + tn + "' of class '" + un->second + "' is not evaluated by the library yet (constant, scale, mix and imagemap are)";
-            else if (error.empty()) warn("Couldn't find float texture named '" + tn + "' for parameter '" + pname + "'");
-        }
-        return m.params.find_one_float(pname, d);
-    };
-    // `bumpmap`: get_float_texture_or_none (every material's From<&TextureParams>): a float texture by name, never a literal
-    int64_t bump_tex = -1;
-    {
-        const std::string bn = m.params.find_one_texture("bumpmap");
-        if (!bn.empty()) {
-            auto dt = gs_.device_textures.find(bn);
-            if (dt != gs_.device_textures.end() && dt->second.is_float) bump_tex = (int64_t)dt->second.id;
-            else if (gs_.float_textures.count(bn)) {
-                const float v = gs_.float_textures[bn]; const float c3_[3] = {v, v, v};
-                uint32_t id = 0;
-                if (!check(ABI(pbrt_hip_add_texture_constant(scene_, c3_, &id)), "add_texture_constant")) return 0;
-                bump_tex = (int64_t)id;
-            } else if (gs_.unsupported_textures.count(bn)) { if (error.empty()) error = "'bumpmap' texture '" + bn + "' of class '" + gs_.unsupported_textures[bn] + "' is not evaluated by the library"; }
-            else warn("Couldn't find float texture named '" + bn + "' for parameter 'bumpmap'");
-            if (bump_tex >= 0 && (m.type == "mix" || m.type == "none" || m.type.empty())) bump_tex = -1;   // MixMaterial and "none" have no bump map
-        }
-    }
-    const bool remap = m.params.find_one_bool("remaproughness", true);
-    // every float that defines the material, in order, is the cache key
-    std::vector<float> kv;
-    auto put3 = [&](const std::array<float, 3>& a) { kv.insert(kv.end(), a.begin(), a.end()); };
-    const std::array<float, 3> zero = {0.0f, 0.0f, 0.0f}, one = {1.0f, 1.0f, 1.0f}, quarter = {0.25f, 0.25f, 0.25f};
-    std::array<float, 3> a3 = zero, b3 = zero, c3 = zero, d3 = zero, e3 = zero;
-    float f0 = 0, f1 = 0, f2 = 0;
-    const std::string& t = m.type;
-    // Quirk B14 (glass.rs:158-161, uber.rs:201-204): the reference asks `tp.get_float_texture("eta")`, which is a lookup in the table of NAMED float textures — one
-    // declared as `Texture "eta" "float" ...` — and not a parameter look-up: the `"float eta" 2` that pbrt-v3 scenes (and the reference's own depth-of-field.pbrt) write is never
-    // read.  Without such a texture the index of refraction is the "index" parameter, default 1.5.  Its render of depth-of-field.pbrt shows eta 1.5 spheres, pixel for pixel.
-    auto eta_of = [&]() {
-        auto named = gs_.float_textures.find("eta");
-        if (named != gs_.float_textures.end()) return named->second;   // a constant float texture that happens to be called "eta"
-        auto dev = gs_.device_textures.find("eta");
-        if (dev != gs_.device_textures.end() && dev->second.is_float) { ftex_param[3] = (int64_t)dev->second.id; return 1.5f; }   // the float texture NAMED "eta": the index of refraction of every hit (glass.rs:158-161)
-        if (dev != gs_.device_textures.end() || gs_.unsupported_textures.count("eta")) {
-            if (error.empty()) error = "Material \"" + m.type + "\": the texture named \"eta\" would set the index of refraction per hit (glass.rs:158), but it is not a float texture the library evaluates";
-            return 1.5f;
-        }
-        if (m.params.floats.count("eta") || !m.params.find_one_texture("eta").empty())
-            warn("Material \"" + m.type + "\": the reference does not read the parameter \"eta\" (it looks up a float texture NAMED \"eta\", glass.rs:158 / uber.rs:201); using \"index\"");
-        return float_tex("index", 1.5f);
-    };
-    auto uv_rough = [&](float dflt, float& u, float& v) {  // `uroughness` / `vroughness` fall back to `roughness` (metal.rs:69-76, uber.rs:148-155)
-        const float r = float_tex("roughness", dflt);
-        const bool hu = m.params.floats.count("uroughness") || !m.params.find_one_texture("uroughness").empty();
-        const bool hv = m.params.floats.count("vroughness") || !m.params.find_one_texture("vroughness").empty();
-        u = hu ? float_tex("uroughness", r) : r; v = hv ? float_tex("vroughness", r) : r;
-    };
-    if (t == "none" || t.empty()) { /* no BSDF: graphics_state.rs make_material returns None */ }
-    else if (t == "matte") {
-        a3 = spectrum_tex("Kd", kd); f0 = float_tex("sigma", sigma); put3(a3); kv.push_back(f0);
-    }
-    else if (t == "mirror") { a3 = spectrum_tex("Kr", {0.9f, 0.9f, 0.9f}); put3(a3); }
-    else if (t == "plastic") { a3 = spectrum_tex("Kd", quarter); b3 = spectrum_tex("Ks", quarter); f0 = float_tex("roughness", 0.1f); put3(a3); put3(b3); kv.push_back(f0); }
-    else if (t == "glass") {
-        a3 = spectrum_tex("Kr", one); b3 = spectrum_tex("Kt", one); f0 = float_tex("uroughness", 0.0f); f1 = float_tex("vroughness", 0.0f); f2 = eta_of();
-        put3(a3); put3(b3); kv.push_back(f0); kv.push_back(f1); kv.push_back(f2);
-    } else if (t == "metal") {
-        std::array<float, 3> cu_n, cu_k;   // the defaults are copper's measured n and k (metal.rs:136-147)
-        pbrt_hip_host_copper_rgb(cu_n.data(), cu_k.data());
-        a3 = spectrum_tex("eta", cu_n); b3 = spectrum_tex("k", cu_k); uv_rough(0.01f, f0, f1);
-        put3(a3); put3(b3); kv.push_back(f0); kv.push_back(f1);
-    } else if (t == "uber") {
-        a3 = spectrum_tex("Kd", quarter); b3 = spectrum_tex("Ks", quarter); c3 = spectrum_tex("Kr", zero); d3 = spectrum_tex("Kt", zero); e3 = spectrum_tex("opacity", one);
-        uv_rough(0.1f, f0, f1); f2 = eta_of();
-        put3(a3); put3(b3); put3(c3); put3(d3); put3(e3); kv.push_back(f0); kv.push_back(f1); kv.push_back(f2);
-    } else if (t == "substrate") {
-        a3 = spectrum_tex("Kd", {0.5f, 0.5f, 0.5f}); b3 = spectrum_tex("Ks", {0.5f, 0.5f, 0.5f}); f0 = float_tex("uroughness", 0.1f); f1 = float_tex("vroughness", 0.1f);
-        put3(a3); put3(b3); kv.push_back(f0); kv.push_back(f1);
-    } else if (t == "translucent") {
-        a3 = spectrum_tex("Kd", quarter); b3 = spectrum_tex("Ks", quarter); c3 = spectrum_tex("reflect", {0.5f, 0.5f, 0.5f}); d3 = spectrum_tex("transmit", {0.5f, 0.5f, 0.5f});
-        f0 = float_tex("roughness", 0.1f);
-        put3(a3); put3(b3); put3(c3); put3(d3); kv.push_back(f0);
-    } else if (t == "mix") {  // graphics_state.rs:310-330: two named materials, an unknown name falls back to matte made from the same parameters
-        a3 = spectrum_tex("amount", {0.5f, 0.5f, 0.5f}); put3(a3);
-        uint32_t sub[2];
-        const char* pn[2] = {"namedmaterial1", "namedmaterial2"};
-        for (int k = 0; k < 2; k++) {
-            const std::string nm = m.params.find_one_string(pn[k], "");
-            auto it = gs_.named_materials.find(nm);
-            MaterialDesc md;
-            if (it != gs_.named_materials.end()) md = it->second;
-            else { warn("Named material '" + nm + "' undefined. Using 'matte'."); md.type = "matte"; md.params = m.params; }
-            sub[k] = material_id_for(md);
-            if (!error.empty()) return 0;
-            kv.push_back((float)sub[k]);
-        }
-        f0 = (float)sub[0]; f1 = (float)sub[1];
-    } else {
-        if (error.empty()) error = "Material \"" + t + "\" is outside the hot-path scope (supported: matte, mirror, plastic, glass, metal, uber, substrate, translucent, mix)";
-        return 0;
-    }
-    if (!error.empty()) return 0;
-    std::string key = t + (remap ? ":r" : ":n");
-    for (float v : kv) { uint32_t u; std::memcpy(&u, &v, 4); char b[12]; std::snprintf(b, sizeof b, ":%08x", u); key += b; }
-    if (bump_tex >= 0) key += "|bump=" + std::to_string(bump_tex);
-    for (int k = 0; k < 4; k++) if (ftex_param[k] >= 0) key += "|ftex" + std::to_string(k) + "=" + std::to_string(ftex_param[k]);
-    for (int k = 0; k < 10; k++) if (tex_param[k] >= 0) key += "|tex" + std::to_string(k) + "=" + std::to_string(tex_param[k]);
-    auto it = material_cache_.find(key);
-    if (it != material_cache_.end()) return it->second;
-    uint32_t id = 0;
-    int rc;
-    if (t == "none" || t.empty()) rc = ABI(pbrt_hip_add_material_none(scene_, &id));
-    else if (t == "matte") rc = ABI(pbrt_hip_add_material_matte(scene_, a3.data(), f0, &id));
-    else if (t == "mirror") rc = ABI(pbrt_hip_add_material_mirror(scene_, a3.data(), &id));
-    else if (t == "plastic") rc = ABI(pbrt_hip_add_material_plastic(scene_, a3.data(), b3.data(), f0, remap ? 1 : 0, &id));
-    else if (t == "glass") rc = ABI(pbrt_hip_add_material_glass(scene_, a3.data(), b3.data(), f0, f1, f2, remap ? 1 : 0, &id));
-    else if (t == "metal") rc = ABI(pbrt_hip_add_material_metal(scene_, a3.data(), b3.data(), f0, f1, remap ? 1 : 0, &id));
-    else if (t == "substrate") rc = ABI(pbrt_hip_add_material_substrate(scene_, a3.data(), b3.data(), f0, f1, remap ? 1 : 0, &id));
-    else if (t == "translucent") rc = ABI(pbrt_hip_add_material_translucent(scene_, a3.data(), b3.data(), c3.data(), d3.data(), f0, remap ? 1 : 0, &id));
-    else if (t == "mix") rc = ABI(pbrt_hip_add_material_mix(scene_, (uint32_t)f0, (uint32_t)f1, a3.data(), &id));
-    else rc = ABI(pbrt_hip_add_material_uber(scene_, a3.data(), b3.data(), c3.data(), d3.data(), e3.data(), f0, f1, f2, remap ? 1 : 0, &id));
-    if (!check(rc, "add_material")) return 0;
-    // colours first, then the scalars, then the structural parameters (opacity / amount rebuild or annotate the lobe list the others have filled in)
-    for (int k = 0; k < 4; k++)
-        if (tex_param[k] >= 0 && !check(ABI(pbrt_hip_set_material_texture(scene_, id, k, (uint32_t)tex_param[k])), "set_material_texture")) return 0;
-    for (int k = 0; k < 3; k++)
-        if (ftex_param[k] >= 0 && !check(ABI(pbrt_hip_set_material_float_texture(scene_, id, k, (uint32_t)ftex_param[k])), "set_material_float_texture")) return 0;
-    for (int k = 4; k < 8; k++)
-        if (tex_param[k] >= 0 && !check(ABI(pbrt_hip_set_material_texture(scene_, id, k, (uint32_t)tex_param[k])), "set_material_texture")) return 0;
-    if (ftex_param[3] >= 0 && !check(ABI(pbrt_hip_set_material_float_texture(scene_, id, 3, (uint32_t)ftex_param[3])), "set_material_float_texture")) return 0;   // index: after opacity (an uber's is made per hit with it)
-    for (int k = 8; k < 10; k++)   // translucent's reflect / transmit: after Kd / Ks and the roughness (the per-hit lobe list takes their textures over)
-        if (tex_param[k] >= 0 && !check(ABI(pbrt_hip_set_material_texture(scene_, id, k, (uint32_t)tex_param[k])), "set_material_texture")) return 0;
-    if (bump_tex >= 0 && !check(ABI(pbrt_hip_set_material_bump(scene_, id, (uint32_t)bump_tex)), "set_material_bump")) return 0;
-    material_cache_[key] = id;
-    return id;
-}
-
-// material: shape parameters override the material's (TextureParams looks in the shape's set first, graphics_state.rs:147-165)
-MaterialDesc Api::material_for_shape(const ParamSet& p) const {
-    MaterialDesc eff = gs_.material;
-    static const char* kMatParams[] = {"Kd", "Ks", "Kr", "Kt", "sigma", "roughness", "uroughness", "vroughness", "eta", "index", "k", "opacity", "bumpmap", "reflect", "transmit", "amount"};
-    for (const char* name : kMatParams) {
-        auto f = p.floats.find(name); auto tx = p.textures.find(name);
-        if (tx != p.textures.end()) { eff.params.textures[name] = tx->second; eff.params.floats.erase(name); }
-        else if (f != p.floats.end()) { eff.params.floats[name] = f->second; eff.params.textures.erase(name); }
-    }
-    { auto b = p.bools.find("remaproughness"); if (b != p.bools.end()) eff.params.bools["remaproughness"] = b->second; }
-    return eff;
-}
+// material_id_for, material_for_shape: materials.cpp
 
 static bool is_quadric_shape(const std::string& name) {
     return name == "sphere" || name == "cylinder" || name == "cone" || name == "paraboloid" || name == "disk" || name == "hyperboloid";
@@ -870,12 +480,10 @@ void Api::pbrt_shape(const std::string& name, const ParamSet& p, const std::stri
     auto alpha_of = [&](const char* pname) {
         std::string tn = p.find_one_texture(pname);
         if (!tn.empty()) {
-            auto dt = gs_.device_textures.find(tn);
-            if (dt != gs_.device_textures.end() && dt->second.is_float) { alpha_tex[std::strcmp(pname, "alpha") ? 1 : 0] = dt->second.id; return 1.0f; }
-            auto it = gs_.float_textures.find(tn);
-            if (it != gs_.float_textures.end()) return it->second;
-            auto un = gs_.unsupported_textures.find(tn);
-            if (un != gs_.unsupported_textures.end()) { if (error.empty()) error = std::string("'") + pname + "' texture '" + tn + "' of class '" + un->second + "' is outside the hot-path scope"; }
+            const TexRef r = lookup_texture(tn, true);
+            if (r.kind == TexRef::Device && r.is_float) { alpha_tex[std::strcmp(pname, "alpha") ? 1 : 0] = r.id; return 1.0f; }
+            if (r.kind == TexRef::Constant) return r.value[0];
+            if (r.kind == TexRef::Unsupported) { if (error.empty()) error = std::string("'") + pname + "' texture '" + tn + "' of class '" + r.cls + "' is outside the hot-path scope"; }
             else warn("Couldn't find float texture '" + tn + "' for '" + pname + "' parameter. Using float parameter instead.");
         }
         return p.find_one_float(pname, 1.0f);

@@ -61,6 +61,10 @@ struct RenderReport {
     std::vector<std::string> warnings;
 };
 
+// Every call an Api member makes into the library goes through this: device < 0 = check mode, in which directives are parsed, validated and counted, nothing is sent to the
+// library and nothing is rendered (there is no CPU renderer to fall back to).
+#define ABI(call) (check_only_ ? (int)PBRT_HIP_OK : (call))
+
 class Api {
   public:
     explicit Api(int device = 0);
@@ -149,6 +153,23 @@ class Api {
     bool verify_options(const char* func);
     bool verify_world(const char* func);
     void concat(const Xform& t);
+    // --- the table of texture names (textures.cpp): read by lookup_texture (resolve asks it for a parameter), written by declare_texture
+    struct TexRef {
+        enum Kind { Constant, Device, Unsupported, WrongType /* only a constant of the other type */, Unknown } kind = Constant;
+        std::array<float, 3> value{};   // Constant: the texture's value (a float in all three channels) or the literal
+        bool is_float = false; uint32_t id = 0;   // Device: what the library evaluates, as declared
+        std::string name, cls;          // the texture named ("" = the parameter was a literal or absent); Unsupported: its class
+    };
+    enum class TexDecl { Nothing, Constant, Device, Unsupported };
+    TexRef lookup_texture(const std::string& name, bool want_float) const;
+    TexRef resolve(const ParamSet& p, const std::string& pname, bool want_float, std::array<float, 3> d) const;
+    void declare_texture(const std::string& name, TexDecl what, bool is_float, std::array<float, 3> value, uint32_t id = 0, const std::string& cls = "", bool folded = false);
+    struct Operand { bool ok = true, constant = false; std::array<float, 3> value{}; uint32_t id = 0; };
+    Operand operand(const ParamSet& p, const char* pname, bool want_float, float dflt, const std::string& owner = "");
+    uint32_t operand_id(const Operand& o, bool& ok);
+    bool imagemap_texture(const ParamSet& p, bool is_float, const std::string& scene_dir, uint32_t& id);
+    bool procedural_2d_texture(const std::string& name, const std::string& tex_class, const ParamSet& p, bool is_float, uint32_t& id);
+    // --- materials (materials.cpp)
     uint32_t material_id_for(const MaterialDesc& m);
     MaterialDesc material_for_shape(const ParamSet& shape_params) const;
     void quadric_shape(const std::string& name, const ParamSet& p);
