@@ -588,6 +588,23 @@ int pbrt_hip_light_probe_batch(PbrtHipScene*, uint32_t light, int op, int varian
  * output layout are pbrt_hip_light_probe_batch's; the handle's pbrt_hip_set_path_sphere_lights switch is not consulted.  PBRT_HIP_ERR_UNSUPPORTED: the light's shape is not
  * a quadric.  PBRT_HIP_ERR_INVALID_ARG: unknown light or op; a null handle; a null array with n > 0; n > 2^32 - 1.  PBRT_HIP_ERR_STATE: no accelerator built. */
 int pbrt_hip_sphere_light_probe_batch(PbrtHipScene*, uint32_t light, int op, uint64_t n, const float* ref /*10n*/, const float* u /*2n*/, const float* wi /*3n*/, float* out /*28n*/);
+/* pbrt_hip_spatial_probe_begin / _batch / _voxel: the spatial light distribution (light strategy 2) on explicit points (a test aid like the probes above).
+ * _begin sets the tables up exactly as a strategy-2 render does: the world bound of the built tree, the voxel resolution (out_nv), a pool of *out_capacity slots
+ * (PBRT_HIP_SPATIAL_POOL_BYTES is honoured), tables and counters cleared.  PBRT_HIP_ERR_STATE: no accelerator, or fewer than two lights (a render builds no tables then).
+ * _batch, strategy 2: one claim pass over the n points p (the first point in an untouched voxel claims a pool slot, as the render's claim pass does), one pass of the kernel that
+ * builds the claimed voxels' distributions (the instantiation a render of this scene launches), one pass that picks a light per point with the sample u[i]:
+ * out_pi[3i..] = the point's voxel, out_light[i] = the light picked, out_pick_pdf[i] = its discrete probability.  Tables stay from one call to the next, until the next _begin or
+ * render.  strategy 0 / 1: the pick alone, on the scene-wide uniform / power table; out_pi is not written and no _begin is needed.  out_counters (may be null) = slots claimed,
+ * slots computed, pool-exhausted flag, blocks-finished count, as left on the device.  PBRT_HIP_ERR_OOM: the pool ran out (as a render reports it; the handle stays usable).
+ * PBRT_HIP_ERR_STATE: strategy 2 without _begin since the last render; no accelerator; no light.  PBRT_HIP_ERR_INVALID_ARG: a null array with n > 0; n > 2^32 - 1; unknown strategy.
+ * _voxel reads back func[n_lights], cdf[n_lights + 1] and func_int of a computed voxel.  PBRT_HIP_ERR_STATE: no tables, or the voxel has no slot.  PBRT_HIP_ERR_INVALID_ARG: pi outside the grid.
+ * All three: PBRT_HIP_ERR_UNSUPPORTED for a scene the path integrator refuses, one that holds a light made by pbrt_hip_add_sphere_light on a handle without
+ * pbrt_hip_set_path_sphere_lights (_voxel cannot meet it: such a scene gets no tables).  A slot's layout is fixed by the number of lights at _begin: _batch with strategy 2 and
+ * _voxel return PBRT_HIP_ERR_STATE when a light was added since. */
+int pbrt_hip_spatial_probe_begin(PbrtHipScene*, int out_nv[3], uint32_t* out_capacity);
+int pbrt_hip_spatial_probe_batch(PbrtHipScene*, uint64_t n, const float* p /*3n*/, const float* u /*n*/, int strategy, int32_t* out_pi /*3n*/, uint32_t* out_light /*n*/,
+                                 float* out_pick_pdf /*n*/, uint32_t out_counters[4]);
+int pbrt_hip_spatial_probe_voxel(PbrtHipScene*, const int pi[3], float* func, float* cdf, float* func_int);
 /* pbrt_hip_curve_probe_batch: the two device functions behind a curve segment, on explicit rays (a test aid like the probes above).  prim = the segment's slot in the primitive list.
  * Each ray is tested with its OWN t_max by curve_test — Curve::intersect(r, is_shadow_ray) up to the accept decision (curve.rs:543-645 with recursive_intersect, :339-501) —; on a hit
  * in closest-hit mode (shadow == 0) curve_surface rebuilds the SurfaceInteraction from (ray, t, u, v) as the shade pass does (:463-471, :496-534).  out, 20 floats per ray: hit flag

@@ -4,6 +4,7 @@
 #include "oracle_render.hpp"
 #include <chrono>
 #include <cstdlib>
+#include <map>
 
 using namespace orc;
 
@@ -1142,6 +1143,35 @@ int oracle_spatial_voxel(OracleScene* s, const int pi[3], float* out_func, float
     for (size_t i = 0; i < d.func.size(); i++) out_func[i] = d.func[i];
     for (size_t i = 0; i < d.cdf.size(); i++) out_cdf[i] = d.cdf[i];
     *out_func_int = d.func_int;
+    return 0;
+}
+// The light pick of uniform_sample_one_light at explicit points (integrator/common.rs:104-113): the distribution of `strategy` as Integrator::preprocess builds it
+// (strategy 2: SpatialLightDistribution::new with 64 voxels, then per point lookup's voxel, compute_distribution — once per voxel within the call — and
+// Distribution1D::sample_discrete(u); 0 / 1: sample_discrete on the uniform / power distribution, out_pi left alone).  out_nv: the voxel resolution (strategy 2).
+int oracle_spatial_lookup_batch(OracleScene* s, uint64_t n, const float* p, const float* u, int strategy, int32_t* out_pi, uint32_t* out_light, float* out_pick_pdf, int out_nv[3]) {
+    if (!s || !s->built || strategy < 0 || strategy > 2 || (n && (!p || !u || !out_light || !out_pick_pdf || (strategy == 2 && !out_pi)))) return -1;
+    Renderer& r = s->r;
+    if (s->sc.lights.empty()) return -2;
+    const int keep = r.light_strategy;
+    r.light_strategy = strategy;
+    r.preprocess_light_distribution();
+    r.light_strategy = keep;
+    if (out_nv) for (int i = 0; i < 3; i++) out_nv[i] = r.spatial ? r.n_voxels[i] : 0;
+    std::map<size_t, Dist1D> voxels;
+    for (uint64_t i = 0; i < n; i++) {
+        const Dist1D* d = &r.light_distrib;
+        if (r.spatial) {
+            int pi[3]; r.spatial_voxel_of(V3(p[3 * i], p[3 * i + 1], p[3 * i + 2]), pi);
+            for (int k = 0; k < 3; k++) out_pi[3 * i + k] = pi[k];
+            const size_t idx = ((size_t)pi[0] * r.n_voxels[1] + pi[1]) * r.n_voxels[2] + pi[2];
+            auto it = voxels.find(idx);
+            if (it == voxels.end()) { it = voxels.emplace(idx, Dist1D()).first; r.spatial_compute(pi, it->second); }
+            d = &it->second;
+        }
+        Float pdf;
+        out_light[i] = (uint32_t)d->sample_discrete(u[i], pdf);
+        out_pick_pdf[i] = pdf;
+    }
     return 0;
 }
 int oracle_render_path(OracleScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size,

@@ -1794,10 +1794,8 @@ struct Renderer {
         if (tiles_out) *tiles_out = std::move(tiles);
     }
 
-    // SamplerIntegrator::render (sampler_integrator.rs:243-304).  Tiles are merged in increasing tile index
-    // (= the reference with --nthreads 1; with more threads the reference's merge order is completion order).
-    void render(int tile_size, int tile_part, int tile_parts, int n_threads, Float* out_xyz, Float* out_weight, std::vector<FilmTile>* keep_tiles = nullptr) {
-        // Integrator::preprocess: light distribution (path.rs:81-83, light_distrib/mod.rs:49-60)
+    // Integrator::preprocess: light distribution (path.rs:81-83, light_distrib/mod.rs:49-60) for `light_strategy`
+    void preprocess_light_distribution() {
         const Scene& s = *sc;
         std::vector<Float> lf;
         int strat = s.lights.size() == 1 ? 0 : light_strategy;
@@ -1805,6 +1803,12 @@ struct Renderer {
         if (!lf.empty()) light_distrib.init(lf);
         spatial = strat == 2;
         if (spatial) spatial_init(64);  // create_light_sample_distribution (light_distrib/mod.rs:59-69)
+    }
+
+    // SamplerIntegrator::render (sampler_integrator.rs:243-304).  Tiles are merged in increasing tile index
+    // (= the reference with --nthreads 1; with more threads the reference's merge order is completion order).
+    void render(int tile_size, int tile_part, int tile_parts, int n_threads, Float* out_xyz, Float* out_weight, std::vector<FilmTile>* keep_tiles = nullptr) {
+        preprocess_light_distribution();
         int sb[4]; sample_bounds(sb);
         int ntx = (sb[2] - sb[0] + tile_size - 1) / tile_size, nty = (sb[3] - sb[1] + tile_size - 1) / tile_size;
         int tile_count = ntx * nty;

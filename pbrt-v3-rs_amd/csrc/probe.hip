@@ -1,7 +1,7 @@
 // Test hooks (include/pbrt_hip.h: pbrt_hip_bsdf_probe_batch, pbrt_hip_sampler_value_batch, pbrt_hip_light_probe_batch, pbrt_hip_sphere_light_probe_batch, pbrt_hip_raysort_probe, pbrt_hip_texture_probe_batch,
-// pbrt_hip_bump_probe_batch, pbrt_hip_traverse_probe, pbrt_hip_surface_probe_batch): the device's BSDF, sampler, light, texture and hit-to-interaction code, the ray binning between wavefront rounds and the
-// traversal kernel's queue on explicit inputs.
-// Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h, shading_diff.h); no formula lives here.
+// pbrt_hip_bump_probe_batch, pbrt_hip_traverse_probe, pbrt_hip_surface_probe_batch, pbrt_hip_spatial_probe_begin / _batch / _voxel): the device's BSDF, sampler, light, texture and hit-to-interaction code,
+// the spatial light distribution, the ray binning between wavefront rounds and the traversal kernel's queue on explicit inputs.
+// Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h, shading_diff.h, spatial.h); no formula lives here.
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
 #include "pt_device.h"
@@ -10,6 +10,7 @@
 #include "texture.h"
 #include "sphere_light.h"
 #include "shading_diff.h"
+#include "spatial.h"
 #include "film_plan.h"
 #include <cstring>
 #include <vector>
@@ -284,6 +285,26 @@ __global__ __launch_bounds__(256) void film_probe_fill_kernel(uint32_t band_px, 
     phfilm::mark_rounded_up(px_rounded, pix, xy.x, xy.y, px, py);
 }
 
+// The spatial light distribution on explicit points (spatial.h).  The claim pass: spatial_voxel_of + spatial_claim as spatial_mark_kernel pairs them, the voxel written out as
+// lookup's three coordinates (v = (x * nv[1] + y) * nv[2] + z taken apart as spatial_compute_kernel does).  Between the two runs the render's own spatial_compute_kernel.
+__global__ __launch_bounds__(256) void spatial_probe_mark_kernel(SpatialRec sr, uint32_t n, const float* p_in, int32_t* out_pi) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t v = spatial_voxel_of(sr, ld3(p_in + 3 * (size_t)i));
+        spatial_claim(sr, v);
+        int32_t* o = out_pi + 3 * (size_t)i;
+        o[2] = (int32_t)(v % (uint32_t)sr.nv[2]);
+        o[1] = (int32_t)((v / (uint32_t)sr.nv[2]) % (uint32_t)sr.nv[1]);
+        o[0] = (int32_t)(v / ((uint32_t)sr.nv[2] * (uint32_t)sr.nv[1]));
+    }
+}
+// The pick: spatial_pick_light as shade_kernel calls it in the rows compiled for the spatial distribution; sr.enabled = 0 reads the scene-wide table (strategies 0 and 1)
+__global__ __launch_bounds__(256) void spatial_probe_pick_kernel(DeviceScene sc, SpatialRec sr, uint32_t n, const float* p_in, const float* u_in, uint32_t* out_light, float* out_pdf) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const LightPick pick = spatial_pick_light<true>(sc, sr, ld3(p_in + 3 * (size_t)i), u_in[i]);
+        out_light[i] = pick.light_num; out_pdf[i] = pick.pdf;
+    }
+}
+
 }  // namespace ph
 
 using namespace phost;
@@ -483,6 +504,105 @@ int pbrt_hip_sphere_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, u
     PH_CHECK(s, hipGetLastError());
     PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
     PH_CHECK(s, hipStreamSynchronize(s->stream));
+    return PBRT_HIP_OK;
+    });
+}
+
+namespace {
+// what the three spatial probe calls refuse alike; a scene the path integrator refuses (refuse_sphere_lights) has no distribution pass either
+int spatial_probe_refusals(PbrtHipScene* s, const char* who, size_t min_lights) {
+    const std::string w(who);
+    if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, w + ": build_accel first (the world bound comes from the tree)");
+    if (s->lights.size() < min_lights)
+        return set_err(s, PBRT_HIP_ERR_STATE, w + (min_lights > 1 ? ": fewer than two lights (a render builds no voxel tables for such a scene: light_distrib/mod.rs:59-64)" : ": the scene holds no light"));
+    if (s->sphere_lights != 0 && !s->path_sphere_lights)
+        return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, w + ": the scene holds a sphere light (pbrt_hip_add_sphere_light), which the path integrator samples only after pbrt_hip_set_path_sphere_lights");
+    return PBRT_HIP_OK;
+}
+}  // namespace
+
+int pbrt_hip_spatial_probe_begin(PbrtHipScene* s, int out_nv[3], uint32_t* out_capacity) {
+    return ph_guard(s, "pbrt_hip_spatial_probe_begin", [&]() -> int {
+    if (!s || !out_nv || !out_capacity) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "spatial_probe_begin: null argument");
+    int rc;
+    if ((rc = spatial_probe_refusals(s, "spatial_probe_begin", 2))) return rc;
+    PH_CHECK(s, hipSetDevice(s->device));
+    if ((rc = upload_scene(s))) return rc;
+    ph::SpatialRec sr;
+    if ((rc = spatial_probe_begin(s, &sr))) return rc;
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    for (int i = 0; i < 3; i++) out_nv[i] = sr.nv[i];
+    *out_capacity = sr.capacity;
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_spatial_probe_batch(PbrtHipScene* s, uint64_t n, const float* p, const float* u, int strategy, int32_t* out_pi, uint32_t* out_light, float* out_pick_pdf, uint32_t out_counters[4]) {
+    return ph_guard(s, "pbrt_hip_spatial_probe_batch", [&]() -> int {
+    if (!s || (n && (!p || !u || !out_light || !out_pick_pdf || (strategy == 2 && !out_pi)))) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "spatial_probe_batch: null argument");
+    if (strategy < 0 || strategy > 2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "spatial_probe_batch: strategy must be 0 (uniform), 1 (power) or 2 (spatial)");
+    if (n > 0xFFFFFFFFull) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "spatial_probe_batch: too many points");
+    int rc;
+    if ((rc = spatial_probe_refusals(s, "spatial_probe_batch", 1))) return rc;
+    PH_CHECK(s, hipSetDevice(s->device));
+    if ((rc = upload_scene(s))) return rc;
+    if ((rc = upload_light_distribution(s, strategy == 2 ? 0 : strategy))) return rc;   // as render_tiles does
+    ph::SpatialRec sr{};
+    if (strategy == 2 && (rc = spatial_probe_tables(s, &sr))) return rc;
+    if (strategy == 2 && sr.stride != 2 * s->lights.size() + 2)   // (a slot holds func[n], cdf[n + 1], func_int of the lights there were at _begin)
+        return set_err(s, PBRT_HIP_ERR_STATE, "spatial_probe_batch: the scene's lights changed since pbrt_hip_spatial_probe_begin; call it again");
+    uint32_t ctr[4] = {0, 0, 0, 0};
+    if (n) {
+        const size_t o_p = 0, o_u = o_p + up256(n * 12), o_pi = o_u + up256(n * 4), o_l = o_pi + up256(n * 12), o_pdf = o_l + up256(n * 4), total = o_pdf + up256(n * 4);
+        Scratch sx;
+        PH_CHECK(s, hipMalloc(&sx.p, total));
+        char* d = static_cast<char*>(sx.p);
+        PH_CHECK(s, hipMemcpyAsync(d + o_p, p, n * 12, hipMemcpyHostToDevice, s->stream));
+        PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 4, hipMemcpyHostToDevice, s->stream));
+        const dim3 grid((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)), block(256);
+        if (strategy == 2) {
+            hipLaunchKernelGGL(ph::spatial_probe_mark_kernel, grid, block, 0, s->stream, sr, (uint32_t)n, (const float*)(d + o_p), (int32_t*)(d + o_pi));
+            PH_CHECK(s, hipGetLastError());
+            spatial_probe_compute(s, sr);
+            PH_CHECK(s, hipGetLastError());
+        }
+        hipLaunchKernelGGL(ph::spatial_probe_pick_kernel, grid, block, 0, s->stream, s->ds, sr, (uint32_t)n, (const float*)(d + o_p), (const float*)(d + o_u), (uint32_t*)(d + o_l),
+                           (float*)(d + o_pdf));
+        PH_CHECK(s, hipGetLastError());
+        if (strategy == 2) PH_CHECK(s, hipMemcpyAsync(out_pi, d + o_pi, n * 12, hipMemcpyDeviceToHost, s->stream));
+        PH_CHECK(s, hipMemcpyAsync(out_light, d + o_l, n * 4, hipMemcpyDeviceToHost, s->stream));
+        PH_CHECK(s, hipMemcpyAsync(out_pick_pdf, d + o_pdf, n * 4, hipMemcpyDeviceToHost, s->stream));
+        PH_CHECK(s, hipStreamSynchronize(s->stream));
+    }
+    if (strategy == 2) PH_CHECK(s, hipMemcpy(ctr, sr.counters, sizeof ctr, hipMemcpyDeviceToHost));
+    if (out_counters) std::memcpy(out_counters, ctr, sizeof ctr);
+    if (ctr[ph::SP_OVERFLOW])
+        return set_err(s, PBRT_HIP_ERR_OOM, "spatial_probe_batch: SpatialLightDistribution pool exhausted (" + std::to_string(ctr[ph::SP_CLAIMED]) + " voxels x " + std::to_string(s->lights.size()) + " lights)");
+    return PBRT_HIP_OK;
+    });
+}
+
+int pbrt_hip_spatial_probe_voxel(PbrtHipScene* s, const int pi[3], float* func, float* cdf, float* func_int) {
+    return ph_guard(s, "pbrt_hip_spatial_probe_voxel", [&]() -> int {
+    if (!s || !pi || !func || !cdf || !func_int) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "spatial_probe_voxel: null argument");
+    ph::SpatialRec sr{};
+    int rc;
+    if ((rc = spatial_probe_tables(s, &sr))) return rc;
+    if (sr.stride != 2 * s->lights.size() + 2)
+        return set_err(s, PBRT_HIP_ERR_STATE, "spatial_probe_voxel: the scene's lights changed since pbrt_hip_spatial_probe_begin; call it again");
+    for (int i = 0; i < 3; i++)
+        if (pi[i] < 0 || pi[i] >= sr.nv[i]) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "spatial_probe_voxel: voxel outside the grid");
+    PH_CHECK(s, hipSetDevice(s->device));
+    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    const size_t v = ((size_t)pi[0] * (size_t)sr.nv[1] + (size_t)pi[1]) * (size_t)sr.nv[2] + (size_t)pi[2];
+    int32_t slot = -1;
+    PH_CHECK(s, hipMemcpy(&slot, sr.vox_slot + v, 4, hipMemcpyDeviceToHost));
+    if (slot < 0 || (uint32_t)slot >= sr.capacity) return set_err(s, PBRT_HIP_ERR_STATE, "spatial_probe_voxel: no distribution was computed for this voxel");
+    const size_t n = s->lights.size();
+    const float* base = sr.pool + (size_t)slot * sr.stride;
+    PH_CHECK(s, hipMemcpy(func, base, n * 4, hipMemcpyDeviceToHost));
+    PH_CHECK(s, hipMemcpy(cdf, base + n, (n + 1) * 4, hipMemcpyDeviceToHost));
+    PH_CHECK(s, hipMemcpy(func_int, base + 2 * n + 1, 4, hipMemcpyDeviceToHost));
     return PBRT_HIP_OK;
     });
 }

@@ -9,7 +9,7 @@
 #include "scene_types.h"
 #include "shade_shapes.h"
 #include <hip/hip_runtime.h>
-namespace ph { struct TravParams; }
+namespace ph { struct TravParams; struct SpatialRec; }
 #include <string>
 #include <vector>
 
@@ -189,6 +189,11 @@ int render_direct_tiles(PbrtHipScene* s, int strategy, int max_depth, const int 
 size_t direct_chunk_bytes_per_sample(uint32_t n_frames);
 // ORs the voxels whose light distribution the context's last spatial render filled into `touched` (one byte per voxel, sized on first use); *count = voxels set so far
 int spatial_voxels_touched(PbrtHipScene* s, std::vector<uint8_t>& touched, uint64_t* count);
+// the spatial light distribution on explicit points (probe.hip: pbrt_hip_spatial_probe_*).  _begin: setup_spatial, as a strategy-2 render's bind step calls it; the record is kept with the
+// workspace until the next render resets the tables.  _tables: that record (ERR_STATE without one).  _compute: the distribution pass a render of this scene launches.
+int spatial_probe_begin(PbrtHipScene* s, ph::SpatialRec* out);
+int spatial_probe_tables(PbrtHipScene* s, ph::SpatialRec* out);
+void spatial_probe_compute(PbrtHipScene* s, const ph::SpatialRec& sr);
 // multi.hip
 int render_path_multi(PbrtHipScene* s, int max_depth, float rr_threshold, int light_strategy, const int pixel_bounds[4], int tile_size, int tile_part, int tile_parts,
                       float* out_xyz, float* out_weight, PbrtHipStats* out_stats);

@@ -49,6 +49,43 @@ PH_DEV uint32_t spatial_voxel_of(const SpatialRec& sr, f3 p) {
     return (uint32_t)((x * sr.nv[1] + y) * sr.nv[2] + z);
 }
 
+// lookup's first toucher (:183-236): the path that finds voxel v empty claims the next pool slot for it; a claim past the pool's end raises the flag the render call fails on
+PH_DEV void spatial_claim(const SpatialRec& sr, uint32_t v) {
+    if (sr.vox_slot[v] == -1 && atomicCAS(&sr.vox_slot[v], -1, -2) == -1) {
+        const uint32_t slot = atomicAdd(&sr.counters[SP_CLAIMED], 1u);
+        if (slot < sr.capacity) sr.new_list[slot] = v;
+        else sr.counters[SP_OVERFLOW] = 1u;
+    }
+}
+
+// uniform_sample_one_light's pick (integrator/common.rs:104-113): light_distribution.lookup(&isect.hit.p) (path.rs:156-157), then Distribution1D::sample_discrete on it.
+// SPATIAL: the kernel is one of those compiled for the spatial distribution (shade_shapes.h); without it, or with sr.enabled off, the scene-wide tables are read.
+// sample_discrete: with a single light the CDF is {0, 1} and the answer is 0 for every sample in [0,1): keeping that case wave-uniform lets the light record be fetched with scalar loads.
+// The text is a macro that declares `light_num` — the one name it leaves behind; its helpers live in a block of their own — and assigns `pick_pdf` in the scope it is expanded in (a statement: no semicolon after it): shade_kernel expands it where the lines stood, spatial_pick_light below is
+// the same text as a function, for callers outside the render kernels.  (As a function called from shade_kernel the lines are inlined only after the kernel's first simplification
+// passes, which leaves four of the shade kernels with another block order and the headline row, ShadeRowSky, with two more spilled SGPRs.)
+#define PH_SPATIAL_PICK_LIGHT(SPATIAL, sc, sr, p, sample, light_num, pick_pdf)                                                              \
+    uint32_t light_num;                                                                                                                     \
+    {                                                                                                                                       \
+        const float* ld_func = (sc).ld_func; const float* ld_cdf = (sc).ld_cdf; float ld_func_int = (sc).ld_func_int;                       \
+        if ((SPATIAL) && (sr).enabled) {  /* light_distribution.lookup(&isect.hit.p) (path.rs:156-157) */                                  \
+            const int32_t slot = (sr).vox_slot[spatial_voxel_of((sr), (p))];                                                                \
+            if (slot >= 0) {                                                                                                                \
+                ld_func = (sr).pool + (size_t)slot * (sr).stride;                                                                           \
+                ld_cdf = ld_func + (sc).n_lights; ld_func_int = ld_cdf[(sc).n_lights + 1];                                                  \
+            } else ld_func_int = 0.0f;  /* pool exhausted: the render call fails (ERR_OOM), nothing is returned */                          \
+        }                                                                                                                                   \
+        light_num = ((sc).n_lights == 1) ? 0u : find_interval_cdf(ld_cdf, (sc).n_lights + 1, (sample));                                     \
+        pick_pdf = ld_func_int > 0.0f ? ph_div(ld_func[light_num], ld_func_int * (float)(sc).n_lights) : 0.0f;                              \
+    }
+struct LightPick { uint32_t light_num; float pdf; };
+template <bool SPATIAL>
+PH_DEV LightPick spatial_pick_light(const DeviceScene& sc, const SpatialRec& sr, f3 p, float sample) {
+    float pick_pdf;
+    PH_SPATIAL_PICK_LIGHT(SPATIAL, sc, sr, p, sample, light_num, pick_pdf)
+    return LightPick{light_num, pick_pdf};
+}
+
 #define PH_SPATIAL_BLOCK 256
 #define PH_SPATIAL_CHUNK 2048
 

@@ -163,12 +163,7 @@ __global__ __launch_bounds__(256) void spatial_mark_kernel(DeviceScene sc, WfPar
         if (inst != 0u && !(sc.instances[inst - 1u].flags & PH_INST_IDENTITY)) {  // world-space p of an instanced hit (make_surface_hit_any)
             f3 pe; p = xf_point_abs_err(sc.instances[inst - 1u].i2w, p, mk3(0.0f, 0.0f, 0.0f), pe);
         }
-        const uint32_t v = spatial_voxel_of(sr, p);
-        if (sr.vox_slot[v] == -1 && atomicCAS(&sr.vox_slot[v], -1, -2) == -1) {
-            const uint32_t slot = atomicAdd(&sr.counters[SP_CLAIMED], 1u);
-            if (slot < sr.capacity) sr.new_list[slot] = v;
-            else sr.counters[SP_OVERFLOW] = 1u;
-        }
+        spatial_claim(sr, spatial_voxel_of(sr, p));
     }
 }
 
@@ -507,18 +502,7 @@ __global__ __launch_bounds__(PH_SHADE_BLOCK) PH_SHADE_ATTR void shade_kernel(Dev
                             if (sc.n_lights > 0) {
                                 PHC_BEGIN(4);
                                 const float sample = s_u[0][tid]; c = 1;
-                                // sample_discrete; with a single light the CDF is {0, 1} and the answer is 0 for every sample in [0,1):
-                                // keeping that case wave-uniform lets the light record be fetched with scalar loads
-                                const float* ld_func = sc.ld_func; const float* ld_cdf = sc.ld_cdf; float ld_func_int = sc.ld_func_int;
-                                if (Row::spatial && w.spatial.enabled) {  // light_distribution.lookup(&isect.hit.p) (path.rs:156-157)
-                                    const int32_t slot = w.spatial.vox_slot[spatial_voxel_of(w.spatial, si.p)];
-                                    if (slot >= 0) {
-                                        ld_func = w.spatial.pool + (size_t)slot * w.spatial.stride;
-                                        ld_cdf = ld_func + sc.n_lights; ld_func_int = ld_cdf[sc.n_lights + 1];
-                                    } else ld_func_int = 0.0f;  // pool exhausted: the render call fails (ERR_OOM), nothing is returned
-                                }
-                                const uint32_t light_num = (sc.n_lights == 1) ? 0u : find_interval_cdf(ld_cdf, sc.n_lights + 1, sample);
-                                pick_pdf = ld_func_int > 0.0f ? ph_div(ld_func[light_num], ld_func_int * (float)sc.n_lights) : 0.0f;
+                                PH_SPATIAL_PICK_LIGHT(Row::spatial, sc, w.spatial, si.p, sample, light_num, pick_pdf)  // lookup + sample_discrete: declares light_num (spatial.h)
                                 PHC_END(4);
                                 if (pick_pdf != 0.0f) {
                                     const LightRec& light = sc.lights[light_num];
@@ -826,6 +810,7 @@ struct Wavefront {
     DevBuf d_order, d_sort_bins, d_heads, d_keys_cl, d_keys_sh;  // ray binning between rounds (raysort.h), per-XCD queue heads
     DevBuf d_morder, d_mkeys, d_mbins;  // shade-side work queues (matsort.h)
     size_t n_vox = 0;   // voxels of the last spatial render's table (d_vox_slot)
+    ph::SpatialRec probe_sr{}; bool probe_live = false;   // the tables pbrt_hip_spatial_probe_begin set up, until a render sets up its own
     std::vector<hipEvent_t> events;
     // The buffers that grow with the chunk, with their bytes per path (chunk_plan.h): 463 B, 591 B with a texture pass.  Two closest-hit ray queues of 2B rays, one hit queue of 2B,
     // the path state read from one half and written to the other (WfParams).  The shade-side queues count in the estimate of every scene, as they always have, though a scene of
@@ -961,6 +946,7 @@ static int refuse_sphere_lights(PbrtHipScene* s) {
 // voxel distributions is inside the timed render here too).
 static int setup_spatial(PbrtHipScene* s, ph::SpatialRec& sr) {
     Wavefront& w = *s->wf;
+    w.probe_live = false;
     const size_t n_lights = s->lights.size();
     float diag[3];
     for (int i = 0; i < 3; i++) { sr.lo[i] = s->bvh.root_lo[i]; sr.hi[i] = s->bvh.root_hi[i]; diag[i] = sr.hi[i] - sr.lo[i]; }
@@ -1021,6 +1007,24 @@ static void launch_shade_sphere_lights(PbrtHipScene* s, uint32_t blocks, const p
 static void launch_spatial_compute(PbrtHipScene* s, bool sphere_lights, const ph::SpatialRec& sr) {
     if (sphere_lights) hipLaunchKernelGGL(ph::spatial_compute_kernel<true>, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, sr);
     else hipLaunchKernelGGL(ph::spatial_compute_kernel<false>, dim3(1024), dim3(PH_SPATIAL_BLOCK), 0, s->stream, s->ds, sr);
+}
+// The same two steps for the probe (scene_host.h): the tables as bind_path_frame sets them up, the distribution pass as run_chunk launches it for this scene.
+int spatial_probe_begin(PbrtHipScene* s, ph::SpatialRec* out) {
+    if (!s->wf) s->wf = new Wavefront();
+    ph::SpatialRec sr{};
+    int rc;
+    if ((rc = setup_spatial(s, sr))) return rc;
+    s->wf->probe_sr = sr; s->wf->probe_live = true;
+    *out = sr;
+    return PBRT_HIP_OK;
+}
+int spatial_probe_tables(PbrtHipScene* s, ph::SpatialRec* out) {
+    if (!s->wf || !s->wf->probe_live) return set_err(s, PBRT_HIP_ERR_STATE, "spatial_probe: pbrt_hip_spatial_probe_begin first (a render resets the tables)");
+    *out = s->wf->probe_sr;
+    return PBRT_HIP_OK;
+}
+void spatial_probe_compute(PbrtHipScene* s, const ph::SpatialRec& sr) {
+    launch_spatial_compute(s, (s->sphere_lights != 0 && s->path_sphere_lights) || s->quadric_lights != 0, sr);
 }
 // (the launchers of the table's two anchors are what instantiates them: compiled with the others, picked by nothing)
 template <class V> static void launch_tex_variant(PbrtHipScene* s, uint32_t blocks, const ph::WfParams& wp, int it) {

@@ -173,6 +173,9 @@ class Binding:
             "bump_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp]),
             "set_path_sphere_lights": (C.c_int, [vp, C.c_int]),
             "sphere_light_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, fp, fp, fp, fp]),
+            "spatial_probe_begin": (C.c_int, [vp, ip, u32p]),
+            "spatial_probe_batch": (C.c_int, [vp, C.c_uint64, fp, fp, C.c_int, C.POINTER(C.c_int32), u32p, fp, u32p]),
+            "spatial_probe_voxel": (C.c_int, [vp, ip, fp, fp, fp]),
             "add_curve": (C.c_int, [vp, fp, fp, C.c_int, fp, fp, fp, C.c_int, C.c_uint32, C.c_uint32]),
             "curve_probe_batch": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint64, vp, fp]),
             "surface_probe_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint64, vp, vp, fp, fp]),
@@ -816,6 +819,32 @@ class Scene:
         out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
         self._chk(self.b.fn("sphere_light_probe_batch")(self.h, light, op, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
         return out
+
+    def spatial_probe_begin(self):
+        """Set the spatial light distribution's tables up as a light_strategy=2 render does (pbrt_hip_spatial_probe_begin) -> ((nx, ny, nz), pool capacity in voxels)."""
+        nv = np.zeros(3, np.int32); cap = np.zeros(1, np.uint32)
+        self._chk(self.b.fn("spatial_probe_begin")(self.h, _ptr(nv, C.c_int), _ptr(cap, C.c_uint32)))
+        return (int(nv[0]), int(nv[1]), int(nv[2])), int(cap[0])
+
+    def spatial_probe_batch(self, p, u, strategy=2):
+        """The light pick at explicit points (pbrt_hip_spatial_probe_batch): p (n,3), u (n,).  strategy 2: claim pass, distribution pass and pick on the tables of
+        spatial_probe_begin, which stay between calls; 0 / 1: the pick on the scene-wide uniform / power table.
+        Returns (pi (n,3) int32 — zeros under 0 / 1 —, light (n,) uint32, pick_pdf (n,) float32, counters (4,) uint32 = claimed, computed, pool-exhausted flag, blocks)."""
+        p = _f32(p, (-1, 3)); n = len(p)
+        u = _f32(u, (-1,))
+        assert len(u) == n
+        pi = np.zeros((n, 3), np.int32); light = np.zeros(n, np.uint32); pdf = np.zeros(n, np.float32); ctr = np.zeros(4, np.uint32)
+        self._chk(self.b.fn("spatial_probe_batch")(self.h, n, _ptr(p, C.c_float), _ptr(u, C.c_float), strategy, _ptr(pi, C.c_int32), _ptr(light, C.c_uint32), _ptr(pdf, C.c_float),
+                                                   _ptr(ctr, C.c_uint32)))
+        return pi, light, pdf, ctr
+
+    def spatial_probe_voxel(self, pi, n_lights):
+        """(func (n_lights,), cdf (n_lights + 1,), func_int) of a voxel a spatial_probe_batch computed (pbrt_hip_spatial_probe_voxel); n_lights: the scene's number of lights."""
+        n = int(n_lights)
+        pi = np.ascontiguousarray(pi, np.int32)
+        func = np.zeros(n, np.float32); cdf = np.zeros(n + 1, np.float32); fi = np.zeros(1, np.float32)
+        self._chk(self.b.fn("spatial_probe_voxel")(self.h, _ptr(pi, C.c_int), _ptr(func, C.c_float), _ptr(cdf, C.c_float), _ptr(fi, C.c_float)))
+        return func, cdf, fi[0]
 
     SURFACE_PROBE_AUX, SURFACE_PROBE_STRIDE = 48, 40
 

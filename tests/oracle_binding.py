@@ -61,6 +61,7 @@ def oracle_binding():
         L.oracle_bsdf_probe.argtypes = [vp, C.c_uint32, C.c_int, fp, fp, fp, C.c_int, fp]
         L.oracle_spatial_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.oracle_spatial_voxel.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.oracle_spatial_lookup_batch.argtypes = [vp, C.c_uint64, fp, fp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), fp, C.POINTER(C.c_int)]
         L.oracle_texture_probe_work.argtypes = [vp, C.c_uint32, C.c_uint64, fp, C.POINTER(C.c_uint64)]
         L.oracle_ray_stats_batch.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
         _binding = b
@@ -159,6 +160,19 @@ class OracleScene(pbrt_hip.Scene):
         self._chk(self.b.lib.oracle_spatial_voxel(self.h, pi.ctypes.data_as(C.POINTER(C.c_int)), func.ctypes.data_as(C.POINTER(C.c_float)),
                                                  cdf.ctypes.data_as(C.POINTER(C.c_float)), C.byref(fi)))
         return func, cdf, fi.value
+
+    def spatial_lookup_batch(self, p, u, strategy=2):
+        """uniform_sample_one_light's pick at explicit points (oracle_spatial_lookup_batch): p (n,3), u (n,).  strategy 2: lookup's voxel, compute_distribution (once per voxel
+        within the call), sample_discrete(u); 0 / 1: sample_discrete on the uniform / power distribution.
+        Returns (pi (n,3) int32 — zeros under 0 / 1 —, light (n,) uint32, pick_pdf (n,) float32, voxel resolution (3,) — zeros under 0 / 1)."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3); n = len(p)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1)
+        assert len(u) == n
+        pi = np.zeros((n, 3), np.int32); light = np.zeros(n, np.uint32); pdf = np.zeros(n, np.float32); nv = np.zeros(3, np.int32)
+        fp = C.POINTER(C.c_float)
+        self._chk(self.b.lib.oracle_spatial_lookup_batch(self.h, n, p.ctypes.data_as(fp), u.ctypes.data_as(fp), strategy, pi.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        light.ctypes.data_as(C.POINTER(C.c_uint32)), pdf.ctypes.data_as(fp), nv.ctypes.data_as(C.POINTER(C.c_int))))
+        return pi, light, pdf, (int(nv[0]), int(nv[1]), int(nv[2]))
 
     def record_rays(self, cap):
         self.b.lib.oracle_record_rays(self.h, cap)
