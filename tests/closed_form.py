@@ -1,9 +1,14 @@
 """Closed-form radiance for PathIntegrator::li (integrators/src/path.rs:103-284): scene builders, float64 expectations written from
 the physics with numpy alone (they never call the oracle or the library), and the statistical check the closed-form tests share.
 
-Every builder takes a pbrt_hip.Scene or an OracleScene.  The scenes are chosen so that every pixel has the same expected value.  What a mean cannot see: `eta_scale` (path.rs:192-203)
-and the bounce at which Russian roulette starts (`bounces > 3`) only steer RR's termination probability, whose `1/(1-q)` weight
-keeps the mean; a mistake in either changes the variance, not the expectation, and no test here pins it.
+Every builder takes a pbrt_hip.Scene or an OracleScene.  The scenes are chosen so that every pixel has the same expected value.  What a mean cannot see: `eta_scale` (path.rs:192-203),
+the bounce at which Russian roulette starts (`bounces > 3`), the value of q (the 0.05 floor, the max component, `<` against rr_threshold)
+and the order in which a path consumes sampler dimensions only steer which samples die and what the survivors weigh; the `1/(1-q)`
+weight keeps the mean.  Those are pinned sample by sample by tests/li_replay.py, a float64 replay of li on specular chains, in
+test_closed_form_li.py::test_li_replay (the oracle) and test_closed_form_li_gpu.py::test_li_replay_on_device: eta_scale and the start of RR
+by the stack_* cases, eta_scale staying out of reflections and the RR dimension being consumed only when RR runs by the walk_* cases,
+the floor by stack_eta1.1_* and corridor, `<` by corridor_kr1, BSDF::eta = 1 for glass (glass.rs:109) and for uber with opacity < 1
+(uber.rs:133) by glass_* and sheet_*.
 """
 import ctypes as C
 import math
@@ -312,14 +317,17 @@ def corridor_rays(host, Scene, kr, res, angle_deg=50.0):
 
 def mirror_rr_survival(kr, N, rr_threshold=1.0):
     """Probability that Russian roulette lets a path of N mirror reflections reach the sky: after the vertex at bounces = b
-    (beta = kr^(b+1), eta_scale = 1) RR runs if max(beta) < rr_threshold and b > 3, and stops the path with q = max(0.05, 1 - max(beta)).
+    (eta_scale = 1) RR runs if max(beta) < rr_threshold and b > 3, and stops the path with q = max(0.05, 1 - max(beta)).  beta is kr^(b+1)
+    over the 1 - q of every RR the path has survived: the weights already applied feed the next q.
     The mean is kept by the 1/(1-q) weight; survival * E is the wrong answer where that weight is dropped."""
     m = float(np.max(kr))
-    p = 1.0
-    for b in range(4, N):
-        beta = m ** (b + 1)
-        if beta < rr_threshold:
-            p *= 1.0 - max(0.05, 1.0 - beta)
+    p = 1.0; beta = 1.0
+    for b in range(N):
+        beta *= m
+        if b > 3 and beta < rr_threshold:
+            q = max(0.05, 1.0 - beta)
+            p *= 1.0 - q
+            beta /= 1.0 - q
     return p
 
 

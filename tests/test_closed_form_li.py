@@ -3,11 +3,15 @@
 The bit-exact suite holds the device to the oracle; these tests hold the oracle to physics written independently in float64, so
 a mistake both sides share (depth cut-off, RR weight, MIS halves, emission after specular bounces, the (eta_i/eta_t)^2 radiance
 factor, the null-BSDF skip, the light-choice pdf) turns a test red.  Every statistical case also checks that it could tell the
-right answer from the plausible wrong ones (closed_form.assert_mean)."""
+right answer from the plausible wrong ones (closed_form.assert_mean).
+
+What a mean cannot see — eta_scale, the bounce at which Russian roulette starts, the value of q, the order in which a path consumes
+sampler dimensions — is held sample by sample by the float64 replay of tests/li_replay.py (section F below)."""
 import numpy as np
 import pytest
 
 import closed_form as cf
+import li_replay as lr
 import pbrt_hip
 from oracle_binding import OracleScene
 
@@ -124,7 +128,8 @@ def test_null_stack(host, K):
 @pytest.mark.parametrize("tilt", [0.0, 40.0])
 @pytest.mark.parametrize("D", [1, 2, 3])
 def test_glass_slab(host, D, tilt):
-    """Form D: E = Le sum_{k=1..D} P_k (closed_form.glass_slab_expect).  eta_scale only steers RR here, not the mean."""
+    """Form D: E = Le sum_{k=1..D} P_k (closed_form.glass_slab_expect).  RR keeps the mean; eta_scale does not even move here: glass builds
+    its BSDF without an eta (glass.rs:109), so BSDF::eta is 1 (test_li_replay's glass cases pin that per sample)."""
     rgb, _, _ = render(cf.glass_slab(host, LE, tilt_deg=tilt, res=24, spp=32), max_depth=D)
     E = cf.glass_slab_expect(LE, D, tilt_deg=tilt)
     wrongs = {"depth D-1": cf.glass_slab_expect(LE, D - 1, tilt_deg=tilt), "depth D+1": cf.glass_slab_expect(LE, D + 1, tilt_deg=tilt),
@@ -196,6 +201,47 @@ def test_mirror_corridor_rr_groups(host):
         En = E[sel][0]
         cf.assert_mean(rgb[sel], En, wrongs={"RR weight 1/(1-q) dropped": En * cf.mirror_rr_survival(KR, n)}, se_target=0.01,
                        label=f"mirror corridor N={n} ({sel.sum()} pixels)")
+
+
+# ---- F: the replay, sample by sample -------------------------------------------------------------------------------------
+
+def test_replay_against_closed_form():
+    """The replay itself, with no renderer and no sampler: RR off, every sample of a Kt-only stack crosses its 8 interfaces and carries
+    Le (kt (1 - F))^8 (the 1/eta^2 and eta^2 of each slab cancel); with a max depth of 7 the depth cut-off leaves nothing."""
+    faces = lr.slabs([lr.uber(kt=lr.KT, eta=1.5)] * 4)
+    u = np.full((5, 5 + 3 * 8), 0.5)
+    r = lr.replay(faces, u, np.ones(5), LE, 8, rr_threshold=0.0)
+    F = cf.fresnel_dielectric(1.0, 1.5)
+    np.testing.assert_allclose(r["L"], np.broadcast_to(np.asarray(LE) * (np.asarray(lr.KT, np.float32).astype(np.float64) * (1 - F)) ** 8, (5, 3)), rtol=1e-12)
+    assert (r["fate"] == lr.ESCAPED).all() and (r["vertices"] == 8).all() and not r["excluded"].any()
+    r = lr.replay(faces, u, np.ones(5), LE, 7, rr_threshold=0.0)
+    assert (r["fate"] == lr.DEPTH).all() and not r["L"].any()
+
+
+@pytest.mark.parametrize("case", lr.CASES, ids=repr)
+def test_li_replay(host, case):
+    """Every pixel of the oracle's film equals the float64 replay of its samples (li_replay.py): zeros exactly, the rest within
+    lr.TOL.  Before the oracle renders, the case proves from the replay alone that at most 0.5 % of its samples lie within 1e-5 of
+    a decision, that samples survive, die by Russian roulette and run longer than 4 vertices (10 % each), and that every misreading
+    of li in case.catches would move at least 10 % of its pixels (li_replay.assert_case_sound)."""
+    s = case.scene(host, OracleScene)
+    inputs = case.inputs(host, s)
+    if case.corridor is not None:    # the rim band of closed_form.mirror_bounces, as in test_mirror_corridor_per_pixel
+        assert inputs[3].mean() > 0.9 and inputs[2].min() >= 5, np.unique(inputs[2], return_counts=True)
+    fig = lr.assert_case_sound(case, inputs, lr.TOL)
+    xyz, wt, st, _ = s.render_path_ex(max_depth=case.max_depth, rr_threshold=case.rr_threshold)
+    assert st.camera_rays == case.res * case.res * case.spp
+    rgb = s.film_to_rgb(xyz, wt)
+    print(f"{case}: relative deviation {lr.deviation(rgb, case.predict(inputs))[0]:.3g}, excluded {fig['excluded']:.4%}, fates {fig['fates']}, "
+          f"longer than 4 vertices {fig['long']:.1%}, power {fig['power']}")
+    lr.assert_film_matches(rgb, case.predict(inputs), lr.TOL, label=str(case))
+
+
+def test_li_replay_cases_cover_every_misreading():
+    """Each misreading the replay can switch on is caught by some case: the floor by the eta 1.1 stacks and the corridor, `<=` by the
+    corridor whose kr is 1, BSDF::eta by the glass stacks and the sheet."""
+    caught = {w for c in lr.CASES for w in c.catches}
+    assert caught == set(lr.WRONGS), set(lr.WRONGS) - caught
 
 
 # ---- Sobol tables: a render beyond the tables given is refused -----------------------------------------------------------

@@ -1,11 +1,13 @@
 """PathIntegrator::li on the device against closed-form radiance (tests/closed_form.py), at sizes the oracle cannot reach: 64 x 64
 tessellated faces (49 152 lights), 512^2 frames, forced chunking, tile parts, the Halton depth limit, the null-skip cap.  Each
-new scene shape is also held bit for bit against the oracle on a small crop."""
+new scene shape is also held bit for bit against the oracle on a small crop.  What a mean cannot see (eta_scale, where RR starts, q, the order of
+the sampler's dimensions) is held sample by sample against the float64 replay of tests/li_replay.py."""
 
 import numpy as np
 import pytest
 
 import closed_form as cf
+import li_replay as lr
 import pbrt_hip
 from oracle_binding import OracleScene, set_libm_mode
 
@@ -181,3 +183,47 @@ def test_new_scene_shapes_bit_exact(host, shape):
     }
     mk, kw = caps[shape]
     assert_crop_bit_exact(mk(), **kw)
+
+
+# ---- the replay, sample by sample (test_closed_form_li.py::test_li_replay proves each case's power on the CPU) --------------------
+
+def _replay_prediction(host, case):
+    s = case.scene(host, pbrt_hip.Scene)
+    inputs = case.inputs(host, s)     # the device's camera rays and the device's sampler_value_batch
+    pred = case.predict(inputs)
+    assert float((pred["excluded"] & inputs[3]).mean()) <= lr.EXCLUSION_CAP
+    return s, pred
+
+
+@pytest.mark.parametrize("case", lr.CASES, ids=repr)
+def test_li_replay_on_device(host, case):
+    """Every pixel of the device's film equals the float64 replay of its samples (zeros exactly, the rest within lr.TOL), and the
+    scene's 8 x 8 crop equals the oracle's bit for bit."""
+    s, pred = _replay_prediction(host, case)
+    xyz, wt, st = s.render_path(max_depth=case.max_depth, rr_threshold=case.rr_threshold)
+    assert st.camera_rays == case.res * case.res * case.spp
+    rgb = s.film_to_rgb(xyz, wt)
+    print(f"{case}: relative deviation {lr.deviation(rgb, pred)[0]:.3g}")
+    lr.assert_film_matches(rgb, pred, lr.TOL, label=str(case))
+    assert_crop_bit_exact(case.capture(host), max_depth=case.max_depth, rr_threshold=case.rr_threshold)
+
+
+@pytest.mark.parametrize("mode", ["chunks", "tile_parts"])
+def test_li_replay_four_materials_through_the_driver(host, mode, monkeypatch):
+    """The stack of four uber materials (four shade-queue keys live in one round) at 4 spp through several path-pool chunks
+    (3 samples per pixel, then 1) and as 3 tile parts summed: the same film, sample for sample."""
+    case = next(c for c in lr.CASES if c.name == "stack_four_materials_spp4")
+    if mode == "chunks":
+        monkeypatch.setenv("PBRT_HIP_MAX_PATHS", str(case.res * case.res * 3))
+    s, pred = _replay_prediction(host, case)
+    kw = dict(max_depth=case.max_depth, rr_threshold=case.rr_threshold)
+    if mode == "tile_parts":
+        xyz = np.zeros((case.res, case.res, 3), np.float32); wt = np.zeros((case.res, case.res), np.float32); rays = 0
+        for p in range(3):
+            x, w, st = s.render_path(tile_part=p, tile_parts=3, **kw)
+            xyz += x; wt += w; rays += st.camera_rays
+    else:
+        xyz, wt, st = s.render_path(**kw)
+        rays = st.camera_rays
+    assert rays == case.res * case.res * case.spp
+    lr.assert_film_matches(s.film_to_rgb(xyz, wt), pred, lr.TOL, label=f"{case} {mode}")
