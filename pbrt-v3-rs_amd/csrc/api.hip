@@ -37,22 +37,19 @@ int ensure_buf(PbrtHipScene* s, DevBuf& b, size_t bytes) {
     return PBRT_HIP_OK;
 }
 
-template <class T> static int upload_vec(PbrtHipScene* s, const std::vector<T>& v, const T** out) {
+template <class T> static int upload_array(PbrtHipScene* s, const T* v, size_t n, const T** out) {
     *out = nullptr;
-    if (v.empty()) return PBRT_HIP_OK;
+    if (n == 0) return PBRT_HIP_OK;
     void* d = nullptr;
-    PH_CHECK(s, hipMalloc(&d, v.size() * sizeof(T)));
+    PH_CHECK(s, hipMalloc(&d, n * sizeof(T)));
     s->owned.push_back(d);
-    PH_CHECK(s, hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s->stream));
+    PH_CHECK(s, hipMemcpyAsync(d, v, n * sizeof(T), hipMemcpyHostToDevice, s->stream));
     *out = reinterpret_cast<const T*>(d);
     return PBRT_HIP_OK;
 }
+template <class T> static int upload_vec(PbrtHipScene* s, const std::vector<T>& v, const T** out) { return upload_array(s, v.data(), v.size(), out); }
 
-void free_tree_dev(PbrtHipScene* s) {
-    if (s->tree_dev_nodes) (void)hipFree(s->tree_dev_nodes);
-    if (s->tree_dev_tris) (void)hipFree(s->tree_dev_tris);
-    s->tree_dev_nodes = s->tree_dev_tris = nullptr; s->tree_dev_n_tris = 0;
-}
+void free_tree_dev(DeviceTree& t) { (void)hipFree(t.nodes); (void)hipFree(t.tris); t = DeviceTree(); }   // (freeing null is no error)
 
 static void free_owned(PbrtHipScene* s) {
     for (void* p : s->owned) (void)hipFree(p);
@@ -102,10 +99,10 @@ int upload_scene(PbrtHipScene* s) {
     DeviceScene& d = s->ds;
     std::memset(&d, 0, sizeof(d));
     int rc;
-    if (s->tree_dev_tris) { d.nodes = reinterpret_cast<const Node64*>(s->tree_dev_nodes); d.tris = reinterpret_cast<const TriRec*>(s->tree_dev_tris); }   // built here, never left
+    if (s->accel_on_device()) { d.nodes = s->accel_nodes(); d.tris = s->accel_records(); }   // built here, never left
     else {
-        if ((rc = upload_vec(s, s->bvh.nodes, &d.nodes))) return rc;
-        if ((rc = upload_vec(s, s->bvh.tris, &d.tris))) return rc;
+        if ((rc = upload_array(s, s->accel_nodes(), s->accel_n_nodes(), &d.nodes))) return rc;
+        if ((rc = upload_array(s, s->accel_records(), s->accel_n_records(), &d.tris))) return rc;
     }
     d.root_ref = s->bvh.root_ref;
     d.n_tris = (uint32_t)(s->idx.size() / 3);
@@ -198,7 +195,7 @@ int upload_scene(PbrtHipScene* s) {
     // a forest whose trees are all single leaves has no interior node at all (d.nodes == nullptr): the records still need their bounds / root / transform
     if (!s->inst_recs.empty() && !s->top_items.empty() && d.tris) {   // instance leaf records + hints (patch_inst_records_kernel)
         const uint32_t n_top = (uint32_t)s->top_items.size();
-        const uint32_t n_nodes = (uint32_t)(s->tree_dev_tris ? s->bvh.interior_nodes : s->bvh.nodes.size());
+        const uint32_t n_nodes = (uint32_t)s->accel_n_nodes();
         void* extra = nullptr;
         PH_CHECK(s, hipMalloc(&extra, (size_t)n_top * 48)); s->owned.push_back(extra);
         hipLaunchKernelGGL(patch_inst_records_kernel, dim3((n_top + 255u) / 256u), dim3(256), 0, s->stream, const_cast<TriRec*>(d.tris), n_top, d.instances, static_cast<float*>(extra));
@@ -361,6 +358,13 @@ int launch_traverse(PbrtHipScene* s, bool anyhit, const void* d_rays, void* d_ou
 
 using namespace phost;
 
+int PbrtHipScene::fetch_leaf_records(std::vector<TriRec>& out) {
+    if (!accel_on_device()) { out = bvh.tris; return PBRT_HIP_OK; }
+    out.resize(accel_n_records());
+    PH_CHECK(this, hipMemcpy(out.data(), accel_records(), out.size() * sizeof(TriRec), hipMemcpyDeviceToHost));
+    return PBRT_HIP_OK;
+}
+
 namespace hm {
 M4 m4_inverse(const M4& a) {
     int indxc[4] = {0, 0, 0, 0}, indxr[4] = {0, 0, 0, 0}, ipiv[4] = {0, 0, 0, 0};
@@ -431,7 +435,7 @@ void pbrt_hip_scene_destroy(PbrtHipScene* s) {
     free_wavefront(s);
     free_whitted(s);
     free_owned(s);
-    free_tree_dev(s);
+    free_tree_dev(s->dev_tree);
     for (DevBuf* b : {&s->d_ld_func, &s->d_ld_cdf, &s->d_counter, &s->d_spill, &s->d_error, &s->d_counts, &s->d_rays_tmp, &s->d_out_tmp})
         if (b->p) (void)hipFree(b->p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -1142,146 +1146,163 @@ int pbrt_hip_set_sobol_tables(PbrtHipScene* s, const uint32_t* m32, size_t n32, 
     });
 }
 
-int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_node) {
-    return ph_guard(s, "pbrt_hip_build_accel", [&]() -> int {
-    if (!s) return PBRT_HIP_ERR_INVALID_ARG;
+}  // extern "C"
+
+// ---- build_accel: one entry behind the three public ones (AccelBuilder, scene_host.h), cut into its steps ----------------------------------------------------------------
+// what no builder takes, before any work; changes nothing but the error text
+static int refuse_accel_build(PbrtHipScene* s, AccelBuilder builder, int split_method) {
     if (split_method == 2) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: splitmethod 'middle' panics in the reference (quirk B6, sah.rs:67-76)");
-    if (!s->quadrics.empty()) {   // before any work
+    if (!s->quadrics.empty()) {
         // Both device builders take quadrics (bvh_device.hip, bvh_sah_device.hip).  pbrt_hip_build_accel_device keeps refusing the SAH tree, an answer older tests pin for split
         // method 0: pbrt_hip_build_accel_device_shapes builds it.
-        if (s->build_on_device && split_method != 1 && !s->build_sah_quadrics_on_device)
+        if (builder == AccelBuilder::Device && split_method != 1)
             return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel_device: the SAH tree of a scene with quadric shapes is built on the device by pbrt_hip_build_accel_device_shapes, or on the host (pbrt_hip_build_accel); the HLBVH tree (1) is built on the device");
         // A leftover with no technical reason: a scene whose object definitions are all unused would build (its definitions are ignored, as in any instanced scene), but two older tests
         // pin this answer.  To be dropped together with their assertions.
         if (!s->objects.empty() && s->instances.empty())
             return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: quadric shapes together with object definitions that no instance uses are not supported (a leftover refusal without a technical reason; instance an object, or drop the definitions)");
         // (object instances and alpha-mask textures on the triangle meshes are traversal's business: the QUADRIC rows of TravShapes)
-        s->prim_quadric.resize(s->idx.size() / 3, 0u);
     }
     // every DiffuseAreaLight belongs to a shape (api/src/lib.rs:783-812 creates them per triangle): one that no add_mesh claimed would be sampled
     // through a primitive that does not exist
     for (size_t i = 0; i < s->lights.size(); i++)
         if (s->lights[i].type == PH_L_AREA && s->lights[i].prim == 0xFFFFFFFFu)
             return set_err(s, PBRT_HIP_ERR_STATE, "build_accel: area light " + std::to_string(i) + " was never attached to a mesh (pbrt_hip_add_mesh first_area_light_id)");
-    // material classes (shade-side sorting key): materials with the same sequence of lobe kinds share a class; at most 7 classes
-    {
-        std::vector<uint64_t> sigs;
-        for (phost::MaterialHost::Item& it : s->mats.items) {
-            MaterialRec& m = it.rec;
-            uint64_t sig = 1;
-            for (const LobeRec& l : it.lobes) sig = sig * 8 + (l.kind + 1);
-            size_t c = 0;
-            while (c < sigs.size() && sigs[c] != sig) c++;
-            if (c == sigs.size()) sigs.push_back(sig);
-            m.sort_class = (uint32_t)std::min<size_t>(c, 6);
-            if (m.none) m.sort_class = 7u;
-        }
+    return PBRT_HIP_OK;
+}
+
+// material classes (shade-side sorting key): materials with the same sequence of lobe kinds share a class; at most 7 classes
+static void assign_material_sort_classes(PbrtHipScene* s) {
+    std::vector<uint64_t> sigs;
+    for (phost::MaterialHost::Item& it : s->mats.items) {
+        MaterialRec& m = it.rec;
+        uint64_t sig = 1;
+        for (const LobeRec& l : it.lobes) sig = sig * 8 + (l.kind + 1);
+        size_t c = 0;
+        while (c < sigs.size() && sigs[c] != sig) c++;
+        if (c == sigs.size()) sigs.push_back(sig);
+        m.sort_class = (uint32_t)std::min<size_t>(c, 6);
+        if (m.none) m.sort_class = 7u;
     }
-    if (s->tree_dev_tris) { PH_CHECK(s, hipSetDevice(s->device)); free_tree_dev(s); }   // a rebuild: the tree an earlier device build left there goes first
+}
+
+// shade-side sorting keys travel in the TriRec: the material's class and its id (scene_types.h)
+static std::vector<uint32_t> triangle_build_flags(const PbrtHipScene* s) {
     std::vector<uint32_t> build_flags(s->tri_flags);
-    for (size_t t = 0; t < build_flags.size(); t++) {   // shade-side sorting keys travel in the TriRec: the material's class and its id (scene_types.h)
+    for (size_t t = 0; t < build_flags.size(); t++) {
         const uint32_t mat = s->meshes[s->tri_mesh[t]].material;
         build_flags[t] |= (s->mats.items[mat].rec.sort_class << PH_TRI_CLASS_SHIFT) | (std::min<uint32_t>(mat, 0xFFFu) << PH_TRI_MAT_SHIFT);
     }
+    return build_flags;
+}
+
+// a builder's answer as the entry's: 0, -1 from a device builder (`e` says what), -2 (the reference's HLBVH assertions), anything else
+static int build_answer(PbrtHipScene* s, int brc, bool on_device, const std::string& e) {
+    if (brc == 0) return PBRT_HIP_OK;
+    if (brc == -1 && on_device) return set_err(s, PBRT_HIP_ERR_DEVICE, "build_accel_device: " + e);
+    if (brc == -2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "build_accel: the reference's HLBVH build asserts on this input (hlbvh.rs:338/356/418)");
+    return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "build_accel: bad arguments");
+}
+
+// the device builders, on one tree (spec, trees null) or a forest: SAH leaves its arrays where it built them (s->dev_tree), HLBVH hands them back in s->bvh (its numbering is the host's)
+static int build_on_device(PbrtHipScene* s, const phost::BuildInput& in, int split_method, int max_prims_in_node, const phost::ForestSpec* spec, std::vector<phost::ForestTreeOut>* trees) {
+    PH_CHECK(s, hipSetDevice(s->device));
+    std::string e;
+    const int brc = split_method == 1 ? phost::build_hlbvh_device(in, max_prims_in_node, s->stream, s->bvh, e, spec, trees)
+                                      : phost::build_sah_device(in, max_prims_in_node, s->stream, s->bvh, e, &s->dev_tree, spec, trees);
+    return build_answer(s, brc, true, e);
+}
+
+// One aggregate per instanced object (make_accelerator at ObjectInstance time, lib.rs:953-971) and the scene's own over its triangles and TransformedPrimitives,
+// in one node array and one TriRec array: [scene | objects] (bvh_build.h).  layout, trees: where each instance's tree went and every tree's root.
+static int build_forest(PbrtHipScene* s, const phost::BuildInput& in, bool on_device, int split_method, int max_prims_in_node, phost::ForestLayout& layout, std::vector<phost::ForestTreeOut>& trees) {
+    if (s->open_object >= 0) return set_err(s, PBRT_HIP_ERR_STATE, "build_accel: an object definition is still open (missing ObjectEnd)");
+    std::vector<uint32_t> tri0(s->objects.size()), tri1(s->objects.size()), inst_object(s->instances.size());
+    std::vector<float> inst_i2w(16 * s->instances.size());
+    for (size_t k = 0; k < s->objects.size(); k++) { tri0[k] = s->objects[k].tri0; tri1[k] = s->objects[k].tri1; }
+    for (size_t k = 0; k < s->instances.size(); k++) { inst_object[k] = s->instances[k].object; std::memcpy(&inst_i2w[16 * k], s->instances[k].i2w, 64); }
+    const phost::InstancedScene isc{tri0.data(), tri1.data(), tri0.size(), inst_object.data(), inst_i2w.data(), inst_object.size(), s->top_items.data(), s->top_items.size()};
+    phost::forest_layout(isc, layout);
+    // bit 30 of a leaf reference is PH_LEAF_INST_HINT in an instanced scene: the forest's records must stay below it (both builders)
+    if (layout.items.size() >= 0x40000000ull) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: an instanced scene may hold at most 2^30 leaf records");
+    if (!on_device) return build_answer(s, phost::build_forest_host(in, isc, layout, split_method, max_prims_in_node, s->bvh, trees), false, "");
+    const phost::ForestSpec spec = layout.spec(isc);
+    return build_on_device(s, in, split_method, max_prims_in_node, &spec, &trees);
+}
+
+// every instance's record, from the root of its object's tree
+static void make_instance_records(PbrtHipScene* s, const phost::ForestLayout& layout, const std::vector<phost::ForestTreeOut>& trees) {
+    for (size_t k = 0; k < s->instances.size(); k++) {
+        const PbrtHipScene::InstanceHost& ih = s->instances[k];
+        const phost::ForestTreeOut& b = trees[layout.inst_tree[k]];
+        InstRec r{};
+        std::memcpy(r.w2i, ih.w2i, 64); std::memcpy(r.i2w, ih.i2w, 64);
+        for (int a = 0; a < 3; a++) { r.lo[a] = b.lo[a]; r.hi[a] = b.hi[a]; }
+        r.root_ref = b.root_ref; r.flags = b.n_items == 1 ? PH_INST_SINGLE : 0u;   // an object with one primitive is used directly, without an aggregate (lib.rs:953-956)
+        bool ident = true;
+        for (int a = 0; a < 16; a++) if (ih.i2w[a] != ((a % 5 == 0) ? 1.0f : 0.0f)) ident = false;
+        if (ident) r.flags |= PH_INST_IDENTITY;
+        s->inst_recs.push_back(r);
+    }
+}
+
+// Light::preprocess: bounding sphere of the world bound (bounds3.rs:196-208; infinite.rs:113-117, distant.rs:54-58)
+static void set_world_sphere(PbrtHipScene* s) {
+    s->world_radius = 1.0f; s->world_center[0] = s->world_center[1] = s->world_center[2] = 0.0f;
+    if (s->bvh.root_ref == PH_INVALID_REF) return;
+    const float* lo = s->bvh.root_lo; const float* hi = s->bvh.root_hi;
+    float c[3];
+    for (int k = 0; k < 3; k++) c[k] = (1.0f - 0.5f) * lo[k] + 0.5f * hi[k];  // lerp(0.5, pmin, pmax) (common.rs:166-175)
+    bool inside = (c[0] >= lo[0] && c[0] <= hi[0]) && (c[1] >= lo[1] && c[1] <= hi[1]) && (c[2] >= lo[2] && c[2] <= hi[2]);
+    float dx = c[0] - hi[0], dy = c[1] - hi[1], dz = c[2] - hi[2];
+    s->world_radius = inside ? std::sqrt(dx * dx + dy * dy + dz * dz) : 0.0f;
+    for (int k = 0; k < 3; k++) s->world_center[k] = c[k];
+}
+
+static int build_accel(PbrtHipScene* s, AccelBuilder builder, int split_method, int max_prims_in_node) {
+    if (int rc = refuse_accel_build(s, builder, split_method)) return rc;
+    assign_material_sort_classes(s);
+    if (s->accel_on_device()) { PH_CHECK(s, hipSetDevice(s->device)); free_tree_dev(s->dev_tree); }   // a rebuild: the tree an earlier device build left there goes first
+    const std::vector<uint32_t> build_flags = triangle_build_flags(s);
     phost::BuildInput in;
     in.P = s->P.data(); in.idx = s->idx.data(); in.n_tris = s->idx.size() / 3; in.tri_flags = build_flags.data(); in.tri_mesh = s->tri_mesh.data();
-    if (!s->quadrics.empty()) { in.prim_quadric = s->prim_quadric.data(); in.quad_bounds = s->quadric_bounds.data(); in.n_quadrics = s->quadrics.size(); }
-    auto fail = [&](int brc) {
-        if (brc == -2) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "build_accel: the reference's HLBVH build asserts on this input (hlbvh.rs:338/356/418)");
-        return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "build_accel: bad arguments");
-    };
+    if (!s->quadrics.empty()) { s->prim_quadric.resize(in.n_tris, 0u); in.prim_quadric = s->prim_quadric.data(); in.quad_bounds = s->quadric_bounds.data(); in.n_quadrics = s->quadrics.size(); }
+    const bool on_device = builder != AccelBuilder::Host;
     s->inst_recs.clear();
     if (s->objects.empty()) {
-        int brc;
-        if (s->build_on_device) {   // pbrt_hip_build_accel_device: the same tree, made by kernels (HLBVH: bvh_device.hip, SAH: bvh_sah_device.hip)
-            PH_CHECK(s, hipSetDevice(s->device));
-            std::string e;
-            if (split_method == 1) brc = phost::build_hlbvh_device(in, max_prims_in_node, s->stream, s->bvh, e);
-            else {
-                brc = phost::build_sah_device(in, max_prims_in_node, s->stream, s->bvh, e, &s->tree_dev_nodes, &s->tree_dev_tris);
-                if (brc == 0 && s->tree_dev_tris) s->tree_dev_n_tris = in.n_tris;
-            }
-            if (brc == -1) return set_err(s, PBRT_HIP_ERR_DEVICE, "build_accel_device: " + e);
-        } else brc = phost::build_bvh(in, split_method, max_prims_in_node, 0, s->bvh);
-        if (brc != 0) return fail(brc);
+        // a scene without object definitions: one tree
+        const int rc = on_device ? build_on_device(s, in, split_method, max_prims_in_node, nullptr, nullptr) : build_answer(s, phost::build_bvh(in, split_method, max_prims_in_node, 0, s->bvh), false, "");
+        if (rc) return rc;
     } else {
-        if (s->open_object >= 0) return set_err(s, PBRT_HIP_ERR_STATE, "build_accel: an object definition is still open (missing ObjectEnd)");
-        // One aggregate per instanced object (make_accelerator at ObjectInstance time, lib.rs:953-971) and the scene's own over its triangles and TransformedPrimitives,
-        // in one node array and one TriRec array: [scene | objects] (bvh_build.h)
-        std::vector<uint32_t> tri0(s->objects.size()), tri1(s->objects.size()), inst_object(s->instances.size());
-        std::vector<float> inst_i2w(16 * s->instances.size());
-        for (size_t k = 0; k < s->objects.size(); k++) { tri0[k] = s->objects[k].tri0; tri1[k] = s->objects[k].tri1; }
-        for (size_t k = 0; k < s->instances.size(); k++) { inst_object[k] = s->instances[k].object; std::memcpy(&inst_i2w[16 * k], s->instances[k].i2w, 64); }
-        const phost::InstancedScene isc{tri0.data(), tri1.data(), tri0.size(), inst_object.data(), inst_i2w.data(), inst_object.size(), s->top_items.data(), s->top_items.size()};
         phost::ForestLayout layout;
-        phost::forest_layout(isc, layout);
-        // bit 30 of a leaf reference is PH_LEAF_INST_HINT in an instanced scene: the forest's records must stay below it (both builders)
-        if (layout.items.size() >= 0x40000000ull) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel: an instanced scene may hold at most 2^30 leaf records");
         std::vector<phost::ForestTreeOut> trees;
-        if (s->build_on_device) {
-            PH_CHECK(s, hipSetDevice(s->device));
-            std::string e;
-            const phost::ForestSpec spec = layout.spec(isc);
-            // SAH leaves the forest where it was built (tree_dev_*); HLBVH hands it back in s->bvh, as it does without instances (the SAH over the treelet roots is the host's)
-            const int brc = split_method == 1 ? phost::build_hlbvh_device(in, max_prims_in_node, s->stream, s->bvh, e, &spec, &trees)
-                                              : phost::build_sah_device(in, max_prims_in_node, s->stream, s->bvh, e, &s->tree_dev_nodes, &s->tree_dev_tris, &spec, &trees);
-            if (brc == -1) return set_err(s, PBRT_HIP_ERR_DEVICE, "build_accel_device: " + e);
-            if (brc != 0) return fail(brc);
-            if (s->tree_dev_tris) s->tree_dev_n_tris = layout.items.size();
-        } else {
-            const int brc = phost::build_forest_host(in, isc, layout, split_method, max_prims_in_node, s->bvh, trees);
-            if (brc != 0) return fail(brc);
-        }
-        for (size_t k = 0; k < s->instances.size(); k++) {
-            const PbrtHipScene::InstanceHost& ih = s->instances[k];
-            const phost::ForestTreeOut& b = trees[layout.inst_tree[k]];
-            InstRec r{};
-            std::memcpy(r.w2i, ih.w2i, 64); std::memcpy(r.i2w, ih.i2w, 64);
-            for (int a = 0; a < 3; a++) { r.lo[a] = b.lo[a]; r.hi[a] = b.hi[a]; }
-            r.root_ref = b.root_ref; r.flags = b.n_items == 1 ? PH_INST_SINGLE : 0u;   // an object with one primitive is used directly, without an aggregate (lib.rs:953-956)
-            bool ident = true;
-            for (int a = 0; a < 16; a++) if (ih.i2w[a] != ((a % 5 == 0) ? 1.0f : 0.0f)) ident = false;
-            if (ident) r.flags |= PH_INST_IDENTITY;
-            s->inst_recs.push_back(r);
-        }
+        if (int rc = build_forest(s, in, on_device, split_method, max_prims_in_node, layout, trees)) return rc;
+        make_instance_records(s, layout, trees);
     }
-    // Light::preprocess: bounding sphere of the world bound (bounds3.rs:196-208; infinite.rs:113-117, distant.rs:54-58)
-    s->world_radius = 1.0f; s->world_center[0] = s->world_center[1] = s->world_center[2] = 0.0f;
-    if (s->bvh.root_ref != PH_INVALID_REF) {
-        const float* lo = s->bvh.root_lo; const float* hi = s->bvh.root_hi;
-        float c[3];
-        for (int k = 0; k < 3; k++) c[k] = (1.0f - 0.5f) * lo[k] + 0.5f * hi[k];  // lerp(0.5, pmin, pmax) (common.rs:166-175)
-        bool inside = (c[0] >= lo[0] && c[0] <= hi[0]) && (c[1] >= lo[1] && c[1] <= hi[1]) && (c[2] >= lo[2] && c[2] <= hi[2]);
-        float dx = c[0] - hi[0], dy = c[1] - hi[1], dz = c[2] - hi[2];
-        s->world_radius = inside ? std::sqrt(dx * dx + dy * dy + dz * dz) : 0.0f;
-        for (int k = 0; k < 3; k++) s->world_center[k] = c[k];
-    }
+    set_world_sphere(s);
     s->built = true; s->uploaded = false;
     return PBRT_HIP_OK;
-    });
 }
 
-// BVHAccel::from with splitmethod "sah" (the default) or "hlbvh", constructed on the GPU (bvh_sah_device.hip, bvh_device.hip): same tree, same leaf order as pbrt_hip_build_accel
-int pbrt_hip_build_accel_device(PbrtHipScene* s, int split_method, int max_prims_in_node) {
-    return ph_guard(s, "pbrt_hip_build_accel_device", [&]() -> int {
+// the two device entries: their own argument check in front of build_accel
+static int build_accel_by_kernels(PbrtHipScene* s, AccelBuilder builder, int split_method, int max_prims_in_node) {
     if (!s) return PBRT_HIP_ERR_INVALID_ARG;
     if (split_method != 0 && split_method != 1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "build_accel_device: the device builders make the SAH (0) and the HLBVH (1) tree; EqualCounts is built on the host");
-    s->build_on_device = true;
-    const int rc = pbrt_hip_build_accel(s, split_method, max_prims_in_node);
-    s->build_on_device = false;
-    return rc;
-    });
+    return build_accel(s, builder, split_method, max_prims_in_node);
 }
 
-// pbrt_hip_build_accel_device, except that the SAH tree (0) of a scene with quadric shapes is built as well (bvh_sah_steps.h: init_elem and emit_tri take a quadric slot)
+extern "C" {
+
+int pbrt_hip_build_accel(PbrtHipScene* s, int split_method, int max_prims_in_node) {
+    return ph_guard(s, "pbrt_hip_build_accel", [&]() -> int { return s ? build_accel(s, AccelBuilder::Host, split_method, max_prims_in_node) : PBRT_HIP_ERR_INVALID_ARG; });
+}
+// BVHAccel::from with splitmethod "sah" (the default) or "hlbvh", constructed on the GPU (bvh_sah_device.hip, bvh_device.hip): same tree, same leaf order as pbrt_hip_build_accel
+int pbrt_hip_build_accel_device(PbrtHipScene* s, int split_method, int max_prims_in_node) {
+    return ph_guard(s, "pbrt_hip_build_accel_device", [&]() -> int { return build_accel_by_kernels(s, AccelBuilder::Device, split_method, max_prims_in_node); });
+}
+// pbrt_hip_build_accel_device, except that the SAH tree (0) of a scene with quadric shapes is built as well
 int pbrt_hip_build_accel_device_shapes(PbrtHipScene* s, int split_method, int max_prims_in_node) {
-    return ph_guard(s, "pbrt_hip_build_accel_device_shapes", [&]() -> int {
-    if (!s) return PBRT_HIP_ERR_INVALID_ARG;
-    s->build_sah_quadrics_on_device = true;
-    const int rc = pbrt_hip_build_accel_device(s, split_method, max_prims_in_node);
-    s->build_sah_quadrics_on_device = false;
-    return rc;
-    });
+    return ph_guard(s, "pbrt_hip_build_accel_device_shapes", [&]() -> int { return build_accel_by_kernels(s, AccelBuilder::DeviceShapes, split_method, max_prims_in_node); });
 }
 
 int pbrt_hip_world_bound(const PbrtHipScene* s, float out[6]) {
@@ -1298,7 +1319,7 @@ int pbrt_hip_accel_stats(const PbrtHipScene* s, uint64_t out[8]) {
     return ph_guard(const_cast<PbrtHipScene*>(s), "pbrt_hip_accel_stats", [&]() -> int {
     if (!s || !out) return PBRT_HIP_ERR_INVALID_ARG;
     if (!s->built) return PBRT_HIP_ERR_STATE;
-    out[0] = s->tree_dev_tris ? s->bvh.interior_nodes : s->bvh.nodes.size(); out[1] = s->tree_dev_tris ? s->tree_dev_n_tris : s->bvh.tris.size();
+    out[0] = s->accel_n_nodes(); out[1] = s->accel_n_records();
     out[2] = out[0] * sizeof(Node64); out[3] = out[1] * sizeof(TriRec);
     out[4] = s->bvh.leaf_nodes; out[5] = (uint64_t)s->bvh.max_depth; out[6] = s->bvh.max_leaf_prims;
     out[7] = (uint64_t)(s->bvh.build_seconds * 1e6);
@@ -1311,19 +1332,19 @@ int pbrt_hip_accel_copy(PbrtHipScene* s, void* out_nodes, uint64_t node_capacity
     return ph_guard(s, "pbrt_hip_accel_copy", [&]() -> int {
     if (!s) return PBRT_HIP_ERR_INVALID_ARG;
     if (!s->built) return set_err(s, PBRT_HIP_ERR_STATE, "accel_copy: build_accel first");
-    const size_t nn = s->tree_dev_tris ? s->bvh.interior_nodes : s->bvh.nodes.size(), nt = s->tree_dev_tris ? s->tree_dev_n_tris : s->bvh.tris.size();
+    const size_t nn = s->accel_n_nodes(), nt = s->accel_n_records();
     if (node_capacity < nn || record_capacity < nt) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "accel_copy: buffers too small (pbrt_hip_accel_stats gives the sizes)");
-    if (s->tree_dev_tris) {
+    if (s->accel_on_device()) {
         PH_CHECK(s, hipSetDevice(s->device));
-        if (nn && out_nodes) PH_CHECK(s, hipMemcpy(out_nodes, s->tree_dev_nodes, nn * sizeof(Node64), hipMemcpyDeviceToHost));
-        if (nt && out_leaf_records) PH_CHECK(s, hipMemcpy(out_leaf_records, s->tree_dev_tris, nt * sizeof(TriRec), hipMemcpyDeviceToHost));
+        if (nn && out_nodes) PH_CHECK(s, hipMemcpy(out_nodes, s->accel_nodes(), nn * sizeof(Node64), hipMemcpyDeviceToHost));
+        if (nt && out_leaf_records) PH_CHECK(s, hipMemcpy(out_leaf_records, s->accel_records(), nt * sizeof(TriRec), hipMemcpyDeviceToHost));
         if (!s->inst_recs.empty()) {   // an upload may have filled the instance records and set the hints in place (patch_inst_records_kernel): hand out the builder's form
             if (out_nodes) { Node64* nd = static_cast<Node64*>(out_nodes); for (size_t i = 0; i < nn; i++) { if ((nd[i].c0 & PH_LEAF_BIT) && nd[i].c0 < PH_NEED_POP) nd[i].c0 &= ~PH_LEAF_INST_HINT; if ((nd[i].c1 & PH_LEAF_BIT) && nd[i].c1 < PH_NEED_POP) nd[i].c1 &= ~PH_LEAF_INST_HINT; } }
             if (out_leaf_records) { TriRec* tr = static_cast<TriRec*>(out_leaf_records); for (size_t i = 0; i < nt; i++) { tr[i].flags &= ~PH_TRI_NEXT_INST; if (tr[i].flags & PH_TRI_INSTANCE) { const uint32_t prim = tr[i].prim, fl = tr[i].flags; std::memset(&tr[i], 0, sizeof(TriRec)); tr[i].prim = prim; tr[i].flags = fl; } } }
         }
     } else {
-        if (nn && out_nodes) std::memcpy(out_nodes, s->bvh.nodes.data(), nn * sizeof(Node64));
-        if (nt && out_leaf_records) std::memcpy(out_leaf_records, s->bvh.tris.data(), nt * sizeof(TriRec));
+        if (nn && out_nodes) std::memcpy(out_nodes, s->accel_nodes(), nn * sizeof(Node64));
+        if (nt && out_leaf_records) std::memcpy(out_leaf_records, s->accel_records(), nt * sizeof(TriRec));
     }
     return PBRT_HIP_OK;
     });

@@ -21,6 +21,7 @@
 // Inside a treelet emit_lbvh always splits a sorted range into a lower and an upper part, so the depth-first leaf order of a treelet IS the sorted
 // order; a tree's leaf order is its treelets' ranges concatenated in the depth-first order of its upper SAH tree.
 #include "scene_host.h"
+#include "device_build_stage.h"
 #include "host_math.h"
 #include "hlbvh_forest_stitch.h"
 #include <algorithm>
@@ -64,23 +65,7 @@ __global__ __launch_bounds__(PHD_RS_BLOCK) void rs_hist_kernel(const uint32_t* k
     __syncthreads();
     block_hist[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
 }
-// exclusive scan of `m` counters in place, one block
-__global__ __launch_bounds__(1024) void scan_kernel(uint32_t* a, uint32_t m) {
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (m + 1023u) / 1024u, lo = threadIdx.x * per, hi = lo + per < m ? lo + per : m;
-    uint32_t sum = 0u;
-    for (uint32_t i = lo; i < hi; i++) sum += a[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024u; o <<= 1) {
-        const uint32_t add = threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
-    for (uint32_t i = lo; i < hi; i++) { const uint32_t v = a[i]; a[i] = run; run += v; }
-}
+// (the scan of the block histograms between the two: exclusive_scan_kernel, device_build_stage.h)
 __global__ __launch_bounds__(PHD_RS_BLOCK) void rs_scatter_kernel(const uint32_t* keys, const uint32_t* vals, uint32_t* keys_out, uint32_t* vals_out, uint32_t n, uint32_t per, int shift,
                                                                  const uint32_t* block_base /*scanned [256][gridDim.x]*/) {
     __shared__ uint32_t run[256];                       // where the block's next key of each digit goes
@@ -380,9 +365,6 @@ __global__ __launch_bounds__(256) void f_gather_kernel(const uint32_t* ids, cons
 
 namespace phost {
 
-#define PHD_CHECK(call)                                                                 \
-    do { hipError_t e__ = (call); if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); (void)hipGetLastError(); goto fail; } } while (0)
-
 // Builds the HLBVH of `in` on the current device — or, with `forest`, the scene's aggregate and the aggregates of its instanced objects in one go, laid out
 // [scene | object | object ..] as build_forest_host lays them out; every kernel runs over all trees at once.  Without `forest` the input is one tree of all its triangles.
 // The host waits for the device three times: for the number of treelets, for the treelet roots (the SAH over them, per tree, is the host's: hlbvh_forest_stitch.h) and for the result.
@@ -390,194 +372,140 @@ namespace phost {
 int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, const ForestSpec* forest, std::vector<ForestTreeOut>* trees_out) {
     out = BuildOutput();
     if (trees_out) trees_out->clear();
-    if (!forest && in.items) { err = "device build: an item list without its forest (instanced scenes come as a forest, or take the host builder)"; return -1; }
-    if (in.n_tris >= 0x3FFFFFFFu || (forest && (forest->n_items >= 0x3FFFFFFFu || forest->n_trees == 0 || !forest->tree_start || !forest->items))) {
-        err = "device build: bad arguments (a forest needs its items and tree ranges; at most 2^30 primitives)"; return -1;
-    }
-    const uint32_t n = (uint32_t)(forest ? forest->n_items : in.n_tris);
+    if (check_device_build_input(in, forest, err) != 0) return -1;
+    const DeviceBuildItems bi(in, forest);
+    const uint32_t n = bi.n, n_trees = bi.n_trees;
     if (n == 0) return 0;
-    const uint32_t n_trees = forest ? forest->n_trees : 1u;
-    const uint32_t one_tree[2] = {0u, n};
-    const uint32_t* tree_start = forest ? forest->tree_start : one_tree;
-    const uint32_t* h_items = forest ? forest->items : nullptr;   // null: item i is triangle i
-    const size_t n_inst = forest ? forest->n_inst : 0;
-    const uint32_t* inst_tree = forest ? forest->inst_tree : nullptr; const float* inst_i2w = forest ? forest->inst_i2w : nullptr;
-    for (uint32_t t = 0; t < n_trees; t++) if (tree_start[t] >= tree_start[t + 1] || tree_start[t + 1] > n) { err = "device build: empty or unordered tree range"; return -1; }
-    if (tree_start[0] != 0 || tree_start[n_trees] != n) { err = "device build: tree ranges do not cover the items"; return -1; }
-    const uint32_t top_end = tree_start[1];
-    if (n_inst && (n_trees < 2 || !inst_tree || !inst_i2w)) { err = "device build: instances without object trees"; return -1; }
-    for (size_t k = 0; k < n_inst; k++) if (inst_tree[k] == 0 || inst_tree[k] >= n_trees) { err = "device build: an instance names no object tree"; return -1; }
-    if (h_items) for (uint32_t i = 0; i < n; i++) {   // every index a kernel follows
-        const uint32_t it = h_items[i];
-        if ((it & PH_ITEM_INST) ? (i >= top_end || (size_t)(it & ~PH_ITEM_INST) >= n_inst) : (size_t)it >= in.n_tris) { err = "device build: an item names no triangle or instance"; return -1; }
-    }
-    const uint32_t* pq = in.prim_quadric;   // null: every slot holds a triangle
-    if (pq && !in.quad_bounds) { err = "device build: quadric slots without their bounds"; return -1; }
-    if (pq) for (uint32_t i = 0; i < n; i++) {   // a quadric stands in the scene's own tree only (object definitions hold none), and names one of the n_quadrics bounds
-        const uint32_t it = h_items ? h_items[i] : i;
-        if ((it & PH_ITEM_INST) || !pq[it]) continue;
-        if ((forest && i >= top_end) || (size_t)(pq[it] - 1u) >= in.n_quadrics) { err = "device build: a quadric slot inside an object's tree, or one that names no quadric"; return -1; }
-    }
+    const uint32_t* tree_start = bi.tree_start(); const uint32_t top_end = bi.top_end(); const size_t n_inst = bi.n_inst();
     const uint32_t max_prims = (uint32_t)(max_prims_in_node & 0xff);   // bvh/mod.rs:357 `as u8`
-    auto t0 = std::chrono::steady_clock::now();
-    const bool prof = std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr;
-    auto lap = [&](const char* what) { if (prof) { (void)hipStreamSynchronize(stream); std::fprintf(stderr, "build_hlbvh_forest_device n=%u trees=%u: %-28s at %.3f s\n", n, n_trees, what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } };
-    std::vector<void*> allocs;
-    auto dalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; } allocs.push_back(p); return p; };
-    size_t n_verts = 0;   // over the triangle slots: a quadric slot's index triple is {0, 0, 0} and stands for no vertex (a scene of quadrics only has none: nothing of P is read)
-    if (!pq) for (size_t i = 0; i < 3 * in.n_tris; i++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[i] + 1);
-    else for (size_t t = 0; t < in.n_tris; t++) if (!pq[t]) for (int k = 0; k < 3; k++) n_verts = std::max<size_t>(n_verts, (size_t)in.idx[3 * t + k] + 1);
-    float* dP = (float*)dalloc(n_verts * 12); uint32_t* dIdx = (uint32_t*)dalloc(in.n_tris * 12);
-    uint32_t* d_items = h_items ? (uint32_t*)dalloc((size_t)n * 4) : nullptr; uint32_t* d_tree_start = (uint32_t*)dalloc(((size_t)n_trees + 1) * 4); uint32_t* tree_of = (uint32_t*)dalloc((size_t)n * 4);
-    uint32_t* d_pq = pq ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr; float* d_qb = pq ? (float*)dalloc(in.n_quadrics * 24) : nullptr;
-    uint32_t* d_inst_tree = (uint32_t*)dalloc(n_inst * 4); float* d_i2w = (float*)dalloc(n_inst * 64); float* d_inst_bounds = (float*)dalloc(n_inst * 24);
-    float* blo = (float*)dalloc((size_t)n * 12); float* bhi = (float*)dalloc((size_t)n * 12);
-    uint32_t* tb = (uint32_t*)dalloc((size_t)n_trees * 24);
-    uint32_t* keys[2] = {(uint32_t*)dalloc((size_t)n * 4), (uint32_t*)dalloc((size_t)n * 4)};
-    uint32_t* vals[2] = {(uint32_t*)dalloc((size_t)n * 4), (uint32_t*)dalloc((size_t)n * 4)};
-    uint32_t* codes_keep = (uint32_t*)dalloc((size_t)n * 4);
-    const uint32_t nb = std::min<uint32_t>(1024u, (n + 2047u) / 2048u), per = (((n + nb - 1u) / nb) + 255u) & ~255u;
-    uint32_t* bh = (uint32_t*)dalloc((size_t)256 * nb * 4);
-    const uint32_t n_blocks = (n + 255u) / 256u;
-    uint32_t* head_counts = (uint32_t*)dalloc(((size_t)n_blocks + 1) * 4);
-    uint32_t* tl_of_pos = (uint32_t*)dalloc((size_t)n * 4);
-    uint32_t* leaf_last = (uint32_t*)dalloc((size_t)n * 4);
-    phd::DNode* pool = (phd::DNode*)dalloc((size_t)2 * n * sizeof(phd::DNode));
-    phd::EmitItem* items = (phd::EmitItem*)dalloc((size_t)2 * n * sizeof(phd::EmitItem));
-    uint32_t* lvl = (uint32_t*)dalloc((PHD_MAX_LEVELS + 2) * 4); uint32_t* n_items = (uint32_t*)dalloc(16);
-    uint32_t* d_flags = in.tri_flags ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr; uint32_t* d_mesh = in.tri_mesh ? (uint32_t*)dalloc(in.n_tris * 4) : nullptr;
-    TriRec* d_tris = (TriRec*)dalloc((size_t)n * sizeof(TriRec));
+    // host staging stands before the arena: it outlives the arena's wait for the stream, whichever way the function is left
+    std::vector<phd::TreeletInfo> info; std::vector<float> rb; std::vector<StitchTreelet> tl; StitchPlan plan;
+    const BuildLaps lap{"build_hlbvh_forest_device n=" + std::to_string(n) + " trees=" + std::to_string(n_trees), stream};
     std::vector<uint32_t> tb_init((size_t)n_trees * 6);
-    std::vector<phd::TreeletInfo> info;
-    std::vector<float> rb;
-    std::vector<StitchTreelet> tl;
-    StitchPlan plan;
+    for (uint32_t t = 0; t < n_trees; t++) for (int k = 0; k < 3; k++) { tb_init[6 * (size_t)t + k] = 0xFFFFFFFFu; tb_init[6 * (size_t)t + 3 + k] = 0u; }
+    DeviceArena arena(stream);
+    const DeviceBuildInput d = upload_build_input(arena, in, bi);
+    uint32_t* tree_of = arena.alloc<uint32_t>(n);
+    uint32_t* d_inst_tree = arena.upload(n_inst ? forest->inst_tree : nullptr, n_inst); float* d_i2w = arena.upload(n_inst ? forest->inst_i2w : nullptr, n_inst * 16);
+    float* d_inst_bounds = arena.alloc<float>(n_inst * 6);
+    float* blo = arena.alloc<float>((size_t)n * 3); float* bhi = arena.alloc<float>((size_t)n * 3);
+    uint32_t* tb = arena.upload(tb_init.data(), tb_init.size());
+    uint32_t* keys[2] = {arena.alloc<uint32_t>(n), arena.alloc<uint32_t>(n)};
+    uint32_t* vals[2] = {arena.alloc<uint32_t>(n), arena.alloc<uint32_t>(n)};
+    uint32_t* codes_keep = arena.alloc<uint32_t>(n);
+    const uint32_t nb = std::min<uint32_t>(1024u, (n + 2047u) / 2048u), per = (((n + nb - 1u) / nb) + 255u) & ~255u;
+    uint32_t* bh = arena.alloc<uint32_t>((size_t)256 * nb);
+    const uint32_t n_blocks = (n + 255u) / 256u;
+    uint32_t* head_counts = arena.alloc<uint32_t>((size_t)n_blocks + 1);
+    uint32_t* tl_of_pos = arena.alloc<uint32_t>(n);
+    uint32_t* leaf_last = arena.alloc<uint32_t>(n);
+    phd::DNode* pool = arena.alloc<phd::DNode>((size_t)2 * n);
+    phd::EmitItem* items = arena.alloc<phd::EmitItem>((size_t)2 * n);
+    uint32_t* lvl = arena.alloc<uint32_t>(PHD_MAX_LEVELS + 2); uint32_t* n_items = arena.alloc<uint32_t>(4);
+    TriRec* d_tris = arena.alloc<TriRec>(n);
+    if (!arena.ok()) { err = "device build: " + arena.why(); return -1; }
     uint32_t nt = 0;
-    int rc = -1;
-    for (void* p : allocs) if (!p) { err = "device build: out of device memory"; goto fail; }
-    {
-        for (uint32_t t = 0; t < n_trees; t++) for (int k = 0; k < 3; k++) { tb_init[6 * (size_t)t + k] = 0xFFFFFFFFu; tb_init[6 * (size_t)t + 3 + k] = 0u; }
-        if (n_verts) PHD_CHECK(hipMemcpyAsync(dP, in.P, n_verts * 12, hipMemcpyHostToDevice, stream));
-        PHD_CHECK(hipMemcpyAsync(dIdx, in.idx, in.n_tris * 12, hipMemcpyHostToDevice, stream));
-        if (d_items) PHD_CHECK(hipMemcpyAsync(d_items, h_items, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-        PHD_CHECK(hipMemcpyAsync(d_tree_start, tree_start, ((size_t)n_trees + 1) * 4, hipMemcpyHostToDevice, stream));
-        PHD_CHECK(hipMemcpyAsync(tb, tb_init.data(), (size_t)n_trees * 24, hipMemcpyHostToDevice, stream));
-        if (d_pq) {
-            PHD_CHECK(hipMemcpyAsync(d_pq, pq, in.n_tris * 4, hipMemcpyHostToDevice, stream));
-            if (in.n_quadrics) PHD_CHECK(hipMemcpyAsync(d_qb, in.quad_bounds, in.n_quadrics * 24, hipMemcpyHostToDevice, stream));
-        }
-        if (n_inst) {
-            PHD_CHECK(hipMemcpyAsync(d_inst_tree, inst_tree, n_inst * 4, hipMemcpyHostToDevice, stream));
-            PHD_CHECK(hipMemcpyAsync(d_i2w, inst_i2w, n_inst * 64, hipMemcpyHostToDevice, stream));
-        }
-        if (d_flags) PHD_CHECK(hipMemcpyAsync(d_flags, in.tri_flags, in.n_tris * 4, hipMemcpyHostToDevice, stream));
-        if (d_mesh) PHD_CHECK(hipMemcpyAsync(d_mesh, in.tri_mesh, in.n_tris * 4, hipMemcpyHostToDevice, stream));
-        PHD_CHECK(hipMemsetAsync(head_counts, 0, ((size_t)n_blocks + 1) * 4, stream));
-        PHD_CHECK(hipMemsetAsync(pool, 0xFF, (size_t)2 * n * sizeof(phd::DNode), stream));
-        PHD_CHECK(hipMemsetAsync(leaf_last, 0, (size_t)n * 4, stream));
-        PHD_CHECK(hipMemsetAsync(lvl, 0, (PHD_MAX_LEVELS + 2) * 4, stream));
-        const dim3 g(n_blocks), b(256);
-        lap("allocations and uploads");
-        hipLaunchKernelGGL(phd::f_tree_of_kernel, g, b, 0, stream, d_tree_start, n_trees, n, tree_of);
-        // K1: the objects' trees first — the scene's tree holds TransformedPrimitives, whose bounds are the objects' tree bounds carried to world space
-        if (n > top_end) hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((n - top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, d_pq, d_qb, tree_of, top_end, n, blo, bhi, tb);
-        if (n_inst) hipLaunchKernelGGL(phd::f_inst_bounds_kernel, dim3((uint32_t)((n_inst + 255u) / 256u)), b, 0, stream, tb, d_inst_tree, d_i2w, (uint32_t)n_inst, d_inst_bounds);
-        hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((top_end + 255u) / 256u), b, 0, stream, dP, dIdx, d_items, d_inst_bounds, d_pq, d_qb, tree_of, 0u, top_end, blo, bhi, tb);
-        hipLaunchKernelGGL(phd::f_morton_kernel, g, b, 0, stream, blo, bhi, n, tb, tree_of, keys[0], codes_keep, vals[0]);
-        int cur = 0;
-        auto sort_pass = [&](int shift) {
-            hipLaunchKernelGGL(phd::rs_hist_kernel, dim3(nb), dim3(PHD_RS_BLOCK), 0, stream, keys[cur], n, per, shift, bh);
-            hipLaunchKernelGGL(phd::scan_kernel, dim3(1), dim3(1024), 0, stream, bh, 256u * nb);
-            hipLaunchKernelGGL(phd::rs_scatter_kernel, dim3(nb), dim3(PHD_RS_BLOCK), 0, stream, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, per, shift, bh);
-            cur ^= 1;
-        };
-        for (int pass = 0; pass < 4; pass++) sort_pass(pass * 8);   // K3: by the 30-bit code ..
-        if (n_trees > 1) {                                          // .. then by the tree, as many digits as n_trees - 1 has
-            hipLaunchKernelGGL(phd::f_lookup_kernel, g, b, 0, stream, vals[cur], tree_of, n, keys[cur]);
-            for (int shift = 0; shift < 32 && ((n_trees - 1u) >> shift) != 0u; shift += 8) sort_pass(shift);
-            hipLaunchKernelGGL(phd::f_lookup_kernel, g, b, 0, stream, vals[cur], codes_keep, n, keys[cur]);   // the keys were the trees: the codes again, in the sorted order
-        }
-        uint32_t* ids = vals[cur]; uint32_t* codes = keys[cur];
-        // K4: run heads, counted and compacted
-        hipLaunchKernelGGL(phd::f_heads_count_kernel, g, b, 0, stream, codes, tree_of, n, head_counts);
-        hipLaunchKernelGGL(phd::scan_kernel, dim3(1), dim3(1024), 0, stream, head_counts, n_blocks + 1u);
-        PHD_CHECK(hipGetLastError());
-        PHD_CHECK(hipMemcpyAsync(&nt, head_counts + n_blocks, 4, hipMemcpyDeviceToHost, stream));
-        PHD_CHECK(hipStreamSynchronize(stream));
-        lap("bounds, codes, sort, heads");
-        if (nt == 0 || nt > n) { err = "device build: treelet count out of range"; goto fail; }
-        uint32_t* d_tl_first = (uint32_t*)dalloc(((size_t)nt + 1) * 4); uint32_t* d_tl_dense = (uint32_t*)dalloc((size_t)nt * 4); uint32_t* d_tl_out = (uint32_t*)dalloc((size_t)nt * 4);
-        phd::TreeletInfo* d_info = (phd::TreeletInfo*)dalloc((size_t)nt * sizeof(phd::TreeletInfo)); float* d_rb = (float*)dalloc((size_t)nt * 24);
-        if (!d_tl_first || !d_tl_dense || !d_tl_out || !d_info || !d_rb) { err = "device build: out of device memory"; goto fail; }
-        const dim3 gt((nt + 255u) / 256u);
-        hipLaunchKernelGGL(phd::f_heads_write_kernel, g, b, 0, stream, codes, tree_of, n, head_counts, nt, d_tl_first, tl_of_pos);
-        hipLaunchKernelGGL(phd::f_emit_roots_kernel, gt, b, 0, stream, d_tl_first, nt, items, lvl, n_items, d_info);
-        {   // K5: emit_lbvh, level by level, over the treelets of all trees
-            auto grid_of = [&](int L) { const uint64_t most = std::min<uint64_t>((uint64_t)n, (uint64_t)nt << std::min(L, 24)); return dim3((uint32_t)((most + 255u) / 256u)); };
-            for (int L = 0; L < PHD_MAX_LEVELS; L++) {
-                hipLaunchKernelGGL(phd::emit_level_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, n_items, codes, max_prims, pool, leaf_last, d_info);
-                hipLaunchKernelGGL(phd::emit_close_level_kernel, dim3(1), dim3(64), 0, stream, lvl, L, n_items);
-            }
-            for (int L = PHD_MAX_LEVELS - 1; L >= 0; L--) hipLaunchKernelGGL(phd::emit_up_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, ids, blo, bhi, pool);
-            for (int L = 0; L < PHD_MAX_LEVELS; L++) hipLaunchKernelGGL(phd::emit_down_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, pool, d_info);
-        }
-        hipLaunchKernelGGL(phd::f_roots_kernel, gt, b, 0, stream, pool, d_tl_first, nt, d_rb);
-        PHD_CHECK(hipGetLastError());
-        info.resize(nt); rb.resize(6 * (size_t)nt);
-        PHD_CHECK(hipMemcpyAsync(info.data(), d_info, (size_t)nt * sizeof(phd::TreeletInfo), hipMemcpyDeviceToHost, stream));
-        PHD_CHECK(hipMemcpyAsync(rb.data(), d_rb, (size_t)nt * 24, hipMemcpyDeviceToHost, stream));
-        PHD_CHECK(hipStreamSynchronize(stream));
-        lap("treelets");
-        tl.resize(nt);
-        for (uint32_t t = 0; t < nt; t++) {
-            StitchTreelet& q = tl[t];
-            q.first = info[t].first; q.n = info[t].n; q.interior = info[t].interior; q.leaves = info[t].leaves; q.max_leaf = info[t].max_leaf; q.depth = info[t].depth;
-            for (int k = 0; k < 3; k++) { q.lo[k] = rb[6 * (size_t)t + k]; q.hi[k] = rb[6 * (size_t)t + 3 + k]; }
-        }
-        const int prc = plan_hlbvh_forest(tl.data(), nt, tree_start, n_trees, plan);
-        if (prc == -2) { rc = -2; err = "the reference's HLBVH build asserts on this input (hlbvh.rs:338/356/418)"; goto fail; }
-        if (prc != 0) { err = "device build: the treelets do not tile the trees"; goto fail; }
-        lap("SAH over the treelet roots");
-        out.interior_nodes = plan.interior_nodes;
-        Node64* d_nodes = (Node64*)dalloc(std::max<size_t>(out.interior_nodes, 1) * sizeof(Node64));
-        if (!d_nodes) { err = "device build: out of device memory"; goto fail; }
-        PHD_CHECK(hipMemcpyAsync(d_tl_dense, plan.dense_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
-        PHD_CHECK(hipMemcpyAsync(d_tl_out, plan.out_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(phd::f_convert_kernel, dim3((uint32_t)(((uint64_t)2 * n + 255u) / 256u)), b, 0, stream, pool, n, tl_of_pos, d_tl_first, d_tl_dense, d_tl_out, d_nodes);
-        hipLaunchKernelGGL(phd::f_gather_kernel, g, b, 0, stream, ids, leaf_last, tl_of_pos, d_tl_first, d_tl_out, n, d_items, dP, dIdx, d_flags, d_mesh, d_pq, d_tris);
-        PHD_CHECK(hipGetLastError());
-        out.nodes.resize(out.interior_nodes);
-        out.tris.resize(n);
-        if (out.interior_nodes) PHD_CHECK(hipMemcpyAsync(out.nodes.data(), d_nodes, out.interior_nodes * sizeof(Node64), hipMemcpyDeviceToHost, stream));
-        PHD_CHECK(hipMemcpyAsync(out.tris.data(), d_tris, (size_t)n * sizeof(TriRec), hipMemcpyDeviceToHost, stream));
-        PHD_CHECK(hipStreamSynchronize(stream));
-        lap("nodes, records, downloads");
-        place_upper_nodes(plan, out.nodes.data());
-        if (forest || pq) {   // a single tree of triangles keeps the kernels' numbering.  A forest takes the host builder's, tree by tree (trees are independent: spread them over a few threads where there is much to do),
-                              // and so does the single tree of a scene with quadrics: such a scene's arrays are the host builder's entry by entry, with or without instances
-            const uint32_t n_thr = out.interior_nodes >= (1u << 18) ? std::min<uint32_t>(std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency())), n_trees) : 1u;
-            std::vector<uint32_t> cut(n_thr + 1, n_trees);   // cut the trees into runs of about equal node counts
-            cut[0] = 0;
-            for (uint32_t k = 1, t = 0; k < n_thr; k++) { const uint64_t want = (uint64_t)out.interior_nodes * k / n_thr; while (t < n_trees && plan.node_base[t] < want) t++; cut[k] = t; }
-            ThreadGroup th;
-            for (uint32_t k = 1; k < n_thr; k++) if (cut[k + 1] > cut[k]) th.run([&plan, &out, a = cut[k], e = cut[k + 1]]() { renumber_like_host(plan, out.nodes.data(), a, e); });
-            renumber_like_host(plan, out.nodes.data(), cut[0], cut[1]);
-            th.join();
-        }
-        lap("numbering");
-        out.root_ref = plan.trees[0].root_ref;
-        for (int k = 0; k < 3; k++) { out.root_lo[k] = plan.trees[0].lo[k]; out.root_hi[k] = plan.trees[0].hi[k]; }
-        if (trees_out) *trees_out = plan.trees;
-        out.leaf_nodes = plan.leaf_nodes; out.max_leaf_prims = plan.max_leaf_prims; out.max_depth = plan.max_depth;   // over all trees of the forest
-        out.total_nodes = out.interior_nodes + out.leaf_nodes;
-        out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        rc = 0;
+    PH_BUILD_CHECK(hipMemsetAsync(head_counts, 0, ((size_t)n_blocks + 1) * 4, stream));
+    PH_BUILD_CHECK(hipMemsetAsync(pool, 0xFF, (size_t)2 * n * sizeof(phd::DNode), stream));
+    PH_BUILD_CHECK(hipMemsetAsync(leaf_last, 0, (size_t)n * 4, stream));
+    PH_BUILD_CHECK(hipMemsetAsync(lvl, 0, (PHD_MAX_LEVELS + 2) * 4, stream));
+    const dim3 g(n_blocks), b(256);
+    lap("allocations and uploads");
+    hipLaunchKernelGGL(phd::f_tree_of_kernel, g, b, 0, stream, d.tree_start, n_trees, n, tree_of);
+    // K1: the objects' trees first — the scene's tree holds TransformedPrimitives, whose bounds are the objects' tree bounds carried to world space
+    if (n > top_end) hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((n - top_end + 255u) / 256u), b, 0, stream, d.P, d.idx, d.items, d_inst_bounds, d.prim_quadric, d.quad_bounds, tree_of, top_end, n, blo, bhi, tb);
+    if (n_inst) hipLaunchKernelGGL(phd::f_inst_bounds_kernel, dim3((uint32_t)((n_inst + 255u) / 256u)), b, 0, stream, tb, d_inst_tree, d_i2w, (uint32_t)n_inst, d_inst_bounds);
+    hipLaunchKernelGGL(phd::f_bounds_kernel, dim3((top_end + 255u) / 256u), b, 0, stream, d.P, d.idx, d.items, d_inst_bounds, d.prim_quadric, d.quad_bounds, tree_of, 0u, top_end, blo, bhi, tb);
+    hipLaunchKernelGGL(phd::f_morton_kernel, g, b, 0, stream, blo, bhi, n, tb, tree_of, keys[0], codes_keep, vals[0]);
+    int cur = 0;
+    auto sort_pass = [&](int shift) {
+        hipLaunchKernelGGL(phd::rs_hist_kernel, dim3(nb), dim3(PHD_RS_BLOCK), 0, stream, keys[cur], n, per, shift, bh);
+        hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, bh, 256u * nb);
+        hipLaunchKernelGGL(phd::rs_scatter_kernel, dim3(nb), dim3(PHD_RS_BLOCK), 0, stream, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, per, shift, bh);
+        cur ^= 1;
+    };
+    for (int pass = 0; pass < 4; pass++) sort_pass(pass * 8);   // K3: by the 30-bit code ..
+    if (n_trees > 1) {                                          // .. then by the tree, as many digits as n_trees - 1 has
+        hipLaunchKernelGGL(phd::f_lookup_kernel, g, b, 0, stream, vals[cur], tree_of, n, keys[cur]);
+        for (int shift = 0; shift < 32 && ((n_trees - 1u) >> shift) != 0u; shift += 8) sort_pass(shift);
+        hipLaunchKernelGGL(phd::f_lookup_kernel, g, b, 0, stream, vals[cur], codes_keep, n, keys[cur]);   // the keys were the trees: the codes again, in the sorted order
     }
-fail:
-    for (void* p : allocs) if (p) (void)hipFree(p);
-    return rc;
+    uint32_t* ids = vals[cur]; uint32_t* codes = keys[cur];
+    // K4: run heads, counted and compacted
+    hipLaunchKernelGGL(phd::f_heads_count_kernel, g, b, 0, stream, codes, tree_of, n, head_counts);
+    hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, head_counts, n_blocks + 1u);
+    PH_BUILD_CHECK(hipGetLastError());
+    PH_BUILD_CHECK(hipMemcpyAsync(&nt, head_counts + n_blocks, 4, hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipStreamSynchronize(stream));
+    lap("bounds, codes, sort, heads");
+    if (nt == 0 || nt > n) { err = "device build: treelet count out of range"; return -1; }
+    uint32_t* d_tl_first = arena.alloc<uint32_t>((size_t)nt + 1); uint32_t* d_tl_dense = arena.alloc<uint32_t>(nt); uint32_t* d_tl_out = arena.alloc<uint32_t>(nt);
+    phd::TreeletInfo* d_info = arena.alloc<phd::TreeletInfo>(nt); float* d_rb = arena.alloc<float>((size_t)nt * 6);
+    if (!arena.ok()) { err = "device build: " + arena.why(); return -1; }
+    const dim3 gt((nt + 255u) / 256u);
+    hipLaunchKernelGGL(phd::f_heads_write_kernel, g, b, 0, stream, codes, tree_of, n, head_counts, nt, d_tl_first, tl_of_pos);
+    hipLaunchKernelGGL(phd::f_emit_roots_kernel, gt, b, 0, stream, d_tl_first, nt, items, lvl, n_items, d_info);
+    {   // K5: emit_lbvh, level by level, over the treelets of all trees
+        auto grid_of = [&](int L) { const uint64_t most = std::min<uint64_t>((uint64_t)n, (uint64_t)nt << std::min(L, 24)); return dim3((uint32_t)((most + 255u) / 256u)); };
+        for (int L = 0; L < PHD_MAX_LEVELS; L++) {
+            hipLaunchKernelGGL(phd::emit_level_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, n_items, codes, max_prims, pool, leaf_last, d_info);
+            hipLaunchKernelGGL(phd::emit_close_level_kernel, dim3(1), dim3(64), 0, stream, lvl, L, n_items);
+        }
+        for (int L = PHD_MAX_LEVELS - 1; L >= 0; L--) hipLaunchKernelGGL(phd::emit_up_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, ids, blo, bhi, pool);
+        for (int L = 0; L < PHD_MAX_LEVELS; L++) hipLaunchKernelGGL(phd::emit_down_kernel, grid_of(L), dim3(256), 0, stream, items, lvl, L, pool, d_info);
+    }
+    hipLaunchKernelGGL(phd::f_roots_kernel, gt, b, 0, stream, pool, d_tl_first, nt, d_rb);
+    PH_BUILD_CHECK(hipGetLastError());
+    info.resize(nt); rb.resize(6 * (size_t)nt);
+    PH_BUILD_CHECK(hipMemcpyAsync(info.data(), d_info, (size_t)nt * sizeof(phd::TreeletInfo), hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(rb.data(), d_rb, (size_t)nt * 24, hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipStreamSynchronize(stream));
+    lap("treelets");
+    tl.resize(nt);
+    for (uint32_t t = 0; t < nt; t++) {
+        StitchTreelet& q = tl[t];
+        q.first = info[t].first; q.n = info[t].n; q.interior = info[t].interior; q.leaves = info[t].leaves; q.max_leaf = info[t].max_leaf; q.depth = info[t].depth;
+        for (int k = 0; k < 3; k++) { q.lo[k] = rb[6 * (size_t)t + k]; q.hi[k] = rb[6 * (size_t)t + 3 + k]; }
+    }
+    const int prc = plan_hlbvh_forest(tl.data(), nt, tree_start, n_trees, plan);
+    if (prc == -2) { err = "the reference's HLBVH build asserts on this input (hlbvh.rs:338/356/418)"; return -2; }
+    if (prc != 0) { err = "device build: the treelets do not tile the trees"; return -1; }
+    lap("SAH over the treelet roots");
+    out.interior_nodes = plan.interior_nodes;
+    Node64* d_nodes = arena.alloc<Node64>(std::max<size_t>(out.interior_nodes, 1));
+    if (!d_nodes) { err = "device build: " + arena.why(); return -1; }
+    PH_BUILD_CHECK(hipMemcpyAsync(d_tl_dense, plan.dense_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(d_tl_out, plan.out_base.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(phd::f_convert_kernel, dim3((uint32_t)(((uint64_t)2 * n + 255u) / 256u)), b, 0, stream, pool, n, tl_of_pos, d_tl_first, d_tl_dense, d_tl_out, d_nodes);
+    hipLaunchKernelGGL(phd::f_gather_kernel, g, b, 0, stream, ids, leaf_last, tl_of_pos, d_tl_first, d_tl_out, n, d.items, d.P, d.idx, d.tri_flags, d.tri_mesh, d.prim_quadric, d_tris);
+    PH_BUILD_CHECK(hipGetLastError());
+    out.nodes.resize(out.interior_nodes);
+    out.tris.resize(n);
+    if (out.interior_nodes) PH_BUILD_CHECK(hipMemcpyAsync(out.nodes.data(), d_nodes, out.interior_nodes * sizeof(Node64), hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(out.tris.data(), d_tris, (size_t)n * sizeof(TriRec), hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipStreamSynchronize(stream));
+    lap("nodes, records, downloads");
+    place_upper_nodes(plan, out.nodes.data());
+    if (forest || in.prim_quadric) {   // a single tree of triangles keeps the kernels' numbering.  A forest takes the host builder's, tree by tree (trees are independent: spread them over a few threads where there is much to do),
+                          // and so does the single tree of a scene with quadrics: such a scene's arrays are the host builder's entry by entry, with or without instances
+        const uint32_t n_thr = out.interior_nodes >= (1u << 18) ? std::min<uint32_t>(std::min<uint32_t>(16u, std::max(1u, std::thread::hardware_concurrency())), n_trees) : 1u;
+        std::vector<uint32_t> cut(n_thr + 1, n_trees);   // cut the trees into runs of about equal node counts
+        cut[0] = 0;
+        for (uint32_t k = 1, t = 0; k < n_thr; k++) { const uint64_t want = (uint64_t)out.interior_nodes * k / n_thr; while (t < n_trees && plan.node_base[t] < want) t++; cut[k] = t; }
+        ThreadGroup th;
+        for (uint32_t k = 1; k < n_thr; k++) if (cut[k + 1] > cut[k]) th.run([&plan, &out, a = cut[k], e = cut[k + 1]]() { renumber_like_host(plan, out.nodes.data(), a, e); });
+        renumber_like_host(plan, out.nodes.data(), cut[0], cut[1]);
+        th.join();
+    }
+    lap("numbering");
+    out.root_ref = plan.trees[0].root_ref;
+    for (int k = 0; k < 3; k++) { out.root_lo[k] = plan.trees[0].lo[k]; out.root_hi[k] = plan.trees[0].hi[k]; }
+    if (trees_out) *trees_out = plan.trees;
+    out.leaf_nodes = plan.leaf_nodes; out.max_leaf_prims = plan.max_leaf_prims; out.max_depth = plan.max_depth;   // over all trees of the forest
+    out.total_nodes = out.interior_nodes + out.leaf_nodes;
+    out.build_seconds = lap.seconds();
+    return 0;
 }
-
 
 }  // namespace phost
 

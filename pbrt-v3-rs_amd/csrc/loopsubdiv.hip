@@ -5,11 +5,7 @@
 // Children are implicit: vertex i's child is i, face i's children are 4 i + 0..3 — the numbers the reference's allocation loops hand out (:409-424).  A new edge vertex is
 // V + the rank of its owning face-edge among the owners in (face, edge) order, the order in which the reference's HashMap meets an edge first (:454-483).
 #include "loopsubdiv_device.h"
-#include <cstdio>
-#include <cstdlib>
-#include <hip/hip_runtime.h>
-#include <string>
-#include <vector>
+#include "device_build_stage.h"
 
 namespace pls {
 
@@ -118,8 +114,8 @@ __global__ __launch_bounds__(256) void k_even(Mesh in, Mesh out) {
 // face-edge (i, k) owns its edge when it has no neighbour there or its face comes first
 __device__ inline uint32_t owner_flag(const Mesh& m, uint32_t e) { const int32_t f2 = m.ff[e]; return (f2 == -1 || (int32_t)(e / 3u) < f2) ? 1u : 0u; }
 
-// prefix sum of the owner flags, in the pattern of the SAH builder's k_flags / k_scan_chunks / k_scan_write (bvh_sah_device.hip): flags and chunk sums, the chunk sums scanned
-// by one block, the flags replaced by their exclusive prefix
+// prefix sum of the owner flags, in the pattern of the SAH builder's k_flags / exclusive_scan_kernel / k_scan_write (bvh_sah_device.hip): flags and chunk sums, the chunk sums scanned
+// by one block (device_build_stage.h), the flags replaced by their exclusive prefix
 __global__ __launch_bounds__(256) void k_owner_flags(Mesh m, uint32_t* scan, uint32_t* chunk_sums) {
     __shared__ uint32_t part[4];
     const uint32_t n = 3u * m.n_faces, base = blockIdx.x * CHUNK, lim = base + CHUNK < n ? base + CHUNK : n;
@@ -129,22 +125,6 @@ __global__ __launch_bounds__(256) void k_owner_flags(Mesh m, uint32_t* scan, uin
     if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) chunk_sums[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-__global__ __launch_bounds__(1024) void k_scan_chunks(uint32_t* a, uint32_t m) {   // exclusive scan of m counters in place, one block
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (m + 1023u) / 1024u, lo = threadIdx.x * per < m ? threadIdx.x * per : m, hi = lo + per < m ? lo + per : m;
-    uint32_t sum = 0u;
-    for (uint32_t i = lo; i < hi; i++) sum += a[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024u; o <<= 1) {
-        const uint32_t add = threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
-    for (uint32_t i = lo; i < hi; i++) { const uint32_t v = a[i]; a[i] = run; run += v; }
 }
 __global__ __launch_bounds__(256) void k_scan_write(uint32_t* scan, uint32_t n, const uint32_t* chunk_base) {
     __shared__ uint32_t part[256];
@@ -311,93 +291,77 @@ __global__ __launch_bounds__(256) void k_world(uint32_t n, M16 a, M16 ai, float*
 
 namespace phost {
 
-#define PLS_CHECK(call)                                                                 \
-    do { hipError_t e__ = (call); if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); (void)hipGetLastError(); goto fail; } } while (0)
-
 int loopsubdiv_device(const ploop::Control& c, const float* P, int n_levels, const float* o2w_m, const float* o2w_minv, hipStream_t stream, float* out_P, float* out_N,
                       uint32_t* out_idx, std::string& err) {
     using namespace pls;
     const size_t nv = (size_t)c.out_verts, nf = (size_t)c.out_faces;
     const size_t max_edges3 = 3 * (n_levels > 0 ? nf / 4 : nf);   // the face-edges of the last level's input
     const uint32_t max_chunks = (uint32_t)((max_edges3 + CHUNK - 1) / CHUNK);
-    std::vector<void*> allocs;
-    auto dalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) { (void)hipGetLastError(); p = nullptr; } allocs.push_back(p); return p; };
+    DeviceArena arena(stream);
     Mesh lv[2];
     for (int k = 0; k < 2; k++) {
-        lv[k].P = (float*)dalloc(nv * 12); lv[k].start_face = (int32_t*)dalloc(nv * 4); lv[k].vflags = (uint32_t*)dalloc(nv * 4);
-        lv[k].fv = (int32_t*)dalloc(nf * 12); lv[k].ff = (int32_t*)dalloc(nf * 12);
+        lv[k].P = arena.alloc<float>(nv * 3); lv[k].start_face = arena.alloc<int32_t>(nv); lv[k].vflags = arena.alloc<uint32_t>(nv);
+        lv[k].fv = arena.alloc<int32_t>(nf * 3); lv[k].ff = arena.alloc<int32_t>(nf * 3);
         lv[k].n_verts = 0; lv[k].n_faces = 0;
     }
-    uint32_t* scan = (uint32_t*)dalloc(max_edges3 * 4);
-    uint32_t* chunk_sums = (uint32_t*)dalloc((size_t)max_chunks * 4);
-    float* d_N = (float*)dalloc(nv * 12);
-    float* d_trig = (float*)dalloc(c.trig.size() * 4);
-    int32_t* d_ioff = (int32_t*)dalloc(c.interior_off.size() * 4);
-    int32_t* d_boff = (int32_t*)dalloc(c.boundary_off.size() * 4);
-    const bool prof = std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr;   // the kernels' time, uploads and downloads excluded, to stderr
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int rc = -1;
-    for (void* p : allocs) if (!p) { err = "out of device memory"; goto fail; }
-    {
-        const dim3 b(256);
-        int cur = 0;
-        uint64_t V = c.n_verts, E = c.n_edges, F = c.n_faces;
-        if (prof) { PLS_CHECK(hipEventCreate(&ev0)); PLS_CHECK(hipEventCreate(&ev1)); }
-        PLS_CHECK(hipMemcpyAsync(lv[0].P, P, V * 12, hipMemcpyHostToDevice, stream));
-        PLS_CHECK(hipMemcpyAsync(lv[0].start_face, c.start_face.data(), V * 4, hipMemcpyHostToDevice, stream));
-        PLS_CHECK(hipMemcpyAsync(lv[0].vflags, c.vflags.data(), V * 4, hipMemcpyHostToDevice, stream));
-        PLS_CHECK(hipMemcpyAsync(lv[0].fv, c.fv.data(), F * 12, hipMemcpyHostToDevice, stream));
-        PLS_CHECK(hipMemcpyAsync(lv[0].ff, c.ff.data(), F * 12, hipMemcpyHostToDevice, stream));
-        if (!c.trig.empty()) PLS_CHECK(hipMemcpyAsync(d_trig, c.trig.data(), c.trig.size() * 4, hipMemcpyHostToDevice, stream));
-        PLS_CHECK(hipMemcpyAsync(d_ioff, c.interior_off.data(), c.interior_off.size() * 4, hipMemcpyHostToDevice, stream));
-        PLS_CHECK(hipMemcpyAsync(d_boff, c.boundary_off.data(), c.boundary_off.size() * 4, hipMemcpyHostToDevice, stream));
-        if (prof) PLS_CHECK(hipEventRecord(ev0, stream));
-        for (int l = 0; l < n_levels; l++) {
-            Mesh& in = lv[cur]; Mesh& out = lv[cur ^ 1];
-            in.n_verts = (uint32_t)V; in.n_faces = (uint32_t)F;
-            const uint32_t n_fe = 3u * (uint32_t)F, n_chunks = (n_fe + CHUNK - 1u) / CHUNK;
-            hipLaunchKernelGGL(k_even, dim3(((uint32_t)V + 255u) / 256u), b, 0, stream, in, out);
-            hipLaunchKernelGGL(k_owner_flags, dim3(n_chunks), b, 0, stream, in, scan, chunk_sums);
-            hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(1024), 0, stream, chunk_sums, n_chunks);
-            hipLaunchKernelGGL(k_scan_write, dim3(n_chunks), b, 0, stream, scan, n_fe, chunk_sums);
-            hipLaunchKernelGGL(k_edge_verts, dim3((n_fe + 255u) / 256u), b, 0, stream, in, out, scan);
-            hipLaunchKernelGGL(k_child_faces, dim3((4u * (uint32_t)F + 255u) / 256u), b, 0, stream, in, out, scan);
-            PLS_CHECK(hipGetLastError());
-            const uint64_t nV = V + E, nE = 2 * E + 3 * F, nF = 4 * F;
-            V = nV; E = nE; F = nF;
-            cur ^= 1;
-        }
-        if (V != c.out_verts || F != c.out_faces) { err = "level counts disagree with the control mesh's"; goto fail; }
-        Mesh& m = lv[cur];
-        m.n_verts = (uint32_t)V; m.n_faces = (uint32_t)F;
-        float* p_limit = lv[cur ^ 1].P;   // the other level's positions are done with
-        const dim3 per_vert(((uint32_t)V + 255u) / 256u);
-        hipLaunchKernelGGL(k_limit, per_vert, b, 0, stream, m, p_limit);
-        hipLaunchKernelGGL(k_normals, per_vert, b, 0, stream, m, (const float*)p_limit, (const float*)d_trig, (const int32_t*)d_ioff, (const int32_t*)d_boff, (uint32_t)c.interior_off.size(), d_N);
-        if (o2w_m) {
-            M16 a, ai;
-            for (int k = 0; k < 16; k++) { a.m[k] = o2w_m[k]; ai.m[k] = o2w_minv[k]; }
-            hipLaunchKernelGGL(k_world, per_vert, b, 0, stream, (uint32_t)V, a, ai, p_limit, d_N);
-        }
-        PLS_CHECK(hipGetLastError());
-        if (prof) PLS_CHECK(hipEventRecord(ev1, stream));
-        PLS_CHECK(hipMemcpyAsync(out_P, p_limit, V * 12, hipMemcpyDeviceToHost, stream));
-        PLS_CHECK(hipMemcpyAsync(out_N, d_N, V * 12, hipMemcpyDeviceToHost, stream));
-        PLS_CHECK(hipMemcpyAsync(out_idx, m.fv, F * 12, hipMemcpyDeviceToHost, stream));   // face.v[0..3] in face order (:639-643); no index is negative
-        PLS_CHECK(hipStreamSynchronize(stream));
-        if (prof) {
-            float ms = 0.0f;
-            PLS_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
-            std::fprintf(stderr, "loopsubdiv_device faces=%u levels=%d triangles=%llu: kernels %.3f ms\n", c.n_faces, n_levels, (unsigned long long)c.out_faces, ms);
-        }
-        rc = 0;
+    uint32_t* scan = arena.alloc<uint32_t>(max_edges3);
+    uint32_t* chunk_sums = arena.alloc<uint32_t>((size_t)max_chunks);
+    float* d_N = arena.alloc<float>(nv * 3);
+    float* d_trig = arena.upload(c.trig.data(), c.trig.size());
+    int32_t* d_ioff = arena.upload(c.interior_off.data(), c.interior_off.size());
+    int32_t* d_boff = arena.upload(c.boundary_off.data(), c.boundary_off.size());
+    const bool prof = build_profile_on();   // the kernels' time, uploads and downloads excluded, to stderr
+    DeviceEvent ev0, ev1;
+    if (!arena.ok()) { err = arena.why(); return -1; }
+    const dim3 b(256);
+    int cur = 0;
+    uint64_t V = c.n_verts, E = c.n_edges, F = c.n_faces;
+    if (prof) { PH_BUILD_CHECK(hipEventCreate(&ev0.e)); PH_BUILD_CHECK(hipEventCreate(&ev1.e)); }
+    PH_BUILD_CHECK(hipMemcpyAsync(lv[0].P, P, V * 12, hipMemcpyHostToDevice, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(lv[0].start_face, c.start_face.data(), V * 4, hipMemcpyHostToDevice, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(lv[0].vflags, c.vflags.data(), V * 4, hipMemcpyHostToDevice, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(lv[0].fv, c.fv.data(), F * 12, hipMemcpyHostToDevice, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(lv[0].ff, c.ff.data(), F * 12, hipMemcpyHostToDevice, stream));
+    if (prof) PH_BUILD_CHECK(hipEventRecord(ev0.e, stream));
+    for (int l = 0; l < n_levels; l++) {
+        Mesh& in = lv[cur]; Mesh& out = lv[cur ^ 1];
+        in.n_verts = (uint32_t)V; in.n_faces = (uint32_t)F;
+        const uint32_t n_fe = 3u * (uint32_t)F, n_chunks = (n_fe + CHUNK - 1u) / CHUNK;
+        hipLaunchKernelGGL(k_even, dim3(((uint32_t)V + 255u) / 256u), b, 0, stream, in, out);
+        hipLaunchKernelGGL(k_owner_flags, dim3(n_chunks), b, 0, stream, in, scan, chunk_sums);
+        hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, chunk_sums, n_chunks);
+        hipLaunchKernelGGL(k_scan_write, dim3(n_chunks), b, 0, stream, scan, n_fe, chunk_sums);
+        hipLaunchKernelGGL(k_edge_verts, dim3((n_fe + 255u) / 256u), b, 0, stream, in, out, scan);
+        hipLaunchKernelGGL(k_child_faces, dim3((4u * (uint32_t)F + 255u) / 256u), b, 0, stream, in, out, scan);
+        PH_BUILD_CHECK(hipGetLastError());
+        const uint64_t nV = V + E, nE = 2 * E + 3 * F, nF = 4 * F;
+        V = nV; E = nE; F = nF;
+        cur ^= 1;
     }
-fail:
-    if (rc != 0) (void)hipStreamSynchronize(stream);   // nothing of ours is in flight when the buffers go
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    for (void* p : allocs) if (p) (void)hipFree(p);
-    return rc;
+    if (V != c.out_verts || F != c.out_faces) { err = "level counts disagree with the control mesh's"; return -1; }
+    Mesh& m = lv[cur];
+    m.n_verts = (uint32_t)V; m.n_faces = (uint32_t)F;
+    float* p_limit = lv[cur ^ 1].P;   // the other level's positions are done with
+    const dim3 per_vert(((uint32_t)V + 255u) / 256u);
+    hipLaunchKernelGGL(k_limit, per_vert, b, 0, stream, m, p_limit);
+    hipLaunchKernelGGL(k_normals, per_vert, b, 0, stream, m, (const float*)p_limit, (const float*)d_trig, (const int32_t*)d_ioff, (const int32_t*)d_boff, (uint32_t)c.interior_off.size(), d_N);
+    if (o2w_m) {
+        M16 a, ai;
+        for (int k = 0; k < 16; k++) { a.m[k] = o2w_m[k]; ai.m[k] = o2w_minv[k]; }
+        hipLaunchKernelGGL(k_world, per_vert, b, 0, stream, (uint32_t)V, a, ai, p_limit, d_N);
+    }
+    PH_BUILD_CHECK(hipGetLastError());
+    if (prof) PH_BUILD_CHECK(hipEventRecord(ev1.e, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(out_P, p_limit, V * 12, hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(out_N, d_N, V * 12, hipMemcpyDeviceToHost, stream));
+    PH_BUILD_CHECK(hipMemcpyAsync(out_idx, m.fv, F * 12, hipMemcpyDeviceToHost, stream));   // face.v[0..3] in face order (:639-643); no index is negative
+    PH_BUILD_CHECK(hipStreamSynchronize(stream));
+    if (prof) {
+        float ms = 0.0f;
+        PH_BUILD_CHECK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
+        std::fprintf(stderr, "loopsubdiv_device faces=%u levels=%d triangles=%llu: kernels %.3f ms\n", c.n_faces, n_levels, (unsigned long long)c.out_faces, ms);
+    }
+    return 0;   // (the arena waits for the stream before its buffers go, on every way out)
 }
 
 }  // namespace phost

@@ -87,6 +87,19 @@ static void drop_bulk(PbrtHipScene* r) {
     drop(r->P); drop(r->N); drop(r->S); drop(r->UV); drop(r->idx); drop(r->tri_mesh); drop(r->tri_flags); drop(r->bvh.nodes); drop(r->bvh.tris);
 }
 
+// a tree that lives on the handle's device -> a copy of it on device `dst_device` (the current one), by hipMemcpyPeer
+static int peer_copy_tree(PbrtHipScene* s, const DeviceTree& src, int dst_device, DeviceTree& dst) {
+    const size_t nb = src.n_nodes * sizeof(Node64), tb = src.n_tris * sizeof(TriRec);
+    if (hipMalloc((void**)&dst.nodes, nb ? nb : 16) != hipSuccess || hipMalloc((void**)&dst.tris, tb ? tb : 16) != hipSuccess) {
+        (void)hipGetLastError(); free_tree_dev(dst);
+        return set_err(s, PBRT_HIP_ERR_OOM, "render: no device memory for the tree on device " + std::to_string(dst_device));
+    }
+    dst.n_nodes = src.n_nodes; dst.n_tris = src.n_tris;
+    if (nb) PH_CHECK(s, hipMemcpyPeer(dst.nodes, dst_device, src.nodes, s->device, nb));
+    if (tb) PH_CHECK(s, hipMemcpyPeer(dst.tris, dst_device, src.tris, s->device, tb));
+    return PBRT_HIP_OK;
+}
+
 // The handle's captured state -> every replica.  A bulk copy only when something changed since the replicas last uploaded it, and then ONE replica at a time (copy, upload,
 // drop the bulky host arrays again): at most one extra copy of the scene is ever held on the host.  A tree that was built on the first device and lives only there
 // (pbrt_hip_build_accel_device) goes to the other devices by hipMemcpyPeer — no 730 MB round trip through the host for 10 M triangles.
@@ -97,19 +110,10 @@ static int sync_replicas(PbrtHipScene* s) {
         if (bulk) {
             m.replicas_current = false;   // until every replica has the new state
             PH_CHECK(s, hipSetDevice(r->device));
-            free_tree_dev(r);
+            free_tree_dev(r->dev_tree);
             static_cast<SceneHostState&>(*r) = static_cast<const SceneHostState&>(*s);   // (a device-built tree leaves bvh.nodes / bvh.tris empty: nothing bulky to copy there)
             r->uploaded = false; r->light_strategy_uploaded = -1; r->count_traversal = false;
-            if (s->tree_dev_tris) {
-                const size_t nb = s->bvh.interior_nodes * sizeof(Node64), tb = s->tree_dev_n_tris * sizeof(TriRec);
-                if (hipMalloc(&r->tree_dev_nodes, nb ? nb : 16) != hipSuccess || hipMalloc(&r->tree_dev_tris, tb ? tb : 16) != hipSuccess) {
-                    (void)hipGetLastError(); free_tree_dev(r);
-                    return set_err(s, PBRT_HIP_ERR_OOM, "render: no device memory for the tree on device " + std::to_string(r->device));
-                }
-                r->tree_dev_n_tris = s->tree_dev_n_tris;
-                if (nb) PH_CHECK(s, hipMemcpyPeer(r->tree_dev_nodes, r->device, s->tree_dev_nodes, s->device, nb));
-                if (tb) PH_CHECK(s, hipMemcpyPeer(r->tree_dev_tris, r->device, s->tree_dev_tris, s->device, tb));
-            }
+            if (s->accel_on_device()) { const int rc = peer_copy_tree(s, s->dev_tree, r->device, r->dev_tree); if (rc != PBRT_HIP_OK) return rc; }
             const int rc = upload_scene(r);
             if (rc != PBRT_HIP_OK) { s->err = "device " + std::to_string(r->device) + ": " + r->err; return rc; }
             drop_bulk(r);

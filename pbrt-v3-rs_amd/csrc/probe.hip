@@ -649,13 +649,9 @@ int pbrt_hip_surface_probe_batch(PbrtHipScene* s, int op, int variant, uint32_t 
     if (n == 0) return PBRT_HIP_OK;
     PH_CHECK(s, hipSetDevice(s->device));
     // the leaf records, to check every hit against: the host's copy, or the device's where the tree was left there
-    std::vector<TriRec> fetched;
-    const TriRec* recs = s->bvh.tris.data(); size_t n_recs = s->bvh.tris.size();
-    if (n_recs == 0 && s->tree_dev_tris) {
-        fetched.resize(s->tree_dev_n_tris);
-        PH_CHECK(s, hipMemcpy(fetched.data(), s->tree_dev_tris, fetched.size() * sizeof(TriRec), hipMemcpyDeviceToHost));
-        recs = fetched.data(); n_recs = fetched.size();
-    }
+    std::vector<TriRec> recs;
+    if (int frc = s->fetch_leaf_records(recs)) return frc;
+    const size_t n_recs = recs.size();
     for (uint64_t i = 0; i < n; i++) {
         const PbrtHipHit& h = hits[i];
         if (h.prim == 0xFFFFFFFFu || h.prim >= s->tri_mesh.size()) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "surface_probe_batch: a hit names no primitive");

@@ -76,19 +76,28 @@ struct SceneHostState {
 
 struct MultiDevice;  // multi.hip
 
+enum class AccelBuilder { Host, Device, DeviceShapes };   // which builder a public entry asks build_accel (api.hip) for: pbrt_hip_build_accel, _device, _device_shapes
+// A tree that stays where a device builder made it (the SAH builder's, bvh_sah_device.hip): device allocations the handle owns, and how many entries each holds.
+struct DeviceTree { Node64* nodes = nullptr; TriRec* tris = nullptr; size_t n_nodes = 0, n_tris = 0; };
+
 struct PbrtHipScene : SceneHostState {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    bool build_on_device = false;    // set for the duration of pbrt_hip_build_accel_device / pbrt_hip_build_accel_device_shapes
-    bool build_sah_quadrics_on_device = false;   // ... of pbrt_hip_build_accel_device_shapes only: the SAH device builder takes the scene's quadrics
     MultiDevice* multi = nullptr;    // non-null on a handle made by pbrt_hip_scene_create_multi: the other devices' contexts and the exchange state
 
     // ---- device residency ---------------------------------------------------------------------------------------------
     DeviceScene ds{};
     std::vector<void*> owned;        // every hipMalloc of the scene, freed on destroy / rebuild
-    // a tree pbrt_hip_build_accel_device(0, ..) left where it was built: `bvh.nodes` / `bvh.tris` stay empty on the host (accel_copy reads them back on request; the multi-device driver replicates by hipMemcpyPeer)
-    void* tree_dev_nodes = nullptr; void* tree_dev_tris = nullptr; size_t tree_dev_n_tris = 0;
+    // a tree pbrt_hip_build_accel_device(0, ..) left where it was built: `bvh.nodes` / `bvh.tris` stay empty on the host.  Only build_accel, free_tree_dev and the multi-device
+    // driver's peer copy touch it; every reader goes through the accessors below (the arrays are device memory when accel_on_device(), else the host vectors') and never asks where the tree is.
+    DeviceTree dev_tree;
+    bool accel_on_device() const { return dev_tree.tris != nullptr; }
+    const Node64* accel_nodes() const { return accel_on_device() ? dev_tree.nodes : bvh.nodes.data(); }
+    size_t accel_n_nodes() const { return accel_on_device() ? dev_tree.n_nodes : bvh.nodes.size(); }
+    const TriRec* accel_records() const { return accel_on_device() ? dev_tree.tris : bvh.tris.data(); }
+    size_t accel_n_records() const { return accel_on_device() ? dev_tree.n_tris : bvh.tris.size(); }
+    int fetch_leaf_records(std::vector<TriRec>& out);   // the leaf records on the host: a device-to-host copy or a plain copy (api.hip); a PBRT_HIP_* code
     bool uploaded = false;
     // the light side of the scene's shade-pass features (shade_shapes.h), derived by upload_scene from the light list it uploads: every call that changes a light clears `uploaded`,
     // so the next render derives them again.  The sampler and the light strategy are read when the variant is picked (wavefront.hip, plan_path_frame).
@@ -150,11 +159,11 @@ void free_wavefront(PbrtHipScene* s);
 // bvh_device.hip.  forest non-null: the forest form, as build_sah_device's below (the arrays come back on the host)
 int build_hlbvh_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, const ForestSpec* forest = nullptr,
                        std::vector<ForestTreeOut>* trees_out = nullptr);
-// bvh_sah_device.hip.  keep_nodes / keep_tris non-null: the Node64 / TriRec arrays are not copied to `out` but handed over as device allocations (the caller frees them)
+// bvh_sah_device.hip.  keep non-null: the Node64 / TriRec arrays are not copied to `out` but handed over as device allocations (the caller frees them: free_tree_dev)
 // forest non-null: the scene's aggregate and its instanced objects' aggregates in one build, laid out as build_forest_host lays them out; trees_out: every tree's root
-int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, void** keep_nodes = nullptr, void** keep_tris = nullptr,
+int build_sah_device(const BuildInput& in, int max_prims_in_node, hipStream_t stream, BuildOutput& out, std::string& err, DeviceTree* keep = nullptr,
                      const ForestSpec* forest = nullptr, std::vector<ForestTreeOut>* trees_out = nullptr);
-void free_tree_dev(PbrtHipScene* s);
+void free_tree_dev(DeviceTree& t);   // on the current device
 // wavefront.hip: the renderer's building blocks, shared with the multi-device driver (multi.hip)
 #define PH_MAX_TILE_PARTS 64
 int check_render_args(PbrtHipScene* s, int max_depth, int light_strategy, const int* pixel_bounds, int tile_size, int part, int parts);
