@@ -1,6 +1,7 @@
-// What the device-side builders (bvh_device.hip, bvh_sah_device.hip, loopsubdiv.hip) share on the HIP side: a scratch arena, the upload of a checked BuildInput
+// What the device-side builders (bvh_device.hip, bvh_sah_device.hip, loopsubdiv.hip) share on the HIP side: the scratch arena (device_arena.h), the upload of a checked BuildInput
 // (device_build_input.h), the PBRT_HIP_BUILD_PROFILE lap printer and the one-block exclusive scan.
 #pragma once
+#include "device_arena.h"
 #include "device_build_input.h"
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -15,26 +16,6 @@ namespace phost {
 #define PH_BUILD_CHECK(call) \
     do { hipError_t e__ = (call); if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); (void)hipGetLastError(); return -1; } } while (0)
 
-// Device scratch of one build.  alloc and upload never throw: a failure gives null and is kept in why() (the first one), so a builder allocates everything it knows the size
-// of and asks ok() once.  The destructor waits for the stream (nothing of the build is in flight when the buffers go) and frees whatever was not released to the caller.
-class DeviceArena {
-public:
-    explicit DeviceArena(hipStream_t stream) : stream_(stream) {}
-    DeviceArena(const DeviceArena&) = delete; DeviceArena& operator=(const DeviceArena&) = delete;
-    ~DeviceArena() { if (!owned_.empty()) (void)hipStreamSynchronize(stream_); for (void* p : owned_) if (p) (void)hipFree(p); }
-    template <class T> T* alloc(size_t count) { void* p = nullptr; if (failed(hipMalloc(&p, count ? count * sizeof(T) : 16), "hipMalloc")) return nullptr; owned_.push_back(p); return static_cast<T*>(p); }
-    template <class T> T* upload(const T* src, size_t count) {   // alloc, and the copy queued on the stream; the caller keeps `src` alive past this arena (declare it first)
-        T* p = alloc<T>(count);
-        if (p && count) (void)failed(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream_), "hipMemcpyAsync (upload)");
-        return p;
-    }
-    bool ok() const { return why_.empty(); }
-    const std::string& why() const { return why_; }   // "<the HIP call>: <its error string>"
-    template <class T> T* release(T* p) { for (void*& q : owned_) if (q == (void*)p) q = nullptr; return p; }   // handed to the caller, who frees it
-private:
-    bool failed(hipError_t e, const char* call) { if (e == hipSuccess) return false; (void)hipGetLastError(); if (why_.empty()) why_ = std::string(call) + ": " + hipGetErrorString(e); return true; }
-    hipStream_t stream_; std::vector<void*> owned_; std::string why_;
-};
 struct DeviceEvent { hipEvent_t e = nullptr; ~DeviceEvent() { if (e) (void)hipEventDestroy(e); } };
 
 inline bool build_profile_on() { return std::getenv("PBRT_HIP_BUILD_PROFILE") != nullptr; }

@@ -2,6 +2,7 @@
 // pbrt_hip_bump_probe_batch, pbrt_hip_traverse_probe, pbrt_hip_surface_probe_batch, pbrt_hip_spatial_probe_begin / _batch / _voxel): the device's BSDF, sampler, light, texture and hit-to-interaction code,
 // the spatial light distribution, the ray binning between wavefront rounds and the traversal kernel's queue on explicit inputs.
 // Each kernel only unpacks its arguments and calls the PH_DEV functions the render kernels call (pt_device.h, bsdf_general.h, wf_device.h, texture.h, sphere_light.h, shading_diff.h, spatial.h); no formula lives here.
+// Each entry point makes its checks, then upload_scene, then names its device arrays on a ProbeStage (probe_stage.h), launches and returns the stage's finish().
 #define PH_OUTLINE_MATH 1
 #include "scene_host.h"
 #include "pt_device.h"
@@ -12,7 +13,9 @@
 #include "shading_diff.h"
 #include "spatial.h"
 #include "film_plan.h"
+#include "probe_stage.h"
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace ph {
@@ -74,18 +77,30 @@ __global__ __launch_bounds__(256) void sampler_value_kernel(DeviceScene sc, Samp
     out[i] = sampler_dim(sc, sp, c, c.dim);
 }
 
+// What the two light probe kernels share.  The reference point: a SurfHit that holds what the light code reads (p, p_error, n, time), from 10 floats ...
+PH_DEV SurfHit light_probe_ref(const float* rf) {
+    SurfHit hit;
+    hit.p = ld3(rf); hit.p_error = ld3(rf + 3); hit.n = ld3(rf + 6); hit.time = rf[9];
+    hit.wo = mk3(0.0f, 0.0f, 0.0f); hit.ns = hit.n; hit.dpdu_s = hit.wo; hit.prim = 0u;
+    return hit;
+}
+// ... and op 0's part of the output row: the LiSample, then the shadow ray shade_kernel makes next if it is valid
+PH_DEV void put_li_sample(float* o, const SurfHit& hit, const LiSample& r) {
+    o[0] = r.wi.x; o[1] = r.wi.y; o[2] = r.wi.z; o[3] = r.pdf; o[4] = r.value.r; o[5] = r.value.g; o[6] = r.value.b; o[7] = r.valid ? 1.0f : 0.0f;
+    o[8] = r.vp.x; o[9] = r.vp.y; o[10] = r.vp.z; o[11] = r.vperr.x; o[12] = r.vperr.y; o[13] = r.vperr.z; o[14] = r.vn.x; o[15] = r.vn.y; o[16] = r.vn.z;
+    if (!r.valid) return;
+    const RayIn sr = spawn_ray_to_hit(hit, r.vp, r.vperr, r.vn);
+    o[17] = sr.ox; o[18] = sr.oy; o[19] = sr.oz; o[20] = sr.dx; o[21] = sr.dy; o[22] = sr.dz; o[23] = sr.t_max;
+}
 // VARIANT 0: light_le / light_sample_li / light_pdf_li<true>, as the textured shade kernels and spatial_compute_kernel instantiate them; 1: the <false> instantiations of the
-// texture-free kernels; 2: wh_light_sample_li<true>, the Whitted light loop's (op 0 only).  The reference point is a SurfHit that holds what the light code reads: p, p_error, n, time.
+// texture-free kernels; 2: wh_light_sample_li<true>, the Whitted light loop's (op 0 only).
 // PBRT_HIP_LIGHT_PROBE_STRIDE floats out per probe, zeroed first (include/pbrt_hip.h gives the layout)
 template <int VARIANT>
 __global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene sc, uint32_t light, int op, uint32_t n, const float* ref_in, const float* u_in, const float* wi_in, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     constexpr bool MAP = VARIANT != 1;
-    const float* rf = ref_in + 10 * (size_t)i;
-    SurfHit hit;
-    hit.p = ld3(rf); hit.p_error = ld3(rf + 3); hit.n = ld3(rf + 6); hit.time = rf[9];
-    hit.wo = mk3(0.0f, 0.0f, 0.0f); hit.ns = hit.n; hit.dpdu_s = hit.wo; hit.prim = 0u;
+    const SurfHit hit = light_probe_ref(ref_in + 10 * (size_t)i);
     const f2 u = mk2(u_in[2 * (size_t)i], u_in[2 * (size_t)i + 1]);
     const f3 wi = ld3(wi_in + 3 * (size_t)i);
     const LightRec& l = sc.lights[light];
@@ -93,12 +108,7 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene
     for (int k = 0; k < PBRT_HIP_LIGHT_PROBE_STRIDE; k++) o[k] = 0.0f;
     if (op == 0) {
         const LiSample r = VARIANT == 2 ? wh_light_sample_li<true>(sc, l, hit, u) : light_sample_li<MAP>(sc, l, hit, u);
-        o[0] = r.wi.x; o[1] = r.wi.y; o[2] = r.wi.z; o[3] = r.pdf; o[4] = r.value.r; o[5] = r.value.g; o[6] = r.value.b; o[7] = r.valid ? 1.0f : 0.0f;
-        o[8] = r.vp.x; o[9] = r.vp.y; o[10] = r.vp.z; o[11] = r.vperr.x; o[12] = r.vperr.y; o[13] = r.vperr.z; o[14] = r.vn.x; o[15] = r.vn.y; o[16] = r.vn.z;
-        if (r.valid) {   // the shadow ray shade_kernel makes next
-            const RayIn sr = spawn_ray_to_hit(hit, r.vp, r.vperr, r.vn);
-            o[17] = sr.ox; o[18] = sr.oy; o[19] = sr.oz; o[20] = sr.dx; o[21] = sr.dy; o[22] = sr.dz; o[23] = sr.t_max;
-        }
+        put_li_sample(o, hit, r);
     } else if (op == 1) {
         o[0] = light_pdf_li<MAP>(sc, l, hit, wi);
     } else {
@@ -111,21 +121,13 @@ __global__ __launch_bounds__(PH_PROBE_BLOCK) void light_probe_kernel(DeviceScene
 __global__ __launch_bounds__(PH_PROBE_BLOCK) void sphere_light_probe_kernel(DeviceScene sc, uint32_t light, int op, uint32_t n, const float* ref_in, const float* u_in, const float* wi_in, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float* rf = ref_in + 10 * (size_t)i;
-    SurfHit hit;
-    hit.p = ld3(rf); hit.p_error = ld3(rf + 3); hit.n = ld3(rf + 6); hit.time = rf[9];
-    hit.wo = mk3(0.0f, 0.0f, 0.0f); hit.ns = hit.n; hit.dpdu_s = hit.wo; hit.prim = 0u;
+    const SurfHit hit = light_probe_ref(ref_in + 10 * (size_t)i);
     const LightRec& l = sc.lights[light];
     float* o = out + PBRT_HIP_LIGHT_PROBE_STRIDE * (size_t)i;
     for (int k = 0; k < PBRT_HIP_LIGHT_PROBE_STRIDE; k++) o[k] = 0.0f;
     if (op == 0) {
         const LiSample r = wh_light_sample_li<true>(sc, l, hit, mk2(u_in[2 * (size_t)i], u_in[2 * (size_t)i + 1]));
-        o[0] = r.wi.x; o[1] = r.wi.y; o[2] = r.wi.z; o[3] = r.pdf; o[4] = r.value.r; o[5] = r.value.g; o[6] = r.value.b; o[7] = r.valid ? 1.0f : 0.0f;
-        o[8] = r.vp.x; o[9] = r.vp.y; o[10] = r.vp.z; o[11] = r.vperr.x; o[12] = r.vperr.y; o[13] = r.vperr.z; o[14] = r.vn.x; o[15] = r.vn.y; o[16] = r.vn.z;
-        if (r.valid) {   // the shadow ray shade_kernel makes next
-            const RayIn sr = spawn_ray_to_hit(hit, r.vp, r.vperr, r.vn);
-            o[17] = sr.ox; o[18] = sr.oy; o[19] = sr.oz; o[20] = sr.dx; o[21] = sr.dy; o[22] = sr.dz; o[23] = sr.t_max;
-        }
+        put_li_sample(o, hit, r);
     } else {
         o[0] = sl_light_pdf_li(sc, l, hit, ld3(wi_in + 3 * (size_t)i));
     }
@@ -310,12 +312,15 @@ __global__ __launch_bounds__(256) void spatial_probe_pick_kernel(DeviceScene sc,
 using namespace phost;
 
 namespace {
-// one scratch allocation per call, split into 256-byte aligned parts; freed by the caller's guard
-struct Scratch {
-    void* p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-};
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+// f(std::integral_constant<int, V>()) for the V of 0 .. N - 1 that `variant` is, so that a kernel template takes it: [&](auto v) { ... kernel<v()> ... }.  The caller has refused every other value.
+template <int N, class F> void with_variant(int variant, F&& f) {
+    if constexpr (N > 1) if (variant < N - 1) return with_variant<N - 1>(variant, f);
+    f(std::integral_constant<int, N - 1>());
+}
+// a caller's rays as the kernels read them (load_ray): PbrtHipRay and ph::RayIn are one layout under two names
+static_assert(sizeof(PbrtHipRay) == sizeof(ph::RayIn), "PbrtHipRay is ph::RayIn's layout");
+const ph::RayIn* device_rays(const PbrtHipRay* rays) { return reinterpret_cast<const ph::RayIn*>(rays); }
+dim3 probe_grid(uint64_t n) { return dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)); }   // of blocks of PH_PROBE_BLOCK threads, one thread per probe
 bool material_reads_a_texture(const MaterialRec& m) {
     return m.textured || m.kd_tex1 || m.bump_tex1 || m.sigma_tex1 || m.opacity_tex1 || m.amount_tex1 || m.rt_mode || m.refl_tex1 || m.trans_tex1 || m.index_tex1;
 }
@@ -336,16 +341,26 @@ int texture_probe_common(PbrtHipScene* s, const char* who, uint32_t tex, int var
     PH_CHECK(s, hipSetDevice(s->device));
     int rc;
     if ((rc = upload_scene(s))) return rc;   // textures do not need the accelerator: an empty one is fine
-    const size_t o_in = 0, o_out = o_in + up256(n * in_stride * 4), total = o_out + up256(n * out_stride * 4);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_in, in, n * in_stride * 4, hipMemcpyHostToDevice, s->stream));
-    launch(dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), (const float*)(d + o_in), (float*)(d + o_out));
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * out_stride * 4, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    ProbeStage st(s);
+    const float* d_in = st.in(in, n * in_stride);
+    float* d_out = st.out(out, n * out_stride);
+    if (!st.ok()) return st.finish();
+    launch(probe_grid(n), dim3(PH_PROBE_BLOCK), d_in, d_out);
+    return st.finish();
+}
+// what the two light probes do once each has made its own checks: `launch` starts the kernel on the staged ref (10 floats a probe), u (2), wi (3) and out (PBRT_HIP_LIGHT_PROBE_STRIDE)
+template <class Launch>
+int light_probe_common(PbrtHipScene* s, uint64_t n, const float* ref, const float* u, const float* wi, float* out, Launch launch) {
+    if (n == 0) return PBRT_HIP_OK;
+    PH_CHECK(s, hipSetDevice(s->device));
+    int rc;
+    if ((rc = upload_scene(s))) return rc;
+    ProbeStage st(s);
+    const float* d_ref = st.in(ref, n * 10), *d_u = st.in(u, n * 2), *d_wi = st.in(wi, n * 3);
+    float* d_out = st.out(out, n * PBRT_HIP_LIGHT_PROBE_STRIDE);
+    if (!st.ok()) return st.finish();
+    launch(probe_grid(n), dim3(PH_PROBE_BLOCK), d_ref, d_u, d_wi, d_out);
+    return st.finish();
 }
 }  // namespace
 static_assert(PH_PROBE_BLOCK <= PH_TEX_LDS_THREADS, "the texture probes evaluate textures: their blocks must fit the evaluator's LDS stack");
@@ -372,25 +387,15 @@ int pbrt_hip_bsdf_probe_batch(PbrtHipScene* s, uint32_t material, int op, int pa
     PH_CHECK(s, hipSetDevice(s->device));
     int rc;
     if ((rc = upload_scene(s))) return rc;   // materials and lobes; an empty accelerator is fine
-    const size_t o_wo = 0, o_wi = o_wo + up256(n * 12), o_u = o_wi + up256(n * 12), o_fl = o_u + up256(n * 8), o_out = o_fl + up256(n * 4), total = o_out + up256(n * 32);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_wo, wo, n * 12, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_wi, wi, n * 12, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 8, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_fl, flags, n * 4, hipMemcpyHostToDevice, s->stream));
-    const dim3 grid((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), block(PH_PROBE_BLOCK);
-    if (path == 0)
-        hipLaunchKernelGGL(ph::bsdf_probe_kernel<true>, grid, block, 0, s->stream, s->ds, material, op, (uint32_t)n, (const float*)(d + o_wo), (const float*)(d + o_wi), (const float*)(d + o_u),
-                           (const uint32_t*)(d + o_fl), fr, (float*)(d + o_out));
-    else
-        hipLaunchKernelGGL(ph::bsdf_probe_kernel<false>, grid, block, 0, s->stream, s->ds, material, op, (uint32_t)n, (const float*)(d + o_wo), (const float*)(d + o_wi), (const float*)(d + o_u),
-                           (const uint32_t*)(d + o_fl), fr, (float*)(d + o_out));
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * 32, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    ProbeStage st(s);
+    const float* d_wo = st.in(wo, n * 3), *d_wi = st.in(wi, n * 3), *d_u = st.in(u, n * 2);
+    const uint32_t* d_flags = st.in(flags, n);
+    float* d_out = st.out(out, n * 8);
+    if (!st.ok()) return st.finish();
+    with_variant<2>(path, [&](auto v) {   // path 0 is GEN = true
+        hipLaunchKernelGGL(ph::bsdf_probe_kernel<v() == 0>, probe_grid(n), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, material, op, (uint32_t)n, d_wo, d_wi, d_u, d_flags, fr, d_out);
+    });
+    return st.finish();
     });
 }
 
@@ -420,19 +425,13 @@ int pbrt_hip_sampler_value_batch(PbrtHipScene* s, uint64_t n, const int* xy, con
     PH_CHECK(s, hipSetDevice(s->device));
     int rc;
     if ((rc = upload_scene(s))) return rc;   // the sampler tables; an empty accelerator is fine
-    const size_t o_xy = 0, o_s = o_xy + up256(n * 8), o_d = o_s + up256(n * 4), o_out = o_d + up256(n * 4), total = o_out + up256(n * 4);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_xy, xy, n * 8, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_s, sample, n * 4, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_d, dim, n * 4, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(ph::sampler_value_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->stream, s->ds, s->sampler, (uint32_t)n, (const int*)(d + o_xy), (const uint32_t*)(d + o_s),
-                       (const uint32_t*)(d + o_d), use_lds ? 1 : 0, (float*)(d + o_out));
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * 4, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    ProbeStage st(s);
+    const int* d_xy = st.in(xy, n * 2);
+    const uint32_t* d_sample = st.in(sample, n), *d_dim = st.in(dim, n);
+    float* d_out = st.out(out, n);
+    if (!st.ok()) return st.finish();
+    hipLaunchKernelGGL(ph::sampler_value_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->stream, s->ds, s->sampler, (uint32_t)n, d_xy, d_sample, d_dim, use_lds ? 1 : 0, d_out);
+    return st.finish();
     });
 }
 
@@ -451,29 +450,9 @@ int pbrt_hip_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, int vari
             return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: a light whose shape is a quadric (a spherical, disk or cylinder area light) is sampled by variant 2, the Whitted light loop's sample_li, alone");
     }
     if (variant == 1 && l.map_mip1) return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "light_probe_batch: variant 1 is the code of scenes without textures; this light holds a radiance, projection or goniometric map");
-    if (n == 0) return PBRT_HIP_OK;
-    PH_CHECK(s, hipSetDevice(s->device));
-    int rc;
-    if ((rc = upload_scene(s))) return rc;
-    const size_t stride = PBRT_HIP_LIGHT_PROBE_STRIDE * sizeof(float);
-    const size_t o_ref = 0, o_u = o_ref + up256(n * 40), o_wi = o_u + up256(n * 8), o_out = o_wi + up256(n * 12), total = o_out + up256(n * stride);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_ref, ref, n * 40, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 8, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_wi, wi, n * 12, hipMemcpyHostToDevice, s->stream));
-    const dim3 grid((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), block(PH_PROBE_BLOCK);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, light, op, (uint32_t)n, (const float*)(d + o_ref), (const float*)(d + o_u), (const float*)(d + o_wi), (float*)(d + o_out));
-    };
-    if (variant == 0) launch(ph::light_probe_kernel<0>);
-    else if (variant == 1) launch(ph::light_probe_kernel<1>);
-    else launch(ph::light_probe_kernel<2>);
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    return light_probe_common(s, n, ref, u, wi, out, [&](dim3 grid, dim3 block, const float* d_ref, const float* d_u, const float* d_wi, float* d_out) {
+        with_variant<3>(variant, [&](auto v) { hipLaunchKernelGGL(ph::light_probe_kernel<v()>, grid, block, 0, s->stream, s->ds, light, op, (uint32_t)n, d_ref, d_u, d_wi, d_out); });
+    });
     });
 }
 
@@ -487,24 +466,9 @@ int pbrt_hip_sphere_light_probe_batch(PbrtHipScene* s, uint32_t light, int op, u
     const LightRec& l = s->lights[light];
     if (l.type != PH_L_AREA || l.prim >= s->tri_mesh.size() || !(s->meshes[s->tri_mesh[l.prim]].flags & PH_MESH_QUADRIC))
         return set_err(s, PBRT_HIP_ERR_UNSUPPORTED, "sphere_light_probe_batch: the light's shape is not a quadric (a spherical, disk or cylinder area light: pbrt_hip_add_sphere_light, pbrt_hip_add_quadric_light); pbrt_hip_light_probe_batch probes the others");
-    if (n == 0) return PBRT_HIP_OK;
-    PH_CHECK(s, hipSetDevice(s->device));
-    int rc;
-    if ((rc = upload_scene(s))) return rc;
-    const size_t stride = PBRT_HIP_LIGHT_PROBE_STRIDE * sizeof(float);
-    const size_t o_ref = 0, o_u = o_ref + up256(n * 40), o_wi = o_u + up256(n * 8), o_out = o_wi + up256(n * 12), total = o_out + up256(n * stride);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_ref, ref, n * 40, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 8, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_wi, wi, n * 12, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(ph::sphere_light_probe_kernel, dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, light, op, (uint32_t)n,
-                       (const float*)(d + o_ref), (const float*)(d + o_u), (const float*)(d + o_wi), (float*)(d + o_out));
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    return light_probe_common(s, n, ref, u, wi, out, [&](dim3 grid, dim3 block, const float* d_ref, const float* d_u, const float* d_wi, float* d_out) {
+        hipLaunchKernelGGL(ph::sphere_light_probe_kernel, grid, block, 0, s->stream, s->ds, light, op, (uint32_t)n, d_ref, d_u, d_wi, d_out);
+    });
     });
 }
 
@@ -553,26 +517,21 @@ int pbrt_hip_spatial_probe_batch(PbrtHipScene* s, uint64_t n, const float* p, co
         return set_err(s, PBRT_HIP_ERR_STATE, "spatial_probe_batch: the scene's lights changed since pbrt_hip_spatial_probe_begin; call it again");
     uint32_t ctr[4] = {0, 0, 0, 0};
     if (n) {
-        const size_t o_p = 0, o_u = o_p + up256(n * 12), o_pi = o_u + up256(n * 4), o_l = o_pi + up256(n * 12), o_pdf = o_l + up256(n * 4), total = o_pdf + up256(n * 4);
-        Scratch sx;
-        PH_CHECK(s, hipMalloc(&sx.p, total));
-        char* d = static_cast<char*>(sx.p);
-        PH_CHECK(s, hipMemcpyAsync(d + o_p, p, n * 12, hipMemcpyHostToDevice, s->stream));
-        PH_CHECK(s, hipMemcpyAsync(d + o_u, u, n * 4, hipMemcpyHostToDevice, s->stream));
+        ProbeStage st(s);
+        const float* d_p = st.in(p, n * 3), *d_u = st.in(u, n);
+        int32_t* d_pi = st.out(strategy == 2 ? out_pi : nullptr, n * 3);   // (strategies 0 and 1 write no voxel: nothing comes down)
+        uint32_t* d_light = st.out(out_light, n);
+        float* d_pdf = st.out(out_pick_pdf, n);
+        if (!st.ok()) return st.finish();
         const dim3 grid((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)), block(256);
         if (strategy == 2) {
-            hipLaunchKernelGGL(ph::spatial_probe_mark_kernel, grid, block, 0, s->stream, sr, (uint32_t)n, (const float*)(d + o_p), (int32_t*)(d + o_pi));
+            hipLaunchKernelGGL(ph::spatial_probe_mark_kernel, grid, block, 0, s->stream, sr, (uint32_t)n, d_p, d_pi);
             PH_CHECK(s, hipGetLastError());
             spatial_probe_compute(s, sr);
             PH_CHECK(s, hipGetLastError());
         }
-        hipLaunchKernelGGL(ph::spatial_probe_pick_kernel, grid, block, 0, s->stream, s->ds, sr, (uint32_t)n, (const float*)(d + o_p), (const float*)(d + o_u), (uint32_t*)(d + o_l),
-                           (float*)(d + o_pdf));
-        PH_CHECK(s, hipGetLastError());
-        if (strategy == 2) PH_CHECK(s, hipMemcpyAsync(out_pi, d + o_pi, n * 12, hipMemcpyDeviceToHost, s->stream));
-        PH_CHECK(s, hipMemcpyAsync(out_light, d + o_l, n * 4, hipMemcpyDeviceToHost, s->stream));
-        PH_CHECK(s, hipMemcpyAsync(out_pick_pdf, d + o_pdf, n * 4, hipMemcpyDeviceToHost, s->stream));
-        PH_CHECK(s, hipStreamSynchronize(s->stream));
+        hipLaunchKernelGGL(ph::spatial_probe_pick_kernel, grid, block, 0, s->stream, s->ds, sr, (uint32_t)n, d_p, d_u, d_light, d_pdf);
+        if ((rc = st.finish())) return rc;
     }
     if (strategy == 2) PH_CHECK(s, hipMemcpy(ctr, sr.counters, sizeof ctr, hipMemcpyDeviceToHost));
     if (out_counters) std::memcpy(out_counters, ctr, sizeof ctr);
@@ -618,18 +577,12 @@ int pbrt_hip_curve_probe_batch(PbrtHipScene* s, uint32_t prim, int shadow, uint6
     PH_CHECK(s, hipSetDevice(s->device));
     int rc;
     if ((rc = upload_scene(s))) return rc;
-    const size_t stride = PBRT_HIP_CURVE_PROBE_STRIDE * sizeof(float);
-    const size_t o_rays = 0, o_out = o_rays + up256(n * sizeof(PbrtHipRay)), total = o_out + up256(n * stride);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_rays, rays, n * sizeof(PbrtHipRay), hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(ph::curve_probe_kernel, dim3((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, s->prim_quadric[prim] - 1u,
-                       shadow ? 1u : 0u, (uint32_t)n, (const ph::RayIn*)(d + o_rays), (float*)(d + o_out));
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * stride, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    ProbeStage st(s);
+    const ph::RayIn* d_rays = st.in(device_rays(rays), n);
+    float* d_out = st.out(out, n * PBRT_HIP_CURVE_PROBE_STRIDE);
+    if (!st.ok()) return st.finish();
+    hipLaunchKernelGGL(ph::curve_probe_kernel, probe_grid(n), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, s->prim_quadric[prim] - 1u, shadow ? 1u : 0u, (uint32_t)n, d_rays, d_out);
+    return st.finish();
     });
 }
 
@@ -671,38 +624,24 @@ int pbrt_hip_surface_probe_batch(PbrtHipScene* s, int op, int variant, uint32_t 
     }
     int rc;
     if ((rc = upload_scene(s))) return rc;
-    const size_t in_b = PBRT_HIP_SURFACE_PROBE_AUX * sizeof(float), out_b = PBRT_HIP_SURFACE_PROBE_STRIDE * sizeof(float);
-    const size_t o_rays = 0, o_hits = o_rays + up256(n * sizeof(PbrtHipRay)), o_aux = o_hits + up256(n * sizeof(PbrtHipHit)), o_out = o_aux + up256(n * in_b), total = o_out + up256(n * out_b);
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
-    PH_CHECK(s, hipMemcpyAsync(d + o_rays, rays, n * sizeof(PbrtHipRay), hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_hits, hits, n * sizeof(PbrtHipHit), hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_aux, aux, n * in_b, hipMemcpyHostToDevice, s->stream));
-    const dim3 grid((uint32_t)((n + PH_PROBE_BLOCK - 1) / PH_PROBE_BLOCK)), block(PH_PROBE_BLOCK);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, s->cam, cam_ray ? s->sampler.spp : 1u, op, texture, cam_ray ? 1u : 0u, (uint32_t)n, (const ph::RayIn*)(d + o_rays),
-                           (const PbrtHipHit*)(d + o_hits), (const float*)(d + o_aux), (float*)(d + o_out));
-    };
-    if (variant == 0) launch(ph::surface_probe_kernel<0>);
-    else if (variant == 1) launch(ph::surface_probe_kernel<1>);
-    else launch(ph::surface_probe_kernel<2>);
-    PH_CHECK(s, hipGetLastError());
-    PH_CHECK(s, hipMemcpyAsync(out, d + o_out, n * out_b, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
-    return PBRT_HIP_OK;
+    ProbeStage st(s);
+    const ph::RayIn* d_rays = st.in(device_rays(rays), n);
+    const PbrtHipHit* d_hits = st.in(hits, n);
+    const float* d_aux = st.in(aux, n * PBRT_HIP_SURFACE_PROBE_AUX);
+    float* d_out = st.out(out, n * PBRT_HIP_SURFACE_PROBE_STRIDE);
+    if (!st.ok()) return st.finish();
+    with_variant<3>(variant, [&](auto v) {
+        hipLaunchKernelGGL(ph::surface_probe_kernel<v()>, probe_grid(n), dim3(PH_PROBE_BLOCK), 0, s->stream, s->ds, s->cam, cam_ray ? s->sampler.spp : 1u, op, texture, cam_ray ? 1u : 0u, (uint32_t)n,
+                           d_rays, d_hits, d_aux, d_out);
+    });
+    return st.finish();
     });
 }
 
 int pbrt_hip_texture_probe_batch(PbrtHipScene* s, uint32_t texture, int variant, uint64_t n, const float* contexts, float* out) {
     return ph_guard(s, "pbrt_hip_texture_probe_batch", [&]() -> int {
     return texture_probe_common(s, "texture_probe_batch", texture, variant, 5, n, contexts, 15, out, 3, [&](dim3 grid, dim3 block, const float* d_in, float* d_out) {
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, texture, (uint32_t)n, d_in, d_out); };
-        if (variant == 0) launch(ph::texture_probe_kernel<0>);
-        else if (variant == 1) launch(ph::texture_probe_kernel<1>);
-        else if (variant == 2) launch(ph::texture_probe_kernel<2>);
-        else if (variant == 3) launch(ph::texture_probe_kernel<3>);
-        else launch(ph::texture_probe_kernel<4>);
+        with_variant<5>(variant, [&](auto v) { hipLaunchKernelGGL(ph::texture_probe_kernel<v()>, grid, block, 0, s->stream, s->ds, texture, (uint32_t)n, d_in, d_out); });
     });
     });
 }
@@ -710,11 +649,7 @@ int pbrt_hip_texture_probe_batch(PbrtHipScene* s, uint32_t texture, int variant,
 int pbrt_hip_bump_probe_batch(PbrtHipScene* s, uint32_t texture, int variant, uint64_t n, const float* in, float* out) {
     return ph_guard(s, "pbrt_hip_bump_probe_batch", [&]() -> int {
     return texture_probe_common(s, "bump_probe_batch", texture, variant, 4, n, in, 33, out, 6, [&](dim3 grid, dim3 block, const float* d_in, float* d_out) {
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s->stream, s->ds, texture, (uint32_t)n, d_in, d_out); };
-        if (variant == 0) launch(ph::bump_probe_kernel<0>);
-        else if (variant == 1) launch(ph::bump_probe_kernel<1>);
-        else if (variant == 2) launch(ph::bump_probe_kernel<2>);
-        else launch(ph::bump_probe_kernel<3>);
+        with_variant<4>(variant, [&](auto v) { hipLaunchKernelGGL(ph::bump_probe_kernel<v()>, grid, block, 0, s->stream, s->ds, texture, (uint32_t)n, d_in, d_out); });
     });
     });
 }
@@ -729,21 +664,14 @@ int pbrt_hip_raysort_probe(PbrtHipScene* s, uint32_t n_cl, uint32_t n_sh, const 
     for (uint32_t i = 0; i < n_cl; i++) if (keys_cl[i] >= PH_SORT_KEYS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a closest-hit key is not below 4096, marked or not");
     for (uint32_t i = 0; i < n_sh; i++) if (keys_sh[i] >= PH_SORT_BINS) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "raysort_probe: a key is not below 4096");
     PH_CHECK(s, hipSetDevice(s->device));
-    const size_t o_cl = 0, o_sh = o_cl + up256((size_t)n_cl * 4), o_n = o_sh + up256((size_t)n_sh * 4), o_order = o_n + 256, o_ws = o_order + up256(n * 4),
-                 total = o_ws + up256(raysort_workspace_bytes(sort_blocks));
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
     const uint32_t counts[2] = {n_cl, n_sh};
-    if (n_cl) PH_CHECK(s, hipMemcpyAsync(d + o_cl, keys_cl, (size_t)n_cl * 4, hipMemcpyHostToDevice, s->stream));
-    if (n_sh) PH_CHECK(s, hipMemcpyAsync(d + o_sh, keys_sh, (size_t)n_sh * 4, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_n, counts, 8, hipMemcpyHostToDevice, s->stream));
-    launch_raysort(s, (const uint32_t*)(d + o_cl), (const uint32_t*)(d + o_sh), (const uint32_t*)(d + o_n), (const uint32_t*)(d + o_n) + 1, (uint32_t*)(d + o_order), (uint32_t*)(d + o_ws),
-                   sort_blocks);
-    PH_CHECK(s, hipGetLastError());
-    if (n) PH_CHECK(s, hipMemcpyAsync(order_out, d + o_order, n * 4, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));   // (`counts` and the caller's arrays are pageable: the copies above have left them by now)
-    return PBRT_HIP_OK;
+    ProbeStage st(s);
+    const uint32_t* d_cl = st.in(keys_cl, n_cl), *d_sh = st.in(keys_sh, n_sh), *d_n = st.in(counts, 2);
+    uint32_t* d_order = st.out(order_out, n);
+    uint32_t* d_ws = st.work<uint32_t>(raysort_workspace_bytes(sort_blocks) / sizeof(uint32_t));
+    if (!st.ok()) return st.finish();
+    launch_raysort(s, d_cl, d_sh, d_n, d_n + 1, d_order, d_ws, sort_blocks);
+    return st.finish();   // (`counts` and the caller's arrays are pageable: the copies have left them once the stream has been waited for)
     });
 }
 
@@ -781,35 +709,25 @@ int pbrt_hip_traverse_probe(PbrtHipScene* s, int mode, const PbrtHipRay* rays_cl
     if ((rc = upload_scene(s))) return rc;
     if ((rc = ensure_traversal_workspace(s))) return rc;
     if (blocks > s->trav_blocks) return set_err(s, PBRT_HIP_ERR_INVALID_ARG, "traverse_probe: blocks exceeds the resident grid (the spill region is sized for it)");
-    const size_t ray_b = sizeof(PbrtHipRay), hit_b = sizeof(PbrtHipHit);
-    const size_t o_cl = 0, o_sh = o_cl + up256((size_t)n_cl * ray_b), o_n = o_sh + up256((size_t)n_sh * ray_b), o_heads = o_n + 256, o_order = o_heads + up256(PH_TRAVERSE_PROBE_HEADS * 64),
-                 o_hits = o_order + up256((size_t)n * 4), o_occ = o_hits + up256((size_t)n_cl * hit_b), total = o_occ + up256((size_t)n_sh) + 256;
-    Scratch sx;
-    PH_CHECK(s, hipMalloc(&sx.p, total));
-    char* d = static_cast<char*>(sx.p);
     const uint32_t counts[2] = {n_cl, n_sh};
-    if (n_cl) PH_CHECK(s, hipMemcpyAsync(d + o_cl, rays_cl, (size_t)n_cl * ray_b, hipMemcpyHostToDevice, s->stream));
-    if (n_sh) PH_CHECK(s, hipMemcpyAsync(d + o_sh, rays_sh, (size_t)n_sh * ray_b, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemcpyAsync(d + o_n, counts, 8, hipMemcpyHostToDevice, s->stream));
-    if (order && n) PH_CHECK(s, hipMemcpyAsync(d + o_order, order, (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
-    PH_CHECK(s, hipMemsetAsync(d + o_heads, 0, PH_TRAVERSE_PROBE_HEADS * 64, s->stream));
-    PH_CHECK(s, hipMemsetAsync(s->d_counter.p, 0, 4, s->stream));
+    ProbeStage st(s);
+    const ph::RayIn* d_cl = st.in(device_rays(rays_cl), n_cl), *d_sh = st.in(device_rays(rays_sh), n_sh);
+    const uint32_t* d_n = st.in(counts, 2), *d_order = st.in(order, n);
+    uint32_t* d_heads = st.work<uint32_t>(PH_TRAVERSE_PROBE_HEADS * 16, 0);   // (a head is a 64-byte line)
     // results start as 0xFF bytes: a ray the queue never served is told from every answer the kernel writes
-    if (n_cl) PH_CHECK(s, hipMemsetAsync(d + o_hits, 0xFF, (size_t)n_cl * hit_b, s->stream));
-    if (n_sh) PH_CHECK(s, hipMemsetAsync(d + o_occ, 0xFF, (size_t)n_sh, s->stream));
+    PbrtHipHit* d_hits = st.out(hits_out, n_cl, 0xFF);
+    uint8_t* d_occ = st.out(occluded_out, n_sh, 0xFF);
+    if (!st.ok()) return st.finish();
+    PH_CHECK(s, hipMemsetAsync(s->d_counter.p, 0, 4, s->stream));
     ph::TravParams tp{};
-    const uint32_t* d_n = (const uint32_t*)(d + o_n);
     tp.n = 0; tp.counter = (uint32_t*)s->d_counter.p;
-    if (mode == 1) { tp.rays = (const ph::RayIn*)(d + o_sh); tp.out = d + o_occ; tp.n_ptr = d_n + 1; }
-    else { tp.rays = (const ph::RayIn*)(d + o_cl); tp.out = d + o_hits; tp.n_ptr = d_n; }
-    if (mode == 2) { tp.rays2 = (const ph::RayIn*)(d + o_sh); tp.out2 = (uint8_t*)(d + o_occ); tp.n2_ptr = d_n + 1; }
-    tp.heads = (uint32_t*)(d + o_heads); tp.n_heads = n_heads; tp.head_chunk = head_chunk;
-    tp.order = order ? (const uint32_t*)(d + o_order) : nullptr;
+    if (mode == 1) { tp.rays = d_sh; tp.out = d_occ; tp.n_ptr = d_n + 1; }
+    else { tp.rays = d_cl; tp.out = d_hits; tp.n_ptr = d_n; }
+    if (mode == 2) { tp.rays2 = d_sh; tp.out2 = d_occ; tp.n2_ptr = d_n + 1; }
+    tp.heads = d_heads; tp.n_heads = n_heads; tp.head_chunk = head_chunk;
+    tp.order = order ? d_order : nullptr;
     launch_traverse_kernel(s, mode, blocks, tp);
-    PH_CHECK(s, hipGetLastError());
-    if (n_cl) PH_CHECK(s, hipMemcpyAsync(hits_out, d + o_hits, (size_t)n_cl * hit_b, hipMemcpyDeviceToHost, s->stream));
-    if (n_sh) PH_CHECK(s, hipMemcpyAsync(occluded_out, d + o_occ, (size_t)n_sh, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));   // (`counts` and the caller's arrays are pageable: the copies above have left them by now)
+    if ((rc = st.finish())) return rc;   // (`counts` and the caller's arrays are pageable: the copies have left them once the stream has been waited for)
     return traversal_overflow_check(s);
     });
 }
@@ -875,29 +793,26 @@ int pbrt_hip_film_probe(PbrtHipScene* s, int tile_size, int tile_part, int tile_
         if ((rc = ensure_buf(s, own, tile_floats * 4))) return rc;
         tiles = own.p;
     }
+    ProbeStage st(s);
     if (rec.n_px == 0) PH_CHECK(s, hipMemsetAsync(tiles, 0, tile_floats * 4, s->stream));
     else {
         if ((rc = samples_plan_bands(s, &rec, 0, 0))) return rc;
         if ((rc = samples_alloc(s, &rec))) return rc;
-        const size_t n_rec = (size_t)spp * rec.n_px, o_L = 0, o_p = up256(n_rec * 12), total = o_p + up256(n_rec * 8);
-        Scratch sx;
-        PH_CHECK(s, hipMalloc(&sx.p, total));
-        char* d = static_cast<char*>(sx.p);
-        PH_CHECK(s, hipMemcpyAsync(d + o_L, L, n_rec * 12, hipMemcpyHostToDevice, s->stream));
-        PH_CHECK(s, hipMemcpyAsync(d + o_p, p_film, n_rec * 8, hipMemcpyHostToDevice, s->stream));
+        const size_t n_rec = (size_t)spp * rec.n_px;
+        const float* d_L = st.in(L, n_rec * 3), *d_p = st.in(p_film, n_rec * 2);
+        if (!st.ok()) return st.finish();
         for (size_t b = 0; b < rec.bands.size(); b++) {
             SampleRecords br;
             if ((rc = samples_band(s, rec, b, &br))) return rc;
             const uint64_t threads = (uint64_t)br.n_px * spp;
             hipLaunchKernelGGL(ph::film_probe_fill_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s->stream, br.n_px, br.band.px0, rec.n_px, spp, br.px_xy,
-                               (const float*)(d + o_L), (const float*)(d + o_p), br.rec_L, br.rec_py, br.px_rounded);
+                               d_L, d_p, br.rec_L, br.rec_py, br.px_rounded);
             PH_CHECK(s, hipGetLastError());
             if ((rc = samples_to_tiles(s, br, tiles))) return rc;
         }
-        PH_CHECK(s, hipStreamSynchronize(s->stream));   // (the caller's arrays are pageable: the copies above have left them by now; the scratch goes with this scope)
     }
-    if (out_tiles) PH_CHECK(s, hipMemcpyAsync(out_tiles, tiles, tile_floats * 4, hipMemcpyDeviceToHost, s->stream));
-    PH_CHECK(s, hipStreamSynchronize(s->stream));
+    if (out_tiles) st.fetch(out_tiles, static_cast<const float*>(tiles), tile_floats);
+    if ((rc = st.finish())) return rc;   // (the caller's arrays are pageable: the copies have left them by now)
     if (out_xyz) return merge_own_tiles(s, tile_size, tile_part, tile_parts, out_xyz, out_weight);
     return PBRT_HIP_OK;
     });

@@ -797,28 +797,26 @@ class Scene:
 
     LIGHT_PROBE_STRIDE = 28
 
+    def _light_probe(self, fn, head, ref, u, wi):
+        """What the two light probes share: ref (n,10), u (n,2) or 0.5s, wi (n,3) or +z, and the zeroed (n,28) result, around the call fn(handle, *head, n, ref, u, wi, out)."""
+        ref = _f32(ref, (-1, 10)); n = len(ref)
+        u = _f32(u, (-1, 2)) if u is not None else np.full((n, 2), 0.5, np.float32)
+        wi = _f32(wi, (-1, 3)) if wi is not None else np.tile(np.array([0, 0, 1], np.float32), (n, 1))
+        assert len(u) == n and len(wi) == n
+        out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
+        self._chk(self.b.fn(fn)(self.h, *head, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
+        return out
+
     def light_probe_batch(self, light, op, ref, u=None, wi=None, variant=0):
         """Light number `light` on explicit reference points (pbrt_hip_light_probe_batch), a probe for the parity tests: ref (n,10) = p, p_error, n, time; u (n,2); wi (n,3).
         Returns (n,28): op 0 -> sample_li's wi, pdf, radiance, valid, far point / error / normal, shadow ray origin / direction / t_max; op 1 -> pdf_li; op 2 -> le.
         variant 0 / 1: the code of scenes with / without textures; 2: the Whitted light loop's sample_li (spherical lights)."""
-        ref = _f32(ref, (-1, 10)); n = len(ref)
-        u = _f32(u, (-1, 2)) if u is not None else np.full((n, 2), 0.5, np.float32)
-        wi = _f32(wi, (-1, 3)) if wi is not None else np.tile(np.array([0, 0, 1], np.float32), (n, 1))
-        assert len(u) == n and len(wi) == n
-        out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
-        self._chk(self.b.fn("light_probe_batch")(self.h, light, op, variant, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
-        return out
+        return self._light_probe("light_probe_batch", (light, op, variant), ref, u, wi)
 
     def sphere_light_probe_batch(self, light, op, ref, u=None, wi=None):
         """A spherical, disk or cylinder area light as the path integrator's sphere-light shade pass calls it (pbrt_hip_sphere_light_probe_batch): op 0 -> sample_li, op 1 -> pdf_li.  Inputs and the
         (n,28) output are light_probe_batch's."""
-        ref = _f32(ref, (-1, 10)); n = len(ref)
-        u = _f32(u, (-1, 2)) if u is not None else np.full((n, 2), 0.5, np.float32)
-        wi = _f32(wi, (-1, 3)) if wi is not None else np.tile(np.array([0, 0, 1], np.float32), (n, 1))
-        assert len(u) == n and len(wi) == n
-        out = np.zeros((n, self.LIGHT_PROBE_STRIDE), np.float32)
-        self._chk(self.b.fn("sphere_light_probe_batch")(self.h, light, op, n, _ptr(ref, C.c_float), _ptr(u, C.c_float), _ptr(wi, C.c_float), _ptr(out, C.c_float)))
-        return out
+        return self._light_probe("sphere_light_probe_batch", (light, op), ref, u, wi)
 
     def spatial_probe_begin(self):
         """Set the spatial light distribution's tables up as a light_strategy=2 render does (pbrt_hip_spatial_probe_begin) -> ((nx, ny, nz), pool capacity in voxels)."""
